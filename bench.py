@@ -14,6 +14,13 @@ Inputs (scene tables) are resident in HBM before the timed region starts.
 --config c5: configs[4], grid10k (10,004 spheres), 4096x4096, spp 64 (the cell-grid scan).
 The line has the same shape for every config; the driver's headline run is the default.
 
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--full adds what takes work beyond the timed steps: the roofline object, cull_factor, hbm_read_equivalent, the per-rank
+split and (N = 1, unless --no-cpu-baseline) the CPU baseline.
+--dump-outputs DIR: after the timed steps, rank 0 writes the image of the last timed step as DIR/hdr.npy (float32 sums
+of the samples) and DIR/ldr.npy (the tonemapped bytes as float32), both [H, W, 3]; when the two would exceed 64 MB
+(c5) they hold a fixed seeded sample of pixels instead, [K, 3], with DIR/pixel_index.npy (float64, row-major index).
+
 Launch: python bench.py --gpus 1 ...   or
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                --master-port P bench.py --gpus N --steps K --warmup W
@@ -177,14 +184,40 @@ def per_rank_report(rows):
     return per, slowest
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 12345
+
+
+def dump_outputs(out_dir, hdr, ldr):
+    """Write the last timed step's image (module docstring): the whole [H, W, 3] arrays when they fit in 64 MB, else the same
+    fixed, seeded, sorted sample of pixels from both."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    hdr = np.asarray(hdr, dtype=np.float32)
+    ldr = np.asarray(ldr).astype(np.float32)
+    if hdr.nbytes + ldr.nbytes > DUMP_LIMIT_BYTES:
+        H, W, ch = hdr.shape
+        k = DUMP_LIMIT_BYTES // 2 // (ch * 4 + 8)  # hdr + ldr rows (float32) + index (float64) in half the budget
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, size=min(k, H * W), replace=False))
+        hdr, ldr = hdr.reshape(H * W, ch)[idx], ldr.reshape(H * W, ch)[idx]
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "hdr.npy"), hdr)
+    np.save(os.path.join(out_dir, "ldr.npy"), ldr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, cull factor, HBM read equivalent, per-rank split and CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's image to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[args.config]
     W_IMG, H_IMG, SPP_PER_GPU = cfg["W"], cfg["H"], cfg["spp"]
 
@@ -288,7 +321,7 @@ def main():
     k = float(max(1, args.steps))
     mine = [phase["render"] / k, phase["accumulate"] / k, phase["resolve"] / k, phase["gather"] / k, phase["wall"] / k]
     rank_rows = [mine]
-    if dist is not None:
+    if dist is not None and args.full:
         rank_rows = [None] * N
         dist.all_gather_object(rank_rows, mine)
 
@@ -302,15 +335,13 @@ def main():
         value = total_samples * args.steps / dt / 1e6
         st_last, parts_h, parts_l = last
         # assembling the gathered strips is outside the timed region (host side de-interleave for the PPM)
-        full = D.assemble([p.cpu().numpy() for p in parts_l], H_IMG, N)
-        assert full.shape == (H_IMG, W_IMG, 3)
+        ldr_img = D.assemble([p.cpu().numpy() for p in parts_l], H_IMG, N)
+        assert ldr_img.shape == (H_IMG, W_IMG, 3)
         if os.environ.get("RT_BENCH_DUMP_LDR"):  # tests: the gathered image of the last step
             import numpy as np
-            np.save(os.environ["RT_BENCH_DUMP_LDR"], full)
-        kernel_name = ("rt_trace_kernel<cell-grid scan, 1024 threads, pooled slab items, hit stash>" if args.config == "c5"
-                       else "rt_trace_kernel<LDS tables, 1024 threads, matrix-core filter, hit stash>")
-        roofline, cull = roofline_object(cfg, kernel_name, avg_ms, avg_trav, n_spheres, kernel_sources_hash(), n_gpus=N)
-        per_rank, slowest = per_rank_report(rank_rows)
+            np.save(os.environ["RT_BENCH_DUMP_LDR"], ldr_img)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, D.assemble([p.cpu().numpy() for p in parts_h], H_IMG, N), ldr_img)
         out = {
             "metric": cfg["metric"],
             "value": value, "unit": "Msamples/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
@@ -322,14 +353,21 @@ def main():
                                       (" aperture=%.1f" % cfg["aperture"]) if cfg["aperture"] >= 0 else "", RENDER_SEED, N),
                        "name": args.config, "n_spheres": n_spheres, "spp": spp, "spp_per_gpu": SPP_PER_GPU, "samples_per_step": total_samples,
                        "traversals_per_sample": avg_trav / (W_IMG * rows * spp), "passes": st_last.passes},
-            "roofline": roofline,
-            "cull_factor": cull,
-            # labelled extra (north_star): rank 0's launch; `traffic` is only known for the profiled 1-GPU workload
-            "hbm_read_equivalent": hbm_read_equivalent(avg_ms, avg_trav, n_spheres, roofline.get("traffic")),
-            "per_rank": per_rank, "slowest_rank": slowest,
         }
-        if N == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg)
+        if args.full:
+            kernel_name = ("rt_trace_kernel<cell-grid scan, 1024 threads, pooled slab items, hit stash>" if args.config == "c5"
+                           else "rt_trace_kernel<LDS tables, 1024 threads, matrix-core filter, hit stash>")
+            roofline, cull = roofline_object(cfg, kernel_name, avg_ms, avg_trav, n_spheres, kernel_sources_hash(), n_gpus=N)
+            per_rank, slowest = per_rank_report(rank_rows)
+            out.update({
+                "roofline": roofline,
+                "cull_factor": cull,
+                # labelled extra (north_star): rank 0's launch; `traffic` is only known for the profiled 1-GPU workload
+                "hbm_read_equivalent": hbm_read_equivalent(avg_ms, avg_trav, n_spheres, roofline.get("traffic")),
+                "per_rank": per_rank, "slowest_rank": slowest,
+            })
+            if N == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -81,6 +81,31 @@ def test_multi_gpu_line_extras_have_the_documented_shape():
     assert h2["measured_hbm_GBps"] is None and h2["measured_frac_of_hbm_peak"] is None
 
 
+def test_dump_outputs_writes_float_images_and_a_fixed_sample_over_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the whole HDR / LDR image as float32 while they fit the byte limit; above it, the same seeded pixels of
+    both (sorted row-major indices in float64), identical from run to run, and the files stay within the limit."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    hdr = rng.random((40, 60, 3), dtype=np.float32) * 100
+    ldr = rng.integers(0, 256, (40, 60, 3), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "whole"), hdr, ldr)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["hdr.npy", "ldr.npy"]
+    h, l = np.load(tmp_path / "whole" / "hdr.npy"), np.load(tmp_path / "whole" / "ldr.npy")
+    assert h.dtype == l.dtype == np.float32 and np.array_equal(h, hdr) and np.array_equal(l, ldr.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), hdr, ldr)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["hdr.npy", "ldr.npy", "pixel_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 20000
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) < 40 * 60 and np.all(np.diff(idx) > 0)
+    i = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "hdr.npy"), hdr.reshape(-1, 3)[i])
+    assert np.array_equal(np.load(tmp_path / "a" / "ldr.npy"), ldr.reshape(-1, 3)[i].astype(np.float32))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
 def test_strip_exchange_hands_rccl_the_same_buffers_as_the_gloo_rehearsal(monkeypatch):
     """The `nccl` branch of StripExchange.gather has only run at N = 1 on hardware; its tensors (one uint8 buffer per rank:
     HDR floats then LDR bytes, padded to the largest shard) must have the shapes, dtypes and contents the host-memory gloo

@@ -26,12 +26,7 @@ def test_fixture_is_what_the_extraction_script_reads():
     assert d["corner_pixel_2_2"] == SKY and i["corner_pixel_2_2"] == SKY
     assert d["top_colors"][0]["rgb"] == SKY and d["top_colors"][0]["pixels"] > 350_000
     assert i["top_colors"][0]["rgb"] == SKY and i["top_colors"][0]["pixels"] > 350_000
-    if os.path.isdir("/root/reference/media"):  # build container only: the fixture is current
-        import subprocess
-        import sys
-        here = json.dumps(MEDIA, indent=1)
-        subprocess.check_call([sys.executable, os.path.join(GOLDEN, "extract_reference_media_colors.py")], stdout=subprocess.DEVNULL)
-        assert json.dumps(json.load(open(os.path.join(GOLDEN, "reference_media_colors.json"))), indent=1) == here
+    # that the fixture is current is checked next to the images, outside the suite: extract_reference_media_colors.py --check
 
 
 def _sky_emit(oracle, sc):

@@ -3,4 +3,4 @@
 set -e
 N=${1:-2}
 RT_BENCH_REHEARSAL=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus $N --steps 2 --warmup 1
+    bench.py --full --gpus $N --steps 2 --warmup 1
