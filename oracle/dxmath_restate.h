@@ -5,10 +5,12 @@
 // dxmath_restate.h — CPU restatement of the DirectXMath 3.11 (SSE2 code path) functions the
 // reference's hot path calls.  DirectXMath is NOT vendored in /root/reference (it ships in Windows
 // SDK 10.0.16299.0, common-lib.vcxproj:17); its published algorithms are restated here from the
-// library's public source, per the table in SURVEY.md §8(c).  PARITY UNPINNED with respect to the
-// original binary: the reference has no tests or golden vectors at this level and is
-// itself non-deterministic.  What pins this file: closed-form checks in
-// tests/test_oracle_units.py (XMFresnelTerm(1,1.5)=0.04, Snell, XMCOLOR quantisation, ...).
+// library's public source, per the table in SURVEY.md §8(c).  THIS FILE IS WHAT REMAINS UNPINNED with
+// respect to the original: the reference's own sources are compiled over it (oracle/ref_shim/DirectXMath.h,
+// oracle/_ref/libref.so) and compared with the oracle bit for bit (tests/test_reference_code_cpu.py), which pins the
+// control flow written on top of these functions but not the functions themselves -- both sides share them.  What
+// pins this file: closed-form checks in tests/test_oracle_units.py (XMFresnelTerm(1,1.5)=0.04, Snell, XMCOLOR
+// quantisation, ...).  MSVC's libm is replaced by design (elementary-function contract below).
 //
 // Every operation is spelled in the library's evaluation order with separate multiply and add
 // (SSE2 has no FMA; the oracle is compiled with -ffp-contract=off).

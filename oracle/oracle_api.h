@@ -1,7 +1,10 @@
 /* ORACLE — TEST INFRASTRUCTURE ONLY.  C ABI of the CPU restatement (liboracle.so), used by tests/,
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg as the checker.  It shares the POD
  * records of include/rt_api.h so the same flat scene feeds both the oracle and the HIP library.
- * PARITY UNPINNED w.r.t. the original binary; pinned by tests/golden/halton_known_answers.json. */
+ * What pins it to the original: its control flow is compared, function by function and bit for bit, with the reference's own
+ * sources compiled over oracle/ref_shim/ (ref_api.h, tests/test_reference_code_cpu.py, and the answers recorded from them in
+ * tests/golden/reference_code_answers.npz).  Still restated from memory, and shared by both sides of that comparison: the
+ * DirectXMath semantics of dxmath_restate.h; MSVC's libm and std::rand are replaced by design. */
 #ifndef ORACLE_API_H
 #define ORACLE_API_H
 #include "../include/rt_api.h"
@@ -74,6 +77,20 @@ int orc_unit_scatter(const rt_material* m, const float ray_dir[3], const float p
 /* Material::Emit + Material::Shade with an unoccluded sun (light.cpp:21-40) for one hit */
 void orc_unit_emit_shade(const rt_material* m, const rt_light* sun, const float view_origin[3], const float pos[3],
                          const float normal[3], const float uv[2], float out_local[3]);
+/* --- unit entry points added for tests/test_reference_code_cpu.py (the oracle against the reference's compiled sources) --- */
+/* Camera::GetRay for (uv.x, uv.y, offset.x, offset.y) quadruples of any camera record -> origin xyz, direction xyz */
+int orc_unit_camera_rays(const rt_camera* camera, const float* uv_offset, uint32_t n, float* out_rays);
+/* Texture::Evaluate of the record's texture -> 4 floats per uv */
+int orc_unit_texture_eval(const rt_material* m, const float* uv, uint32_t n, float* out4);
+/* Scatter for n hits against ONE material object, in order.  in (17 floats): ray origin 3, ray direction 3, hit pos 3, normal 3,
+ * uv 2, three uniforms.  out (11 floats): scattered flag, attenuation 3, scattered origin 3, direction 3, draws consumed.
+ * use_counters == 0: each hit consumes its three uniforms in call order (orc_unit_scatter).  use_counters != 0 (needs
+ * orc_use_reference_halton_counters(1)): the uniforms are ignored, the material draws HaltonSample(counter++, base) from its own
+ * counters, which start at 0 and run on through the n hits; draws consumed reads 0. */
+int orc_unit_scatter_n(const rt_material* m, const float* in17, uint32_t n, int use_counters, float* out11);
+/* Emit + Shade of sphere `sphere_index` of the uploaded scene for n given hits (pos 3, normal 3, uv 2), with the uploaded light
+ * list in list order and the list scan over the uploaded spheres as every light's occlusion test */
+int orc_unit_emit_shade_scene(orc_ctx* ctx, uint32_t sphere_index, const float view_origin[3], const float* hits8, uint32_t n, float* out3);
 void orc_xoshiro_seed(uint64_t seed, uint32_t pixel_id, uint32_t sample, uint32_t out_state[4]);
 void orc_xoshiro_draws(uint64_t seed, uint32_t pixel_id, uint32_t sample, uint32_t n, float* out);
 void orc_tonemap(const float hdr_rgb[3], uint32_t n_samples, uint8_t out_rgb[3]);

@@ -288,6 +288,90 @@ void orc_unit_emit_shade(const rt_material* m, const rt_light* sun, const float 
     out_local[0] = local.x; out_local[1] = local.y; out_local[2] = local.z;
 }
 
+int orc_unit_camera_rays(const rt_camera* camera, const float* uv_offset, uint32_t n, float* out_rays) {
+    if (!camera || !uv_offset || !out_rays) return Fail("orc_unit_camera_rays: null argument");
+    const Camera cam(*camera);
+    for (uint32_t k = 0; k < n; ++k) {
+        const float* q = uv_offset + 4 * k;
+        const Ray r = cam.GetRay(XMFLOAT2(q[0], q[1]), XMFLOAT2(q[2], q[3]));
+        float* o = out_rays + 6 * k;
+        o[0] = r.origin.x; o[1] = r.origin.y; o[2] = r.origin.z;
+        o[3] = r.direction.x; o[4] = r.direction.y; o[5] = r.direction.z;
+    }
+    return 0;
+}
+
+namespace {
+// one sphere carrying the material record: LoadScene is what turns records into the oracle's objects
+void OneMaterialScene(const rt_material& m, SpheresApp& app) {
+    FlatScene fs;
+    fs.spheres.push_back({0.f, 0.f, 0.f, 1.f});
+    fs.materials.push_back(m);
+    fs.camera = rt_camera{};
+    fs.sun = rt_light{};
+    fs.sky = rt_material{};
+    app.LoadScene(fs, 1);
+}
+Payload HitOf(const float* h) {
+    Payload hit{};
+    hit.pos = XMVectorSet(h[0], h[1], h[2], 0.f);
+    hit.normal = XMVectorSet(h[3], h[4], h[5], 0.f);
+    hit.uv = XMFLOAT2(h[6], h[7]);
+    return hit;
+}
+}  // namespace
+
+int orc_unit_texture_eval(const rt_material* m, const float* uv, uint32_t n, float* out4) {
+    if (!m || !uv || !out4) return Fail("orc_unit_texture_eval: null argument");
+    rt_material rec = *m;
+    rec.type = RT_MAT_DIELECTRIC_OPAQUE;  // GetAlbedo is the texture's Evaluate
+    SpheresApp app;
+    OneMaterialScene(rec, app);
+    for (uint32_t k = 0; k < n; ++k) {
+        const XMVECTOR v = app.MaterialOf(0)->GetAlbedo(XMFLOAT2(uv[2 * k], uv[2 * k + 1]));
+        out4[4 * k] = v.x; out4[4 * k + 1] = v.y; out4[4 * k + 2] = v.z; out4[4 * k + 3] = v.w;
+    }
+    return 0;
+}
+
+int orc_unit_scatter_n(const rt_material* m, const float* in17, uint32_t n, int use_counters, float* out11) {
+    if (!m || !in17 || !out11) return Fail("orc_unit_scatter_n: null argument");
+    if (use_counters && !Random::ReferenceHaltonCounters()) return Fail("orc_unit_scatter_n: counter mode is off");
+    SpheresApp app;
+    OneMaterialScene(*m, app);
+    const Material* mat = app.MaterialOf(0);
+    for (uint32_t k = 0; k < n; ++k) {
+        const float* q = in17 + 17 * k;
+        const Ray ray{XMVectorSet(q[0], q[1], q[2], 1.f), XMVectorSet(q[3], q[4], q[5], 0.f)};
+        const Payload hit = HitOf(q + 6);
+        XMVECTOR atten = ORC_XM_Zero;
+        Ray outRay{ORC_XM_Zero, ORC_XM_Zero};
+        if (!use_counters) Random::ScriptDraws(q + 14, 3);
+        const bool scattered = mat->Scatter(ray, hit, atten, outRay);
+        const uint32_t used = use_counters ? 0u : Random::ScriptDrawsUsed();
+        Random::ScriptDraws(nullptr, 0);
+        float* o = out11 + 11 * k;
+        o[0] = scattered ? 1.f : 0.f;
+        o[1] = atten.x; o[2] = atten.y; o[3] = atten.z;
+        o[4] = outRay.origin.x; o[5] = outRay.origin.y; o[6] = outRay.origin.z;
+        o[7] = outRay.direction.x; o[8] = outRay.direction.y; o[9] = outRay.direction.z;
+        o[10] = (float)used;
+    }
+    return 0;
+}
+
+int orc_unit_emit_shade_scene(orc_ctx* ctx, uint32_t sphere_index, const float view_origin[3], const float* hits8, uint32_t n, float* out3) {
+    if (!ctx || !ctx->app.HasScene()) return Fail("orc_unit_emit_shade_scene: no scene");
+    if (!view_origin || !hits8 || !out3) return Fail("orc_unit_emit_shade_scene: null argument");
+    if (sphere_index >= ctx->app.SphereCount()) return Fail("orc_unit_emit_shade_scene: sphere index out of range");
+    const XMVECTOR vo = XMVectorSet(view_origin[0], view_origin[1], view_origin[2], 1.f);
+    for (uint32_t k = 0; k < n; ++k) {
+        const XMVECTOR v = ctx->app.EmitShadeOf(sphere_index, HitOf(hits8 + 8 * k), vo);
+        out3[3 * k] = v.x; out3[3 * k + 1] = v.y; out3[3 * k + 2] = v.z;
+    }
+    return 0;
+}
+
 void orc_xoshiro_seed(uint64_t seed, uint32_t pixel_id, uint32_t sample, uint32_t out_state[4]) {
     Xoshiro128 x;
     x.Seed(seed, pixel_id, sample);

@@ -57,7 +57,9 @@ def build(force=False):
     from the one recorded at the last build (content, not mtime: snapshots need not keep modification times)."""
     import glob
     import hashlib
-    srcs = sorted(glob.glob(os.path.join(_HERE, "*.cpp")) + glob.glob(os.path.join(_HERE, "*.h")) + glob.glob(os.path.join(_HERE, "*.inc")) +
+    # (ref_driver.cpp, ref_api.h and ref_shim/ are the recipe of _ref/libref.so, hashed by __graft_entry__.build_reference_library())
+    srcs = sorted(p for p in glob.glob(os.path.join(_HERE, "*.cpp")) + glob.glob(os.path.join(_HERE, "*.h")) if not os.path.basename(p).startswith("ref_"))
+    srcs = sorted(srcs + glob.glob(os.path.join(_HERE, "*.inc")) +
                   [os.path.join(_HERE, "Makefile"), os.path.join(_HERE, "..", "include", "rt_api.h")])
     h = hashlib.sha256()
     for p in srcs:
@@ -132,6 +134,10 @@ def lib():
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
         L.orc_unit_emit_shade.argtypes = [C.POINTER(RtMaterial), C.POINTER(RtLight), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.orc_unit_camera_rays.argtypes = [C.POINTER(RtCamera), C.c_void_p, C.c_uint32, C.c_void_p]
+        L.orc_unit_texture_eval.argtypes = [C.POINTER(RtMaterial), C.c_void_p, C.c_uint32, C.c_void_p]
+        L.orc_unit_scatter_n.argtypes = [C.POINTER(RtMaterial), C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+        L.orc_unit_emit_shade_scene.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_xoshiro_seed.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
         L.orc_xoshiro_draws.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.orc_tonemap.argtypes = [C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint8)]
@@ -292,6 +298,45 @@ def math_array(op, x, y=None):
     out = np.zeros_like(x)
     _check(lib().orc_unit_math(op, x.ctypes.data, y.ctypes.data, x.shape[0], out.ctypes.data))
     return out
+
+
+def camera_rays(camera, uv_offset):
+    """Camera::GetRay of a camera record for [n, 4] (uv.x, uv.y, offset.x, offset.y) -> [n, 6] origin, direction"""
+    q = np.ascontiguousarray(uv_offset, dtype=np.float32).reshape(-1, 4)
+    out = np.zeros((q.shape[0], 6), dtype=np.float32)
+    cam = RtCamera.from_buffer_copy(bytes(camera))
+    _check(lib().orc_unit_camera_rays(C.byref(cam), q.ctypes.data, q.shape[0], out.ctypes.data))
+    return out
+
+
+def texture_eval(material, uv):
+    uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+    out = np.zeros((uv.shape[0], 4), dtype=np.float32)
+    m = RtMaterial.from_buffer_copy(bytes(material))
+    _check(lib().orc_unit_texture_eval(C.byref(m), uv.ctypes.data, uv.shape[0], out.ctypes.data))
+    return out
+
+
+def scatter_n(material, in17, use_counters=False):
+    """[n, 17] (ray origin, ray direction, pos, normal, uv, 3 uniforms) through ONE material object, in order ->
+    [n, 11] flag, attenuation, origin, direction, draws consumed (oracle_api.h orc_unit_scatter_n)"""
+    q = np.ascontiguousarray(in17, dtype=np.float32).reshape(-1, 17)
+    out = np.zeros((q.shape[0], 11), dtype=np.float32)
+    m = RtMaterial.from_buffer_copy(bytes(material))
+    _check(lib().orc_unit_scatter_n(C.byref(m), q.ctypes.data, q.shape[0], 1 if use_counters else 0, out.ctypes.data))
+    return out
+
+
+def _emit_shade_scene(self, sphere_index, view_origin, hits8):
+    """Emit + Shade of one sphere's material for [n, 8] hits (pos, normal, uv) with the uploaded lights and occluders"""
+    q = np.ascontiguousarray(hits8, dtype=np.float32).reshape(-1, 8)
+    vo = np.ascontiguousarray(view_origin, dtype=np.float32).reshape(3)
+    out = np.zeros((q.shape[0], 3), dtype=np.float32)
+    _check(lib().orc_unit_emit_shade_scene(self._h, sphere_index, vo.ctypes.data, q.ctypes.data, q.shape[0], out.ctypes.data))
+    return out
+
+
+Oracle.emit_shade_scene = _emit_shade_scene
 
 
 def write_ppm(path, ldr):

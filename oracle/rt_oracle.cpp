@@ -913,6 +913,12 @@ const Material* SpheresApp::MaterialOf(size_t sphereIndex) const {
     return static_cast<const Sphere*>(m_sceneList->items[sphereIndex].get())->material.get();
 }
 
+XMVECTOR SpheresApp::EmitShadeOf(size_t sphereIndex, const Payload& hit, const XMVECTOR& viewOrigin) const {
+    m_activeAccel = m_sceneList.get();
+    const Material* mat = MaterialOf(sphereIndex);
+    return mat->Emit(hit) + mat->Shade(hit, m_lights, viewOrigin);
+}
+
 // ============================================================ scene generators (A18)
 // spheres-app.cpp:35-49 InitCamera and :51-130 InitScene, with std::ranlux24_base(seed) (portable:
 // fully specified by the C++ standard) and u = engine() * 2^-24 replacing

@@ -1,8 +1,9 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY (see dxmath_restate.h header).  PARITY UNPINNED with respect
-// to the original Windows binary (it cannot be built here and is non-deterministic, SURVEY.md §0
-// F1/F2); pinned instead by the Halton known answers captured from the reference's own
-// quasi-random.cpp (SURVEY.md §8(c) -> tests/golden/halton_known_answers.json) and by closed-form
-// checks of every restated function.
+// ORACLE — TEST INFRASTRUCTURE ONLY (see dxmath_restate.h header).  The original Windows binary is non-deterministic
+// (SURVEY.md §0 F2), but its SOURCES are compiled (oracle/_ref/libref.so: the reference's six translation units over
+// oracle/ref_shim/) and every class restated below is compared with them bit for bit by
+// tests/test_reference_code_cpu.py, live and through tests/golden/reference_code_answers.npz; also pinned by the Halton
+// known answers (tests/golden/halton_known_answers.json) and closed-form checks.  Still restated from memory: the
+// DirectXMath semantics of dxmath_restate.h; MSVC's libm and std::rand are replaced by design.
 //
 // rt_oracle.h — CPU restatement of the reference's render-loop hot path, class for class:
 //   Ray, Payload, AABB, Hitable, Sphere, BvhNode      common-lib/ray-tracing.{h,cpp}
@@ -357,6 +358,8 @@ public:
     void Resolve(uint32_t nSamples);
     std::optional<Payload> ClosestHitWith(const Ray& ray, Accel accel) const;
     const Material* MaterialOf(size_t sphereIndex) const;
+    // Emit + Shade of one sphere's material for a given hit, with the scene's light list and the list scan as occlusion test
+    XMVECTOR EmitShadeOf(size_t sphereIndex, const Payload& hit, const XMVECTOR& viewOrigin) const;
     static void TonemapPixel(const float hdrRgb[3], uint32_t nSamples, uint8_t outRgb[3]);
     static XMCOLOR TonemapColor(const XMVECTOR& hdrColor, uint32_t n);
     XMVECTOR TraceSample(uint32_t W, uint32_t H, uint32_t i, uint32_t j, uint32_t s, uint32_t maxDepth, uint64_t seed,
@@ -371,6 +374,7 @@ public:
     uint32_t SampleCount() const { return m_sampleCount; }
     const Camera& GetCamera() const { return *m_camera; }
     bool HasScene() const { return (bool)m_camera; }
+    size_t SphereCount() const { return m_sceneList ? m_sceneList->items.size() : 0; }
 
 private:
     std::unique_ptr<Camera> m_camera;
