@@ -141,6 +141,12 @@ struct rt_ctx {
     DevBuf<float> pilotRays, pilotHits;
     DevBuf<uint32_t> tileOrder, matType;
     DevBuf<uint8_t> tileClass;
+    // candidate masks of the tiles' primary rays (BuildTileMasks; rt_tile_mask.h): valid for the same (scene, image, strip)
+    bool tileMaskValid = false;
+    uint32_t maskW = 0, maskH = 0, maskLimit = 0, maskTiles = 0;
+    rt_rowset maskRs{};
+    DevBuf<uint32_t> tileMasks;  // kTileMaskWords per full tile
+    uint64_t freshScans = 0;     // blocks of 64 fresh paths launched by the last rt_render that ran passes (rt_unit_tile_masks)
 
     // frame pipelining (rt_set_frame_pipelining; rt_params.h): regions of a sample ring, two continuation buffers
     uint32_t pipeDepth = 0;     // calls a path may be carried across (0 = off)
@@ -1141,6 +1147,41 @@ static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
     return RT_OK;
 }
 
+// Candidate masks of the full tiles' primary rays for the accumulation that is starting (rt_tile_mask.h): one small kernel on
+// the stream, no host wait.  Like the tile order they are a function of the scene (camera included), the image size and the strip,
+// and are kept across accumulations of the same picture.  Only the flat matrix-core scan of the hit-stash kernels reads them.
+// RT_PRIMARY_MASK=0 (both knobs are read when an accumulation starts): no masks, every scan runs the filter.  RT_PRIMARY_MASK_LIMIT: tiles with more candidate groups
+// than this keep the filter.
+static int BuildTileMasks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t npix) {
+    const uint32_t limit = EnvU32("RT_PRIMARY_MASK_LIMIT", rtd::kTileMaskLimitDefault);
+    const uint32_t nFull = npix >> 6;
+    const rtd::TraceParams& b = ctx->base;
+    const bool wanted = EnvU32("RT_PRIMARY_MASK", 1u) != 0u && nFull != 0u && b.n_levels == 1u && b.level_cnt[0] <= 128u &&
+                        ChooseVariant(ctx, b).flat;
+    if (!wanted) {
+        ctx->tileMaskValid = false;
+        return RT_OK;
+    }
+    if (ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && ctx->maskLimit == limit && std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0)
+        return RT_OK;
+    ctx->tileMaskValid = false;
+    int rc;
+    if ((rc = ctx->tileMasks.Reserve((size_t)nFull * rtd::kTileMaskWords)) != RT_OK) return rc;
+    rtd::TraceParams tp = b;
+    tp.W = W;
+    tp.H = H;
+    tp.rs = rs;
+    hipLaunchKernelGGL(rtd::rt_tile_mask_kernel, dim3((nFull + 3) / 4), dim3(256), 0, ctx->stream, tp, nFull, limit, ctx->tileMasks.ptr);
+    RT_HIP(hipGetLastError());
+    ctx->tileMaskValid = true;
+    ctx->maskW = W;
+    ctx->maskH = H;
+    ctx->maskLimit = limit;
+    ctx->maskTiles = nFull;
+    ctx->maskRs = rs;
+    return RT_OK;
+}
+
 // ------------------------------------------------------------------------------ frame pipelining
 // (rt_params.h "frame pipelining")  Host side: one region of the sample ring per rt_render call, two
 // continuation buffers used alternately, and three launches per call: preparation + ray-generation tables, the carrying
@@ -1330,7 +1371,7 @@ int rt_create(int device_ordinal, rt_ctx** out) {
     ctx->blockThreads = EnvU32("RT_BLOCK_THREADS", ctx->useMfma ? 1024 : 256);
     if (ctx->blockThreads != 256 && ctx->blockThreads != 512 && ctx->blockThreads != 1024) ctx->blockThreads = 256;
     int rc = ctx->queue.Reserve(rtd::kQueueShards * rtd::kShardStrideWords);  // eight queue cursors, 128 bytes apart
-    if (rc == RT_OK) rc = ctx->counters.Reserve(2);
+    if (rc == RT_OK) rc = ctx->counters.Reserve(4);
     if (rc != RT_OK) return rc;
     {
         // sample-buffer workspace: sized for this GPU's HBM (288 GB on MI355X), so that BASELINE configs 3 (on one GPU:
@@ -1381,6 +1422,7 @@ void rt_destroy(rt_ctx* ctx) {
     ctx->pilotRays.Release();
     ctx->pilotHits.Release();
     ctx->tileOrder.Release();
+    ctx->tileMasks.Release();
     ctx->tileClass.Release();
     ctx->matType.Release();
     ctx->ring.Release();
@@ -1502,6 +1544,7 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
         if ((rc = ctx->matType.Reserve(n)) != RT_OK) return rc;
         RT_HIP(hipMemcpy(ctx->matType.ptr, types.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
         ctx->tileOrderValid = false;
+        ctx->tileMaskValid = false;
     }
 
     ShadowGrid SG;
@@ -1814,6 +1857,7 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
         ctx->rs = rs;
         ctx->accumulated = 0;
         if ((rc = BuildTileOrder(ctx, W, H, rs, npix)) != RT_OK) return rc;
+        if ((rc = BuildTileMasks(ctx, W, H, rs, npix)) != RT_OK) return rc;
     } else if (!sameStrip || s0 != ctx->accumulated + 1) {
         return Fail(RT_ERR_SEQUENCE, "rt_render: sample range or row set does not continue the accumulation");
     }
@@ -1854,7 +1898,8 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
     uint32_t passes = 0;
     auto runPasses = [&]() -> int {
         int rc;
-        RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+        RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 4 * sizeof(unsigned long long), ctx->stream));
+        ctx->freshScans = 0;
         const uint32_t sEnd = aheadEnd ? aheadEnd : s1;
         for (uint32_t s = s0; s < sEnd; s += sppPass) {
             const uint32_t spp = (sEnd - s) < sppPass ? (sEnd - s) : sppPass;
@@ -1871,6 +1916,9 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
             tp.seed = seed;
             tp.path_list = nullptr;
             tp.tile_order = ctx->tileOrderValid ? ctx->tileOrder.ptr : nullptr;
+            // (the table must be the one of THIS accumulation's picture: rt_unit_tile_masks may have rebuilt it for another since)
+            tp.tile_masks = (ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0) ? ctx->tileMasks.ptr : nullptr;
+            ctx->freshScans += ((uint64_t)tp.total_paths + 63u) / 64u;
             tp.samples = ctx->samples.ptr;
             tp.trav_out = nullptr;
             tp.counters = ctx->counters.ptr;
@@ -2097,7 +2145,7 @@ int rt_unit_trace(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ijs, uint
     RT_HIP(dTrav.Alloc(n));
     RT_HIP(dOut.Alloc((size_t)n * 3));
     RT_HIP(hipMemcpy(dIjs.p, ijs, (size_t)n * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
-    RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 4 * sizeof(unsigned long long), ctx->stream));
     rtd::TraceParams tp = ctx->base;
     tp.W = W;
     tp.H = H;
@@ -2228,6 +2276,93 @@ int rt_unit_layout_info(const rt_sphere* spheres, uint32_t n, uint32_t out[5]) {
     out[2] = L.gridOn ? L.gridNv : 0u;
     out[3] = L.nAlways;
     out[4] = L.nLevels;
+    return RT_OK;
+}
+
+int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t cap_tiles, uint32_t* n_tiles, uint32_t* words,
+                       uint32_t cap_spheres, uint32_t* group_of_sphere, uint64_t scans[2]) {
+    if (!ctx || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: invalid argument");
+    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_tile_masks: no scene uploaded");
+    const uint32_t rows = RowsetLocalRows(rs);
+    if (rows == 0 || (uint64_t)rs.first_row + rs.num_rows > H || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: bad row set");
+    RT_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = BuildTileMasks(ctx, W, H, rs, W * rows)) != RT_OK) return rc;
+    *n_tiles = ctx->tileMaskValid ? ctx->maskTiles : 0u;
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    if (words && *n_tiles != 0u) {
+        if (cap_tiles < *n_tiles) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: capacity too small");
+        RT_HIP(hipMemcpy(words, ctx->tileMasks.ptr, (size_t)*n_tiles * rtd::kTileMaskWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    if (group_of_sphere) {
+        if (cap_spheres < ctx->n) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: sphere capacity too small");
+        std::vector<uint32_t> orig(ctx->base.n_padded);
+        RT_HIP(hipMemcpy(orig.data(), ctx->orig.ptr, orig.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < ctx->n; ++k) group_of_sphere[k] = 0xffffffffu;
+        for (uint32_t e = 0; e < (uint32_t)orig.size(); ++e)
+            if (orig[e] < ctx->n) group_of_sphere[orig[e]] = e >> 2;  // flat scan: scan entry = 4 * group + member
+    }
+    if (scans) {
+        unsigned long long c[4] = {0, 0, 0, 0};
+        RT_HIP(hipMemcpy(c, ctx->counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
+        scans[0] = ctx->freshScans;  // host arithmetic: every block of 64 fresh paths of the last rt_render that launched
+        scans[1] = c[3];
+    }
+    return RT_OK;
+}
+
+int rt_unit_tile_masks_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t limit,
+                            uint32_t cap_tiles, uint32_t* n_tiles, uint32_t* words, uint32_t* group_of_sphere) {
+    if (!spheres || n == 0 || !camera || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks_host: invalid argument");
+    const uint32_t rows = RowsetLocalRows(rs);
+    if (rows == 0 || (uint64_t)rs.first_row + rs.num_rows > H || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks_host: bad row set");
+    SceneLayout L;
+    BuildLayout(spheres, n, TreeTopFromEnv(), L);
+    const uint32_t nTop = L.levelCnt[L.nLevels - 1];
+    const uint32_t nFull = (W * rows) >> 6;
+    *n_tiles = (L.nLevels == 1 && !L.gridOn && nTop <= 128u) ? nFull : 0u;
+    if (*n_tiles == 0u || !words) return RT_OK;
+    if (cap_tiles < nFull) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks_host: capacity too small");
+    const rtd::TileMaskCam c = rtd::tile_mask_cam(camera->origin, camera->x, camera->y, camera->origin_image_plane, camera->aperture, camera->focal_length, W, H);
+    for (uint32_t t = 0; t < nFull; ++t) {
+        uint32_t* w = words + (size_t)rtd::kTileMaskWords * t;
+        for (uint32_t k = 0; k < rtd::kTileMaskWords; ++k) w[k] = 0u;
+        bool bad = false;
+        uint32_t cnt = 0;
+        for (uint32_t g = 0; g < nTop; ++g) {
+            const float4 B = L.tree[L.levelOff[L.nLevels - 1] + g];
+            const float b[4] = {B.x, B.y, B.z, B.w};
+            const int r = rtd::tile_group_reached(c, rs, t, b);
+            bad = bad || r < 0;
+            if (r > 0) {
+                uint32_t word, bit;
+                rtd::tile_mask_slot(g, word, bit);
+                w[word] |= bit;
+                ++cnt;
+            }
+        }
+        w[4] = rtd::tile_mask_flags(bad, cnt, limit);
+        w[5] = cnt;
+    }
+    if (group_of_sphere) {
+        for (uint32_t k = 0; k < n; ++k) group_of_sphere[k] = 0xffffffffu;
+        for (uint32_t e = 0; e < (uint32_t)L.orig.size(); ++e)
+            if (L.orig[e] < n) group_of_sphere[L.orig[e]] = e >> 2;
+    }
+    return RT_OK;
+}
+
+int rt_unit_tile_cone(const rt_camera* camera, uint32_t W, uint32_t H, uint32_t i0, uint32_t i1, uint32_t j, double out[9]) {
+    if (!camera || !out || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_cone: invalid argument");
+    const rtd::TileMaskCam c = rtd::tile_mask_cam(camera->origin, camera->x, camera->y, camera->origin_image_plane, camera->aperture, camera->focal_length, W, H);
+    const rtd::TileCone t = rtd::tile_run_cone(c, i0, i1, j);
+    for (int k = 0; k < 3; ++k) {
+        out[k] = t.o[k];
+        out[3 + k] = t.D[k];
+    }
+    out[6] = t.rhoL;
+    out[7] = t.rhoF;
+    out[8] = t.ok ? 1.0 : 0.0;
     return RT_OK;
 }
 

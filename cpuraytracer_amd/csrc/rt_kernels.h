@@ -38,6 +38,7 @@
 #include "rt_params.h"
 #include "rt_scan.h"
 #include "rt_shade.h"
+#include "rt_tile_mask.h"
 
 namespace rtd {
 
@@ -599,9 +600,13 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             state = kNeedShadow;
         }
     };
+    // Tile masks (rt_tile_mask.h; flat hit-stash variants): when the 64 fresh paths of K_GEN are one full tile at one sample, the scan
+    // that follows in the same iteration holds that tile's 64 primary rays and nothing else, and takes the tile's candidate words.
+    constexpr bool kPrim = kStash && kScan == 1;
     for (;;) {
         RT_SITE(K_ITER);
         RT_STAMP(ts0);
+        uint32_t primTile = 0xffffffffu;  // wave-uniform: the tile whose mask this iteration's scan takes (none)
         // ------------------------------------------------ refill idle lanes (ballot + prefix)
         // New paths come from a per-wave cache of 64 prepared paths in LDS: when it runs empty ALL 64 lanes generate
         // the next 64 paths of the wave's queue block at once (index arithmetic, stream seeding, Camera::GetRay with
@@ -691,6 +696,18 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                     }
 #endif
                     const uint32_t nGen = (blkEnd - blkNext) < (uint32_t)kWaveSize ? (blkEnd - blkNext) : (uint32_t)kWaveSize;
+                    if (kPrim) {
+                        // one full tile at one sample (path_coordinates: tile spans are multiples of 64), and the tile has a mask
+                        if (p.tile_masks != nullptr && nGen == (uint32_t)kWaveSize && (blkNext & 63u) == 0u) {
+                            RT_SITE(K_GEN_TILE);
+                            const uint32_t tw = fastdiv(blkNext, p.fd_tile);
+                            if (tw < (p.npix_local >> 6)) {
+                                const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p.tile_order ? p.tile_order[tw] : tw));
+                                const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_masks[kTileMaskWords * tile + 4u]);
+                                if (flags & 1u) primTile = tile;
+                            }
+                        }
+                    }
                     if (lane < nGen) {
                         RT_SITE(K_GEN_LANE);
                         uint32_t i, j, sN;
@@ -853,8 +870,15 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         if (kMfma) {
             // every lane takes part: lane l also supplies operands for, and filters half the spheres of,
             // the ray owned by lane l^32, whether or not its own ray is live
-            scan_list_mfma<kScan == 2>(scanTab, leafTab, origTab, mfmaOps, nTiles, nTop, treeTab, p.level_off, p.n_levels, p.bound_norm, p.single_mask, p.n_always, p.tree_box_on ? p.tree_box : nullptr, ro, rd,
-                                       live, tmin, idx, waveCand, lane, dbgScan);
+            const uint32_t* tileMask = nullptr;
+            if (kPrim && primTile != 0xffffffffu) {
+                tileMask = p.tile_masks + kTileMaskWords * primTile;
+                // statistics (rt_unit_tile_masks): one LDS add per masked scan into the workgroup's constants block -- no register
+                // lives across the persistent loop for it (two wave-uniform counters cost the kernel two VGPR spills and 1.1 %)
+                if (lane == 0) __hip_atomic_fetch_add(&ldsK->prim_masked, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            scan_list_mfma<kScan == 2, kPrim>(scanTab, leafTab, origTab, mfmaOps, nTiles, nTop, treeTab, p.level_off, p.n_levels, p.bound_norm, p.single_mask, p.n_always, p.tree_box_on ? p.tree_box : nullptr, ro, rd,
+                                       live, tmin, idx, waveCand, lane, dbgScan, tileMask);
         } else if (kScan == 3) {
             const GridParams G{gridCells, p.grid_nu, p.grid_nv, p.grid_ax_u, p.grid_ax_v, p.grid_g0u, p.grid_g0v, p.grid_inv_h, p.grid_rmax_over_h, p.grid_big_norm};
             const GridQuant Q{gridQ, p.grid_q[0], p.grid_q[1], p.grid_q[2], p.grid_q[3], p.grid_q[4], p.grid_q[5], p.grid_q[6], p.grid_q[7]};
@@ -960,6 +984,12 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
     if (lane == 0) {
         atomicAdd(&p.counters[0], t);
         atomicAdd(&p.counters[1], s);
+        if (kPrim && p.tile_masks != nullptr) {
+            // the wave that leaves last adds the workgroup's count of masked scans (every other wave's adds precede its ticket)
+            const uint32_t ticket = __hip_atomic_fetch_add(&ldsK->exit_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (ticket == (uint32_t)(kThreads / kWaveSize) - 1u)
+                atomicAdd(&p.counters[3], (unsigned long long)__hip_atomic_load(&ldsK->prim_masked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        }
 #ifdef RT_STAMPS
         atomicAdd(&g_dbg[0], cyRefill);
         atomicAdd(&g_dbg[1], cyScan);
@@ -1104,6 +1134,43 @@ __global__ void __launch_bounds__(1024) rt_tile_order_kernel(const uint8_t* cls,
             pos[k] += c == k ? 1u : 0u;
         }
         order[at] = t;
+    }
+}
+
+// ====================================================== candidate masks of the tiles' primary rays
+// rt_tile_mask.h: one wave per full tile, lane l decides groups l and l + 64 of the flat scan's top level; the two ballots are
+// permuted into the scan's word layout (bit N from the top of word k = group kBase[k] + N + (N & 16), kBase = 0, 64, 16, 80) and
+// lane 0 writes the tile's eight words with two 16-byte stores.  A tile with more than `limit` candidate groups, or one the
+// construction does not apply to, gets flags = 0 and keeps the matrix-core filter.
+static_assert(kTileMaskPerRay == 2.0 * (double)kMarginRel, "the masks bound the filter's own per-ray margin");
+__global__ void __launch_bounds__(256) rt_tile_mask_kernel(const TraceParams p, uint32_t nFull, uint32_t limit, uint32_t* __restrict__ words) {
+    const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (tile >= nFull) return;  // wave-uniform
+    RT_SITE(T_MASK);
+    const TileMaskCam c = tile_mask_cam(p.cam_o, p.cam_x, p.cam_y, p.cam_oip, p.aperture, p.focal, p.W, p.H);
+    const uint32_t topLevel = p.n_levels - 1u;
+    const uint32_t nTop = p.level_cnt[topLevel];
+    const float4* bounds = p.tree + p.level_off[topLevel];
+    int r0 = 0, r1 = 0;
+    if (lane < nTop) {
+        const float4 B = bounds[lane];
+        const float b[4] = {B.x, B.y, B.z, B.w};
+        r0 = tile_group_reached(c, p.rs, tile, b);
+    }
+    if (lane + 64u < nTop && nTop <= 128u) {
+        const float4 B = bounds[lane + 64u];
+        const float b[4] = {B.x, B.y, B.z, B.w};
+        r1 = tile_group_reached(c, p.rs, tile, b);
+    }
+    const uint64_t m0 = __ballot(r0 > 0), m1 = __ballot(r1 > 0);
+    const bool bad = __ballot(r0 < 0 || r1 < 0) != 0ull || nTop > 128u;
+    if (lane == 0) {
+        auto wordA = [](uint64_t m) { return __builtin_bitreverse32((uint32_t)m & 0xffffu) | (__builtin_bitreverse32((uint32_t)(m >> 32) & 0xffffu) >> 16); };
+        auto wordB = [](uint64_t m) { return __builtin_bitreverse32((uint32_t)(m >> 16) & 0xffffu) | (__builtin_bitreverse32((uint32_t)(m >> 48) & 0xffffu) >> 16); };
+        const uint32_t cnt = (uint32_t)(__popcll(m0) + __popcll(m1));
+        uint4* w = reinterpret_cast<uint4*>(words + (size_t)kTileMaskWords * tile);
+        w[0] = make_uint4(wordA(m0), wordA(m1), wordB(m0), wordB(m1));
+        w[1] = make_uint4(tile_mask_flags(bad, cnt, limit), cnt, 0u, 0u);
     }
 }
 

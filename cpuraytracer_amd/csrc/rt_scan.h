@@ -479,11 +479,17 @@ RT_DEV bool next_candidate(unsigned long long& cur, unsigned long long& nxt, uin
     return true;
 }
 
-template <bool kTree>
+// kPrim (flat scan of the hit-stash kernels only): tileMask, when not null, points to the four candidate words of the tile whose
+// 64 primary rays this scan holds (rt_tile_mask.h: a superset of every group a primary ray of that tile can have a root in, laid
+// out as cw0..cw3 below).  The scan then takes them in place of the filter's result -- no operand build, no matrix-core pass, no
+// bitmap exchange -- and goes on with the same list build, phases A and B and merge: only the candidate set is looser.
+template <bool kTree, bool kPrim = false>
 RT_DEV void scan_list_mfma(const float4* __restrict__ tab, const float4* __restrict__ leaf, const uint32_t* __restrict__ orig,
                            const float* __restrict__ ops, uint32_t nTiles,
                            uint32_t nTop, const float4* __restrict__ tree, const uint32_t* levelOff, uint32_t nLevels, float boundNorm,
-                           const unsigned long long* singleMask, uint32_t nAlways, const float* treeBox, V3 o, V3 d, bool live, float& tmin, int& idx, uint16_t* waveCand, uint32_t lane, unsigned long long* dbg) {
+                           const unsigned long long* singleMask, uint32_t nAlways, const float* treeBox, V3 o, V3 d, bool live, float& tmin, int& idx, uint16_t* waveCand, uint32_t lane, unsigned long long* dbg,
+                           const uint32_t* tileMask = nullptr) {
+    static_assert(!kPrim || !kTree, "tile masks belong to the flat scan");
     RT_SITE(S_SCAN);
     const float a = dot3(d, d);
     tmin = __builtin_inff();
@@ -500,6 +506,15 @@ RT_DEV void scan_list_mfma(const float4* __restrict__ tab, const float4* __restr
     // ray-side operands: values (k = 0,1 | 2,3) of the b chain [dx, dy | dz, d.o] and of the a*cc chain [gx, gy | gz, a].
     // Tile 0 (rays of lanes 0-31) takes k = 0,1 from the owner and k = 2,3 from lane+32; tile 1 the other way round:
     // v_permlane32_swap exchanges exactly those halves (upper half of the first register <-> lower half of the second).
+    unsigned long long cur, nxt;  // candidates of the two bitmap halves
+    RT_STAMP(tf0);
+    if (kPrim && tileMask != nullptr) {
+        RT_SITE(S_MASKED);
+        // a wave-uniform address: every lane reads the same four words (one 16-byte request)
+        const uint4 m = *reinterpret_cast<const uint4*>(tileMask);
+        cur = live ? (((unsigned long long)m.x << 32) | (unsigned long long)m.y) : 0ull;
+        nxt = live ? (((unsigned long long)m.z << 32) | (unsigned long long)m.w) : 0ull;
+    } else {
     uint32_t b01x = split_ray_value(d.x), b01y = split_ray_value(d.y), b23x = split_ray_value(d.z), b23y = split_ray_value(dO);
     // a*cc chain, ray side: slots (x0h, x0l, x0h, x1h, x1l, x1h, ch, cl) = dwords (x0h|x0l, x0h|x1h, x1l|x1h, ch|cl)
     const uint32_t sgx = split_ray_value(gx), sgy = split_ray_value(gy), sgz = split_ray_value(gz), sga = split_ray_value(a);
@@ -525,7 +540,6 @@ RT_DEV void scan_list_mfma(const float4* __restrict__ tab, const float4* __restr
     const bf16x8 Bg0 = __builtin_bit_cast(bf16x8, (u32x4){g01a, g01b, g01c, split_ray_value(__uint_as_float(cr0))});
     const bf16x8 Bg1 = __builtin_bit_cast(bf16x8, (u32x4){g23a, g23b, g23c, split_ray_value(__uint_as_float(cr1))});
     const float btT0 = __uint_as_float(bt0), btT1 = __uint_as_float(bt1);
-    RT_STAMP(tf0);
     const uint32_t* opsImg = reinterpret_cast<const uint32_t*>(ops);
     // rejected-bits words: w0* = ray tile 0 (the ray of lane l&31), w1* = ray tile 1 (the ray of lane (l&31)+32);
     // *a = tiles 0,1, *b = tiles 2,3 (all ones = nothing to resolve when the image has only two tiles)
@@ -558,7 +572,6 @@ RT_DEV void scan_list_mfma(const float4* __restrict__ tab, const float4* __restr
             w1b = r1;
         }
     }
-    RT_STAMP(tf1);
     // every ray has two producer lanes (l&31 filtered rows of half 0, (l&31)+32 those of half 1); after the swaps
     // w0* holds the half-0 words and w1* the half-1 words of THIS lane's own ray
     {
@@ -566,8 +579,10 @@ RT_DEV void scan_list_mfma(const float4* __restrict__ tab, const float4* __restr
         const auto rb = __builtin_amdgcn_permlane32_swap(w0b, w1b, false, false);
         w0a = ra[0]; w1a = ra[1]; w0b = rb[0]; w1b = rb[1];
     }
-    unsigned long long cur = ~(((unsigned long long)w0a << 32) | (unsigned long long)w0b);  // candidates of half 0
-    unsigned long long nxt = ~(((unsigned long long)w1a << 32) | (unsigned long long)w1b);  // candidates of half 1
+    cur = ~(((unsigned long long)w0a << 32) | (unsigned long long)w0b);  // candidates of half 0
+    nxt = ~(((unsigned long long)w1a << 32) | (unsigned long long)w1b);  // candidates of half 1
+    }
+    RT_STAMP(tf1);
     uint32_t hOff = 0u;
 #ifdef RT_STAMPS
     const uint32_t tot = (uint32_t)(__popcll(cur) + __popcll(nxt));

@@ -280,6 +280,20 @@ int rt_unit_layout_info(const rt_sphere* spheres, uint32_t n, uint32_t out[5]);
  * source the kernels use): for n segments (su, sv, eu, ev, D: 5 floats each, grid coordinates) and slabs iu, the rows [r0, r1] of
  * slab iu the walk visits (r0 > r1: none) and the entry parameter sEnter.  out_rows: 2 ints per query.  Needs no GPU. */
 int rt_unit_grid_rows(const float* segments, const int32_t* iu, uint32_t n, int32_t nv, int32_t* out_rows, float* out_s_enter);
+/* Candidate masks of the primary rays (csrc/rt_tile_mask.h), as rt_render builds them for the uploaded scene when an accumulation of a
+ * W x H image over row set rs starts: 8 words per full tile of 64 consecutive local pixels -- [0..3] the flat scan's candidate words
+ * (bit N from the top of word k = group kBase[k] + N + (N & 16), kBase = 0, 64, 16, 80), [4] bit 0 = the tile has a mask (else it keeps
+ * the matrix-core filter), [5] = candidate groups.  *n_tiles = 0: this scene / these settings use no masks.  group_of_sphere (by
+ * original sphere index, may be null): the group each sphere belongs to.  scans (may be null): [0] blocks of 64 fresh paths (host arithmetic) and [1]
+ * the scans that took a mask (counted by the kernel), in the last rt_render that launched a trace kernel of its own. */
+int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t cap_tiles, uint32_t* n_tiles, uint32_t* words,
+                       uint32_t cap_spheres, uint32_t* group_of_sphere, uint64_t scans[2]);
+/* ... the same masks evaluated on the host from the same source (candidate limit given).  Needs no GPU. */
+int rt_unit_tile_masks_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t limit,
+                            uint32_t cap_tiles, uint32_t* n_tiles, uint32_t* words, uint32_t* group_of_sphere);
+/* ... and the cone of the primary rays of pixels i0..i1 of row j: out = camera origin 3, axis D = Fc - origin 3, rhoL, rhoF, valid.
+ * Every point (1 - l) O + l F of such a ray lies within |1 - l| rhoL + l rhoF of origin + l D.  Needs no GPU. */
+int rt_unit_tile_cone(const rt_camera* camera, uint32_t W, uint32_t H, uint32_t i0, uint32_t i1, uint32_t j, double out[9]);
 /* The resolve of spheres-app.cpp:196-214 for given HDR triples -> R,G,B bytes */
 int rt_unit_tonemap(rt_ctx* ctx, const float* hdr_rgb, uint32_t n, uint32_t n_samples, uint8_t* out_rgb);
 

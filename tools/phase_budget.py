@@ -38,7 +38,9 @@ PHASES = collections.OrderedDict([
     ("slow paths of the divisions and square roots (range guards failed)", ["M_DIV_SLOW", "M_SQRT_SLOW", "M_ROOT_SLOW"]),
     ("queue (block claims)", ["K_NEXTBLOCK", "K_CLAIM"]),
     ("stash push / pop", ["K_POP", "K_POP_LANE", "K_PUSH", "K_PUSH_LANE"]),
+    ("ray generation: tile-mask lookup (fresh tile -> tile id, flags word)", ["K_GEN_TILE"]),
     ("scan: operand build, bitmap exchange, result read", ["S_SCAN"]),
+    ("scan: candidate words from the tile mask (primary rays)", ["S_MASKED"]),
     ("scan: MFMA + mfma_post", ["S_TILEPAIR"]),
     ("scan: one-sphere groups straight to the exact list", ["S_SINGLE", "S_SINGLE_PUSH0", "S_SINGLE_PUSH1"]),
     ("scan: pooled (ray, group) list build", ["S_PASS", "S_TAKE", "S_TAKE_PUSH0", "S_TAKE_PUSH1", "S_PUSH_WORD"]),
