@@ -144,8 +144,10 @@ struct rt_ctx {
     // candidate masks of the tiles' primary rays (BuildTileMasks; rt_tile_mask.h): valid for the same (scene, image, strip)
     bool tileMaskValid = false;
     uint32_t maskW = 0, maskH = 0, maskLimit = 0, maskTiles = 0;
+    uint32_t maskSpheres = 0;    // sphere-list limit the tables were built with (0: no lists)
     rt_rowset maskRs{};
     DevBuf<uint32_t> tileMasks;  // kTileMaskWords per full tile
+    DevBuf<uint16_t> tileSpheres;  // kTileSphereHalfs per full tile (built together with the masks)
     uint64_t freshScans = 0;     // blocks of 64 fresh paths launched by the last rt_render that ran passes (rt_unit_tile_masks)
 
     // frame pipelining (rt_set_frame_pipelining; rt_params.h): regions of a sample ring, two continuation buffers
@@ -1151,9 +1153,15 @@ static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
 // the stream, no host wait.  Like the tile order they are a function of the scene (camera included), the image size and the strip,
 // and are kept across accumulations of the same picture.  Only the flat matrix-core scan of the hit-stash kernels reads them.
 // RT_PRIMARY_MASK=0 (both knobs are read when an accumulation starts): no masks, every scan runs the filter.  RT_PRIMARY_MASK_LIMIT: tiles with more candidate groups
-// than this keep the filter.
+// than this keep the filter.  RT_PRIMARY_SPHERES: tiles with a mask and at most this many reachable spheres also get a sphere list and
+// resolve their primary rays directly (rt_scan.h scan_tile_spheres); 0 = no lists, values above kTileSphereMax are clamped.
+static uint32_t TileSphereLimitFromEnv() {
+    const uint32_t v = EnvU32("RT_PRIMARY_SPHERES", rtd::kTileSphereLimitDefault);
+    return v > rtd::kTileSphereMax ? rtd::kTileSphereMax : v;
+}
 static int BuildTileMasks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t npix) {
     const uint32_t limit = EnvU32("RT_PRIMARY_MASK_LIMIT", rtd::kTileMaskLimitDefault);
+    const uint32_t sphLimit = TileSphereLimitFromEnv();
     const uint32_t nFull = npix >> 6;
     const rtd::TraceParams& b = ctx->base;
     const bool wanted = EnvU32("RT_PRIMARY_MASK", 1u) != 0u && nFull != 0u && b.n_levels == 1u && b.level_cnt[0] <= 128u &&
@@ -1162,21 +1170,25 @@ static int BuildTileMasks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
         ctx->tileMaskValid = false;
         return RT_OK;
     }
-    if (ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && ctx->maskLimit == limit && std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0)
+    if (ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && ctx->maskLimit == limit && ctx->maskSpheres == sphLimit &&
+        std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0)
         return RT_OK;
     ctx->tileMaskValid = false;
     int rc;
     if ((rc = ctx->tileMasks.Reserve((size_t)nFull * rtd::kTileMaskWords)) != RT_OK) return rc;
+    if (sphLimit != 0u && (rc = ctx->tileSpheres.Reserve((size_t)nFull * rtd::kTileSphereHalfs)) != RT_OK) return rc;
     rtd::TraceParams tp = b;
     tp.W = W;
     tp.H = H;
     tp.rs = rs;
-    hipLaunchKernelGGL(rtd::rt_tile_mask_kernel, dim3((nFull + 3) / 4), dim3(256), 0, ctx->stream, tp, nFull, limit, ctx->tileMasks.ptr);
+    hipLaunchKernelGGL(rtd::rt_tile_mask_kernel, dim3((nFull + 3) / 4), dim3(256), 0, ctx->stream, tp, nFull, limit, ctx->tileMasks.ptr,
+                       sphLimit, sphLimit != 0u ? ctx->tileSpheres.ptr : nullptr);
     RT_HIP(hipGetLastError());
     ctx->tileMaskValid = true;
     ctx->maskW = W;
     ctx->maskH = H;
     ctx->maskLimit = limit;
+    ctx->maskSpheres = sphLimit;
     ctx->maskTiles = nFull;
     ctx->maskRs = rs;
     return RT_OK;
@@ -1371,7 +1383,7 @@ int rt_create(int device_ordinal, rt_ctx** out) {
     ctx->blockThreads = EnvU32("RT_BLOCK_THREADS", ctx->useMfma ? 1024 : 256);
     if (ctx->blockThreads != 256 && ctx->blockThreads != 512 && ctx->blockThreads != 1024) ctx->blockThreads = 256;
     int rc = ctx->queue.Reserve(rtd::kQueueShards * rtd::kShardStrideWords);  // eight queue cursors, 128 bytes apart
-    if (rc == RT_OK) rc = ctx->counters.Reserve(4);
+    if (rc == RT_OK) rc = ctx->counters.Reserve(6);
     if (rc != RT_OK) return rc;
     {
         // sample-buffer workspace: sized for this GPU's HBM (288 GB on MI355X), so that BASELINE configs 3 (on one GPU:
@@ -1423,6 +1435,7 @@ void rt_destroy(rt_ctx* ctx) {
     ctx->pilotHits.Release();
     ctx->tileOrder.Release();
     ctx->tileMasks.Release();
+    ctx->tileSpheres.Release();
     ctx->tileClass.Release();
     ctx->matType.Release();
     ctx->ring.Release();
@@ -1898,7 +1911,7 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
     uint32_t passes = 0;
     auto runPasses = [&]() -> int {
         int rc;
-        RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 4 * sizeof(unsigned long long), ctx->stream));
+        RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 6 * sizeof(unsigned long long), ctx->stream));
         ctx->freshScans = 0;
         const uint32_t sEnd = aheadEnd ? aheadEnd : s1;
         for (uint32_t s = s0; s < sEnd; s += sppPass) {
@@ -1918,6 +1931,7 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
             tp.tile_order = ctx->tileOrderValid ? ctx->tileOrder.ptr : nullptr;
             // (the table must be the one of THIS accumulation's picture: rt_unit_tile_masks may have rebuilt it for another since)
             tp.tile_masks = (ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0) ? ctx->tileMasks.ptr : nullptr;
+            tp.tile_spheres = (tp.tile_masks != nullptr && ctx->maskSpheres != 0u) ? ctx->tileSpheres.ptr : nullptr;
             ctx->freshScans += ((uint64_t)tp.total_paths + 63u) / 64u;
             tp.samples = ctx->samples.ptr;
             tp.trav_out = nullptr;
@@ -2145,7 +2159,7 @@ int rt_unit_trace(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ijs, uint
     RT_HIP(dTrav.Alloc(n));
     RT_HIP(dOut.Alloc((size_t)n * 3));
     RT_HIP(hipMemcpy(dIjs.p, ijs, (size_t)n * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
-    RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 6 * sizeof(unsigned long long), ctx->stream));
     rtd::TraceParams tp = ctx->base;
     tp.W = W;
     tp.H = H;
@@ -2348,6 +2362,77 @@ int rt_unit_tile_masks_host(const rt_sphere* spheres, uint32_t n, const rt_camer
         for (uint32_t k = 0; k < n; ++k) group_of_sphere[k] = 0xffffffffu;
         for (uint32_t e = 0; e < (uint32_t)L.orig.size(); ++e)
             if (L.orig[e] < n) group_of_sphere[L.orig[e]] = e >> 2;
+    }
+    return RT_OK;
+}
+
+int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t cap_tiles, uint32_t* n_tiles, uint16_t* lists, uint64_t scans[3]) {
+    if (!ctx || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres: invalid argument");
+    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_tile_spheres: no scene uploaded");
+    const uint32_t rows = RowsetLocalRows(rs);
+    if (rows == 0 || (uint64_t)rs.first_row + rs.num_rows > H || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres: bad row set");
+    RT_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = BuildTileMasks(ctx, W, H, rs, W * rows)) != RT_OK) return rc;
+    *n_tiles = (ctx->tileMaskValid && ctx->maskSpheres != 0u) ? ctx->maskTiles : 0u;
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    if (lists && *n_tiles != 0u) {
+        if (cap_tiles < *n_tiles) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres: capacity too small");
+        RT_HIP(hipMemcpy(lists, ctx->tileSpheres.ptr, (size_t)*n_tiles * rtd::kTileSphereHalfs * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    }
+    if (scans) {
+        unsigned long long c[5] = {0, 0, 0, 0, 0};
+        RT_HIP(hipMemcpy(c, ctx->counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
+        scans[0] = ctx->freshScans;
+        scans[1] = c[3];
+        scans[2] = c[4];
+    }
+    return RT_OK;
+}
+
+int rt_unit_tile_spheres_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t mask_limit,
+                              uint32_t sphere_limit, uint32_t cap_tiles, uint32_t* n_tiles, uint16_t* lists, uint32_t* entry_of_sphere) {
+    if (!spheres || n == 0 || !camera || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres_host: invalid argument");
+    const uint32_t rows = RowsetLocalRows(rs);
+    if (rows == 0 || (uint64_t)rs.first_row + rs.num_rows > H || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres_host: bad row set");
+    if (sphere_limit > rtd::kTileSphereMax) sphere_limit = rtd::kTileSphereMax;
+    SceneLayout L;
+    BuildLayout(spheres, n, TreeTopFromEnv(), L);
+    const uint32_t nTop = L.levelCnt[L.nLevels - 1];
+    const uint32_t nFull = (W * rows) >> 6;
+    *n_tiles = (L.nLevels == 1 && !L.gridOn && nTop <= 128u && sphere_limit != 0u) ? nFull : 0u;
+    if (entry_of_sphere) {
+        for (uint32_t k = 0; k < n; ++k) entry_of_sphere[k] = 0xffffffffu;
+        for (uint32_t e = 0; e < (uint32_t)L.orig.size(); ++e)
+            if (L.orig[e] < n) entry_of_sphere[L.orig[e]] = e;
+    }
+    if (*n_tiles == 0u || !lists) return RT_OK;
+    if (cap_tiles < nFull) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres_host: capacity too small");
+    const rtd::TileMaskCam c = rtd::tile_mask_cam(camera->origin, camera->x, camera->y, camera->origin_image_plane, camera->aperture, camera->focal_length, W, H);
+    std::vector<int> reached(nTop);
+    for (uint32_t t = 0; t < nFull; ++t) {
+        uint16_t* rec = lists + (size_t)rtd::kTileSphereHalfs * t;
+        for (uint32_t k = 0; k < rtd::kTileSphereHalfs; ++k) rec[k] = 0;
+        bool bad = false;
+        uint32_t cnt = 0;
+        for (uint32_t g = 0; g < nTop; ++g) {
+            const float4 B = L.tree[L.levelOff[L.nLevels - 1] + g];
+            const float b[4] = {B.x, B.y, B.z, B.w};
+            reached[g] = rtd::tile_group_reached(c, rs, t, b);
+            bad = bad || reached[g] < 0;
+            cnt += reached[g] > 0 ? 1u : 0u;
+        }
+        uint32_t nS = 0;
+        const bool masked = rtd::tile_mask_flags(bad, cnt, mask_limit) != 0u;
+        for (uint32_t e = 0; masked && e < 4u * nTop && e < (uint32_t)L.leaf.size() && nS <= sphere_limit; ++e) {
+            const float4 B = L.leaf[e];
+            const float b[4] = {B.x, B.y, B.z, B.w};
+            if (rtd::tile_entry_listed(c, rs, t, reached[e >> 2], L.orig[e], b)) {
+                if (nS < sphere_limit) rec[1u + nS] = (uint16_t)e;
+                ++nS;
+            }
+        }
+        rec[0] = (uint16_t)((masked && nS <= sphere_limit) ? nS : rtd::kTileSphereNone);
     }
     return RT_OK;
 }

@@ -704,7 +704,13 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                             if (tw < (p.npix_local >> 6)) {
                                 const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p.tile_order ? p.tile_order[tw] : tw));
                                 const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_masks[kTileMaskWords * tile + 4u]);
-                                if (flags & 1u) primTile = tile;
+                                if (flags & 1u) {
+                                    primTile = tile;
+                                    // bit 31: the tile has a sphere list as well (tile < 2^25: the strip has at most 2^31 pixels)
+                                    if (p.tile_spheres != nullptr &&
+                                        (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_spheres[(size_t)kTileSphereHalfs * tile]) != kTileSphereNone)
+                                        primTile = tile | 0x80000000u;
+                                }
                             }
                         }
                     }
@@ -871,6 +877,11 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             // every lane takes part: lane l also supplies operands for, and filters half the spheres of,
             // the ray owned by lane l^32, whether or not its own ray is live
             const uint32_t* tileMask = nullptr;
+            if (kPrim && primTile != 0xffffffffu && (primTile & 0x80000000u) != 0u) {
+                // the tile's sphere list: every lane tests its own ray against the listed spheres (rt_scan.h scan_tile_spheres)
+                if (lane == 0) __hip_atomic_fetch_add(&ldsK->prim_direct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                scan_tile_spheres(scanTab, origTab, p.tile_spheres + (size_t)kTileSphereHalfs * (primTile & 0x7fffffffu), ro, rd, live, tmin, idx, lane);
+            } else {
             if (kPrim && primTile != 0xffffffffu) {
                 tileMask = p.tile_masks + kTileMaskWords * primTile;
                 // statistics (rt_unit_tile_masks): one LDS add per masked scan into the workgroup's constants block -- no register
@@ -879,6 +890,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             }
             scan_list_mfma<kScan == 2, kPrim>(scanTab, leafTab, origTab, mfmaOps, nTiles, nTop, treeTab, p.level_off, p.n_levels, p.bound_norm, p.single_mask, p.n_always, p.tree_box_on ? p.tree_box : nullptr, ro, rd,
                                        live, tmin, idx, waveCand, lane, dbgScan, tileMask);
+            }
         } else if (kScan == 3) {
             const GridParams G{gridCells, p.grid_nu, p.grid_nv, p.grid_ax_u, p.grid_ax_v, p.grid_g0u, p.grid_g0v, p.grid_inv_h, p.grid_rmax_over_h, p.grid_big_norm};
             const GridQuant Q{gridQ, p.grid_q[0], p.grid_q[1], p.grid_q[2], p.grid_q[3], p.grid_q[4], p.grid_q[5], p.grid_q[6], p.grid_q[7]};
@@ -988,7 +1000,12 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             // the wave that leaves last adds the workgroup's count of masked scans (every other wave's adds precede its ticket)
             const uint32_t ticket = __hip_atomic_fetch_add(&ldsK->exit_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
             if (ticket == (uint32_t)(kThreads / kWaveSize) - 1u)
-                atomicAdd(&p.counters[3], (unsigned long long)__hip_atomic_load(&ldsK->prim_masked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+            {
+                // (a directly resolved scan took its tile's tables as well: [3] counts both kinds, [4] the direct ones)
+                const unsigned long long nDirect = __hip_atomic_load(&ldsK->prim_direct, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                atomicAdd(&p.counters[3], nDirect + (unsigned long long)__hip_atomic_load(&ldsK->prim_masked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                atomicAdd(&p.counters[4], nDirect);
+            }
         }
 #ifdef RT_STAMPS
         atomicAdd(&g_dbg[0], cyRefill);
@@ -1143,7 +1160,10 @@ __global__ void __launch_bounds__(1024) rt_tile_order_kernel(const uint8_t* cls,
 // lane 0 writes the tile's eight words with two 16-byte stores.  A tile with more than `limit` candidate groups, or one the
 // construction does not apply to, gets flags = 0 and keeps the matrix-core filter.
 static_assert(kTileMaskPerRay == 2.0 * (double)kMarginRel, "the masks bound the filter's own per-ray margin");
-__global__ void __launch_bounds__(256) rt_tile_mask_kernel(const TraceParams p, uint32_t nFull, uint32_t limit, uint32_t* __restrict__ words) {
+// Sphere lists (rt_tile_mask.h; lists may be null): the lanes then test the member entries of the candidate groups, 64 entries a round
+// in ascending order, and append the listed ones behind the record's count (ballot + prefix offsets).
+__global__ void __launch_bounds__(256) rt_tile_mask_kernel(const TraceParams p, uint32_t nFull, uint32_t limit, uint32_t* __restrict__ words,
+                                                           uint32_t sphLimit, uint16_t* __restrict__ lists) {
     const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (tile >= nFull) return;  // wave-uniform
     RT_SITE(T_MASK);
@@ -1171,6 +1191,27 @@ __global__ void __launch_bounds__(256) rt_tile_mask_kernel(const TraceParams p, 
         uint4* w = reinterpret_cast<uint4*>(words + (size_t)kTileMaskWords * tile);
         w[0] = make_uint4(wordA(m0), wordA(m1), wordB(m0), wordB(m1));
         w[1] = make_uint4(tile_mask_flags(bad, cnt, limit), cnt, 0u, 0u);
+    }
+    if (lists != nullptr) {  // wave-uniform
+        RT_SITE(T_SPHERES);
+        uint16_t* rec = lists + (size_t)kTileSphereHalfs * tile;
+        const bool masked = tile_mask_flags(bad, (uint32_t)(__popcll(m0) + __popcll(m1)), limit) != 0u && sphLimit != 0u && sphLimit <= kTileSphereMax;
+        uint32_t nS = 0;
+        for (uint32_t e0 = 0; masked && e0 < 4u * nTop && nS <= sphLimit; e0 += 64u) {
+            const uint32_t e = e0 + lane, g = e >> 2;
+            bool in = false;
+            if (g < nTop && e < p.n_padded) {
+                const int gr = (int)(((g < 64u ? m0 : m1) >> (g & 63u)) & 1ull);
+                const float4 B = p.leaf[e];
+                const float b[4] = {B.x, B.y, B.z, B.w};
+                in = tile_entry_listed(c, p.rs, tile, gr, p.orig[e], b);
+            }
+            const uint64_t m = __ballot(in);
+            const uint32_t at = nS + prefix_count(m);
+            if (in && at < sphLimit) rec[1u + at] = (uint16_t)e;
+            nS += (uint32_t)__popcll(m);
+        }
+        if (lane == 0) rec[0] = (uint16_t)((masked && nS <= sphLimit) ? nS : kTileSphereNone);
     }
 }
 

@@ -479,6 +479,69 @@ RT_DEV bool next_candidate(unsigned long long& cur, unsigned long long& nxt, uin
     return true;
 }
 
+// Direct resolve of one tile's 64 primary rays (rt_tile_mask.h sphere lists; flat scan of the hit-stash kernels).  Every ray of the
+// wave faces the SAME short list of spheres, known before the rays exist, so there is nothing to pool: lane k loads the k-th listed
+// entry's record once, the wave-uniform loop broadcasts it with v_readlane, and every lane runs Sphere::Intersect (ray-tracing.cpp:
+// 44-71) for its OWN ray on register operands -- the statements of the pooled exact phase (exactPair below: same operation order,
+// sqrt_rn, pooled_root's two div_rn under the same range guard and the same fallback, with recip_rn(a) taken once per ray) -- and
+// keeps the closest hit as a running minimum of the pooled merge's 64-bit key (t bits, original index, entry): smaller t wins, equal
+// t keeps the lower original index, as there.  A sphere for which no ray of the wave can have a root (root_possible: exact) costs
+// the discriminant only.  No LDS, no ds_bpermute, no per-lane loops.
+RT_DEV void scan_tile_spheres(const float4* __restrict__ tab, const uint32_t* __restrict__ orig, const uint16_t* __restrict__ rec, V3 o, V3 d, bool live,
+                              float& tmin, int& idx, uint32_t lane) {
+    RT_SITE(S_DIRECT);
+    const float a = dot3(d, d);
+    tmin = __builtin_inff();
+    idx = -1;
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec[0]);  // <= 63 (rt_tile_mask.h kTileSphereMax)
+    const uint32_t ent = lane < n ? (uint32_t)rec[1u + lane] : 0u;
+    const float4 S = tab[ent];
+    const uint32_t low = (orig[ent] << 16) | ent;
+#if RT_MARKSTEIN && RT_EXACT_MARKSTEIN
+    const bool aOk = (__float_as_uint(a) - 0x36000000u) <= 0x3b800000u;  // pooled_root's guard: its per-ray part ...
+    const float ya = recip_rn(a);
+#endif
+    unsigned long long best = ~0ull;
+    for (uint32_t k = 0; k < n; ++k) {
+        RT_SITE(S_DIRECT_STEP);
+        const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(S.x), (int)k));
+        const float sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(S.y), (int)k));
+        const float sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(S.z), (int)k));
+        const float sw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(S.w), (int)k));
+        const float ocx = o.x - sx;
+        const float ocy = o.y - sy;
+        const float ocz = o.z - sz;
+        const float b = (ocx * d.x + ocy * d.y) + ocz * d.z;
+        const float cc = ((ocx * ocx + ocy * ocy) + ocz * ocz) - sw;
+        const float e = b * b - a * cc;
+        if (__ballot(live && root_possible(e, b)) == 0ull) continue;  // no ray of the tile has a root in this sphere
+        RT_SITE(S_DIRECT_ROOT);
+        const float sq = sqrt_rn(e > 0.f ? e : 1.f);  // (a root is read only where e > 0: the other lanes keep the wave on the fast path)
+        float t;
+#if RT_MARKSTEIN && RT_EXACT_MARKSTEIN
+        const bool ok = aOk && (__builtin_fabsf(b) + sq) < 0x1p100f;  // ... and its per-pair part
+        if (__builtin_expect(__ballot(!ok) == 0ull, 1)) {
+            t = div_rn(-b - sq, a, ya);
+            if (!(t > 0.001f)) t = div_rn(-b + sq, a, ya);
+        } else
+#endif
+        {
+            RT_SITE(M_ROOT_SLOW);
+            t = (-b - sq) / a;                       // ray-tracing.cpp:56
+            if (!(t > 0.001f)) t = (-b + sq) / a;    // :69
+        }
+        // `e > 0` is the reference's own test (ray-tracing.cpp:54); `t < inf` is the scan's initial tmin
+        const uint32_t lowK = (uint32_t)__builtin_amdgcn_readlane((int)low, (int)k);
+        const unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)lowK;
+        if (live && e > 0.f && t > 0.001f && t < __builtin_inff() && key < best) best = key;
+    }
+    const uint32_t tb = (uint32_t)(best >> 32);
+    if (tb < 0x7f800000u) {
+        tmin = __uint_as_float(tb);
+        idx = (int)(best & 0xffffull);
+    }
+}
+
 // kPrim (flat scan of the hit-stash kernels only): tileMask, when not null, points to the four candidate words of the tile whose
 // 64 primary rays this scan holds (rt_tile_mask.h: a superset of every group a primary ray of that tile can have a root in, laid
 // out as cw0..cw3 below).  The scan then takes them in place of the filter's result -- no operand build, no matrix-core pass, no

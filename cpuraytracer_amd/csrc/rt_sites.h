@@ -15,7 +15,7 @@ namespace rtd {
     X(H_SQ_ROOTS) X(H_SQ_FULL) X(H_SHADE) X(H_INDEXED) X(H_FARHIT) X(S_SCAN) X(S_TILEPAIR) X(S_SINGLE) \
     X(S_SINGLE_PUSH0) X(S_SINGLE_PUSH1) X(S_PASS) X(S_TAKE) X(S_PUSH_WORD) X(S_TAKE_PUSH0) X(S_TAKE_PUSH1) X(S_ASTEP) X(S_ASTEP2) X(S_APUSH) X(S_DRAIN) X(S_BSTEP) X(S_BSTEP2) X(S_BMIN) \
     X(G_SCAN) X(G_DRAIN) X(G_BSTEP) X(G_BMIN) X(G_BIG) X(G_BIGPUSH) X(G_FEED) X(G_FEED_LANE) X(G_ROUND) X(G_STEP) X(G_PUSH) \
-    X(K_GEN_TILE) X(S_MASKED) X(T_MASK)
+    X(K_GEN_TILE) X(S_MASKED) X(T_MASK) X(T_SPHERES) X(S_DIRECT) X(S_DIRECT_STEP) X(S_DIRECT_ROOT)
 enum RtSite : uint32_t {
 #define RT_SITE_ENUM(n) SITE_##n,
     RT_SITE_LIST(RT_SITE_ENUM)

@@ -173,6 +173,29 @@ RT_DEV int tile_group_reached(const TileMaskCam& c, const rt_rowset& rs, uint32_
     return reached;
 }
 
+// ---------------------------------------------------------------- per-tile sphere lists (DESIGN.md §5.2 "sphere lists")
+// For a tile with a mask, the SCAN ENTRIES (spheres, not groups) a primary ray of the tile can reach: the same cone test on the
+// entry's one-sphere bound, which is the sphere-level filter's own (rt_scan.h kMarginKLeaf: centre, |c|^2 - rf^2 with the exact
+// path's rounding folded into rf), with the per-ray term and the geometric slack of tile_group_radius -- whose per-ray term is the
+// group level's 2 * 4096 eps |o|^2, above the one-sphere level's 2 * 64 eps |o|^2.  Only members of the tile's candidate groups are
+// tested (a sphere with an accepted root has its group's bit set: the masks' soundness) and padding entries (orig = 0xffffffff)
+// are never listed.  The scan of such a tile tests each of its 64 rays against the listed spheres directly (rt_scan.h
+// scan_tile_spheres) -- no candidate words, no pooled resolve.  A record is kTileSphereHalfs 16-bit values, 128 bytes: [0] = the
+// count, or kTileSphereNone (no list: no mask, or more spheres than the limit); [1 + k] = the k-th entry, ascending.
+constexpr uint32_t kTileSphereHalfs = 64;
+constexpr uint32_t kTileSphereMax = kTileSphereHalfs - 1u;  // the most a record holds (and a lane per entry in the scan)
+constexpr uint32_t kTileSphereNone = 0xffffu;
+// Tiles with more listed spheres than this keep the masked pooled resolve.  Measured (profiles/primary_spheres_ab.txt; ms of C2 / C4,
+// parent 11.74 / 100.04): limit 0 (off): 11.79 / 100.41, 8: 11.01 / 94.46, 16: 10.57 / 90.67, 24: 10.48 / 89.03, 32: 10.48 / 88.96,
+// 63: 10.50 / 88.87.  The direct loop costs ~45 issue slots per listed sphere at 64 of 64 lanes, so long lists still beat the pools.
+constexpr uint32_t kTileSphereLimitDefault = 24;
+
+// Is scan entry e (one-sphere bound lb, original index og) listed for the tile?  groupReached: tile_group_reached of its group.
+RT_DEV bool tile_entry_listed(const TileMaskCam& c, const rt_rowset& rs, uint32_t tile, int groupReached, uint32_t og, const float lb[4]) {
+    if (groupReached <= 0 || og == 0xffffffffu) return false;
+    return tile_group_reached(c, rs, tile, lb) != 0;
+}
+
 // Where group g sits in the scan's candidate words (rt_scan.h: bit N from the top of word k is group kBase[k] + N + (N & 16),
 // kBase = 0, 64, 16, 80).
 RT_DEV void tile_mask_slot(uint32_t g, uint32_t& word, uint32_t& bit) {

@@ -291,6 +291,17 @@ int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
 /* ... the same masks evaluated on the host from the same source (candidate limit given).  Needs no GPU. */
 int rt_unit_tile_masks_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t limit,
                             uint32_t cap_tiles, uint32_t* n_tiles, uint32_t* words, uint32_t* group_of_sphere);
+/* Sphere lists of the tiles' primary rays (csrc/rt_tile_mask.h), as the device built them for the strip rs of a W x H image under the
+ * current RT_PRIMARY_MASK_LIMIT / RT_PRIMARY_SPHERES: 64 16-bit values per full tile, [0] = the number of listed scan entries or
+ * 0xffff (the tile has no list: no mask, or more reachable spheres than the limit), [1 + k] = the k-th listed scan entry, ascending.
+ * A tile with a list resolves the scan of its 64 fresh primary rays directly against the listed spheres.  *n_tiles = 0: no lists
+ * (this scene / these settings).  scans (may be null): [0] blocks of 64 fresh paths, [1] scans that took a tile's mask or list (as
+ * rt_unit_tile_masks reports), [2] those resolved directly from a sphere list, in the last rt_render that launched a trace kernel of its own. */
+int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t cap_tiles, uint32_t* n_tiles, uint16_t* lists, uint64_t scans[3]);
+/* ... the same lists evaluated on the host from the same source (both limits given).  entry_of_sphere (by original sphere index, may be
+ * null): the scan entry of each sphere.  Needs no GPU. */
+int rt_unit_tile_spheres_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t mask_limit,
+                              uint32_t sphere_limit, uint32_t cap_tiles, uint32_t* n_tiles, uint16_t* lists, uint32_t* entry_of_sphere);
 /* ... and the cone of the primary rays of pixels i0..i1 of row j: out = camera origin 3, axis D = Fc - origin 3, rhoL, rhoF, valid.
  * Every point (1 - l) O + l F of such a ray lies within |1 - l| rhoL + l rhoF of origin + l D.  Needs no GPU. */
 int rt_unit_tile_cone(const rt_camera* camera, uint32_t W, uint32_t H, uint32_t i0, uint32_t i1, uint32_t j, double out[9]);
