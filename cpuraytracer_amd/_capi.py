@@ -47,6 +47,7 @@ MATERIAL_DTYPE = np.dtype([("type", "<u4"), ("tex_type", "<u4"), ("smoothness", 
 
 RT_OK = 0
 RT_ERR_NO_DEVICE = 1
+RT_ERR_SEQUENCE = 6
 RT_SAMPLER_COSINE_HEMISPHERE, RT_SAMPLER_SQRT_DISK = 1, 2
 
 # every symbol include/rt_api.h declares
@@ -56,6 +57,7 @@ EXPORTS = [
     "rt_synchronize", "rt_rowset_local_rows", "rt_rowset_global_row", "rt_unit_halton", "rt_unit_math",
     "rt_unit_primary_rays", "rt_unit_closest_hit", "rt_unit_trace", "rt_unit_camera_rays", "rt_unit_scatter", "rt_unit_tonemap", "rt_unit_layout", "rt_unit_layout_info", "rt_unit_grid_rows",
     "rt_unit_tile_masks", "rt_unit_tile_masks_host", "rt_unit_tile_cone", "rt_unit_tile_spheres", "rt_unit_tile_spheres_host",
+    "rt_set_noise_estimate", "rt_download_moments", "rt_noise_map", "rt_noise_summary", "rt_unit_noise_estimate_host",
 ]
 
 _lib = None
@@ -126,6 +128,12 @@ def load():
         L.rt_unit_tile_spheres.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
         L.rt_unit_tile_spheres_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtCamera), C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.c_uint32,
                                                 C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
+    if hasattr(L, "rt_set_noise_estimate"):
+        L.rt_set_noise_estimate.argtypes = [C.c_void_p, C.c_int]
+        L.rt_download_moments.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_noise_map.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+        L.rt_noise_summary.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float)]
+        L.rt_unit_noise_estimate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
     _lib = L
     return L
 

@@ -14,14 +14,22 @@ static void Usage() {
               "               [--scene cover|three|grid10k] [--scene-seed N] [--seed N] [--device N] [--gpus N] [--out file.ppm] [--quiet]\n"
               "               [--sampler reference|cosine|sqrtdisk|cosine+sqrtdisk]   (default: the reference's mappings)\n"
               "               [--pipeline N]   frames in flight for quiet progressive runs (--frame-spp 1 --quiet); 0 = off\n"
-              "               [--batch N]      quiet progressive frames rendered per launch (rt_set_frame_batch); 1 = off");
+              "               [--batch N]      quiet progressive frames rendered per launch (rt_set_frame_batch); 1 = off\n"
+              "               [--noise-out file.pfm]   per-pixel standard error of the image (HDR units) as a one-channel PFM, rows top to bottom\n"
+              "               [--target-error T [--target-fraction F] [--max-spp N]]   render --frame-spp samples at a time until at most the\n"
+              "                                fraction F (default 0) of the pixels has a relative error above T, or N (default --spp) is reached\n"
+              "               [--noise-floor F]        added to a pixel's r + g + b before the relative error divides by it (default 0.01)");
 }
 
 int main(int argc, char** argv) {
     AppSettingsT st;
     uint32_t spp = 16;
     int device = 0, gpus = 0;
-    std::string out = "out.ppm";
+    std::string out = "out.ppm", noiseOut;
+    float targetError = 0.f;
+    double targetFraction = 0.0;
+    uint32_t maxSpp = 0;
+    bool targetSet = false;
     bool quiet = false, fovSet = false, apSet = false;
     for (int a = 1; a < argc; ++a) {
         const std::string k = argv[a];
@@ -45,6 +53,11 @@ int main(int argc, char** argv) {
         else if (k == "--quiet") quiet = true;
         else if (k == "--pipeline") st.framesInFlight = (uint32_t)std::atoi(val());
         else if (k == "--batch") st.framesPerLaunch = (uint32_t)std::atoi(val());
+        else if (k == "--noise-out") noiseOut = val();
+        else if (k == "--target-error") { targetError = (float)std::atof(val()); targetSet = true; }
+        else if (k == "--target-fraction") targetFraction = std::atof(val());
+        else if (k == "--max-spp") maxSpp = (uint32_t)std::atoi(val());
+        else if (k == "--noise-floor") st.noiseFloor = (float)std::atof(val());
         else if (k == "--sampler") {
             const std::string v = val();
             st.samplerFlags = (v.find("cosine") != std::string::npos ? RT_SAMPLER_COSINE_HEMISPHERE : 0u) |
@@ -59,6 +72,15 @@ int main(int argc, char** argv) {
     }
     if (st.samplesPerFrame == 0 || spp == 0 || st.k_backbufferWidth <= 0 || st.k_backbufferHeight <= 0) { Usage(); return 2; }
     if (spp % st.samplesPerFrame != 0) st.samplesPerFrame = 1;
+    st.noiseEstimate = targetSet || !noiseOut.empty();
+    if (st.noiseEstimate && gpus > 0) {
+        std::fprintf(stderr, "spheres: --noise-out and --target-error are not available with --gpus: the multi-GPU gather carries no second moments\n");
+        return 2;
+    }
+    if (targetSet) {
+        if (maxSpp == 0) maxSpp = spp;
+        if (!(targetError > 0.f) || !(targetFraction >= 0.0) || maxSpp < 2 || maxSpp < st.samplesPerFrame) { Usage(); return 2; }
+    }
     if (gpus > 0) {  // rows sharded over `gpus` devices, RCCL gather to device 0
         MultiGpuResult res;
         std::string err;
@@ -87,8 +109,13 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "spheres: %s\n", e.what());
         return 1;
     }
-    const int rc = app.Run(spp / st.samplesPerFrame);
+    const int rc = targetSet ? app.RunUntil(targetError, targetFraction, maxSpp) : app.Run(spp / st.samplesPerFrame);
     if (rc != 0) return rc;
+    if (!noiseOut.empty() && !app.WriteNoisePFM(noiseOut)) {
+        std::fprintf(stderr, "spheres: cannot write %s: %s\n", noiseOut.c_str(), rt_last_error());
+        return 1;
+    }
+    if (targetSet) std::printf("{\"target_error\": %g, \"target_fraction\": %g, \"spp_reached\": %zu}\n", (double)targetError, targetFraction, app.SampleCount());
     if (!app.WritePPM(out)) {
         std::fprintf(stderr, "spheres: cannot write %s\n", out.c_str());
         return 1;

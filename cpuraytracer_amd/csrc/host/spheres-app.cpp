@@ -169,6 +169,7 @@ size_t SpheresApp::DrawBitmap() {  // spheres-app.cpp:163-222
         RT_CALL(rt_scene_upload(m_device, spheres.data(), materials.data(), (uint32_t)spheres.size(), &camera, lights.data(), (uint32_t)lights.size(), &sky,
                                 exposureAdjustment));
         RT_CALL(rt_set_sampler(m_device, AppSettings.samplerFlags));
+        RT_CALL(rt_set_noise_estimate(m_device, AppSettings.noiseEstimate ? 1 : 0));
         RT_CALL(rt_set_frame_pipelining(m_device, AppSettings.framesInFlight));
         RT_CALL(rt_set_frame_batch(m_device, AppSettings.framesPerLaunch ? AppSettings.framesPerLaunch : 1u));
         m_uploaded = true;
@@ -200,6 +201,41 @@ bool SpheresApp::WritePPM(const std::string& path) const {
     const bool ok = std::fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
     std::fclose(f);
     return ok;
+}
+
+bool SpheresApp::WriteNoisePFM(const std::string& path) const {
+    const uint32_t W = (uint32_t)GetBackBufferWidth();
+    const uint32_t rows = m_lastStats.local_rows;
+    std::vector<float> map((size_t)W * rows * 2), abs((size_t)W * rows);
+    if (rt_noise_map(m_device, AppSettings.noiseFloor, map.data()) != RT_OK) return false;
+    for (size_t p = 0; p < abs.size(); ++p) abs[p] = map[2 * p];
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::fprintf(f, "Pf\n%u %u\n-1.0\n", W, rows);
+    const bool ok = std::fwrite(abs.data(), sizeof(float), abs.size(), f) == abs.size();
+    std::fclose(f);
+    return ok;
+}
+
+int SpheresApp::RunUntil(float relError, double fraction, uint32_t maxSpp) noexcept {
+    try {
+        const uint32_t step = AppSettings.samplesPerFrame;
+        for (;;) {
+            m_lastFrame = true;
+            OnRender();
+            if (m_sampleCount >= 2) {
+                uint32_t above = 0;
+                RT_CALL(rt_noise_summary(m_device, AppSettings.noiseFloor, &relError, 1, &above, nullptr));
+                const double npix = (double)GetBackBufferWidth() * m_lastStats.local_rows;
+                if ((double)above / npix <= fraction) break;
+            }
+            if (m_sampleCount + step > maxSpp) break;
+        }
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "spheres: %s\n", e.what());
+        return 1;
+    }
+    return 0;
 }
 
 void SpheresApp::DisplayStats(const size_t rayCount, const double timeElapsed) const {  // spheres-app.cpp:259-272 -> stdout JSON

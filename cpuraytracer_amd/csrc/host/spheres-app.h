@@ -28,6 +28,8 @@ struct AppSettingsT {
     uint32_t framesInFlight = 0;  // rt_set_frame_pipelining: frames whose unfinished paths may ride along into later frames (0 = off)
     uint32_t framesPerLaunch = 1; // rt_set_frame_batch: quiet frames rendered per launch (1 = off)
     uint32_t samplerFlags = 0;    // RT_SAMPLER_* (rt_api.h): 0 = the reference's uniform hemisphere and linear-r lens disk
+    bool noiseEstimate = false;   // rt_set_noise_estimate: keep the second moments (--noise-out, --target-error)
+    float noiseFloor = 0.01f;     // floor of the relative error (rt_noise_map)
 };
 
 class RayTracingApp {  // app.h:5-30 without the window
@@ -59,6 +61,11 @@ public:
     void DescribeScene(std::vector<rt_sphere>& spheres, std::vector<rt_material>& materials, rt_camera& camera, std::vector<rt_light>& lights,
                        rt_material& sky, float& exposureScale) const;
     bool WritePPM(const std::string& path) const;
+    // The absolute noise map (rt_noise_map, channel 0) as a single-channel little-endian PFM; rows top to bottom, as in the PPM.
+    bool WriteNoisePFM(const std::string& path) const;
+    // Frames of samplesPerFrame samples until at most `fraction` of the pixels have a relative error above relError, or the next
+    // frame would pass maxSpp (every frame waits for its summary, so every frame is resolved).  SampleCount() is the spp reached.
+    int RunUntil(float relError, double fraction, uint32_t maxSpp) noexcept;
     const std::vector<XMVECTOR>& Hdr() const { return m_backbufferHdr; }
     const std::vector<XMCOLOR>& Ldr() const { return m_backbufferLdr; }
     size_t SampleCount() const { return m_sampleCount; }

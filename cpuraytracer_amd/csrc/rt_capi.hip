@@ -115,6 +115,10 @@ struct rt_ctx {
     uint32_t accumulated = 0;  // samples accumulated so far (next s0 must be accumulated + 1)
     uint32_t sampler = 0;      // RT_SAMPLER_* flags of the next / running accumulation (rt_set_sampler)
     DevBuf<float> hdr;         // [W*rows*3]
+    bool noise = false;        // rt_set_noise_estimate: the next / running accumulation keeps second moments
+    DevBuf<float> sq;          // [W*rows*3] sums of squared samples, valid with hdr while noise is on (rt_noise.h)
+    DevBuf<float> noiseMap;    // [W*rows*2] output of rt_noise_map
+    DevBuf<uint32_t> noiseRed; // [kNoiseMaxThresholds + 1] counts and maximum of rt_noise_summary
     DevBuf<uint8_t> ldr;       // [W*rows*3]
     DevBuf<float> samples;     // workspace [pixels*spp_pass*3]
     DevBuf<uint32_t> queue;    // [1]
@@ -1424,6 +1428,9 @@ void rt_destroy(rt_ctx* ctx) {
     ctx->mats.Release();
     ctx->mats16.Release();
     ctx->hdr.Release();
+    ctx->sq.Release();
+    ctx->noiseMap.Release();
+    ctx->noiseRed.Release();
     ctx->ldr.Release();
     ctx->samples.Release();
     ctx->queue.Release();
@@ -1736,6 +1743,19 @@ int rt_set_sampler(rt_ctx* ctx, uint32_t flags) {
     return RT_OK;
 }
 
+int rt_set_noise_estimate(rt_ctx* ctx, int on) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_set_noise_estimate: null ctx");
+    const bool want = on != 0;
+    if (want != ctx->noise) {
+        ctx->pendOn = false;   // as rt_set_sampler: pending frames go with the accumulation they belonged to
+        ctx->aheadValid = false;
+        ctx->accumulated = 0;  // a strip of moments cannot start in the middle: the next rt_render starts over
+        PipelineDrop(ctx);
+    }
+    ctx->noise = want;
+    return RT_OK;
+}
+
 int rt_clear(rt_ctx* ctx) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_clear: null ctx");
     ctx->pendOn = false;
@@ -1754,6 +1774,17 @@ uint32_t rt_rowset_global_row(rt_rowset rs, uint32_t lr) {
 
 static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t s0, uint32_t s1, uint32_t max_depth, uint64_t seed,
                      rt_stats* out_stats, uint32_t aheadEnd = 0);
+
+// The ordered accumulation of the planes [first, first + count) of the sample buffer: with rt_set_noise_estimate on, the kernel that
+// also adds their squares to the strip of second moments (same hdr bits); off, the plain one.
+static void LaunchAccumulate(rt_ctx* ctx, uint32_t npix, uint32_t spp, uint32_t first, uint32_t count) {
+    if (ctx->noise)
+        hipLaunchKernelGGL(rtd::rt_accumulate_moments_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr, ctx->hdr.ptr,
+                           ctx->sq.ptr, npix, spp, first, count);
+    else
+        hipLaunchKernelGGL(rtd::rt_accumulate_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr, ctx->hdr.ptr, npix,
+                           spp, first, count);
+}
 
 // Frame batching: render the pending sample planes with ONE launch (no statistics, nothing waits for the device).
 static int BatchFlush(rt_ctx* ctx) {
@@ -1793,8 +1824,7 @@ int rt_render(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t s0, ui
             ctx->aheadSeed == seed && s0 == ctx->aheadNext && s1 <= ctx->aheadBase + ctx->aheadSpp && ctx->accumulated + 1 == s0) {
             RT_HIP(hipSetDevice(ctx->device));
             const uint32_t npix = ctx->W * ctx->rows;
-            hipLaunchKernelGGL(rtd::rt_accumulate_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr, ctx->hdr.ptr, npix,
-                               ctx->aheadSpp, s0 - ctx->aheadBase, s1 - s0);
+            LaunchAccumulate(ctx, npix, ctx->aheadSpp, s0 - ctx->aheadBase, s1 - s0);
             RT_HIP(hipGetLastError());
             ctx->aheadNext = s1;
             ctx->accumulated += s1 - s0;
@@ -1847,7 +1877,8 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
 
     const bool sameStrip = ctx->W == W && ctx->H == H && ctx->rows == rows && std::memcmp(&ctx->rs, &rs, sizeof(rs)) == 0;
     // frame pipelining: only calls that ask for no statistics may leave work in flight; anything else first settles it
-    bool pipelined = ctx->pipeDepth > 0 && out_stats == nullptr;
+    // (the carrying kernel's commit adds no second moments: with rt_set_noise_estimate on every call renders unpipelined)
+    bool pipelined = ctx->pipeDepth > 0 && out_stats == nullptr && !ctx->noise;
     if (pipelined) {
         rtd::TraceParams probe = ctx->base;
         probe.total_paths = npix;
@@ -1864,6 +1895,10 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
         if ((rc = ctx->hdr.Reserve((size_t)npix * 3)) != RT_OK) return rc;
         if ((rc = ctx->ldr.Reserve((size_t)npix * 3)) != RT_OK) return rc;
         RT_HIP(hipMemsetAsync(ctx->hdr.ptr, 0, (size_t)npix * 3 * sizeof(float), ctx->stream));  // app.cpp:112-119
+        if (ctx->noise) {
+            if ((rc = ctx->sq.Reserve((size_t)npix * 3)) != RT_OK) return rc;
+            RT_HIP(hipMemsetAsync(ctx->sq.ptr, 0, (size_t)npix * 3 * sizeof(float), ctx->stream));
+        }
         ctx->W = W;
         ctx->H = H;
         ctx->rows = rows;
@@ -1959,8 +1994,7 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
             }
             if ((rc = LaunchTrace(ctx, tp)) != RT_OK) return rc;
             RT_HIP(hipEventRecord(ev[1], ctx->stream));
-            hipLaunchKernelGGL(rtd::rt_accumulate_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr,
-                               ctx->hdr.ptr, npix, spp, 0u, aheadEnd ? sppTotal : spp);
+            LaunchAccumulate(ctx, npix, spp, 0u, aheadEnd ? sppTotal : spp);
             RT_HIP(hipGetLastError());
             RT_HIP(hipEventRecord(ev[2], ctx->stream));
             ++passes;
@@ -2058,6 +2092,73 @@ int rt_copy_to_device(rt_ctx* ctx, void* dev_hdr_rgb, void* dev_ldr_rgb) {
     const size_t npix = (size_t)ctx->W * ctx->rows;
     if (dev_hdr_rgb) RT_HIP(hipMemcpyAsync(dev_hdr_rgb, ctx->hdr.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     if (dev_ldr_rgb) RT_HIP(hipMemcpyAsync(dev_ldr_rgb, ctx->ldr.ptr, npix * 3, hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------- noise estimate (rt_noise.h)
+// Like the other readers: a pending batch that starts the picture is rendered first; planes traced ahead never reached the strips.
+static int NoiseReady(rt_ctx* ctx, const char* who, uint32_t minSamples) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    if (!ctx->noise) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": rt_set_noise_estimate is off");
+    if (PendingMustRender(ctx)) {
+        const int rcb = BatchFlush(ctx);
+        if (rcb != RT_OK) return rcb;
+    }
+    if (ctx->accumulated == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": nothing accumulated");
+    if (ctx->accumulated < minSamples) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the estimate needs at least 2 samples per pixel");
+    RT_HIP(hipSetDevice(ctx->device));
+    return RT_OK;
+}
+
+int rt_download_moments(rt_ctx* ctx, float* sq_rgb) {
+    const int rc = NoiseReady(ctx, "rt_download_moments", 1);
+    if (rc != RT_OK) return rc;
+    if (!sq_rgb) return Fail(RT_ERR_INVALID_ARG, "rt_download_moments: null buffer");
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    RT_HIP(hipMemcpy(sq_rgb, ctx->sq.ptr, (size_t)ctx->W * ctx->rows * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_noise_map(rt_ctx* ctx, float floor, float* out_abs_rel) {
+    int rc = NoiseReady(ctx, "rt_noise_map", 2);
+    if (rc != RT_OK) return rc;
+    if (!out_abs_rel) return Fail(RT_ERR_INVALID_ARG, "rt_noise_map: null buffer");
+    const uint32_t npix = ctx->W * ctx->rows;
+    if ((rc = ctx->noiseMap.Reserve((size_t)npix * 2)) != RT_OK) return rc;
+    hipLaunchKernelGGL(rtd::rt_noise_map_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->hdr.ptr, ctx->sq.ptr, npix, ctx->accumulated,
+                       floor, reinterpret_cast<float2*>(ctx->noiseMap.ptr));
+    RT_HIP(hipGetLastError());
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    RT_HIP(hipMemcpy(out_abs_rel, ctx->noiseMap.ptr, (size_t)npix * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_noise_summary(rt_ctx* ctx, float floor, const float* thresholds, uint32_t n_thr, uint32_t* out_counts, float* out_max_rel) {
+    int rc = NoiseReady(ctx, "rt_noise_summary", 2);
+    if (rc != RT_OK) return rc;
+    if (n_thr > rtd::kNoiseMaxThresholds || (n_thr != 0 && (!thresholds || !out_counts)))
+        return Fail(RT_ERR_INVALID_ARG, "rt_noise_summary: at most 8 thresholds, with their buffers");
+    const uint32_t npix = ctx->W * ctx->rows;
+    rtd::NoiseThresholds thr{};
+    thr.n = n_thr;
+    for (uint32_t k = 0; k < n_thr; ++k) thr.t[k] = thresholds[k];
+    if ((rc = ctx->noiseRed.Reserve(rtd::kNoiseMaxThresholds + 1)) != RT_OK) return rc;
+    RT_HIP(hipMemsetAsync(ctx->noiseRed.ptr, 0, (rtd::kNoiseMaxThresholds + 1) * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(rtd::rt_noise_summary_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->hdr.ptr, ctx->sq.ptr, npix,
+                       ctx->accumulated, floor, thr, ctx->noiseRed.ptr);
+    RT_HIP(hipGetLastError());
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    uint32_t red[rtd::kNoiseMaxThresholds + 1];
+    RT_HIP(hipMemcpy(red, ctx->noiseRed.ptr, sizeof(red), hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < n_thr; ++k) out_counts[k] = red[k];
+    if (out_max_rel) std::memcpy(out_max_rel, &red[rtd::kNoiseMaxThresholds], sizeof(float));
+    return RT_OK;
+}
+
+int rt_unit_noise_estimate_host(const float* hdr, const float* sq, uint32_t npix, uint32_t n, float floor, float* out) {
+    if (!hdr || !sq || !out) return Fail(RT_ERR_INVALID_ARG, "rt_unit_noise_estimate_host: null argument");
+    if (n < 2) return Fail(RT_ERR_SEQUENCE, "rt_unit_noise_estimate_host: the estimate needs at least 2 samples per pixel");
+    for (uint32_t p = 0; p < npix; ++p) rtd::noise_estimate(hdr + 3 * (size_t)p, sq + 3 * (size_t)p, n, floor, out + 2 * (size_t)p);
     return RT_OK;
 }
 

@@ -39,6 +39,7 @@
 #include "rt_scan.h"
 #include "rt_shade.h"
 #include "rt_tile_mask.h"
+#include "rt_noise.h"
 
 namespace rtd {
 
@@ -1250,6 +1251,94 @@ __global__ void __launch_bounds__(256) rt_accumulate_kernel(const float* __restr
     hdr[3 * (size_t)pix] = r;
     hdr[3 * (size_t)pix + 1] = g;
     hdr[3 * (size_t)pix + 2] = b;
+}
+
+// ... and, with rt_set_noise_estimate on, the second moments beside it: sq[pixel] += RN(sample^2) for the same planes in the same
+// order (rt_noise.h).  Same addressing, same first / count, same eight planes in flight; hdr and sq are carried in registers and
+// written once.  The hdr arithmetic is rt_accumulate_kernel's statement for statement, so the strip has the same bits either way.
+__global__ void __launch_bounds__(256) rt_accumulate_moments_kernel(const float* __restrict__ samples, float* __restrict__ hdr,
+                                                                    float* __restrict__ sq, uint32_t npix, uint32_t spp, uint32_t first = 0,
+                                                                    uint32_t count = 0xffffffffu) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= npix) return;
+    float r = hdr[3 * (size_t)pix], g = hdr[3 * (size_t)pix + 1], b = hdr[3 * (size_t)pix + 2];
+    float qr = sq[3 * (size_t)pix], qg = sq[3 * (size_t)pix + 1], qb = sq[3 * (size_t)pix + 2];
+    const uint32_t nFull = npix >> 6, tile = pix >> 6;
+    const uint32_t stride = tile < nFull ? 64u : npix - (nFull << 6);
+    const float3* sp = reinterpret_cast<const float3*>(samples) + (size_t)tile * 64u * spp + (pix - (tile << 6));
+    uint32_t s = first < spp ? first : spp;
+    const uint32_t end = count > spp - s ? spp : s + count;
+    for (; s + 8 <= end; s += 8) {
+        float3 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = sp[(size_t)(s + k) * stride];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            r += v[k].x;
+            g += v[k].y;
+            b += v[k].z;
+            // the contract (rt_noise.h): the square rounds to binary32 FIRST, the add rounds second -- never an fmaf
+            qr = qr + (v[k].x * v[k].x);
+            qg = qg + (v[k].y * v[k].y);
+            qb = qb + (v[k].z * v[k].z);
+        }
+    }
+    for (; s < end; ++s) {
+        const float3 v = sp[(size_t)s * stride];
+        r += v.x;
+        g += v.y;
+        b += v.z;
+        qr = qr + (v.x * v.x);  // two roundings, as above
+        qg = qg + (v.y * v.y);
+        qb = qb + (v.z * v.z);
+    }
+    hdr[3 * (size_t)pix] = r;
+    hdr[3 * (size_t)pix + 1] = g;
+    hdr[3 * (size_t)pix + 2] = b;
+    sq[3 * (size_t)pix] = qr;
+    sq[3 * (size_t)pix + 1] = qg;
+    sq[3 * (size_t)pix + 2] = qb;
+}
+
+// ================================================================ noise estimate (rt_noise.h)
+// out[pixel] = (absolute, relative) standard error of the pixel mean after n samples
+__global__ void __launch_bounds__(256) rt_noise_map_kernel(const float* __restrict__ hdr, const float* __restrict__ sq, uint32_t npix, uint32_t n,
+                                                           float floor, float2* __restrict__ out) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= npix) return;
+    const float h[3] = {hdr[3 * (size_t)pix], hdr[3 * (size_t)pix + 1], hdr[3 * (size_t)pix + 2]};
+    const float q[3] = {sq[3 * (size_t)pix], sq[3 * (size_t)pix + 1], sq[3 * (size_t)pix + 2]};
+    float e[2];
+    noise_estimate(h, q, n, floor, e);
+    out[pix] = make_float2(e[0], e[1]);
+}
+// red[k] = pixels whose relative error is above thr.t[k] (k < thr.n), red[kNoiseMaxThresholds] = bit pattern of the largest finite
+// relative error.  Integer atomics only (a sum of counts, a maximum of non-negative floats' patterns): the answer does not depend
+// on the order the waves arrive in.  red is zeroed by the caller.
+__global__ void __launch_bounds__(256) rt_noise_summary_kernel(const float* __restrict__ hdr, const float* __restrict__ sq, uint32_t npix, uint32_t n,
+                                                               float floor, NoiseThresholds thr, uint32_t* __restrict__ red) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = pix < npix;
+    float rel = 0.f;
+    if (live) {
+        const float h[3] = {hdr[3 * (size_t)pix], hdr[3 * (size_t)pix + 1], hdr[3 * (size_t)pix + 2]};
+        const float q[3] = {sq[3 * (size_t)pix], sq[3 * (size_t)pix + 1], sq[3 * (size_t)pix + 2]};
+        float e[2];
+        noise_estimate(h, q, n, floor, e);
+        rel = e[1];
+    }
+    const uint32_t bits = __float_as_uint(rel);
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t k = 0; k < thr.n && k < kNoiseMaxThresholds; ++k) {
+        const uint32_t c = (uint32_t)__popcll(__ballot(live && noise_above(rel, bits, thr.t[k])));
+        if (lane == 0 && c != 0u) atomicAdd(&red[k], c);
+    }
+    uint32_t m = (live && noise_is_finite(bits)) ? bits : 0u;
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
+        m = o > m ? o : m;
+    }
+    if (lane == 0 && m != 0u) atomicMax(&red[kNoiseMaxThresholds], m);
 }
 
 // ================================================== ordered accumulation of pipelined regions (A16)

@@ -11,6 +11,11 @@ from . import _capi
 from ._capi import RtRowset, RtStats, check, whole_image
 
 
+# Default `floor` of the relative noise estimate: added to the pixel's mean (r + g + b, HDR units after exposure, where 1.0 per
+# channel is about display white) so that black pixels have a finite relative error.
+NOISE_FLOOR = 0.01
+
+
 class HipRenderer:
     """One context per device ordinal (rt_create).  Raises when no GPU is present."""
 
@@ -107,6 +112,49 @@ class HipRenderer:
 
     def synchronize(self):
         check(self._L.rt_synchronize(self._h))
+
+    # ---- noise estimate (rt_api.h "noise estimate")
+    def set_noise_estimate(self, on):
+        """rt_set_noise_estimate: the next accumulation keeps the strip of second moments (changing it voids a running one)."""
+        check(self._L.rt_set_noise_estimate(self._h, 1 if on else 0))
+
+    def download_moments(self):
+        """The sums of squared samples, (rows, W, 3) float32."""
+        q = np.zeros((self.rows, self.W, 3), dtype=np.float32)
+        check(self._L.rt_download_moments(self._h, q.ctypes.data))
+        return q
+
+    def noise_map(self, floor=NOISE_FLOOR):
+        """(rows, W, 2) float32: absolute and relative standard error of every pixel's mean."""
+        out = np.zeros((self.rows, self.W, 2), dtype=np.float32)
+        check(self._L.rt_noise_map(self._h, float(floor), out.ctypes.data))
+        return out
+
+    def noise_summary(self, thresholds, floor=NOISE_FLOOR):
+        """(counts, max_rel): counts[k] = pixels whose relative error is above thresholds[k] (at most 8; a non-finite error counts
+        for every threshold), max_rel = the largest finite relative error."""
+        thr = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+        counts = np.zeros(thr.shape[0], dtype=np.uint32)
+        mx = C.c_float(0.0)
+        check(self._L.rt_noise_summary(self._h, float(floor), thr.ctypes.data, thr.shape[0], counts.ctypes.data, C.byref(mx)))
+        return counts, mx.value
+
+    def render_until(self, W, H, max_depth, seed, rel_error, fraction=0.0, step_spp=8, max_spp=1024, floor=NOISE_FLOOR, rowset=None):
+        """Render `step_spp` sample planes at a time, from sample 1, until at most `fraction` of the pixels have a relative error
+        above `rel_error`, or the next step would pass `max_spp`.  Turns the noise estimate on; returns the spp reached."""
+        if step_spp < 1 or max_spp < max(step_spp, 2):
+            raise ValueError("render_until: step_spp must be 1..max_spp and max_spp at least 2 (the estimate needs two samples)")
+        self.set_noise_estimate(True)
+        spp = 0
+        while True:
+            self.render(W, H, spp + 1, spp + 1 + step_spp, max_depth, seed, rowset=rowset, stats=False)
+            spp += step_spp
+            if spp >= 2:
+                counts, _ = self.noise_summary([rel_error], floor=floor)
+                if int(counts[0]) / (self.W * self.rows) <= fraction:
+                    return spp
+            if spp + step_spp > max_spp:
+                return spp
 
     # ---- unit entries
     def unit_halton(self, index, base):

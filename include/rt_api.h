@@ -215,8 +215,36 @@ int rt_set_frame_lookahead(rt_ctx* ctx, uint32_t frames);
 /* Samples per pixel in the HDR strip right now (waits for the stream). */
 int rt_committed_samples(rt_ctx* ctx, uint32_t* out);
 
-/* Forget the accumulated HDR strip and sample count. */
+/* Forget the accumulated HDR strip and sample count (and, with rt_set_noise_estimate on, the strip of second moments). */
 int rt_clear(rt_ctx* ctx);
+
+/* ---------------------------------------------------------- noise estimate
+ * How converged is a pixel?  With the switch on, an accumulation keeps, next to the HDR strip, a strip sq of W*local_rows*3
+ * floats: for every sample plane added to hdr, in the same increasing-s order and for c in r, g, b,
+ *     sq[c] = sq[c] + (v[c] * v[c])      -- the product rounded to binary32 first, the add second, never fused.
+ * The HDR strip has the same bits with the switch on or off; off, exactly the kernels of before are launched.  Like rt_set_sampler
+ * the switch takes effect at the next accumulation (rt_render with s0 == 1) and changing it voids a running one; default off.
+ * rt_clear, a failed pass and rt_scene_upload void sq together with hdr.  Frame batching and render-ahead keep sq in step with hdr.
+ * FRAME PIPELINING WITH THE SWITCH ON RENDERS EVERY CALL UNPIPELINED (same results; the fallback large scenes already take): the
+ * carrying kernel's commit adds no second moments.  Moments are per context: a multi-GPU gather of sq is the caller's. */
+int rt_set_noise_estimate(rt_ctx* ctx, int on);
+/* Copy sq to host: W*local_rows*3 floats.  RT_ERR_SEQUENCE when the switch is off or nothing is accumulated. */
+int rt_download_moments(rt_ctx* ctx, float* sq_rgb);
+/* Per-pixel standard error of the accumulated MEAN after n = the samples in the strip (n >= 2, else RT_ERR_SEQUENCE; also when the
+ * switch is off or nothing is accumulated).  binary64, only + - * / and comparisons, in this order (DESIGN.md "Noise estimate"):
+ *     for c in r,g,b:  S = (double)hdr[c];  Q = (double)sq[c];  mean_c = S / n
+ *                      var_c = (Q - S * mean_c) / (n - 1);   if !(var_c > 0) var_c = 0
+ *     V = (var_r + var_g) + var_b;   M = (mean_r + mean_g) + mean_b;   abs2 = V / n;   d = M + (double)floor
+ *     out[0] = sqrt32((float)abs2)               standard error of the pixel mean, HDR units, channels summed
+ *     out[1] = sqrt32((float)(abs2 / (d * d)))   the same, relative to the pixel's brightness (floor keeps dark pixels finite)
+ * sqrt32 = the correctly rounded binary32 square root (rt_unit_math op 7).  out_abs_rel: 2 floats per pixel, host memory.  A pixel
+ * with M + floor == 0 gets a non-finite out[1] and is reported so (a NaN's sign and payload are unspecified).  Pending batches are
+ * settled as rt_resolve settles them; planes traced ahead are not in the strips. */
+int rt_noise_map(rt_ctx* ctx, float floor, float* out_abs_rel);
+/* Order-independent summary of that map's relative error: out_counts[k] = pixels with rel > thresholds[k] (n_thr <= 8; a non-finite
+ * rel counts as above every threshold), *out_max_rel = the largest finite rel (0 when there is none; may be NULL).  Reduced on the
+ * device with integer atomics only, so repeated calls give identical answers.  Same sequencing as rt_noise_map. */
+int rt_noise_summary(rt_ctx* ctx, float floor, const float* thresholds, uint32_t n_thr, uint32_t* out_counts, float* out_max_rel);
 
 /* Replaces the transform(par) tonemap (spheres-app.cpp:186-214): hdr / n_samples,
  * ACES fit, gamma 1/2.2, XMStoreColor.  n_samples == 0 uses the accumulated count. */
@@ -305,6 +333,9 @@ int rt_unit_tile_spheres_host(const rt_sphere* spheres, uint32_t n, const rt_cam
 /* ... and the cone of the primary rays of pixels i0..i1 of row j: out = camera origin 3, axis D = Fc - origin 3, rhoL, rhoF, valid.
  * Every point (1 - l) O + l F of such a ray lies within |1 - l| rhoL + l rhoF of origin + l D.  Needs no GPU. */
 int rt_unit_tile_cone(const rt_camera* camera, uint32_t W, uint32_t H, uint32_t i0, uint32_t i1, uint32_t j, double out[9]);
+/* The estimate of rt_noise_map for given strips (3 floats per pixel each), from the same source compiled for the host (csrc/rt_noise.h):
+ * out = 2 floats per pixel.  n < 2: RT_ERR_SEQUENCE.  Needs no GPU. */
+int rt_unit_noise_estimate_host(const float* hdr, const float* sq, uint32_t npix, uint32_t n, float floor, float* out);
 /* The resolve of spheres-app.cpp:196-214 for given HDR triples -> R,G,B bytes */
 int rt_unit_tonemap(rt_ctx* ctx, const float* hdr_rgb, uint32_t n, uint32_t n_samples, uint8_t* out_rgb);
 
