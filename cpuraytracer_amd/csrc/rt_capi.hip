@@ -220,6 +220,27 @@ struct SceneLayout {
     float gridQc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// The spheres as the bounds see them: radius |r|.  A negative radius is legal input (the reference's Sphere::Intersect tests r * r
+// and divides the normal by r: the inward normal of a hollow sphere), and the surface it describes is that of |r|.  Everything below
+// that ENCLOSES a sphere or compares sphere sizes (BoundOf, EnclosingRadius, BoxOf, the grid builder, the big-sphere split, the
+// shadow index) reads this copy; the scan entry's r * r has the same bits either way, and the radius table the normals divide by
+// is filled from the caller's signed radii (rt_scene_upload).
+static std::vector<rt_sphere> WithAbsRadii(const rt_sphere* sp, uint32_t n) {
+    std::vector<rt_sphere> out(sp, sp + n);
+    for (rt_sphere& s : out) s.r = std::fabs(s.r);
+    return out;
+}
+
+// A centre or a radius that is not finite: no bound can be built from it (rt_scene_upload refuses the scene).
+static bool AllFinite(const rt_sphere* sp, uint32_t n, uint32_t* which) {
+    for (uint32_t k = 0; k < n; ++k)
+        if (!std::isfinite(sp[k].cx) || !std::isfinite(sp[k].cy) || !std::isfinite(sp[k].cz) || !std::isfinite(sp[k].r)) {
+            if (which) *which = k;
+            return false;
+        }
+    return true;
+}
+
 // Conservative bounding sphere of a set of spheres, in the filter's (C, |C|^2 - Rf^2) form.
 static float4 BoundOf(const rt_sphere* sp, const std::vector<uint32_t>& ids, float* normOut, float marginK) {
     if (ids.empty()) return make_float4(0.f, 0.f, 0.f, 1e30f);  // never a candidate
@@ -553,7 +574,9 @@ static bool BuildGridLayout(const rt_sphere* sp, uint32_t n, const std::vector<u
     return true;
 }
 
-static void BuildLayout(const rt_sphere* sp, uint32_t n, uint32_t topMax, SceneLayout& L) {
+static void BuildLayout(const rt_sphere* signedSp, uint32_t n, uint32_t topMax, SceneLayout& L) {
+    const std::vector<rt_sphere> absSp = WithAbsRadii(signedSp, n);
+    const rt_sphere* sp = absSp.data();  // bounds enclose |r|
     std::vector<float> radii(n);
     for (uint32_t k = 0; k < n; ++k) radii[k] = sp[k].r;
     std::vector<float> sorted = radii;
@@ -689,8 +712,13 @@ struct ShadowGrid {
 // the cover scene); 256 for the scenes whose index stays in global memory (cell-grid and hierarchy scans, 10,000-sphere class): at
 // 64 x 64 a query of grid10k walked ~15 spheres -- 7 rounds of two dependent L2 reads -- at 256 x 256 (cells of about one
 // footprint) ~5.
-static void BuildShadowGrid(const rt_sphere* sp, const SceneLayout& L, const float sunDir[3], uint32_t maxCells, ShadowGrid& G) {
+static void BuildShadowGrid(const rt_sphere* signedSp, const SceneLayout& L, const float sunDir[3], uint32_t maxCells, ShadowGrid& G) {
     G = ShadowGrid{};
+    uint32_t nSp = 0;
+    for (uint32_t o : L.orig)
+        if (o != 0xffffffffu) nSp = std::max(nSp, o + 1u);
+    const std::vector<rt_sphere> absSp = WithAbsRadii(signedSp, nSp);
+    const rt_sphere* sp = absSp.data();  // footprints and the reach are those of |r|
     const double Lx = sunDir[0], Ly = sunDir[1], Lz = sunDir[2];
     const double ln = std::sqrt(Lx * Lx + Ly * Ly + Lz * Lz);
     if (!(ln > 0.5 && ln < 2.0)) return;  // not a direction: keep the scan
@@ -1519,6 +1547,9 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     // light 0 keeps the single-light kernel path's slots; an empty list is uploaded as one dark light that is never consulted
     const rt_light noLight{{0.f, 1.f, 0.f}, {0.f, 0.f, 0.f}, 0.f};
     const rt_light* sun = n_lights ? lights : &noLight;
+    uint32_t bad = 0;  // (refused before any side effect: pending frames stay pending, the previous scene stays)
+    if (!AllFinite(spheres, n, &bad))
+        return Fail(RT_ERR_INVALID_ARG, "rt_scene_upload: sphere " + std::to_string(bad) + " has a centre or a radius that is not finite");
     RT_HIP(hipSetDevice(ctx->device));
     int rc;
     if ((rc = BatchFlush(ctx)) != RT_OK) return rc;  // pending frames were asked of the scene that is being replaced
@@ -2356,6 +2387,7 @@ int rt_unit_tonemap(rt_ctx* ctx, const float* hdr_rgb, uint32_t n, uint32_t n_sa
 // (0xffffffff = padding), bounds: Cx, Cy, Cz, |C|^2 - Rf^2 per group.  Pass cap_groups = 0 to query the count.
 int rt_unit_layout(const rt_sphere* spheres, uint32_t n, uint32_t cap_groups, uint32_t* n_groups, uint32_t* orig, float* bounds) {
     if (!spheres || n == 0 || !n_groups) return Fail(RT_ERR_INVALID_ARG, "rt_unit_layout: invalid argument");
+    if (!AllFinite(spheres, n, nullptr)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_layout: a sphere's centre or radius is not finite");
     SceneLayout L;
     BuildLayout(spheres, n, TreeTopFromEnv(), L);
     *n_groups = L.nGroups;
@@ -2384,6 +2416,7 @@ int rt_unit_grid_rows(const float* segments, const int32_t* iu, uint32_t n, int3
 
 int rt_unit_layout_info(const rt_sphere* spheres, uint32_t n, uint32_t out[5]) {
     if (!spheres || n == 0 || !out) return Fail(RT_ERR_INVALID_ARG, "rt_unit_layout_info: invalid argument");
+    if (!AllFinite(spheres, n, nullptr)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_layout_info: a sphere's centre or radius is not finite");
     SceneLayout L;
     BuildLayout(spheres, n, TreeTopFromEnv(), L);
     out[0] = L.gridOn ? 1u : (L.nLevels > 1 ? 2u : 0u);
@@ -2391,6 +2424,25 @@ int rt_unit_layout_info(const rt_sphere* spheres, uint32_t n, uint32_t out[5]) {
     out[2] = L.gridOn ? L.gridNv : 0u;
     out[3] = L.nAlways;
     out[4] = L.nLevels;
+    return RT_OK;
+}
+
+int rt_unit_grid_info(const rt_sphere* spheres, uint32_t n, uint32_t out_u[5], float out_f[10], int32_t* home_cell) {
+    if (!spheres || n == 0 || !out_u || !out_f) return Fail(RT_ERR_INVALID_ARG, "rt_unit_grid_info: invalid argument");
+    if (!AllFinite(spheres, n, nullptr)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_grid_info: a sphere's centre or radius is not finite");
+    SceneLayout L;
+    BuildLayout(spheres, n, TreeTopFromEnv(), L);
+    out_u[0] = L.gridOn ? 1u : 0u;
+    if (!L.gridOn) return RT_OK;
+    out_u[1] = L.gridNu; out_u[2] = L.gridNv; out_u[3] = L.gridAxU; out_u[4] = L.gridAxV;
+    out_f[0] = L.gridG0u; out_f[1] = L.gridG0v; out_f[2] = L.gridInvH; out_f[3] = L.gridRmaxOverH;
+    for (int k = 0; k < 6; ++k) out_f[4 + k] = L.treeBox[k];
+    if (home_cell) {  // read back from the table the scan reads: entries [cellStart[c], cellStart[c + 1]) are cell c's spheres
+        for (uint32_t k = 0; k < n; ++k) home_cell[k] = -1;
+        for (uint32_t c = 0; c < L.gridNu * L.gridNv; ++c)
+            for (uint32_t e = L.gridCellStart[c]; e < L.gridCellStart[c + 1]; ++e)
+                if (L.orig[e] < n) home_cell[L.orig[e]] = (int32_t)c;
+    }
     return RT_OK;
 }
 
@@ -2429,6 +2481,7 @@ int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
 int rt_unit_tile_masks_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t limit,
                             uint32_t cap_tiles, uint32_t* n_tiles, uint32_t* words, uint32_t* group_of_sphere) {
     if (!spheres || n == 0 || !camera || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks_host: invalid argument");
+    if (!AllFinite(spheres, n, nullptr)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks_host: a sphere's centre or radius is not finite");
     const uint32_t rows = RowsetLocalRows(rs);
     if (rows == 0 || (uint64_t)rs.first_row + rs.num_rows > H || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks_host: bad row set");
     SceneLayout L;
@@ -2494,6 +2547,7 @@ int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint
 int rt_unit_tile_spheres_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t mask_limit,
                               uint32_t sphere_limit, uint32_t cap_tiles, uint32_t* n_tiles, uint16_t* lists, uint32_t* entry_of_sphere) {
     if (!spheres || n == 0 || !camera || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres_host: invalid argument");
+    if (!AllFinite(spheres, n, nullptr)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres_host: a sphere's centre or radius is not finite");
     const uint32_t rows = RowsetLocalRows(rs);
     if (rows == 0 || (uint64_t)rs.first_row + rs.num_rows > H || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres_host: bad row set");
     if (sphere_limit > rtd::kTileSphereMax) sphere_limit = rtd::kTileSphereMax;

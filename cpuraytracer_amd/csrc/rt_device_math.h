@@ -122,6 +122,22 @@ RT_DEV V3 div3(V3 v, float b) {
     }
 }
 
+// v / b per component (true divide) for b of ANY sign, zero included: a sphere's normal divides by its signed radius
+// (ray-tracing.cpp:62), and div_rn takes the quotient's sign from the numerator alone.  b <= 0 takes the plain division.
+// This is div3 above with the one condition b > 0 added to its fast path: an edit to either belongs in both.
+RT_DEV V3 div3_signed(V3 v, float b) {
+#if RT_MARKSTEIN
+    if (__builtin_expect(b > 0.f && div_exponents_ok(v.x, v.y, v.z, b), 1)) {
+        const float y = recip_rn(b);
+        return {div_rn(v.x, b, y), div_rn(v.y, b, y), div_rn(v.z, b, y)};
+    }
+#endif
+    {
+        RT_SITE(M_DIV_SLOW);
+        return {v.x / b, v.y / b, v.z / b};
+    }
+}
+
 // XMVector3Normalize (SSE2): zero length -> 0, infinite length -> QNaN, else true divide.
 RT_DEV V3 normalize3(V3 v) {
     const float lenSq = dot3(v, v);

@@ -511,7 +511,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         const Mat m = (kMatsL2 && p.mats16_mode == 2u) ? load_material16(mat16Lds, idx)
                                                         : (p.mats16_mode == 1u ? load_material16(p.mats16, idx) : load_material(matTab, idx));
         const V3 center = v3(S.x, S.y, S.z);
-        const V3 nrm = div3(pos - center, radius);  // ray-tracing.cpp:58 (true divide; radius > 0)
+        const V3 nrm = div3_signed(pos - center, radius);  // ray-tracing.cpp:62 (true divide by the SIGNED radius: r < 0 turns the normal inward)
         V3 atten, local, localOcc, tex;
         RT_STAMP(th0);
         const bool scattered = scatter_only(m, rd, nrm, draws, atten, nextDir, tex, mt, K.sampler);  // Scatter first: it draws (spheres-app.cpp:246)

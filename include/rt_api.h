@@ -143,6 +143,11 @@ int rt_set_workspace_limit(rt_ctx* ctx, uint64_t bytes);
 /* Limit: the clustered scan table (groups of four, padded) must stay below 65,536 entries
  * — about 65,000 spheres — because work lists, the shadow index and the closest-hit keys
  * carry entry ids in 16 bits; larger scenes are rejected here with RT_ERR_INVALID_ARG. */
+/* Radii: any finite value.  r < 0 is the reference's hollow sphere (Sphere::Intersect tests r * r and divides the normal by
+ * r, ray-tracing.cpp:48, :62, :75: the same surface as |r| with the normal turned inward) and r == 0 its degenerate point; both
+ * render as the reference renders them.  Every acceleration table (group and leaf bounds, hierarchy, cell grid, shadow
+ * index, per-tile tables) encloses |r|.  A centre or radius that is NaN or infinite is rejected with RT_ERR_INVALID_ARG
+ * and a message naming the sphere: no bound can be built from it. */
 /* lights: SpheresApp::m_lights (spheres-app.h:38, filled at spheres-app.cpp:129) as flat records, in list order -- the order
  * Material::Shade adds their contributions in (material.cpp:4-13); 0 <= n_lights <= RT_MAX_LIGHTS (lights may be NULL when
  * n_lights == 0: Shade then returns zero and no shadow ray is cast).  Every light answers its any-hit shadow query through
@@ -308,6 +313,13 @@ int rt_unit_layout_info(const rt_sphere* spheres, uint32_t n, uint32_t out[5]);
  * source the kernels use): for n segments (su, sv, eu, ev, D: 5 floats each, grid coordinates) and slabs iu, the rows [r0, r1] of
  * slab iu the walk visits (r0 > r1: none) and the entry parameter sEnter.  out_rows: 2 ints per query.  Needs no GPU. */
 int rt_unit_grid_rows(const float* segments, const int32_t* iu, uint32_t n, int32_t nv, int32_t* out_rows, float* out_s_enter);
+/* The cell grid rt_scene_upload would build for these spheres.  out_u[0] = 1: the scene selects the cell-grid scan (else nothing more
+ * is written); out_u[1..4] = cells along u and v, the scene axes (0 x, 1 y, 2 z) that are u and v.  out_f[0..3] = the grid's origin
+ * along u and v, 1 / cell size, and the walk's dilation max|r| / cell size of the small spheres (the kernel adds its rounding reach
+ * and slack); out_f[4..9] = lo.xyz, hi.xyz of the box around the small spheres, radii |r| included, to which rays are clipped.
+ * home_cell (n ints, may be null): cell iu * nv + iv whose run of scan entries holds each sphere, -1 for a big sphere (tested for every
+ * ray).  Needs no GPU. */
+int rt_unit_grid_info(const rt_sphere* spheres, uint32_t n, uint32_t out_u[5], float out_f[10], int32_t* home_cell);
 /* Candidate masks of the primary rays (csrc/rt_tile_mask.h), as rt_render builds them for the uploaded scene when an accumulation of a
  * W x H image over row set rs starts: 8 words per full tile of 64 consecutive local pixels -- [0..3] the flat scan's candidate words
  * (bit N from the top of word k = group kBase[k] + N + (N & 16), kBase = 0, 64, 16, 80), [4] bit 0 = the tile has a mask (else it keeps

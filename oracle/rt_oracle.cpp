@@ -272,7 +272,7 @@ int PaddedListTree::Build(std::vector<int>& ids, int begin, int end) {
     n.left = n.right = n.sphere = -1;
     for (int q = begin; q < end; ++q) {
         const Sphere* s = spheres[ids[q]];
-        const double c[3] = {s->center.x, s->center.y, s->center.z}, r = s->radius;
+        const double c[3] = {s->center.x, s->center.y, s->center.z}, r = std::fabs((double)s->radius);  // the surface's extent: r < 0 is legal
         for (int k = 0; k < 3; ++k) {
             n.lo[k] = std::min(n.lo[k], c[k] - r);
             n.hi[k] = std::max(n.hi[k], c[k] + r);

@@ -116,17 +116,54 @@ def _layout(spheres):
     return orig.reshape(-1, 4), bounds
 
 
-@pytest.mark.parametrize("name", ["cover", "three", "grid10k"])
+def _layout_info(spheres):
+    from cpuraytracer_amd import _capi
+    sph = np.ascontiguousarray(spheres)
+    out = (C.c_uint32 * 5)()
+    _capi.check(_capi.load().rt_unit_layout_info(sph.ctypes.data, sph.shape[0], out))
+    return list(out)
+
+
+def _mixed_sign_spheres(oracle, name):
+    """Scenes with every third radius negative (a legal radius: the reference's hollow sphere), one per scan: a soup of 150 spheres
+    (flat), one of 1,500 (bounds hierarchy), a thin layer of 3,000 small ones over a floor (cell grid); the floors stay positive."""
+    rng = np.random.default_rng({"mixed_flat": 1, "mixed_hierarchy": 2, "mixed_layer": 3}[name])
+    n = {"mixed_flat": 150, "mixed_hierarchy": 1500, "mixed_layer": 3000}[name]
+    sph = np.zeros(n + 1, dtype=oracle.SPHERE_DTYPE)
+    if name == "mixed_layer":
+        sph["cx"][:n], sph["cz"][:n] = rng.uniform(-30, 30, n), rng.uniform(-30, 30, n)
+        sph["cy"][:n] = 0.2 + rng.uniform(0, 0.05, n)
+        sph["r"][:n] = 0.2 * rng.uniform(0.5, 1.0, n)
+        sph[n] = (0.0, -1000.0, 0.0, 1000.0)
+    else:
+        sph["cx"][:n], sph["cz"][:n] = rng.uniform(-20, 20, n), rng.uniform(-20, 20, n)
+        sph["cy"][:n] = rng.uniform(0, 5, n)
+        sph["r"][:n] = np.exp(rng.uniform(np.log(0.05), np.log(1.2), n))
+        sph[n] = (0.0, -401.5, 0.0, 400.0)
+    sph["r"][:n:3] *= -1.0
+    return sph, {"mixed_flat": 0, "mixed_hierarchy": 2, "mixed_layer": 1}[name]
+
+
+@pytest.mark.parametrize("name", ["cover", "three", "grid10k", "mixed_flat", "mixed_hierarchy", "mixed_layer"])
 def test_clustered_layout_is_a_partition_with_enclosing_bounds(built, oracle, name):
-    """Every sphere appears in exactly one group, and each group's bound encloses its members with the margins
-    the filter's conservativeness argument needs."""
-    sc = oracle.build_scene(name, 1, 1.5)
+    """Every sphere appears in exactly one group, and each group's bound encloses its members -- their surfaces, radius |r| -- with
+    the margins the filter's conservativeness argument needs."""
+    if name.startswith("mixed"):
+        spheres, kind = _mixed_sign_spheres(oracle, name)
+        assert (spheres["r"] < 0).sum() >= len(spheres) // 4
+        assert _layout_info(spheres)[0] == kind, "the scene is not laid out for the scan it is meant to select"
+
+        class sc:
+            n = len(spheres)
+        sc.spheres = spheres
+    else:
+        sc = oracle.build_scene(name, 1, 1.5)
     orig, bounds = _layout(sc.spheres)
     assert orig.shape[0] % 2 == 0
     members = orig[orig != 0xFFFFFFFF]
     assert sorted(members.tolist()) == list(range(sc.n))
     c = np.stack([sc.spheres["cx"], sc.spheres["cy"], sc.spheres["cz"]], 1).astype(np.float64)
-    r = sc.spheres["r"].astype(np.float64)
+    r = np.abs(sc.spheres["r"].astype(np.float64))  # a bound encloses the surface: |r| (the same number for the stock scenes)
     # rt_scan.h: kMarginK = 4096 when the groups ARE the matrix-core level (<= 128 groups), kMarginKValu = 2048
     # when a hierarchy sits above them and they are tested on the VALU
     keps = (4096 if orig.shape[0] <= 128 else 2048) * 2.0 ** -24

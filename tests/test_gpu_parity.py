@@ -1363,6 +1363,18 @@ def test_error_codes(hip, scenes_mod):
     assert e.value.code == 2
     with pytest.raises(RtError):
         HipRenderer(4096)
+    # a centre or a radius that is not finite: no bound can be built from it -- refused with a message, the scene in place stays
+    r.render(8, 8, 1, 2, 8, 1)
+    want, _ = r.download(ldr=False)
+    for field, value in (("r", np.nan), ("r", np.inf), ("cx", -np.inf), ("cy", np.nan)):
+        sc = scenes_mod.build_scene("three", 1, 8, 8)
+        sc.spheres[field][1] = value
+        with pytest.raises(RtError) as e:
+            r.upload(sc)
+        assert e.value.code == 2 and "sphere 1" in str(e.value) and "not finite" in str(e.value)
+    r.render(8, 8, 1, 2, 8, 1)
+    got, _ = r.download(ldr=False)
+    assert_same(got, want, "the scene uploaded before the refused ones")
     r.close()
 
 

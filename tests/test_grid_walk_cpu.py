@@ -106,3 +106,86 @@ def test_walk_visits_every_cell_within_d_of_the_segment(seed):
         for (iu, iv) in got:
             assert min(su, eu) - D - 1.5 <= iu + 1 and iu <= max(su, eu) + D + 1.5
     assert missed == 0
+
+
+def _mixed_sign_layer(oracle, n=2400, side=20.0, seed=77):
+    """A thin layer of small spheres over a floor, laid out for the cell grid.  Every third radius is negative and LARGER in size
+    (|r| in 0.15 .. 0.2) than any positive one (0.05 .. 0.1): a dilation, a cell size or a clip box taken from the signed radii would
+    be too small by a factor of two."""
+    rng = np.random.default_rng(seed)
+    centers = np.stack([rng.uniform(-side, side, n), 0.2 + rng.uniform(0, 0.05, n), rng.uniform(-side, side, n)], 1)
+    radii = rng.uniform(0.05, 0.1, n)
+    radii[::3] = -rng.uniform(0.15, 0.2, len(radii[::3]))
+    sph = np.zeros(n + 1, dtype=oracle.SPHERE_DTYPE)
+    sph["cx"][:n], sph["cy"][:n], sph["cz"][:n], sph["r"][:n] = centers[:, 0], centers[:, 1], centers[:, 2], radii
+    sph[n] = (0.0, -1000.0, 0.0, 1000.0)
+    return sph
+
+
+def test_walk_visits_the_home_cell_of_every_sphere_the_oracle_accepts_on_a_mixed_sign_layer(built, oracle):
+    """The property above on a real grid: rt_unit_grid_info gives the grid rt_scene_upload builds (origin, cell size, dilation
+    D0 = max|r| / h, clip box, each sphere's home cell as the scan's cell table holds it).  Rays graze chosen spheres; for every ray
+    whose root the oracle's Sphere::Intersect accepts (a one-sphere scene), the ray is clipped to the box in binary64, put into cell
+    units as the kernel does, and walked with D0 alone (the kernel's D adds its rounding reach and slack: a smaller D asks more of
+    the walk): the sphere's home cell must be among the cells visited.  Needs |r| in D0, in the cell size and in the box."""
+    from cpuraytracer_amd import _capi
+    L = _capi.load()
+    sph = _mixed_sign_layer(oracle)
+    n = len(sph)
+    ou, of, home = (C.c_uint32 * 5)(), (C.c_float * 10)(), np.zeros(n, dtype=np.int32)
+    _capi.check(L.rt_unit_grid_info(sph.ctypes.data, n, ou, of, home.ctypes.data))
+    assert ou[0] == 1, "the layer scene must select the cell grid"
+    nu, nv, axU, axV = int(ou[1]), int(ou[2]), int(ou[3]), int(ou[4])
+    g0 = np.array([of[0], of[1]], dtype=np.float64)
+    invH, D0 = np.float64(of[2]), F(of[3])
+    lo, hi = np.array(of[4:7], dtype=np.float64), np.array(of[7:10], dtype=np.float64)
+    small = np.nonzero(home >= 0)[0]
+    assert len(small) == n - 1 and home[n - 1] == -1  # the floor is the one big sphere
+    c = np.stack([sph["cx"], sph["cy"], sph["cz"]], 1).astype(np.float64)
+    r = np.abs(sph["r"].astype(np.float64))
+    # the tables enclose |r|: dilation, box, and every small sphere sits in the cell that holds its centre
+    assert np.float64(D0) >= r[small].max() * invH and 1.0 / invH >= 2.5 * r[small].max()
+    assert (c[small] - r[small, None] >= lo).all() and (c[small] + r[small, None] <= hi).all()
+    cell = np.floor((c[small][:, [axU, axV]] - g0) * invH).astype(np.int64)
+    assert (cell[:, 0] * nv + cell[:, 1] == home[small]).all()
+
+    rng = np.random.default_rng(78)
+    neg, pos = small[sph["r"][small] < 0], small[sph["r"][small] > 0]
+    targets = np.concatenate([rng.choice(neg, 80, replace=False), rng.choice(pos, 40, replace=False)])
+    ref = oracle.build_scene("three", 1, 1.5)
+    one = oracle.Oracle()
+    checked = checked_neg = far = 0
+    for k in targets:
+        rays = []
+        for q in range(6):
+            ang, dist = rng.uniform(0, 2 * np.pi), rng.uniform(0.5, 15.0)
+            height = [rng.uniform(0.5, 5.0), rng.uniform(0.5, 5.0), 0.225 + rng.normal() * 0.02, rng.uniform(-0.3, 0.15)][q % 4]  # above, level with the layer, below
+            o = c[k] + np.array([dist * np.cos(ang), 0.0, dist * np.sin(ang)])
+            o[1] = height
+            to = c[k] - o
+            perp = np.cross(to, rng.normal(size=3))
+            perp /= np.linalg.norm(perp)
+            aim = c[k] + perp * r[k] * rng.choice([0.2, 0.9, 0.99, 0.9999])  # grazing: the hit point is almost |r| from the centre
+            d = (aim - o) / np.linalg.norm(aim - o) * rng.choice([1.0, 0.01, 30.0])
+            rays.append(np.concatenate([o, d]))
+        rays = np.array(rays, dtype=np.float32)
+        mat = np.zeros(1, dtype=oracle.MATERIAL_DTYPE)
+        one.upload(oracle.Scene(sph[k:k + 1], mat, ref.camera, ref.sun, ref.sky, ref.exposure_scale))
+        hits = one.closest_hit(rays)
+        for ray, hit in zip(rays.astype(np.float64), hits):
+            if hit[1:2].view(np.int32)[0] < 0:
+                continue
+            o, d, t = ray[:3], ray[3:], np.float64(hit[0])
+            with np.errstate(divide="ignore"):
+                t0, t1 = (lo - o) / d, (hi - o) / d
+            tn, tf = max(np.minimum(t0, t1).max(), 0.0), np.maximum(t0, t1).min()
+            assert tn * (1 - 1e-5) - 1e-5 <= t <= tf * (1 + 1e-5) + 1e-5, ("the accepted hit lies outside the clip box", int(k), t, tn, tf)
+            s, e = ((o + tn * d)[[axU, axV]] - g0) * invH, ((o + tf * d)[[axU, axV]] - g0) * invH
+            got = walk(F(s[0]), F(s[1]), F(e[0]), F(e[1]), D0, nu, nv)
+            assert (int(home[k]) // nv, int(home[k]) % nv) in got, ("the walk misses an accepted sphere's home cell", int(k), float(sph["r"][k]))
+            checked += 1
+            checked_neg += sph["r"][k] < 0
+            far += np.abs((o + t * d) - c[k])[[axU, axV]].max() > 0.1  # farther from the centre than any positive radius
+    one.close()
+    # not vacuous: most rays are accepted, most of those on negative spheres, many of them beyond the reach of a signed maximum
+    assert checked >= 400 and checked_neg >= 250 and far >= 100, (checked, checked_neg, far)
