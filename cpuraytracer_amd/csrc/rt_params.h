@@ -7,6 +7,7 @@
 
 #include "../../include/rt_api.h"
 #include "rt_device_math.h"
+#include "rt_layout_consts.h"
 
 namespace rtd {
 
@@ -39,7 +40,6 @@ static __device__ unsigned int g_tlHist[1024];  // waves leaving the loop per 25
 #endif
 
 constexpr int kWaveSize = 64;
-constexpr uint32_t kMaxLevels = 6;  // levels of group bounds (4-ary): 128 * 4^5 groups at most
 constexpr uint32_t kQueueBlock = 128;  // paths a wave takes from the global queue per claim (claimed one block ahead: rt_kernels.h)
 constexpr uint32_t kCarryQueueBlock = 128; // ... in the frame-pipelining kernel (rt_kernels.h): two batches of the path cache
 

@@ -228,10 +228,6 @@ constexpr uint32_t kWaveGridBytes = kGridWork * 4 + kGridExact * 4 + 64 * 8;  //
 static_assert(kWaveGridBytes % 16 == 0 && ((kGridWork + kGridExact) * 4) % 8 == 0, "per-wave regions are float4 aligned, the keys behind the lists 8-byte aligned");
 template <int kScan>
 constexpr uint32_t wave_region_bytes() { return kScan == 3 ? kWaveGridBytes : (kScan == 2 ? kWaveCandBytes : kWaveListBytes); }
-// K of the filter margins (units of eps * a * G; the host folds the same K into each bound): the matrix-core level needs
-// 101*16 (exact-path rounding, amplified by the member offsets) + ~600 (split-bf16 operands); levels tested on the VALU
-// in f32 need 101*16 + 30; a one-sphere bound (offset 0) needs 16 + 30.
-constexpr float kMarginK = 4096.f, kMarginKValu = 2048.f, kMarginKLeaf = 64.f;
 constexpr float kMarginRel = kMarginK * 5.9604645e-8f;                 // K * eps
 constexpr uint32_t kRayCacheBytes = 64 * 48;                            // per-wave cache of prepared paths
 // Flat scan: the LDS copy of the one-sphere bounds keeps each group's four float4 at a stride of FIVE (80 bytes).  Phase A

@@ -59,6 +59,16 @@ def test_no_cpu_fallback_without_device(built):
     assert p.returncode == 1 and "no HIP device" in p.stderr
 
 
+def test_scene_preparation_passes_its_standalone_structure_checks(built):
+    """host/scene_prep_selftest.cpp: PrepareScene alone, with no device and no library, over generated scenes of every layout
+    kind; it checks lengths, permutations, prefix tables and the range of every 16-bit id, and exits 0 only when all hold."""
+    exe = os.path.join(ROOT, "cpuraytracer_amd", "lib", "scene_prep_selftest")
+    p = subprocess.run([exe], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    for kind in ("flat", "grid", "hierarchy"):
+        assert any(ln.startswith("ok ") and ln.split()[-1] == kind for ln in p.stdout.splitlines()), "no %s scene was laid out" % kind
+
+
 def test_null_arguments_are_rejected_without_touching_the_gpu(built):
     from cpuraytracer_amd import _capi
     L = _capi.load()

@@ -212,7 +212,7 @@ def test_box_clip_of_the_descent_keeps_every_accepted_root(built, oracle, seed, 
     assert orig.shape[0] > 128
     cs = np.stack([sph["cx"], sph["cy"], sph["cz"]], 1).astype(np.float64)
     rs = sph["r"].astype(np.float64)
-    # the host's box (rt_capi.hip BuildLayout) and the padding constants
+    # the host's box (host/rt_scene_prep.cpp BuildLayout) and the padding constants
     lo = np.array([np.nextafter(F((cs[:, k] - rs * (1 + 1e-5)).min()), F(-np.inf)) for k in range(3)], dtype=F)
     hi = np.array([np.nextafter(F((cs[:, k] + rs * (1 + 1e-5)).max()), F(np.inf)) for k in range(3)], dtype=F)
     absmax = F(max(np.abs(lo.astype(np.float64)).max(), np.abs(hi.astype(np.float64)).max()) * 1.001)

@@ -6,10 +6,11 @@ set -e
 cd "$(dirname "$0")/../cpuraytracer_amd/csrc"
 mkdir -p ../lib/exp
 FLAGS=$(make -pn | sed -n 's/^HIPFLAGS = //p' | head -1 | sed 's/\$(ARCH)/gfx950/')
+make ../../build/obj/rt_scene_prep.o  # the host-only unit every variant links (no device code, no variant flags)
 for spec in "$@"; do
   name=${spec%%:*}; extra=${spec#*:}; [ "$extra" = "$spec" ] && extra=""
   echo "== $name: $extra"
-  /opt/rocm/bin/hipcc $FLAGS $extra -shared -o ../lib/exp/librt_hip_$name.so rt_capi.hip &
+  /opt/rocm/bin/hipcc $FLAGS $extra -shared -o ../lib/exp/librt_hip_$name.so rt_capi.hip ../../build/obj/rt_scene_prep.o &
 done
 wait
 ls -la ../lib/exp/
