@@ -158,6 +158,7 @@ struct rt_ctx {
     bool tileMaskValid = false;
     uint32_t maskW = 0, maskH = 0, maskLimit = 0, maskTiles = 0;
     uint32_t maskSpheres = 0;    // sphere-list limit the tables were built with (0: no lists)
+    bool skySkip = true;         // RT_SKY_SKIP, read with the knobs above: empty-list tiles are finished without rays (rt_kernels.h kSky)
     rt_rowset maskRs{};
     DevBuf<uint32_t> tileMasks;  // kTileMaskWords per full tile
     DevBuf<uint16_t> tileSpheres;  // kTileSphereHalfs per full tile (built together with the masks)
@@ -553,6 +554,8 @@ static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
 // RT_PRIMARY_MASK=0 (both knobs are read when an accumulation starts): no masks, every scan runs the filter.  RT_PRIMARY_MASK_LIMIT: tiles with more candidate groups
 // than this keep the filter.  RT_PRIMARY_SPHERES: tiles with a mask and at most this many reachable spheres also get a sphere list and
 // resolve their primary rays directly (rt_scan.h scan_tile_spheres); 0 = no lists, values above kTileSphereMax are clamped.
+// RT_SKY_SKIP=0 (read by rt_render where an accumulation starts): tiles whose list is empty generate and scan their rays like every
+// other listed tile (rt_kernels.h kSky).
 static uint32_t TileSphereLimitFromEnv() {
     const uint32_t v = EnvU32("RT_PRIMARY_SPHERES", rtd::kTileSphereLimitDefault);
     return v > rtd::kTileSphereMax ? rtd::kTileSphereMax : v;
@@ -1217,6 +1220,7 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
         ctx->accumulated = 0;
         if ((rc = BuildTileOrder(ctx, W, H, rs, npix)) != RT_OK) return rc;
         if ((rc = BuildTileMasks(ctx, W, H, rs, npix)) != RT_OK) return rc;
+        ctx->skySkip = EnvU32("RT_SKY_SKIP", 1u) != 0u;  // (no table depends on it; the unit entries that rebuild tables leave it alone)
     } else if (!sameStrip || s0 != ctx->accumulated + 1) {
         return Fail(RT_ERR_SEQUENCE, "rt_render: sample range or row set does not continue the accumulation");
     }
@@ -1278,6 +1282,7 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
             // (the table must be the one of THIS accumulation's picture: rt_unit_tile_masks may have rebuilt it for another since)
             tp.tile_masks = (ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0) ? ctx->tileMasks.ptr : nullptr;
             tp.tile_spheres = (tp.tile_masks != nullptr && ctx->maskSpheres != 0u) ? ctx->tileSpheres.ptr : nullptr;
+            tp.sky_skip = (tp.tile_spheres != nullptr && ctx->skySkip) ? 1u : 0u;
             ctx->freshScans += ((uint64_t)tp.total_paths + 63u) / 64u;
             tp.samples = ctx->samples.ptr;
             tp.trav_out = nullptr;
@@ -1723,6 +1728,16 @@ int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint
         scans[1] = c[3];
         scans[2] = c[4];
     }
+    return RT_OK;
+}
+
+int rt_unit_sky_planes(rt_ctx* ctx, uint64_t* planes) {
+    if (!ctx || !planes) return Fail(RT_ERR_INVALID_ARG, "rt_unit_sky_planes: invalid argument");
+    RT_HIP(hipSetDevice(ctx->device));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
+    RT_HIP(hipMemcpy(c, ctx->counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
+    *planes = c[5];
     return RT_OK;
 }
 

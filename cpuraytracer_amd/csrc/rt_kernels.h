@@ -604,6 +604,8 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
     // Tile masks (rt_tile_mask.h; flat hit-stash variants): when the 64 fresh paths of K_GEN are one full tile at one sample, the scan
     // that follows in the same iteration holds that tile's 64 primary rays and nothing else, and takes the tile's candidate words.
     constexpr bool kPrim = kStash && kScan == 1;
+    // ... and a tile whose sphere list is EMPTY is finished in K_GEN without rays (below; never in the frame-pipelining kernel)
+    constexpr bool kSky = kPrim && !kCarry;
     for (;;) {
         RT_SITE(K_ITER);
         RT_STAMP(ts0);
@@ -707,10 +709,42 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                                 const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_masks[kTileMaskWords * tile + 4u]);
                                 if (flags & 1u) {
                                     primTile = tile;
-                                    // bit 31: the tile has a sphere list as well (tile < 2^25: the strip has at most 2^31 pixels)
-                                    if (p.tile_spheres != nullptr &&
-                                        (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_spheres[(size_t)kTileSphereHalfs * tile]) != kTileSphereNone)
-                                        primTile = tile | 0x80000000u;
+                                    if (p.tile_spheres != nullptr) {
+                                        const uint32_t nList = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_spheres[(size_t)kTileSphereHalfs * tile]);
+                                        // bit 31: the tile has a sphere list as well (tile < 2^25: the strip has at most 2^31 pixels)
+                                        if (nList != kTileSphereNone) primTile = tile | 0x80000000u;
+                                        if (kSky && nList == 0u && p.sky_skip != 0u) {
+                                            // An EMPTY list: the list holds every sphere a primary ray of the tile can have a root in
+                                            // (rt_tile_mask.h), so all 64 paths miss on their first scan and end as
+                                            // (0 + 1 * sky) * exposure -- K_TRANS_MISS and finishPath, whatever the jitter and the lens
+                                            // sample.  The wave stores that for every plane of this tile its block still holds (same
+                                            // expressions, same bits; one traversal and one segment per path, one direct scan per
+                                            // plane) without rays, scan or transition.  Every lane stays idle: back to the top of the
+                                            // loop, which pops what the stash holds and comes here again for the paths behind them.
+                                            const uint32_t tileSpan = 64u * p.spp_pass;
+                                            const uint32_t rem = blkNext - tw * tileSpan;
+                                            const uint32_t inTile = (tileSpan - rem) >> 6, inBlock = (blkEnd - blkNext) >> 6;
+                                            const uint32_t nSky = inTile < inBlock ? inTile : inBlock;  // >= 1
+                                            const V3 sky = v3(K.sky_emit[0], K.sky_emit[1], K.sky_emit[2]);
+                                            const V3 skyRad = v3(0.f, 0.f, 0.f) + v3(1.f, 1.f, 1.f) * sky;
+                                            const float expo = K.exposure;
+                                            const float3 smp = make_float3(skyRad.x * expo, skyRad.y * expo, skyRad.z * expo);
+                                            // path_coordinates' slot of path blkNext + lane (no path list here: the launch sets sky_skip)
+                                            const uint32_t slot = tile * tileSpan + rem + p.sample_base + lane;
+                                            for (uint32_t k = 0; k < nSky; ++k) {
+                                                *reinterpret_cast<float3*>(p.samples + (size_t)(slot + 64u * k) * 3) = smp;
+                                                if (p.trav_out) p.trav_out[slot + 64u * k] = 1u;  // (no launch with tile tables sets trav_out today)
+                                            }
+                                            nTrav += nSky;
+                                            nSeg += nSky;
+                                            if (lane == 0) {
+                                                __hip_atomic_fetch_add(&ldsK->prim_direct, nSky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                                __hip_atomic_fetch_add(&ldsK->prim_sky, nSky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                            }
+                                            blkNext += 64u * nSky;
+                                            continue;
+                                        }
+                                    }
                                 }
                             }
                         }
@@ -1006,6 +1040,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                 const unsigned long long nDirect = __hip_atomic_load(&ldsK->prim_direct, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 atomicAdd(&p.counters[3], nDirect + (unsigned long long)__hip_atomic_load(&ldsK->prim_masked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
                 atomicAdd(&p.counters[4], nDirect);
+                if (kSky) atomicAdd(&p.counters[5], (unsigned long long)__hip_atomic_load(&ldsK->prim_sky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
             }
         }
 #ifdef RT_STAMPS

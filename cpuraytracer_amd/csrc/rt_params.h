@@ -212,12 +212,15 @@ struct TraceParams {
     uint32_t stash_process;    // ... hits are processed once MORE than this many lanes hold one (<= stash_cap: what is not
                                // processed must fit the stash)
     uint32_t* shard_heads;      // [kQueueShards][kShardStrideWords]: [k][0] = cursor of queue shard k (blocks claimed from it; zeroed before launch)
-    unsigned long long* counters;  // [0] traversals, [1] segments, [3] scans that took a tile's mask or sphere list, [4] those resolved from the sphere list (kStash flat variants; [2] is the host's)
+    unsigned long long* counters;  // [0] traversals, [1] segments, [3] scans that took a tile's mask or sphere list, [4] those resolved from the sphere list, [5] of those the planes finished without rays (kStash flat variants; [2] is the host's)
     // Per-tile candidate masks of the primary rays (rt_tile_mask.h; flat hit-stash variants): kTileMaskWords words per full tile of the
     // strip, or null (explicit path lists, RT_PRIMARY_MASK=0, every other variant).  Last member: the other kernels' argument offsets stay.
     const uint32_t* tile_masks;
     // ... and their sphere lists (rt_tile_mask.h: kTileSphereHalfs 16-bit values per full tile), or null (no masks, RT_PRIMARY_SPHERES=0)
     const uint16_t* tile_spheres;
+    // 1: a full tile whose sphere list is empty is finished in K_GEN without rays (rt_kernels.h kSky); set only beside tile_spheres
+    // and never with a path list (RT_SKY_SKIP=0: 0)
+    uint32_t sky_skip;
 };
 
 // The scene and pass constants the hit processing and the ray generation read, copied once per workgroup into LDS
@@ -241,6 +244,7 @@ struct SceneConsts {
     uint32_t dry_mask;      // bit k: some wave of this workgroup has seen queue shard k empty (nobody asks memory again)
     uint32_t prim_masked;   // tile masks: scans of this workgroup that took one (statistics; added to counters[3] by the last wave out)
     uint32_t prim_direct;   // ... and those resolved directly from the tile's sphere list (counters[4]; counters[3] gets both)
+    uint32_t prim_sky;      // ... and, of those, the planes of empty-list tiles finished in K_GEN without rays (kSky; counters[5])
 };
 constexpr uint32_t kSceneConstBytes = 256;                         // SceneConsts at the start of the dynamic LDS image ...
 constexpr uint32_t kConstBytes = kSceneConstBytes + 8 * 256;       // ... followed by the elementary functions' tables (255 words)
@@ -257,7 +261,7 @@ RT_DEV void fill_consts(const TraceParams& p, SceneConsts& k) {
     k.sg_nx = p.sg_nx; k.sg_ny = p.sg_ny; k.sg_nglobal = p.sg_nglobal; k.sg_enabled = p.sg_enabled;
     k.W = p.W; k.H = p.H; k.s0 = p.s0; k.lens_k0 = p.lens_k0; k.sampler = p.sampler;
     k.jitter_tab = p.jitter_tab; k.lens_tab = p.lens_tab;
-    k.exit_age_max = 0u; k.exit_ticket = 0u; k.dry_mask = 0u; k.prim_masked = 0u; k.prim_direct = 0u;
+    k.exit_age_max = 0u; k.exit_ticket = 0u; k.dry_mask = 0u; k.prim_masked = 0u; k.prim_direct = 0u; k.prim_sky = 0u;
 }
 
 // --------------------------------------------------------------------------- row sets

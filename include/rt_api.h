@@ -338,6 +338,10 @@ int rt_unit_tile_masks_host(const rt_sphere* spheres, uint32_t n, const rt_camer
  * (this scene / these settings).  scans (may be null): [0] blocks of 64 fresh paths, [1] scans that took a tile's mask or list (as
  * rt_unit_tile_masks reports), [2] those resolved directly from a sphere list, in the last rt_render that launched a trace kernel of its own. */
 int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t cap_tiles, uint32_t* n_tiles, uint16_t* lists, uint64_t scans[3]);
+/* The kernel's own count of tile-planes (64 fresh paths of one full tile at one sample) that were finished without rays because the
+ * tile's sphere list is empty (csrc/rt_kernels.h kSky), in the last rt_render that launched a trace kernel of its own; they are part
+ * of scans[2] above.  0 with RT_SKY_SKIP=0. */
+int rt_unit_sky_planes(rt_ctx* ctx, uint64_t* planes);
 /* ... the same lists evaluated on the host from the same source (both limits given).  entry_of_sphere (by original sphere index, may be
  * null): the scan entry of each sphere.  Needs no GPU. */
 int rt_unit_tile_spheres_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t mask_limit,

@@ -10,7 +10,9 @@ make ../../build/obj/rt_scene_prep.o  # the host-only unit every variant links (
 for spec in "$@"; do
   name=${spec%%:*}; extra=${spec#*:}; [ "$extra" = "$spec" ] && extra=""
   echo "== $name: $extra"
-  /opt/rocm/bin/hipcc $FLAGS $extra -shared -o ../lib/exp/librt_hip_$name.so rt_capi.hip ../../build/obj/rt_scene_prep.o &
+  # (compile and link apart, as the Makefile does: in one hipcc line the object file after rt_capi.hip is read as HIP source)
+  ( /opt/rocm/bin/hipcc $FLAGS $extra -c -o ../../build/obj/rt_capi_$name.o rt_capi.hip &&
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o ../lib/exp/librt_hip_$name.so ../../build/obj/rt_capi_$name.o ../../build/obj/rt_scene_prep.o ) &
 done
 wait
 ls -la ../lib/exp/
