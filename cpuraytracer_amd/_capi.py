@@ -58,6 +58,8 @@ EXPORTS = [
     "rt_unit_primary_rays", "rt_unit_closest_hit", "rt_unit_trace", "rt_unit_camera_rays", "rt_unit_scatter", "rt_unit_tonemap", "rt_unit_layout", "rt_unit_layout_info", "rt_unit_grid_rows", "rt_unit_grid_info",
     "rt_unit_tile_masks", "rt_unit_tile_masks_host", "rt_unit_tile_cone", "rt_unit_tile_spheres", "rt_unit_tile_spheres_host", "rt_unit_sky_planes",
     "rt_set_noise_estimate", "rt_download_moments", "rt_noise_map", "rt_noise_summary", "rt_unit_noise_estimate_host",
+    "rt_render_features", "rt_feature_samples", "rt_download_features", "rt_copy_features_to_device", "rt_clear_features",
+    "rt_unit_features_host",
 ]
 
 _lib = None
@@ -138,6 +140,13 @@ def load():
         L.rt_noise_map.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
         L.rt_noise_summary.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float)]
         L.rt_unit_noise_estimate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
+    if hasattr(L, "rt_render_features"):
+        L.rt_render_features.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
+        L.rt_feature_samples.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.rt_download_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_copy_features_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_clear_features.argtypes = [C.c_void_p]
+        L.rt_unit_features_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtMaterial), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -16,6 +16,8 @@ static void Usage() {
               "               [--pipeline N]   frames in flight for quiet progressive runs (--frame-spp 1 --quiet); 0 = off\n"
               "               [--batch N]      quiet progressive frames rendered per launch (rt_set_frame_batch); 1 = off\n"
               "               [--noise-out file.pfm]   per-pixel standard error of the image (HDR units) as a one-channel PFM, rows top to bottom\n"
+              "               [--features-out PREFIX]  first-hit feature buffers of the rendered samples, as means: PREFIX.albedo.pfm and\n"
+              "                                PREFIX.normal.pfm (three channels), PREFIX.depth.pfm and PREFIX.coverage.pfm (one channel)\n"
               "               [--target-error T [--target-fraction F] [--max-spp N]]   render --frame-spp samples at a time until at most the\n"
               "                                fraction F (default 0) of the pixels has a relative error above T, or N (default --spp) is reached\n"
               "               [--noise-floor F]        added to a pixel's r + g + b before the relative error divides by it (default 0.01)");
@@ -25,7 +27,7 @@ int main(int argc, char** argv) {
     AppSettingsT st;
     uint32_t spp = 16;
     int device = 0, gpus = 0;
-    std::string out = "out.ppm", noiseOut;
+    std::string out = "out.ppm", noiseOut, featuresOut;
     float targetError = 0.f;
     double targetFraction = 0.0;
     uint32_t maxSpp = 0;
@@ -54,6 +56,7 @@ int main(int argc, char** argv) {
         else if (k == "--pipeline") st.framesInFlight = (uint32_t)std::atoi(val());
         else if (k == "--batch") st.framesPerLaunch = (uint32_t)std::atoi(val());
         else if (k == "--noise-out") noiseOut = val();
+        else if (k == "--features-out") featuresOut = val();
         else if (k == "--target-error") { targetError = (float)std::atof(val()); targetSet = true; }
         else if (k == "--target-fraction") targetFraction = std::atof(val());
         else if (k == "--max-spp") maxSpp = (uint32_t)std::atoi(val());
@@ -75,6 +78,10 @@ int main(int argc, char** argv) {
     st.noiseEstimate = targetSet || !noiseOut.empty();
     if (st.noiseEstimate && gpus > 0) {
         std::fprintf(stderr, "spheres: --noise-out and --target-error are not available with --gpus: the multi-GPU gather carries no second moments\n");
+        return 2;
+    }
+    if (!featuresOut.empty() && gpus > 0) {
+        std::fprintf(stderr, "spheres: --features-out is not available with --gpus: the multi-GPU gather carries no feature strips\n");
         return 2;
     }
     if (targetSet) {
@@ -113,6 +120,10 @@ int main(int argc, char** argv) {
     if (rc != 0) return rc;
     if (!noiseOut.empty() && !app.WriteNoisePFM(noiseOut)) {
         std::fprintf(stderr, "spheres: cannot write %s: %s\n", noiseOut.c_str(), rt_last_error());
+        return 1;
+    }
+    if (!featuresOut.empty() && !app.WriteFeaturePFMs(featuresOut)) {
+        std::fprintf(stderr, "spheres: cannot write the feature buffers %s.*.pfm: %s\n", featuresOut.c_str(), rt_last_error());
         return 1;
     }
     if (targetSet) std::printf("{\"target_error\": %g, \"target_fraction\": %g, \"spp_reached\": %zu}\n", (double)targetError, targetFraction, app.SampleCount());

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <utility>
 
+#include "../rt_features.h"
 #include "../rt_noise.h"
 #include "../rt_tile_mask.h"
 
@@ -778,6 +779,26 @@ int rt_unit_noise_estimate_host(const float* hdr, const float* sq, uint32_t npix
     if (!hdr || !sq || !out) return Fail(RT_ERR_INVALID_ARG, "rt_unit_noise_estimate_host: null argument");
     if (n < 2) return Fail(RT_ERR_SEQUENCE, "rt_unit_noise_estimate_host: the estimate needs at least 2 samples per pixel");
     for (uint32_t p = 0; p < npix; ++p) rtd::noise_estimate(hdr + 3 * (size_t)p, sq + 3 * (size_t)p, n, floor, out + 2 * (size_t)p);
+    return RT_OK;
+}
+
+// Host-only: the per-sample step of the feature buffers (rt_features.h feature_sample, the source the kernel compiles) for n hit
+// records of rt_unit_closest_hit's format; materials by ORIGINAL sphere index.
+int rt_unit_features_host(const rt_material* materials, uint32_t n_materials, const rt_material* sky, const float* hits10, uint32_t n, float* out8,
+                          uint32_t* out_ids) {
+    if (!materials || !sky || !hits10 || !out8 || !out_ids) return Fail(RT_ERR_INVALID_ARG, "rt_unit_features_host: null argument");
+    const rtd::V3 skyAlbedo = rtd::feature_sky_albedo(rtd::feature_material(*sky));
+    for (uint32_t k = 0; k < n; ++k) {
+        const float* h = hits10 + 10 * (size_t)k;
+        int32_t oidx;
+        std::memcpy(&oidx, &h[1], sizeof(oidx));
+        const bool hit = oidx >= 0;
+        if (hit && (uint32_t)oidx >= n_materials)
+            return Fail(RT_ERR_INVALID_ARG, "rt_unit_features_host: record " + std::to_string(k) + " names a sphere beyond the material table");
+        const rtd::Mat m = rtd::feature_material(hit ? materials[oidx] : *sky);
+        rtd::feature_sample(hit, m, (uint32_t)oidx, h[0], rtd::v3(h[5], h[6], h[7]), h[8], h[9], skyAlbedo, out8 + rtd::kFeatureChannels * (size_t)k,
+                            out_ids[k]);
+    }
     return RT_OK;
 }
 

@@ -217,6 +217,35 @@ bool SpheresApp::WriteNoisePFM(const std::string& path) const {
     return ok;
 }
 
+bool SpheresApp::WriteFeaturePFMs(const std::string& prefix) const {
+    const uint32_t W = (uint32_t)GetBackBufferWidth(), H = (uint32_t)GetBackBufferHeight();
+    const uint32_t rows = m_lastStats.local_rows;
+    if (m_sampleCount == 0) return false;
+    const rt_rowset rs = m_hasRowset ? m_rowset : rt_rowset{0, H, H, 0, 1};
+    if (rt_render_features(m_device, W, H, rs, 1u, (uint32_t)m_sampleCount + 1u, nullptr) != RT_OK) return false;
+    const size_t npix = (size_t)W * rows;
+    std::vector<float> feat(npix * 8);
+    if (rt_download_features(m_device, feat.data(), nullptr) != RT_OK) return false;
+    const float n = (float)m_sampleCount;
+    struct Plane {
+        const char* name;
+        uint32_t first, channels;
+    };
+    const Plane planes[4] = {{"albedo", 0, 3}, {"normal", 3, 3}, {"depth", 6, 1}, {"coverage", 7, 1}};
+    for (const Plane& pl : planes) {
+        std::vector<float> out(npix * pl.channels);
+        for (size_t p = 0; p < npix; ++p)
+            for (uint32_t c = 0; c < pl.channels; ++c) out[p * pl.channels + c] = feat[p * 8 + pl.first + c] / n;
+        FILE* f = std::fopen((prefix + "." + pl.name + ".pfm").c_str(), "wb");
+        if (!f) return false;
+        std::fprintf(f, "%s\n%u %u\n-1.0\n", pl.channels == 3 ? "PF" : "Pf", W, rows);
+        const bool ok = std::fwrite(out.data(), sizeof(float), out.size(), f) == out.size();
+        std::fclose(f);
+        if (!ok) return false;
+    }
+    return true;
+}
+
 int SpheresApp::RunUntil(float relError, double fraction, uint32_t maxSpp) noexcept {
     try {
         const uint32_t step = AppSettings.samplesPerFrame;

@@ -63,6 +63,10 @@ public:
     bool WritePPM(const std::string& path) const;
     // The absolute noise map (rt_noise_map, channel 0) as a single-channel little-endian PFM; rows top to bottom, as in the PPM.
     bool WriteNoisePFM(const std::string& path) const;
+    // Runs the feature pass (rt_render_features) over the samples rendered so far and writes the means -- the sums divided by the
+    // sample count in binary32 -- as little-endian PFMs, rows top to bottom: prefix.albedo.pfm and prefix.normal.pfm (three channels),
+    // prefix.depth.pfm and prefix.coverage.pfm (one channel).
+    bool WriteFeaturePFMs(const std::string& prefix) const;
     // Frames of samplesPerFrame samples until at most `fraction` of the pixels have a relative error above relError, or the next
     // frame would pass maxSpp (every frame waits for its summary, so every frame is resolved).  SampleCount() is the spp reached.
     int RunUntil(float relError, double fraction, uint32_t maxSpp) noexcept;

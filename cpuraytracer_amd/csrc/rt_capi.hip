@@ -135,6 +135,18 @@ struct rt_ctx {
     DevBuf<float2> jitterTab, lensTab;    // ray-generation tables of the current pass
     double lastResolveMs = 0.0;
 
+    // feature buffers (rt_render_features; rt_features.h): strips, ray-generation tables and sequencing of their own -- nothing
+    // here is read or written by rt_render, and nothing of rt_render's by the feature pass
+    rt_material sky{};            // the scene's sky material (the miss albedo is its texture at uv (0, 0))
+    bool featCleared = false;     // rt_clear_features was called: the next rt_render_features may start at any s0
+    uint32_t featCount = 0;       // samples per pixel in the strips (0: nothing accumulated)
+    uint32_t featNext = 0;        // the s0 that continues the accumulation (the previous call's s1)
+    uint32_t featW = 0, featH = 0, featRows = 0;
+    rt_rowset featRs{};
+    DevBuf<float> feat;           // [W*rows*8] sums of albedo rgb, normal xyz, depth, coverage
+    DevBuf<uint32_t> featIds;     // [W*rows] id of the sample added last
+    DevBuf<float2> featJitter, featLens;  // ray-generation tables of the feature pass
+
     // tuning (env: RT_BLOCKS_PER_CU, RT_FORCE_GLOBAL_TABLES)
     uint32_t blocksPerCu = 4;
     uint32_t blockThreads = 256;
@@ -511,6 +523,52 @@ static int LaunchClosest(rt_ctx* ctx, const float* dRays, uint32_t n, float* dOu
     return RT_OK;
 }
 
+// The feature pass (rt_kernels.h rt_features_kernel) over the strip's npix local pixels: the scan variant and the LDS image of
+// LaunchClosest (four waves, hit-processing tables left out), persistent workgroups -- as many as are resident at once.
+static int LaunchFeatures(rt_ctx* ctx, rtd::TraceParams& tp, const rtd::FeatureParams& fp) {
+    const TraceVariant V = ChooseVariant(ctx, tp);
+    tp.mats_in_lds = 0;
+    tp.sg_in_lds = 0;
+    tp.fd_w = rtd::make_fastdiv(tp.W ? tp.W : 1u);
+    tp.fd_rows = rtd::make_fastdiv(tp.rs.block_rows ? tp.rs.block_rows : 1u);
+    const uint32_t topCnt = tp.level_cnt[tp.n_levels - 1];
+    const size_t waves = 256 / 64;
+    size_t ldsBytes = waves * (V.grid ? rtd::kWaveGridBytes : (V.tree ? rtd::kWaveCandBytes : rtd::kWaveListBytes));
+    if (V.grid) {
+        tp.grid_in_lds = 0;
+    } else if (V.tree) {
+        ldsBytes += MfmaOpsBytesFor(topCnt);
+        const size_t treeBytes = (size_t)(tp.level_off[tp.n_levels - 1] + topCnt) * 16;
+        tp.tree_in_lds = (ctx->treeInLds && ldsBytes + treeBytes <= 160 * 1024) ? 1u : 0u;
+        if (tp.tree_in_lds) ldsBytes += treeBytes;
+    } else if (V.flat || V.ldsTables) {
+        ldsBytes += LdsBytesFor(tp.n, tp.n_padded, false);
+        if (V.flat) ldsBytes += V.leafBytes + MfmaOpsBytesFor(topCnt);
+    }
+    if (ldsBytes > 160 * 1024) return Fail(RT_ERR_HIP, "internal: the feature pass's LDS image exceeds a workgroup's 160 KiB");
+    const uint32_t nTiles = (fp.npix + 63u) / 64u;
+    size_t perCu = (160 * 1024) / (ldsBytes ? ldsBytes : 1);  // workgroups of this image a CU holds, at most 8 (32 waves)
+    perCu = perCu > 8 ? 8 : (perCu < 1 ? 1 : perCu);
+    uint32_t blocks = (uint32_t)((nTiles + waves - 1) / waves);
+    const uint32_t maxBlocks = (uint32_t)ctx->cuCount * (uint32_t)perCu;
+    if (blocks > maxBlocks) blocks = maxBlocks;
+    if (blocks == 0) blocks = 1;
+#define RT_FEATURES(LDS, M)                                                                                            \
+    do {                                                                                                               \
+        const void* fn_ = reinterpret_cast<const void*>(&rtd::rt_features_kernel<LDS, M>);                             \
+        if (ldsBytes > 48 * 1024 && RaiseLdsLimit(ctx->device, fn_) != RT_OK) return RT_ERR_HIP;                       \
+        hipLaunchKernelGGL((rtd::rt_features_kernel<LDS, M>), dim3(blocks), dim3(256), ldsBytes, ctx->stream, tp, fp); \
+    } while (0)
+    if (V.grid) RT_FEATURES(false, 3);
+    else if (V.tree) RT_FEATURES(false, 2);
+    else if (V.flat) RT_FEATURES(true, 1);
+    else if (V.ldsTables) RT_FEATURES(true, 0);
+    else RT_FEATURES(false, 0);
+#undef RT_FEATURES
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
 // Work order of the full tiles for the accumulation that is starting (rt_kernels.h, rt_tile_order_kernel): three pilot rays per
 // tile through the production scan, then a stable sort by the most expensive first-hit material.  All on the stream, no host wait.
 static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t npix) {
@@ -832,6 +890,10 @@ void rt_destroy(rt_ctx* ctx) {
     ctx->noiseMap.Release();
     ctx->noiseRed.Release();
     ctx->ldr.Release();
+    ctx->feat.Release();
+    ctx->featIds.Release();
+    ctx->featJitter.Release();
+    ctx->featLens.Release();
     ctx->samples.Release();
     ctx->queue.Release();
     ctx->counters.Release();
@@ -1025,6 +1087,8 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     ctx->hasScene = true;
     ctx->aheadValid = false;
     ctx->accumulated = 0;
+    ctx->sky = *sky;
+    ctx->featCount = 0;  // the feature strips belonged to the scene that was replaced
     PipelineDrop(ctx);
     return RT_OK;
 }
@@ -1059,6 +1123,7 @@ int rt_set_sampler(rt_ctx* ctx, uint32_t flags) {
         ctx->accumulated = 0;  // samples of two mappings do not mix: the next rt_render starts over
         PipelineDrop(ctx);
         ctx->tileOrderValid = false;  // the pilot rays use the lens mapping
+        ctx->featCount = 0;           // ... and so do the feature pass's primary rays
     }
     ctx->sampler = flags;
     return RT_OK;
@@ -1468,6 +1533,125 @@ int rt_noise_summary(rt_ctx* ctx, float floor, const float* thresholds, uint32_t
     RT_HIP(hipMemcpy(red, ctx->noiseRed.ptr, sizeof(red), hipMemcpyDeviceToHost));
     for (uint32_t k = 0; k < n_thr; ++k) out_counts[k] = red[k];
     if (out_max_rel) std::memcpy(out_max_rel, &red[rtd::kNoiseMaxThresholds], sizeof(float));
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------- feature buffers (rt_features.h)
+// Sequencing of its own (featCount / featNext), strips and ray-generation tables of its own: rt_render's accumulation, tile tables,
+// pending batches, planes traced ahead and carried paths are neither read nor changed.
+int rt_render_features(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t s0, uint32_t s1, double* out_ms) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_render_features: null ctx");
+    if (W == 0 || H == 0 || s0 == 0 || s1 <= s0) return Fail(RT_ERR_INVALID_ARG, "rt_render_features: empty image or sample range");
+    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_render_features: no scene uploaded");
+    const uint32_t rows = rtprep::RowsetRowsWithin(rs, H);
+    if (rows == 0) return Fail(RT_ERR_INVALID_ARG, "rt_render_features: bad row set");
+    const uint64_t npix64 = (uint64_t)W * rows;
+    if (npix64 > (1ull << 31) - 64u || (uint64_t)W * H > 0xffffffffull) return Fail(RT_ERR_INVALID_ARG, "rt_render_features: image too large");
+    // the lens table is indexed by s + i + j: keep that sum, like the tables' sizes, inside 32 bits
+    if ((uint64_t)s1 + W + H > 0xffffffffull) return Fail(RT_ERR_INVALID_ARG, "rt_render_features: sample range too large");
+    RT_HIP(hipSetDevice(ctx->device));
+    const uint32_t npix = (uint32_t)npix64;
+    const bool sameStrip = ctx->featW == W && ctx->featH == H && ctx->featRows == rows && std::memcmp(&ctx->featRs, &rs, sizeof(rs)) == 0;
+    const bool continues = ctx->featCount != 0 && sameStrip && s0 == ctx->featNext;
+    // (a call that starts at 1 always starts over; one that could continue does; after rt_clear_features any s0 starts)
+    const bool starts = s0 == 1 || (ctx->featCleared && !continues);
+    if (!starts && !continues) return Fail(RT_ERR_SEQUENCE, "rt_render_features: sample range or row set does not continue the accumulation");
+    ctx->featCleared = false;
+    int rc;
+    if (starts) {
+        ctx->featCount = 0;
+        if ((rc = ctx->feat.Reserve((size_t)npix * rtd::kFeatureChannels)) != RT_OK) return rc;
+        if ((rc = ctx->featIds.Reserve(npix)) != RT_OK) return rc;
+        ctx->featW = W;
+        ctx->featH = H;
+        ctx->featRows = rows;
+        ctx->featRs = rs;
+    }
+    const uint32_t spp = s1 - s0;
+    const uint32_t k0 = s0 + rs.first_row;
+    const uint32_t nLens = spp + W + rs.num_rows;
+    if ((rc = ctx->featJitter.Reserve(spp)) != RT_OK || (rc = ctx->featLens.Reserve(nLens)) != RT_OK) {
+        ctx->featCount = 0;
+        return rc;
+    }
+    rtd::TraceParams tp = ctx->base;
+    tp.W = W;
+    tp.H = H;
+    tp.rs = rs;
+    tp.s0 = s0;
+    tp.sampler = ctx->sampler;
+    tp.npix_local = npix;
+    tp.jitter_tab = ctx->featJitter.ptr;
+    tp.lens_tab = ctx->featLens.ptr;
+    tp.lens_k0 = k0;
+    rtd::FeatureParams fp{};
+    fp.feat = ctx->feat.ptr;
+    fp.ids = ctx->featIds.ptr;
+    fp.npix = npix;
+    fp.s0 = s0;
+    fp.s1 = s1;
+    fp.cont = starts ? 0u : 1u;
+    const rtd::V3 skyAlbedo = rtd::feature_sky_albedo(rtd::feature_material(ctx->sky));
+    fp.sky[0] = skyAlbedo.x;
+    fp.sky[1] = skyAlbedo.y;
+    fp.sky[2] = skyAlbedo.z;
+    auto run = [&]() -> int {
+        if (out_ms) RT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+        const uint32_t nmax = spp > nLens ? spp : nLens;
+        hipLaunchKernelGGL(rtd::rt_raygen_tables_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, ctx->featJitter.ptr, s0, spp,
+                           ctx->featLens.ptr, k0, nLens, ctx->sampler);
+        RT_HIP(hipGetLastError());
+        const int rcl = LaunchFeatures(ctx, tp, fp);
+        if (rcl != RT_OK) return rcl;
+        if (out_ms) {
+            RT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+            RT_HIP(hipEventSynchronize(ctx->ev[3]));
+            float ms = 0.f;
+            RT_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+            *out_ms = ms;
+        }
+        return RT_OK;
+    };
+    if ((rc = run()) != RT_OK) {
+        ctx->featCount = 0;  // the strips may be half written: the next call must start again
+        return rc;
+    }
+    ctx->featCount += spp;
+    ctx->featNext = s1;
+    return RT_OK;
+}
+
+int rt_feature_samples(rt_ctx* ctx, uint32_t* out) {
+    if (!ctx || !out) return Fail(RT_ERR_INVALID_ARG, "rt_feature_samples: null argument");
+    *out = ctx->featCount;
+    return RT_OK;
+}
+
+int rt_download_features(rt_ctx* ctx, float* feat8, uint32_t* ids) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_download_features: null ctx");
+    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_download_features: nothing accumulated");
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->featW * ctx->featRows;
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    if (feat8) RT_HIP(hipMemcpy(feat8, ctx->feat.ptr, npix * rtd::kFeatureChannels * sizeof(float), hipMemcpyDeviceToHost));
+    if (ids) RT_HIP(hipMemcpy(ids, ctx->featIds.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_copy_features_to_device(rt_ctx* ctx, void* dev_feat8, void* dev_ids) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_copy_features_to_device: null ctx");
+    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_copy_features_to_device: nothing accumulated");
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->featW * ctx->featRows;
+    if (dev_feat8) RT_HIP(hipMemcpyAsync(dev_feat8, ctx->feat.ptr, npix * rtd::kFeatureChannels * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (dev_ids) RT_HIP(hipMemcpyAsync(dev_ids, ctx->featIds.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
+int rt_clear_features(rt_ctx* ctx) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_clear_features: null ctx");
+    ctx->featCount = 0;
+    ctx->featCleared = true;
     return RT_OK;
 }
 

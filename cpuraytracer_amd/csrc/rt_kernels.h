@@ -40,6 +40,7 @@
 #include "rt_shade.h"
 #include "rt_tile_mask.h"
 #include "rt_noise.h"
+#include "rt_features.h"
 
 namespace rtd {
 
@@ -1438,6 +1439,102 @@ __global__ void __launch_bounds__(256) rt_resolve_kernel(const float* __restrict
     if (committedSamples) nSamples = *committedSamples > 0u ? *committedSamples : 1u;
     const float n = (float)nSamples;
     for (int ch = 0; ch < 3; ++ch) ldr[3 * (size_t)pix + ch] = (uint8_t)rne_u8(tonemap_channel(hdr[3 * (size_t)pix + ch], n));
+}
+
+// ============================================================ feature buffers (rt_features.h)
+// First-hit albedo, normal, depth, coverage and object id of the samples [s0, s1) of every local pixel, summed on the device.
+// The ray is gen_primary_ray's, the hit the PRODUCTION scan's -- the same table staging and the same scan functions as
+// k_unit_closest below, i.e. as the variant of rt_trace_kernel that rt_render launches for the scene -- and the sample's values
+// are rt_features.h feature_sample's.  One wave owns 64 consecutive local pixels (a tile; lanes past npix stay in the
+// wave-cooperative scans with live == false), workgroups are persistent over the tiles, the tables are staged once per workgroup,
+// and the loop over s runs here with the eight sums and the id in registers: a continuing call (cont) loads the pixel's sums
+// first and goes on adding in order, so any split of a sample range gives the bits of one call.  One read-modify-write of the
+// strip per call, as two aligned 16-byte halves per pixel; no per-sample buffer in global memory.  The material of the hit
+// sphere comes from the table the hit processing reads (p.mats, per scan entry), through L2: one record per lane and sample.
+// Nothing rt_render relies on is read or written: the ray-generation tables are the feature pass's own.
+struct FeatureParams {
+    float* feat;        // [npix][8] sums (16-byte aligned)
+    uint32_t* ids;      // [npix] id of the sample added last
+    uint32_t npix;      // local pixels of the strip
+    uint32_t s0, s1;    // sample indices [s0, s1), 1-based
+    uint32_t cont;      // 1: the strip holds the sums of the samples before s0
+    float sky[3];       // feature_sky_albedo of the scene's sky
+};
+template <bool kLds, int kScan>
+__global__ void __launch_bounds__(256) rt_features_kernel(const TraceParams p, const FeatureParams f) {
+    extern __shared__ float4 smem[];
+    constexpr uint32_t kWaveRegion = wave_region_bytes<kScan>();
+    constexpr uint32_t kWaves = 256 / kWaveSize;
+    uint16_t* candBase = reinterpret_cast<uint16_t*>(smem);
+    float4* tabBase = smem + kWaves * (kWaveRegion / 16);
+    SceneTabs T;
+    stage_scene<kLds, kScan>(p, tabBase, T);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & (kWaveSize - 1);
+    const uint32_t wave = threadIdx.x / kWaveSize;
+    uint16_t* waveCand = candBase + wave * (kWaveRegion / 2);
+    const uint32_t nTiles = (f.npix + 63u) >> 6;
+    const V3 sky = v3(f.sky[0], f.sky[1], f.sky[2]);
+    for (uint32_t tile = blockIdx.x * kWaves + wave; tile < nTiles; tile += gridDim.x * kWaves) {
+        const uint32_t pl = (tile << 6) + lane;
+        const bool live = pl < f.npix;
+        uint32_t i = 0, j = 0;
+        if (live) {
+            const uint32_t lr = fastdiv(pl, p.fd_w);
+            i = pl - lr * p.W;
+            j = rowset_global_row(p.rs, lr, p.fd_rows);
+        }
+        float acc[kFeatureChannels];
+        for (uint32_t c = 0; c < kFeatureChannels; ++c) acc[c] = 0.f;
+        uint32_t id = kFeatureNoId;
+        float4* strip = reinterpret_cast<float4*>(f.feat) + 2 * (size_t)pl;
+        if (live && f.cont) {
+            const float4 a = strip[0], b = strip[1];
+            acc[0] = a.x; acc[1] = a.y; acc[2] = a.z; acc[3] = a.w;
+            acc[4] = b.x; acc[5] = b.y; acc[6] = b.z; acc[7] = b.w;
+            id = f.ids[pl];
+        }
+        for (uint32_t s = f.s0; s < f.s1; ++s) {
+            V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f);
+            if (live) gen_primary_ray(p, i, j, s, o, d);
+            float tmin = 0.f;
+            int idx = -1;
+            if (kScan == 3) {
+                const GridParams G{T.gridCells, p.grid_nu, p.grid_nv, p.grid_ax_u, p.grid_ax_v, p.grid_g0u, p.grid_g0v, p.grid_inv_h, p.grid_rmax_over_h, p.grid_big_norm};
+                scan_list_grid(T.scan, T.leaf, T.orig, G, T.gridCells, p.n_always, p.tree_box, p.bound_norm, o, d, live, tmin, idx, waveCand, lane);
+            } else if (kScan != 0) {
+                unsigned long long dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                (void)dbg;
+                scan_list_mfma<kScan == 2>(T.scan, T.leaf, T.orig, T.ops, T.nTiles, T.nTop, T.tree, p.level_off, p.n_levels, p.bound_norm, p.single_mask, p.n_always,
+                                           p.tree_box_on ? p.tree_box : nullptr, o, d, live, tmin, idx, waveCand, lane, dbg);
+            } else if (live) {
+                scan_list_deferred(T.scan, T.orig, p.n_padded, o, d, tmin, idx, waveCand + lane);
+            }
+            if (live) {
+                const bool hit = idx >= 0;
+                Mat m{};
+                uint32_t oidx = kFeatureNoId;
+                V3 nrm = v3(0.f, 0.f, 0.f);
+                if (hit) {  // the hit record, as k_unit_closest forms it
+                    const float4 S = T.scan[idx];
+                    const V3 pos = tmin * d + o;
+                    nrm = (pos - v3(S.x, S.y, S.z)) / T.rad[idx];
+                    oidx = T.orig[idx];
+                    m = feature_material(p.mats[idx]);
+                }
+                float v[kFeatureChannels];
+                uint32_t sid;
+                feature_sample(hit, m, oidx, tmin, nrm, 0.5f * nrm.x + 0.5f, 0.5f * nrm.z + 0.5f, sky, v, sid);
+                for (uint32_t c = 0; c < kFeatureChannels; ++c) acc[c] = acc[c] + v[c];
+                id = sid;
+            }
+        }
+        if (live) {
+            strip[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+            strip[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
+            f.ids[pl] = id;
+        }
+    }
 }
 
 // ================================================================== unit-test kernels

@@ -3,18 +3,11 @@
 #pragma once
 
 #include "rt_scan.h"  // root_possible(), wave helpers
+#include "rt_texture.h"
 
 namespace rtd {
 
-// --------------------------------------------------------- textures (A14), getters (A13)
-// Material record held in registers (loaded as three 16-byte reads; a by-value struct copy would
-// be demoted to scratch/LDS by the compiler).
-struct Mat {
-    uint32_t type, tex_type;
-    float smoothness, ior, tiling;
-    float rgb0[3], rgb1[3];
-    float luminance;
-};
+// --------------------------------------------------------- material records (rt_texture.h: Mat, eval_texture)
 RT_DEV Mat load_material(const rt_material* tab, int idx) {
     const float4* q = reinterpret_cast<const float4*>(tab) + (size_t)idx * 3;
     const float4 a = q[0], b = q[1], c = q[2];
@@ -43,16 +36,6 @@ RT_DEV Mat load_material16(const uint4* tab, int idx) {
     m.rgb1[0] = (float)(q.y & 255u) * k; m.rgb1[1] = (float)((q.y >> 8) & 255u) * k; m.rgb1[2] = (float)((q.y >> 16) & 255u) * k;
     return m;
 }
-RT_DEV V3 eval_texture(const Mat& m, float u, float v) {
-    if (m.tex_type == RT_TEX_CHECKER) {  // texture.cpp:20-33
-        const int iu = (int)(m.tiling * u);
-        const int iv = (int)(m.tiling * v);
-        if (iu % 2 == iv % 2) return v3(m.rgb0[0], m.rgb0[1], m.rgb0[2]);
-        return v3(m.rgb1[0], m.rgb1[1], m.rgb1[2]);
-    }
-    return v3(m.rgb0[0], m.rgb0[1], m.rgb0[2]);  // texture.cpp:8-11
-}
-
 // Source of the material draws: the path's xoshiro stream, or (unit tests) scripted uniforms.
 struct StreamDraws {
     Rng rng;

@@ -24,6 +24,7 @@ class HipRenderer:
         self._h = C.c_void_p()
         check(self._L.rt_create(int(device), C.byref(self._h)))
         self.W = self.rows = 0
+        self.feature_W = self.feature_rows = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -155,6 +156,46 @@ class HipRenderer:
                     return spp
             if spp + step_spp > max_spp:
                 return spp
+
+    # ---- feature buffers (rt_api.h "feature buffers")
+    def render_features(self, W, H, s0, s1, rowset=None, timed=False):
+        """rt_render_features: first-hit albedo, normal, depth, coverage and object id of the samples [s0, s1), added to strips of
+        their own (sequenced like render, independently of it).  timed=True waits and returns the HIP-event time in ms; else the
+        call only enqueues work and returns None."""
+        rs = rowset if rowset is not None else whole_image(H)
+        rs = RtRowset.from_buffer_copy(bytes(rs))
+        ms = C.c_double(0.0)
+        check(self._L.rt_render_features(self._h, W, H, rs, s0, s1, C.byref(ms) if timed else None))
+        self.feature_W, self.feature_rows = W, self._L.rt_rowset_local_rows(rs)
+        return ms.value if timed else None
+
+    def feature_samples(self):
+        """Samples per pixel in the feature strips (0: nothing accumulated)."""
+        n = C.c_uint32(0)
+        check(self._L.rt_feature_samples(self._h, C.byref(n)))
+        return n.value
+
+    def download_features(self, normalize=False):
+        """The strips as a dict of arrays shaped like the strip: albedo and normal (rows, W, 3) float32, depth and coverage (rows, W)
+        float32 -- the raw sums, or with normalize=True each sum divided by the sample count in binary32 -- and id (rows, W) uint32, the
+        object id of the sample added last (0xffffffff: it hit nothing)."""
+        rows, W = self.feature_rows, self.feature_W
+        feat = np.zeros((rows, W, 8), dtype=np.float32)
+        ids = np.zeros((rows, W), dtype=np.uint32)
+        check(self._L.rt_download_features(self._h, feat.ctypes.data, ids.ctypes.data))
+        if normalize:
+            feat = feat / np.float32(self.feature_samples())
+            assert feat.dtype == np.float32
+        return {"albedo": np.ascontiguousarray(feat[..., 0:3]), "normal": np.ascontiguousarray(feat[..., 3:6]),
+                "depth": np.ascontiguousarray(feat[..., 6]), "coverage": np.ascontiguousarray(feat[..., 7]), "id": ids}
+
+    def copy_features_to_device(self, feat_ptr=None, id_ptr=None):
+        """rt_copy_features_to_device: the raw sums ((rows, W, 8) float32) and ids ((rows, W) uint32) into caller-owned device memory,
+        asynchronously on the context's stream."""
+        check(self._L.rt_copy_features_to_device(self._h, C.c_void_p(feat_ptr or 0), C.c_void_p(id_ptr or 0)))
+
+    def clear_features(self):
+        check(self._L.rt_clear_features(self._h))
 
     # ---- unit entries
     def unit_halton(self, index, base):

@@ -251,6 +251,36 @@ int rt_noise_map(rt_ctx* ctx, float floor, float* out_abs_rel);
  * device with integer atomics only, so repeated calls give identical answers.  Same sequencing as rt_noise_map. */
 int rt_noise_summary(rt_ctx* ctx, float floor, const float* thresholds, uint32_t n_thr, uint32_t* out_counts, float* out_max_rel);
 
+/* --------------------------------------------------------- feature buffers
+ * First-hit albedo, normal, depth, coverage and object id (DESIGN.md "Feature buffers"; csrc/rt_features.h): what denoisers, edge-aware
+ * filters, compositing and picking take beside the colour.  For a pixel (i, j) and a sample index s the ray is exactly the path's
+ * primary ray (GenerateRays + Camera::GetRay with the context's sampler flags: RT_SAMPLER_SQRT_DISK moves the lens offsets here too)
+ * and the hit is the contract's closest hit (the list scan's result).  The sample's feature vector v[8] and id:
+ *     hit, OPAQUE / METAL / EMISSIVE  v[0..2] = Texture::Evaluate(uv) of the material's texture, uv = (0.5 n.x + 0.5, 0.5 n.z + 0.5)
+ *     hit, TRANSPARENT                v[0..2] = (1, 1, 1)
+ *         either way                  v[3..5] = the hit normal (pos - c) / r (signed r, as the path uses it), v[6] = t, v[7] = 1,
+ *                                     id = the sphere's index in the uploaded list
+ *     miss                            v[0..2] = the sky material's texture at uv (0, 0) (Emit(Payload{})'s colour without the luminance),
+ *                                     v[3..7] = 0, id = 0xffffffff
+ * The context keeps a strip feat[pixel][8] of binary32 sums, feat[c] = feat[c] + v[c] added in increasing s, and id[pixel], the id of
+ * the sample added last; pixels are the local pixels of the row set, in the order of the HDR strip.
+ * Sequencing mirrors rt_render but is INDEPENDENT of the HDR accumulation: a call with s0 == 1, or the first call after
+ * rt_clear_features, starts an accumulation; a call with s0 == the previous s1 and the same W, H and row set continues it (same bits
+ * as one call over the whole range); anything else is RT_ERR_SEQUENCE.  rt_scene_upload voids the strips, and so does an
+ * rt_set_sampler that changes the flags.  rt_clear, rt_render, rt_resolve and the three progressive switches neither read nor change
+ * them, and the feature calls leave everything rt_render relies on untouched (they keep ray-generation tables of their own).
+ * With out_ms == NULL the call only enqueues work on the context's stream; else it waits and returns the HIP-event time. */
+int rt_render_features(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t s0, uint32_t s1, double* out_ms);
+/* Samples per pixel in the feature strips (0: nothing accumulated). */
+int rt_feature_samples(rt_ctx* ctx, uint32_t* out);
+/* Copy the raw sums to host.  feat8: W*local_rows*8 floats; ids: W*local_rows values.  Either pointer may be NULL.
+ * RT_ERR_SEQUENCE when nothing is accumulated. */
+int rt_download_features(rt_ctx* ctx, float* feat8, uint32_t* ids);
+/* Same, device to device into caller-owned device memory.  Asynchronous on the context's stream. */
+int rt_copy_features_to_device(rt_ctx* ctx, void* dev_feat8, void* dev_ids);
+/* Forget the feature strips; the next rt_render_features starts an accumulation at any s0. */
+int rt_clear_features(rt_ctx* ctx);
+
 /* Replaces the transform(par) tonemap (spheres-app.cpp:186-214): hdr / n_samples,
  * ACES fit, gamma 1/2.2, XMStoreColor.  n_samples == 0 uses the accumulated count. */
 int rt_resolve(rt_ctx* ctx, uint32_t n_samples);
@@ -352,6 +382,11 @@ int rt_unit_tile_cone(const rt_camera* camera, uint32_t W, uint32_t H, uint32_t 
 /* The estimate of rt_noise_map for given strips (3 floats per pixel each), from the same source compiled for the host (csrc/rt_noise.h):
  * out = 2 floats per pixel.  n < 2: RT_ERR_SEQUENCE.  Needs no GPU. */
 int rt_unit_noise_estimate_host(const float* hdr, const float* sq, uint32_t npix, uint32_t n, float floor, float* out);
+/* The per-sample step of the feature buffers for n hit records of rt_unit_closest_hit's format (hits10[1] = the original sphere index
+ * as bits, < 0 = miss), from the same source compiled for the host (csrc/rt_features.h): out8 = v[8] per record, out_ids = its id.
+ * materials: by original sphere index (an index >= n_materials is RT_ERR_INVALID_ARG).  Needs no GPU. */
+int rt_unit_features_host(const rt_material* materials, uint32_t n_materials, const rt_material* sky, const float* hits10, uint32_t n,
+                          float* out8, uint32_t* out_ids);
 /* The resolve of spheres-app.cpp:196-214 for given HDR triples -> R,G,B bytes */
 int rt_unit_tonemap(rt_ctx* ctx, const float* hdr_rgb, uint32_t n, uint32_t n_samples, uint8_t* out_rgb);
 
