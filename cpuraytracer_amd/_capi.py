@@ -60,6 +60,7 @@ EXPORTS = [
     "rt_set_noise_estimate", "rt_download_moments", "rt_noise_map", "rt_noise_summary", "rt_unit_noise_estimate_host",
     "rt_render_features", "rt_feature_samples", "rt_download_features", "rt_copy_features_to_device", "rt_clear_features",
     "rt_unit_features_host",
+    "rt_unit_shadow_index_host", "rt_unit_shadow_query_host", "rt_unit_shadow",
 ]
 
 _lib = None
@@ -147,6 +148,11 @@ def load():
         L.rt_copy_features_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_clear_features.argtypes = [C.c_void_p]
         L.rt_unit_features_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtMaterial), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "rt_unit_shadow"):
+        L.rt_unit_shadow_index_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtLight), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                                C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rt_unit_shadow_query_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtLight), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rt_unit_shadow.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     _lib = L
     return L
 

@@ -1,7 +1,8 @@
 // scene_prep_selftest.cpp -- the scene preparation (rt_scene_prep.h) in a program of its own: no device, no Python, no files.
 // Generates scenes from a fixed seed -- every layout kind, the sizes either side of a group of four, negative radii, coincident
 // centres, light lists of every length -- and checks the STRUCTURE of what PrepareScene returns: lengths, permutations, prefix
-// tables, the range of every 16-bit id.  Whether the bounds are conservative is not its business (the fuzz tests own that).
+// tables, the range of every 16-bit id.  Whether the scan's bounds are conservative is not its business (the fuzz tests own that);
+// of the shadow indices it checks the plain inclusion: every sphere's exact footprint lies in cells that list it.
 // Exit status 0 and one line per scene, or the first failed condition and status 1.  Also built with AddressSanitizer and
 // UBSan (make scene_prep_selftest_san): the index arithmetic of the builders then runs under both.
 #include <cmath>
@@ -119,7 +120,7 @@ std::vector<rt_material> MakeMaterials(uint32_t n, bool bytes, Rng& rng) {
     return m;
 }
 
-void CheckShadowGrid(const ShadowGrid& G, const SceneLayout& L, bool isDirection) {
+void CheckShadowGrid(const ShadowGrid& G, const SceneLayout& L, const std::vector<rt_sphere>& sp, bool isDirection) {
     if (!isDirection) CHECK(!G.enabled);
     if (!G.enabled) return;
     CHECK(G.nx >= 1 && G.ny >= 1);
@@ -129,6 +130,27 @@ void CheckShadowGrid(const ShadowGrid& G, const SceneLayout& L, bool isDirection
     for (size_t c = 1; c < G.cellStart.size(); ++c) CHECK(G.cellStart[c - 1] <= G.cellStart[c]);
     for (uint16_t e : G.entries) CHECK(e < L.scan.size() && L.orig[e] != 0xffffffffu);
     for (uint16_t e : G.global) CHECK(e < L.scan.size() && L.orig[e] != 0xffffffffu);
+    // inclusion, in plain double precision: the bounding square of every sphere's exact footprint -- the disc of radius |r| about
+    // the centre's projection -- lies inside the grid, in cells that all list the sphere; or the sphere is in the global list
+    std::vector<char> inGlobal(L.scan.size(), 0);
+    for (uint16_t e : G.global) inGlobal[e] = 1;
+    auto listed = [&](size_t c, size_t e) {
+        for (size_t k = G.cellStart[c]; k < G.cellStart[c + 1]; ++k)
+            if (G.entries[k] == e) return true;
+        return false;
+    };
+    for (size_t e = 0; e < L.scan.size(); ++e) {
+        if (L.orig[e] == 0xffffffffu || inGlobal[e]) continue;
+        const rt_sphere& q = sp[L.orig[e]];
+        const double r = std::fabs((double)q.r);
+        const double u = (double)q.cx * G.e1[0] + (double)q.cy * G.e1[1] + (double)q.cz * G.e1[2];
+        const double v = (double)q.cx * G.e2[0] + (double)q.cy * G.e2[1] + (double)q.cz * G.e2[2];
+        const double x0 = std::floor((u - r - (double)G.u0) * (double)G.invCell), x1 = std::floor((u + r - (double)G.u0) * (double)G.invCell);
+        const double y0 = std::floor((v - r - (double)G.v0) * (double)G.invCell), y1 = std::floor((v + r - (double)G.v0) * (double)G.invCell);
+        CHECK(x0 >= 0.0 && y0 >= 0.0 && x1 < (double)G.nx && y1 < (double)G.ny);
+        for (size_t y = (size_t)y0; y <= (size_t)y1; ++y)
+            for (size_t x = (size_t)x0; x <= (size_t)x1; ++x) CHECK(listed(y * G.nx + x, e));
+    }
 }
 
 // returns the layout kind: 0 flat, 1 grid, 2 hierarchy
@@ -195,8 +217,8 @@ int CheckScene(const std::vector<rt_sphere>& sp, const std::vector<rt_material>&
     // shadow indices
     auto isDirection = [](const rt_light& l) { return l.direction[0] != 0.f || l.direction[1] != 0.f || l.direction[2] != 0.f; };
     CHECK(P.extraShadow.size() + 1 == lights.size());
-    CheckShadowGrid(P.shadow, L, isDirection(lights[0]));
-    for (size_t k = 1; k < lights.size(); ++k) CheckShadowGrid(P.extraShadow[k - 1], L, isDirection(lights[k]));
+    CheckShadowGrid(P.shadow, L, sp, isDirection(lights[0]));
+    for (size_t k = 1; k < lights.size(); ++k) CheckShadowGrid(P.extraShadow[k - 1], L, sp, isDirection(lights[k]));
     if (P.shadow.enabled && L.InGlobalMemory())
         CHECK(P.sgSph.size() == P.shadow.entries.size() + 1);
     else

@@ -1861,6 +1861,118 @@ int rt_unit_grid_rows(const float* segments, const int32_t* iu, uint32_t n, int3
     return RT_OK;
 }
 
+// Host-only: the scene as rt_scene_upload prepares it under the environment of the moment (materials play no part in the index).
+static int PrepareForShadow(const char* who, const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light,
+                            rtprep::PreparedScene& P) {
+    if (!spheres || n == 0 || !lights || n_lights == 0 || n_lights > RT_MAX_LIGHTS || light >= n_lights)
+        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": invalid argument");
+    if (!rtprep::AllFinite(spheres, n, nullptr)) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a sphere's centre or radius is not finite");
+    const std::vector<rt_material> mats(n, rt_material{});
+    P = rtprep::PrepareScene(spheres, mats.data(), n, lights, n_lights, rtprep::PrepOptions::FromEnv());
+    if (P.layout.scan.size() >= 65536) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": scenes beyond 65,535 scan entries are not supported");
+    return RT_OK;
+}
+
+int rt_unit_shadow_index_host(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light, uint32_t out_u[8],
+                              float out_f[10], uint32_t cap_cells, uint16_t* cell_start, uint32_t cap_entries, uint16_t* entries,
+                              uint32_t cap_global, uint16_t* global, uint32_t cap_orig, uint32_t* orig) {
+    if (!out_u || !out_f) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow_index_host: invalid argument");
+    rtprep::PreparedScene P;
+    if (const int rc = PrepareForShadow("rt_unit_shadow_index_host", spheres, n, lights, n_lights, light, P)) return rc;
+    const rtprep::ShadowGrid& G = light == 0u ? P.shadow : P.extraShadow[light - 1u];
+    const std::vector<uint32_t>& O = P.layout.orig;
+    out_u[0] = G.enabled ? 1u : 0u;
+    out_u[1] = G.nx; out_u[2] = G.ny;
+    out_u[3] = (uint32_t)G.cellStart.size(); out_u[4] = (uint32_t)G.entries.size(); out_u[5] = (uint32_t)G.global.size();
+    out_u[6] = (uint32_t)O.size();
+    out_u[7] = P.layout.InGlobalMemory() ? 1u : 0u;
+    for (int k = 0; k < 3; ++k) {
+        out_f[k] = G.e1[k];
+        out_f[3 + k] = G.e2[k];
+    }
+    out_f[6] = G.u0; out_f[7] = G.v0; out_f[8] = G.invCell; out_f[9] = G.p0sq;
+    if ((cell_start && cap_cells < G.cellStart.size()) || (entries && cap_entries < G.entries.size()) || (global && cap_global < G.global.size()) ||
+        (orig && cap_orig < O.size()))
+        return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow_index_host: capacity too small");
+    if (cell_start && !G.cellStart.empty()) std::memcpy(cell_start, G.cellStart.data(), G.cellStart.size() * sizeof(uint16_t));
+    if (entries && !G.entries.empty()) std::memcpy(entries, G.entries.data(), G.entries.size() * sizeof(uint16_t));
+    if (global && !G.global.empty()) std::memcpy(global, G.global.data(), G.global.size() * sizeof(uint16_t));
+    if (orig && !O.empty()) std::memcpy(orig, O.data(), O.size() * sizeof(uint32_t));
+    return RT_OK;
+}
+
+// Host-only: rt_shade.h's shadow_query and any_hit_all themselves (RT_DEV is __host__ __device__), asked as rt_kernels.h's hit
+// processing asks them -- light 0 through the scene constants fill_consts makes of the launch parameters, lights 1 .. through
+// their LightRec -- over the prepared tables where they lie on the host.
+int rt_unit_shadow_query_host(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light,
+                              const float* points, uint32_t n_points, uint8_t* out) {
+    if ((!points || !out) && n_points != 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow_query_host: invalid argument");
+    rtprep::PreparedScene P;
+    if (const int rc = PrepareForShadow("rt_unit_shadow_query_host", spheres, n, lights, n_lights, light, P)) return rc;
+    const rtprep::ShadowGrid& G = light == 0u ? P.shadow : P.extraShadow[light - 1u];
+    const float4* scanTab = reinterpret_cast<const float4*>(P.layout.scan.data());
+    const uint32_t nPad = (uint32_t)P.layout.scan.size();
+    const uint16_t none = 0;  // an empty list still has an address (UploadShadowGrid)
+    const uint16_t* cells = G.cellStart.empty() ? &none : G.cellStart.data();
+    const uint16_t* ents = G.entries.empty() ? &none : G.entries.data();
+    const uint16_t* glob = G.global.empty() ? &none : G.global.data();
+    rtd::TraceParams tp{};
+    rtd::LightRec R{};
+    for (int c = 0; c < 3; ++c) {
+        tp.sun_dir[c] = R.sun_dir[c] = lights[light].direction[c];
+        tp.sg_e1[c] = R.sg_e1[c] = G.e1[c];
+        tp.sg_e2[c] = R.sg_e2[c] = G.e2[c];
+    }
+    tp.sg_enabled = R.sg_enabled = G.enabled ? 1u : 0u;
+    tp.sg_u0 = R.sg_u0 = G.u0; tp.sg_v0 = R.sg_v0 = G.v0; tp.sg_inv_cell = R.sg_inv_cell = G.invCell; tp.sg_p0sq = R.sg_p0sq = G.p0sq;
+    tp.sg_nx = R.sg_nx = G.nx; tp.sg_ny = R.sg_ny = G.ny; tp.sg_nglobal = R.sg_nglobal = (uint32_t)G.global.size();
+    R.cell_start = cells; R.entries = ents; R.global = glob;
+    rtd::SceneConsts K;
+    rtd::fill_consts(tp, K);
+    const float4* entrySph = (light == 0u && !P.sgSph.empty()) ? reinterpret_cast<const float4*>(P.sgSph.data()) : nullptr;
+    for (uint32_t k = 0; k < n_points; ++k) {
+        const rtd::V3 pos = rtd::v3(points[3 * (size_t)k], points[3 * (size_t)k + 1], points[3 * (size_t)k + 2]);
+        const float pp = rtd::dot3(pos, pos);
+        bool useIndex, occ;
+        if (light == 0u) {
+            const rtd::V3 sunDir = rtd::v3(K.sun_dir[0], K.sun_dir[1], K.sun_dir[2]);
+            const float aSun = rtd::dot3(sunDir, sunDir);
+            useIndex = K.sg_enabled && pp <= K.sg_p0sq;
+            occ = useIndex ? rtd::shadow_query(K, scanTab, cells, ents, glob, false, (const float4*)nullptr, (const uint16_t*)nullptr, entrySph, pos, sunDir, aSun)
+                           : rtd::any_hit_all(scanTab, nPad, pos, sunDir, aSun);
+        } else {
+            const rtd::LightRec& Lk = R;
+            const rtd::V3 dirK = rtd::v3(Lk.sun_dir[0], Lk.sun_dir[1], Lk.sun_dir[2]);
+            const float aK = rtd::dot3(dirK, dirK);
+            useIndex = Lk.sg_enabled && pp <= Lk.sg_p0sq;
+            occ = useIndex ? rtd::shadow_query(Lk, scanTab, Lk.cell_start, Lk.entries, Lk.global, false, (const float4*)nullptr, (const uint16_t*)nullptr,
+                                               (const float4*)nullptr, pos, dirK, aK)
+                           : rtd::any_hit_all(scanTab, nPad, pos, dirK, aK);
+        }
+        out[k] = (uint8_t)((occ ? 1u : 0u) | (useIndex ? 0u : 2u));
+    }
+    return RT_OK;
+}
+
+int rt_unit_shadow(rt_ctx* ctx, uint32_t light, const float* points, uint32_t n, uint32_t glob_in_lds, uint8_t* out) {
+    if (!ctx || !points || !out) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow: invalid argument");
+    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_shadow: no scene uploaded");
+    if (light >= std::max(1u, ctx->base.n_lights)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow: the scene has no such light");
+    if (n == 0) return RT_OK;
+    RT_HIP(hipSetDevice(ctx->device));
+    TmpDev<float> dIn;
+    TmpDev<uint8_t> dOut;
+    RT_HIP(dIn.Alloc((size_t)n * 3));
+    RT_HIP(dOut.Alloc(n));
+    RT_HIP(hipMemcpy(dIn.p, points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    const size_t lds = (size_t)rtd::sg_glob_slots(64u) * 16;  // a global list has 64 entries at most (BuildShadowGrid)
+    hipLaunchKernelGGL(rtd::k_unit_shadow, dim3((n + 255) / 256), dim3(256), lds, ctx->stream, ctx->base, light, glob_in_lds, dIn.p, n, dOut.p);
+    RT_HIP(hipGetLastError());
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    RT_HIP(hipMemcpy(out, dOut.p, n, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t cap_tiles, uint32_t* n_tiles, uint32_t* words,
                        uint32_t cap_spheres, uint32_t* group_of_sphere, uint64_t scans[2]) {
     if (!ctx || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: invalid argument");

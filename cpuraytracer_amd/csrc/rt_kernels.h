@@ -1657,6 +1657,46 @@ __global__ void k_unit_scatter(const TraceParams p, const rt_material* mat, cons
     w[7] = (float)draws.used;
     w[8] = local.x; w[9] = local.y; w[10] = local.z;
 }
+// The shadow question of the hit processing (processHit above) for given points and light `light` of the scene's list, over the
+// uploaded tables: out = bit 0 occluded | bit 1 answered by any_hit_all (index off, or |p|^2 > sg_p0sq).  globLds: the index's
+// global list from an LDS copy of (spheres, ids), staged as rt_trace_kernel's prologue stages globSph / globIds (dynamic LDS:
+// sg_glob_slots(global entries) float4); else from its id list.
+__global__ void __launch_bounds__(256) k_unit_shadow(const TraceParams p, uint32_t light, uint32_t globLds, const float* pts, uint32_t n, uint8_t* out) {
+    extern __shared__ float4 smem[];
+    const LightRec* Lk = light != 0u ? p.extra_lights + (light - 1u) : nullptr;
+    const bool enabled = (Lk ? Lk->sg_enabled : p.sg_enabled) != 0u;
+    const uint32_t nGlob = enabled ? (Lk ? Lk->sg_nglobal : p.sg_nglobal) : 0u;
+    const uint16_t* glob = Lk ? Lk->global : p.sg_global;
+    float4* globSph = smem;
+    uint16_t* globIds = reinterpret_cast<uint16_t*>(globSph + nGlob);
+    const bool inLds = globLds != 0u && enabled;
+    if (inLds)
+        for (uint32_t k = threadIdx.x; k < nGlob; k += blockDim.x) {
+            const uint32_t id = glob[k];
+            globSph[k] = p.scan[id];
+            globIds[k] = (uint16_t)id;
+        }
+    __syncthreads();
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const V3 pos = v3(pts[3 * (size_t)k], pts[3 * (size_t)k + 1], pts[3 * (size_t)k + 2]);
+    const float pp = dot3(pos, pos);
+    bool useIndex, occ;
+    if (Lk == nullptr) {
+        const V3 sunDir = v3(p.sun_dir[0], p.sun_dir[1], p.sun_dir[2]);
+        const float aSun = dot3(sunDir, sunDir);
+        useIndex = p.sg_enabled && pp <= p.sg_p0sq;
+        occ = useIndex ? shadow_query(p, p.scan, p.sg_cell_start, p.sg_entries, p.sg_global, inLds, globSph, globIds, p.sg_sph, pos, sunDir, aSun)
+                       : any_hit_all(p.scan, p.n_padded, pos, sunDir, aSun);
+    } else {
+        const V3 dirK = v3(Lk->sun_dir[0], Lk->sun_dir[1], Lk->sun_dir[2]);
+        const float aK = dot3(dirK, dirK);
+        useIndex = Lk->sg_enabled && pp <= Lk->sg_p0sq;
+        occ = useIndex ? shadow_query(*Lk, p.scan, Lk->cell_start, Lk->entries, Lk->global, inLds, globSph, globIds, (const float4*)nullptr, pos, dirK, aK)
+                       : any_hit_all(p.scan, p.n_padded, pos, dirK, aK);
+    }
+    out[k] = (uint8_t)((occ ? 1u : 0u) | (useIndex ? 0u : 2u));
+}
 // Resolve for given HDR triples (tonemap unit test): in 3 floats, out 3 bytes
 __global__ void k_unit_tonemap(const float* hdr, uint32_t n, uint32_t nSamples, uint8_t* out) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;

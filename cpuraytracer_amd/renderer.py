@@ -223,6 +223,15 @@ class HipRenderer:
         check(self._L.rt_unit_closest_hit(self._h, rays.ctypes.data, rays.shape[0], out.ctypes.data))
         return out
 
+    def unit_shadow(self, light, points, glob_in_lds=False):
+        """One byte per point (3 floats each) for light `light` of the uploaded scene: bit 0 = the light is occluded there, bit 1 = the
+        answer came from the any-hit over every scan entry, not from the light's shadow index.  glob_in_lds: the index's global list
+        is walked from its copy in LDS, as the trace kernel stages it."""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(points.shape[0], dtype=np.uint8)
+        check(self._L.rt_unit_shadow(self._h, int(light), points.ctypes.data, points.shape[0], 1 if glob_in_lds else 0, out.ctypes.data))
+        return out
+
     def unit_trace(self, W, H, ijs, max_depth, seed):
         ijs = np.ascontiguousarray(ijs, dtype=np.uint32).reshape(-1, 3)
         rgb = np.zeros((ijs.shape[0], 3), dtype=np.float32)

@@ -387,6 +387,24 @@ int rt_unit_noise_estimate_host(const float* hdr, const float* sq, uint32_t npix
  * materials: by original sphere index (an index >= n_materials is RT_ERR_INVALID_ARG).  Needs no GPU. */
 int rt_unit_features_host(const rt_material* materials, uint32_t n_materials, const rt_material* sky, const float* hits10, uint32_t n,
                           float* out8, uint32_t* out_ids);
+/* The shadow index rt_scene_upload would build for light `light` of the list, under the environment of the moment.
+ * out_u: [0] 1 = the index is enabled (else nothing more is valid: every shadow ray of this light is answered over every scan
+ * entry), [1] nx, [2] ny, [3] elements of cell_start (nx * ny + 1), [4] of entries, [5] of global, [6] scan entries (elements of orig),
+ * [7] 1 = the scan's tables stay in global memory (cell grid, hierarchy).  out_f: e1 3, e2 3, u0, v0, 1 / cell size, p0sq.
+ * cell_start, entries, global (16-bit scan-entry ids) and orig (original sphere index of every scan entry, 0xffffffff = padding) are
+ * written where the pointer is not null; a capacity below the count is RT_ERR_INVALID_ARG.  Needs no GPU. */
+int rt_unit_shadow_index_host(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light, uint32_t out_u[8],
+                              float out_f[10], uint32_t cap_cells, uint16_t* cell_start, uint32_t cap_entries, uint16_t* entries,
+                              uint32_t cap_global, uint16_t* global, uint32_t cap_orig, uint32_t* orig);
+/* The shadow question of the hit processing for n_points points (3 floats each) and that light, answered on the host by the source the
+ * kernels compile (csrc/rt_shade.h shadow_query and any_hit_all over the tables above): one byte per point, bit 0 = occluded, bit 1 =
+ * answered over every scan entry (the index is off, or |p|^2 > p0sq) and not from the index.  Needs no GPU. */
+int rt_unit_shadow_query_host(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light,
+                              const float* points, uint32_t n_points, uint8_t* out);
+/* ... and by the device, over the tables rt_scene_upload put there for the uploaded scene (light 0: the launch parameters' index,
+ * lights 1 ..: their records): the same byte per point.  glob_in_lds != 0: the index's global list is walked from a copy of
+ * (spheres, ids) in LDS, staged as the trace kernel stages it; 0: from its id list in global memory. */
+int rt_unit_shadow(rt_ctx* ctx, uint32_t light, const float* points, uint32_t n, uint32_t glob_in_lds, uint8_t* out);
 /* The resolve of spheres-app.cpp:196-214 for given HDR triples -> R,G,B bytes */
 int rt_unit_tonemap(rt_ctx* ctx, const float* hdr_rgb, uint32_t n, uint32_t n_samples, uint8_t* out_rgb);
 
