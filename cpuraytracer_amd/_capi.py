@@ -56,7 +56,7 @@ EXPORTS = [
     "rt_scene_upload", "rt_render", "rt_clear", "rt_resolve", "rt_last_resolve_ms", "rt_download", "rt_copy_to_device",
     "rt_synchronize", "rt_rowset_local_rows", "rt_rowset_global_row", "rt_unit_halton", "rt_unit_math",
     "rt_unit_primary_rays", "rt_unit_closest_hit", "rt_unit_trace", "rt_unit_camera_rays", "rt_unit_scatter", "rt_unit_tonemap", "rt_unit_layout", "rt_unit_layout_info", "rt_unit_grid_rows", "rt_unit_grid_info",
-    "rt_unit_tile_masks", "rt_unit_tile_masks_host", "rt_unit_tile_cone", "rt_unit_tile_spheres", "rt_unit_tile_spheres_host", "rt_unit_sky_planes",
+    "rt_unit_tile_masks", "rt_unit_tile_masks_host", "rt_unit_tile_cone", "rt_unit_tile_spheres", "rt_unit_tile_spheres_host", "rt_unit_sky_planes", "rt_unit_sky_excluded",
     "rt_set_noise_estimate", "rt_download_moments", "rt_noise_map", "rt_noise_summary", "rt_unit_noise_estimate_host",
     "rt_render_features", "rt_feature_samples", "rt_download_features", "rt_copy_features_to_device", "rt_clear_features",
     "rt_unit_features_host",
@@ -131,6 +131,8 @@ def load():
         L.rt_unit_tile_cone.argtypes = [C.POINTER(RtCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     if hasattr(L, "rt_unit_sky_planes"):
         L.rt_unit_sky_planes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    if hasattr(L, "rt_unit_sky_excluded"):
+        L.rt_unit_sky_excluded.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     if hasattr(L, "rt_unit_tile_spheres"):
         L.rt_unit_tile_spheres.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
         L.rt_unit_tile_spheres_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtCamera), C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.c_uint32,

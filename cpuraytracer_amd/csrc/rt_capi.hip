@@ -158,11 +158,26 @@ struct rt_ctx {
     uint32_t treeTop = 128;  // largest top level the matrix-core filter takes (4 tiles of 32); RT_TREE_TOP overrides
     bool forceGlobal = false;
 
-    // work order of the tiles (BuildTileOrder): valid for the running accumulation's strip
+    // work order of the tiles and the flags of the empty-list tiles (BuildTileOrder): valid for the running accumulation's strip
     bool useTileOrder = true;  // RT_TILE_ORDER=0 keeps the image order
+    bool tileKeyValid = false;    // the key below describes what tileOrderValid / skyFlagsValid say there is
     bool tileOrderValid = false;
-    uint32_t tileW = 0, tileH = 0;  // ... and the image and strip it was built for (with the scene, all it depends on)
+    uint32_t tileW = 0, tileH = 0;  // ... and the image and strip they were built for (with the scene and the lists, all they depend on)
     rt_rowset tileRs{};
+    uint32_t tileListLimit = 0, tileListSpheres = 0;  // the lists' limits the flags were taken under (0, 0: no flags)
+    // Empty-list tiles kept out of the trace queue (rt_kernels.h rt_sky_tiles_kernel).  The flags share the order's key and lifetime;
+    // with them the order ends with exactly the flagged tiles.  Their number reaches the host through pinned memory and an event that
+    // is only ever QUERIED: until it has completed the count is unknown and every launch queues all tiles.
+    bool skyExclude = true;       // RT_SKY_EXCLUDE, read where an accumulation starts
+    bool skyFlagsValid = false;
+    bool skyCountPending = false, skyCountKnown = false;
+    uint32_t skyEmpty = 0;        // flagged tiles, once known
+    bool lastTraceSky = false;    // the last ordinary LaunchTrace took a kernel that finishes empty-list planes itself (rt_kernels.h kSky)
+    uint32_t skyExcluded = 0;     // tiles the last rt_render that launched a trace kernel kept out of its queue (rt_unit_sky_excluded)
+    DevBuf<uint8_t> skyFlags;     // [full tiles]
+    DevBuf<uint32_t> skyInfo;     // [0] flagged tiles, [1..3] the constant sample's bits
+    uint32_t* skyCountHost = nullptr;  // pinned
+    hipEvent_t skyEv = nullptr;
     DevBuf<float> pilotRays, pilotHits;
     DevBuf<uint32_t> tileOrder, matType;
     DevBuf<uint8_t> tileClass;
@@ -451,6 +466,7 @@ static int LaunchTrace(rt_ctx* ctx, rtd::TraceParams& tp, int carryMode = 0) {
         else if (ctx->blockThreads == 512) RT_LAUNCH(LDS, 512, M);     \
         else RT_LAUNCH(LDS, 256, M);                                   \
     } while (0)
+    ctx->lastTraceSky = carryMode == 0 && useStash && !grid && !tree;  // kStash && kScan == 1 && !kCarry
     if (carryMode == 2) RT_LAUNCH_K(true, 1024, 1, true, true, true);
     else if (gridLds && useStash && tp.grid_in_lds) RT_LAUNCH_K(true, 1024, 3, true, true, false, true);
     else if (gridLds && tp.grid_in_lds && tp.ray_cache_off16) RT_LAUNCH_K(true, 1024, 3, true, true);
@@ -569,43 +585,6 @@ static int LaunchFeatures(rt_ctx* ctx, rtd::TraceParams& tp, const rtd::FeatureP
     return RT_OK;
 }
 
-// Work order of the full tiles for the accumulation that is starting (rt_kernels.h, rt_tile_order_kernel): three pilot rays per
-// tile through the production scan, then a stable sort by the most expensive first-hit material.  All on the stream, no host wait.
-static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t npix) {
-    // the order is a function of the scene (camera included), the image size and the strip: a new accumulation of the same
-    // picture -- a progressive restart, the next frame of a turntable with an unchanged scene -- keeps the one it has
-    if (ctx->tileOrderValid && ctx->tileW == W && ctx->tileH == H && std::memcmp(&ctx->tileRs, &rs, sizeof(rs)) == 0) return RT_OK;
-    ctx->tileOrderValid = false;
-    const uint32_t nFull = npix >> 6;
-    if (!ctx->useTileOrder || nFull < 2u * (uint32_t)ctx->cuCount) return RT_OK;  // too little work for the order to matter
-    int rc;
-    const uint32_t nPilot = nFull * rtd::kPilotsPerTile;
-    if ((rc = ctx->pilotRays.Reserve((size_t)nPilot * 6)) != RT_OK) return rc;
-    if ((rc = ctx->pilotHits.Reserve((size_t)nPilot * 10)) != RT_OK) return rc;
-    if ((rc = ctx->tileClass.Reserve(nFull)) != RT_OK) return rc;
-    if ((rc = ctx->tileOrder.Reserve(nFull)) != RT_OK) return rc;
-    rtd::TraceParams tp = ctx->base;
-    tp.W = W;
-    tp.H = H;
-    tp.rs = rs;
-    tp.s0 = 1;
-    tp.sampler = ctx->sampler;
-    tp.jitter_tab = nullptr;
-    tp.lens_tab = nullptr;
-    hipLaunchKernelGGL(rtd::rt_pilot_rays_kernel, dim3((nPilot + 255) / 256), dim3(256), 0, ctx->stream, tp, nFull, ctx->pilotRays.ptr);
-    RT_HIP(hipGetLastError());
-    if ((rc = LaunchClosest(ctx, ctx->pilotRays.ptr, nPilot, ctx->pilotHits.ptr)) != RT_OK) return rc;
-    hipLaunchKernelGGL(rtd::rt_tile_class_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->pilotHits.ptr, nFull, W,
-                       ctx->matType.ptr, ctx->tileClass.ptr);
-    hipLaunchKernelGGL(rtd::rt_tile_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->tileClass.ptr, nFull, ctx->tileOrder.ptr);
-    RT_HIP(hipGetLastError());
-    ctx->tileOrderValid = true;
-    ctx->tileW = W;
-    ctx->tileH = H;
-    ctx->tileRs = rs;
-    return RT_OK;
-}
-
 // Candidate masks of the full tiles' primary rays for the accumulation that is starting (rt_tile_mask.h): one small kernel on
 // the stream, no host wait.  Like the tile order they are a function of the scene (camera included), the image size and the strip,
 // and are kept across accumulations of the same picture.  Only the flat matrix-core scan of the hit-stash kernels reads them.
@@ -613,7 +592,8 @@ static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
 // than this keep the filter.  RT_PRIMARY_SPHERES: tiles with a mask and at most this many reachable spheres also get a sphere list and
 // resolve their primary rays directly (rt_scan.h scan_tile_spheres); 0 = no lists, values above kTileSphereMax are clamped.
 // RT_SKY_SKIP=0 (read by rt_render where an accumulation starts): tiles whose list is empty generate and scan their rays like every
-// other listed tile (rt_kernels.h kSky).
+// other listed tile (rt_kernels.h kSky).  RT_SKY_EXCLUDE=0 (read there too): those tiles are not flagged -- every launch queues every tile
+// and the accumulation reads every plane from the sample buffer (BuildTileOrder).
 static uint32_t TileSphereLimitFromEnv() {
     const uint32_t v = EnvU32("RT_PRIMARY_SPHERES", rtd::kTileSphereLimitDefault);
     return v > rtd::kTileSphereMax ? rtd::kTileSphereMax : v;
@@ -650,6 +630,89 @@ static int BuildTileMasks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
     ctx->maskSpheres = sphLimit;
     ctx->maskTiles = nFull;
     ctx->maskRs = rs;
+    return RT_OK;
+}
+
+// Work order of the full tiles for the accumulation that is starting (rt_kernels.h, rt_tile_order_kernel): three pilot rays per
+// tile through the production scan, then a stable sort by the most expensive first-hit material.  All on the stream, no host wait.
+// Runs AFTER BuildTileMasks: where the tiles have sphere lists (and RT_SKY_SKIP and RT_SKY_EXCLUDE are on) the tiles with an empty
+// list are flagged first (rt_sky_tiles_kernel) and sorted behind all others, and their number is copied to pinned host memory
+// behind an event, for the later calls that find it complete (SkyCountPoll) to leave them out of the queue.
+static void DropTileOrder(rt_ctx* ctx) {
+    ctx->tileKeyValid = ctx->tileOrderValid = ctx->skyFlagsValid = false;
+    ctx->skyCountPending = ctx->skyCountKnown = false;
+    ctx->aheadValid = false;  // (planes traced ahead by a truncated launch are only complete together with the flags)
+}
+static void SkyCountPoll(rt_ctx* ctx) {
+    if (!ctx->skyCountPending) return;
+    const hipError_t e = hipEventQuery(ctx->skyEv);
+    if (e == hipSuccess) {
+        ctx->skyCountPending = false;
+        ctx->skyCountKnown = true;
+        ctx->skyEmpty = *ctx->skyCountHost;
+    } else if (e == hipErrorNotReady) {
+        (void)hipGetLastError();  // "not ready" is an answer, not an error of the calls that follow
+    } else {
+        ctx->skyCountPending = false;  // a real error: the count stays unknown, and the error is left for the call that follows to report
+    }
+}
+static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t npix) {
+    // order and flags are a function of the scene (camera included), the image size, the strip and the lists' limits: a new
+    // accumulation of the same picture -- a progressive restart, the next frame of a turntable with an unchanged scene -- keeps them
+    const uint32_t nFull = npix >> 6;
+    const bool lists = ctx->tileMaskValid && ctx->maskSpheres != 0u && nFull != 0u;  // (BuildTileMasks has just run for this picture)
+    const bool wantFlags = lists && ctx->skySkip && ctx->skyExclude;
+    const uint32_t keyLimit = wantFlags ? ctx->maskLimit : 0u, keySpheres = wantFlags ? ctx->maskSpheres : 0u;
+    if (ctx->tileKeyValid && ctx->tileW == W && ctx->tileH == H && std::memcmp(&ctx->tileRs, &rs, sizeof(rs)) == 0 &&
+        ctx->tileListLimit == keyLimit && ctx->tileListSpheres == keySpheres)
+        return RT_OK;
+    DropTileOrder(ctx);
+    int rc;
+    if (wantFlags) {
+        if (!ctx->skyEv) RT_HIP(hipEventCreateWithFlags(&ctx->skyEv, hipEventDisableTiming));
+        if (!ctx->skyCountHost) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->skyCountHost), sizeof(uint32_t), hipHostMallocDefault));
+        if ((rc = ctx->skyFlags.Reserve(nFull)) != RT_OK) return rc;
+        if ((rc = ctx->skyInfo.Reserve(4)) != RT_OK) return rc;
+        RT_HIP(hipMemsetAsync(ctx->skyInfo.ptr, 0, 4 * sizeof(uint32_t), ctx->stream));
+        hipLaunchKernelGGL(rtd::rt_sky_tiles_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->base, ctx->tileSpheres.ptr, nFull,
+                           ctx->skyFlags.ptr, ctx->skyInfo.ptr);
+        RT_HIP(hipGetLastError());
+        ctx->skyFlagsValid = true;
+    }
+    if (ctx->useTileOrder && nFull >= 2u * (uint32_t)ctx->cuCount) {  // (else too little work for the order to matter)
+        const uint32_t nPilot = nFull * rtd::kPilotsPerTile;
+        if ((rc = ctx->pilotRays.Reserve((size_t)nPilot * 6)) != RT_OK) return rc;
+        if ((rc = ctx->pilotHits.Reserve((size_t)nPilot * 10)) != RT_OK) return rc;
+        if ((rc = ctx->tileClass.Reserve(nFull)) != RT_OK) return rc;
+        if ((rc = ctx->tileOrder.Reserve(nFull)) != RT_OK) return rc;
+        rtd::TraceParams tp = ctx->base;
+        tp.W = W;
+        tp.H = H;
+        tp.rs = rs;
+        tp.s0 = 1;
+        tp.sampler = ctx->sampler;
+        tp.jitter_tab = nullptr;
+        tp.lens_tab = nullptr;
+        hipLaunchKernelGGL(rtd::rt_pilot_rays_kernel, dim3((nPilot + 255) / 256), dim3(256), 0, ctx->stream, tp, nFull, ctx->pilotRays.ptr);
+        RT_HIP(hipGetLastError());
+        if ((rc = LaunchClosest(ctx, ctx->pilotRays.ptr, nPilot, ctx->pilotHits.ptr)) != RT_OK) return rc;
+        hipLaunchKernelGGL(rtd::rt_tile_class_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->pilotHits.ptr, nFull, W,
+                           ctx->matType.ptr, ctx->tileClass.ptr, wantFlags ? ctx->skyFlags.ptr : (const uint8_t*)nullptr);
+        hipLaunchKernelGGL(rtd::rt_tile_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->tileClass.ptr, nFull, ctx->tileOrder.ptr);
+        RT_HIP(hipGetLastError());
+        ctx->tileOrderValid = true;
+        if (wantFlags) {  // only a launch that has the order can leave the flagged tiles out: without it nobody needs their number
+            RT_HIP(hipMemcpyAsync(ctx->skyCountHost, ctx->skyInfo.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            RT_HIP(hipEventRecord(ctx->skyEv, ctx->stream));
+            ctx->skyCountPending = true;
+        }
+    }
+    ctx->tileKeyValid = true;
+    ctx->tileW = W;
+    ctx->tileH = H;
+    ctx->tileRs = rs;
+    ctx->tileListLimit = keyLimit;
+    ctx->tileListSpheres = keySpheres;
     return RT_OK;
 }
 
@@ -906,6 +969,10 @@ void rt_destroy(rt_ctx* ctx) {
     ctx->tileMasks.Release();
     ctx->tileSpheres.Release();
     ctx->tileClass.Release();
+    ctx->skyFlags.Release();
+    ctx->skyInfo.Release();
+    if (ctx->skyCountHost) (void)hipHostFree(ctx->skyCountHost);
+    if (ctx->skyEv) (void)hipEventDestroy(ctx->skyEv);
     ctx->matType.Release();
     ctx->ring.Release();
     ctx->cont[0].Release();
@@ -933,6 +1000,10 @@ int rt_set_stream(rt_ctx* ctx, void* hip_stream) {
         if (rcf != RT_OK) return rcf;
     }
     ctx->aheadValid = false;  // (planes traced ahead were produced on the old stream)
+    // (... and so were the order, the flags and the copy of their count, which must not land in the pinned word after a newer one's:
+    // the one place that waits for it, and only when a picture's tables were built and never rendered from again)
+    if (ctx->skyCountPending) RT_HIP(hipEventSynchronize(ctx->skyEv));
+    DropTileOrder(ctx);
     ctx->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx->ownStream;
     return RT_OK;
 }
@@ -978,7 +1049,7 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     ctx->mats16Ok = P.mats16Ok;
     if (P.mats16Ok && (rc = ctx->mats16.Upload(P.mats16)) != RT_OK) return rc;
     if ((rc = ctx->matType.Upload(P.matType)) != RT_OK) return rc;
-    ctx->tileOrderValid = false;
+    DropTileOrder(ctx);
     ctx->tileMaskValid = false;
     // lights 1 .. : one index each, in global memory (256 x 256 cells at most), and their records
     std::vector<rtd::LightRec> recs;
@@ -1122,7 +1193,7 @@ int rt_set_sampler(rt_ctx* ctx, uint32_t flags) {
         ctx->pendOn = false;   // (pending frames of the old mapping are dropped with the accumulation they belonged to)
         ctx->accumulated = 0;  // samples of two mappings do not mix: the next rt_render starts over
         PipelineDrop(ctx);
-        ctx->tileOrderValid = false;  // the pilot rays use the lens mapping
+        DropTileOrder(ctx);  // the pilot rays use the lens mapping
         ctx->featCount = 0;           // ... and so do the feature pass's primary rays
     }
     ctx->sampler = flags;
@@ -1156,8 +1227,18 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
 
 // The ordered accumulation of the planes [first, first + count) of the sample buffer: with rt_set_noise_estimate on, the kernel that
 // also adds their squares to the strip of second moments (same hdr bits); off, the plain one.
+// With flags of the empty-list tiles (BuildTileOrder) the tile-aware forms: the flagged tiles' planes are the constant, whether the
+// launch that traced the buffer wrote them or left them out.
 static void LaunchAccumulate(rt_ctx* ctx, uint32_t npix, uint32_t spp, uint32_t first, uint32_t count) {
-    if (ctx->noise)
+    if (ctx->skyFlagsValid) {
+        const float* skyC = reinterpret_cast<const float*>(ctx->skyInfo.ptr + 1);  // (the constant sample follows the count)
+        if (ctx->noise)
+            hipLaunchKernelGGL(rtd::rt_accumulate_moments_tiles_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr,
+                               ctx->hdr.ptr, ctx->sq.ptr, npix, spp, first, count, ctx->skyFlags.ptr, skyC);
+        else
+            hipLaunchKernelGGL(rtd::rt_accumulate_tiles_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr,
+                               ctx->hdr.ptr, npix, spp, first, count, ctx->skyFlags.ptr, skyC);
+    } else if (ctx->noise)
         hipLaunchKernelGGL(rtd::rt_accumulate_moments_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr, ctx->hdr.ptr,
                            ctx->sq.ptr, npix, spp, first, count);
     else
@@ -1253,6 +1334,7 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
     if (npix64 > (1ull << 31) || (uint64_t)W * H > 0xffffffffull) return Fail(RT_ERR_INVALID_ARG, "rt_render: image too large");
     RT_HIP(hipSetDevice(ctx->device));
     const uint32_t npix = (uint32_t)npix64;
+    SkyCountPoll(ctx);  // (before any table is rebuilt: the call that builds the flags never sees their number, whatever the timing)
 
     const bool sameStrip = ctx->W == W && ctx->H == H && ctx->rows == rows && std::memcmp(&ctx->rs, &rs, sizeof(rs)) == 0;
     // frame pipelining: only calls that ask for no statistics may leave work in flight; anything else first settles it
@@ -1283,14 +1365,16 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
         ctx->rows = rows;
         ctx->rs = rs;
         ctx->accumulated = 0;
-        if ((rc = BuildTileOrder(ctx, W, H, rs, npix)) != RT_OK) return rc;
+        ctx->skySkip = EnvU32("RT_SKY_SKIP", 1u) != 0u;  // (no mask table depends on it; the unit entries that rebuild tables leave it alone)
+        ctx->skyExclude = EnvU32("RT_SKY_EXCLUDE", 1u) != 0u;
         if ((rc = BuildTileMasks(ctx, W, H, rs, npix)) != RT_OK) return rc;
-        ctx->skySkip = EnvU32("RT_SKY_SKIP", 1u) != 0u;  // (no table depends on it; the unit entries that rebuild tables leave it alone)
+        if ((rc = BuildTileOrder(ctx, W, H, rs, npix)) != RT_OK) return rc;  // (after the masks: it flags the tiles whose list is empty)
     } else if (!sameStrip || s0 != ctx->accumulated + 1) {
         return Fail(RT_ERR_SEQUENCE, "rt_render: sample range or row set does not continue the accumulation");
     }
 
     if (pipelined) {
+        ctx->skyExcluded = 0;  // (the carrying kernel's launch queues every tile)
         int rcp = PipelineRender(ctx, W, H, rs, npix, s0, s1, max_depth, seed);
         if (rcp != RT_OK) {
             ctx->accumulated = 0;
@@ -1326,9 +1410,19 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
     uint32_t passes = 0;
     auto runPasses = [&]() -> int {
         int rc;
-        RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 6 * sizeof(unsigned long long), ctx->stream));
         ctx->freshScans = 0;
         const uint32_t sEnd = aheadEnd ? aheadEnd : s1;
+        // Empty-list tiles stay out of the queue when their number had arrived when this call began (never waited for), they are the order's tail, the
+        // kernel would finish them without rays anyway (sky_skip below) and no partial tile follows the full ones in path-index
+        // space.  Their share of the counters is added behind each launch; their samples are the accumulation's constant (LaunchAccumulate).
+        const uint32_t nFull = npix >> 6;
+        const bool listsHere = ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0 && ctx->maskSpheres != 0u;
+        const uint32_t nSky = (ctx->skyFlagsValid && ctx->skyCountKnown && ctx->tileOrderValid && listsHere && ctx->skySkip && (npix & 63u) == 0u &&
+                               ctx->skyEmpty < nFull)
+                                  ? ctx->skyEmpty
+                                  : 0u;
+        RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 6 * sizeof(unsigned long long), ctx->stream));
+        ctx->skyExcluded = nSky;
         for (uint32_t s = s0; s < sEnd; s += sppPass) {
             const uint32_t spp = (sEnd - s) < sppPass ? (sEnd - s) : sppPass;
             rtd::TraceParams tp = ctx->base;
@@ -1348,7 +1442,8 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
             tp.tile_masks = (ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0) ? ctx->tileMasks.ptr : nullptr;
             tp.tile_spheres = (tp.tile_masks != nullptr && ctx->maskSpheres != 0u) ? ctx->tileSpheres.ptr : nullptr;
             tp.sky_skip = (tp.tile_spheres != nullptr && ctx->skySkip) ? 1u : 0u;
-            ctx->freshScans += ((uint64_t)tp.total_paths + 63u) / 64u;
+            ctx->freshScans += ((uint64_t)tp.total_paths + 63u) / 64u;  // (all tiles: the statistics do not know about the shorter queue)
+            if (nSky != 0u) tp.total_paths = (nFull - nSky) * 64u * spp;
             tp.samples = ctx->samples.ptr;
             tp.trav_out = nullptr;
             tp.counters = ctx->counters.ptr;
@@ -1374,6 +1469,12 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
                 RT_HIP(hipGetLastError());
             }
             if ((rc = LaunchTrace(ctx, tp)) != RT_OK) return rc;
+            if (nSky != 0u) {
+                const unsigned long long planes = (unsigned long long)nSky * spp;
+                hipLaunchKernelGGL(rtd::rt_sky_counters_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->counters.ptr, planes * 64ull,
+                                   ctx->lastTraceSky ? planes : 0ull);
+                RT_HIP(hipGetLastError());
+            }
             RT_HIP(hipEventRecord(ev[1], ctx->stream));
             LaunchAccumulate(ctx, npix, spp, 0u, aheadEnd ? sppTotal : spp);
             RT_HIP(hipGetLastError());
@@ -2034,6 +2135,12 @@ int rt_unit_sky_planes(rt_ctx* ctx, uint64_t* planes) {
     unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
     RT_HIP(hipMemcpy(c, ctx->counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
     *planes = c[5];
+    return RT_OK;
+}
+
+int rt_unit_sky_excluded(rt_ctx* ctx, uint32_t* tiles) {
+    if (!ctx || !tiles) return Fail(RT_ERR_INVALID_ARG, "rt_unit_sky_excluded: invalid argument");
+    *tiles = ctx->skyExcluded;
     return RT_OK;
 }
 

@@ -1099,7 +1099,8 @@ __global__ void __launch_bounds__(256) rt_raygen_tables_kernel(float2* jitter, u
 // A persistent launch ends with the tail of whatever it started last; if those are 51-segment paths through the glass
 // spheres, most of the chip waits for them (2 % of a C2 launch, 11 % at spp 16).  Three pilot rays per full tile (its first,
 // middle and last pixel, sample 1) are traced through the production scan when an accumulation starts; the tile's class is
-// the most expensive material among their first hits -- nothing, anything else, metal, glass -- and the launches of the
+// the most expensive material among their first hits -- nothing, anything else, metal, glass (and, below them all, the tiles whose
+// sphere list is empty: rt_tile_class_kernel) -- and the launches of the
 // accumulation take the tiles by descending class: the sky, whose paths end after one scan, comes last.  Results do not
 // depend on the order (every path has its own slot and stream); only the schedule does.
 #ifndef RT_PILOTS_PER_TILE
@@ -1133,8 +1134,12 @@ RT_DEV uint32_t pilot_class(const float* hits, uint32_t t, const uint32_t* matTy
 // A tile next to a glass tile -- left, right, in the row above or below -- counts as glass too: the cap of a glass sphere
 // that sticks out into the sky can be narrower than the pilots' spacing, and its 51-segment paths, started with the sky in
 // the launch's last half millisecond, were the last three waves of a C2 launch (+1 % of its duration; tools/timeline_bulk.py).
+// skyFlags (may be null; rt_sky_tiles_kernel below): a tile whose sphere list is EMPTY gets a class of its own below the sky, AFTER
+// the neighbour rule -- the pilots guess, the empty list proves that no path of the tile meets anything.  The stored class is
+// 0 for such a tile and 1 + the pilots' class for every other, so that the sorted order ends with exactly the flagged tiles.
+constexpr uint32_t kTileClasses = 5;
 __global__ void __launch_bounds__(256) rt_tile_class_kernel(const float* hits, uint32_t nFull, uint32_t W, const uint32_t* matTypeByOrig,
-                                                            uint8_t* cls) {
+                                                            uint8_t* cls, const uint8_t* skyFlags = nullptr) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nFull) return;
     uint32_t c = pilot_class(hits, t, matTypeByOrig);
@@ -1146,21 +1151,21 @@ __global__ void __launch_bounds__(256) rt_tile_class_kernel(const float* hits, u
             if (near[k] >= 0 && n < (int64_t)nFull && pilot_class(hits, (uint32_t)n, matTypeByOrig) == 3u) c = 3u;
         }
     }
-    cls[t] = (uint8_t)c;
+    cls[t] = (uint8_t)((skyFlags != nullptr && skyFlags[t] != 0u) ? 0u : c + 1u);
 }
 // Stable counting sort of the tiles by descending class; one workgroup, thread k owns a contiguous run of tiles.
 __global__ void __launch_bounds__(1024) rt_tile_order_kernel(const uint8_t* cls, uint32_t nFull, uint32_t* order) {
-    __shared__ uint32_t waveTot[16][4];
+    __shared__ uint32_t waveTot[16][kTileClasses];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     const uint32_t per = (nFull + 1023u) / 1024u;
     const uint32_t t0 = tid * per < nFull ? tid * per : nFull, t1 = (t0 + per) < nFull ? (t0 + per) : nFull;
-    uint32_t cnt[4] = {0u, 0u, 0u, 0u};
+    uint32_t cnt[kTileClasses] = {0u, 0u, 0u, 0u, 0u};
     for (uint32_t t = t0; t < t1; ++t) {
         const uint32_t c = cls[t];
-        for (uint32_t k = 0; k < 4u; ++k) cnt[k] += c == k ? 1u : 0u;
+        for (uint32_t k = 0; k < kTileClasses; ++k) cnt[k] += c == k ? 1u : 0u;
     }
-    uint32_t pos[4];  // where this thread's tiles of class k start
-    for (uint32_t k = 0; k < 4u; ++k) {
+    uint32_t pos[kTileClasses];  // where this thread's tiles of class k start
+    for (uint32_t k = 0; k < kTileClasses; ++k) {
         uint32_t incl = cnt[k];
         for (int off = 1; off < 64; off <<= 1) {
             const uint32_t v = (uint32_t)__shfl_up((int)incl, off);
@@ -1171,7 +1176,7 @@ __global__ void __launch_bounds__(1024) rt_tile_order_kernel(const uint8_t* cls,
     }
     __syncthreads();
     uint32_t base = 0;
-    for (int k = 3; k >= 0; --k) {
+    for (int k = (int)kTileClasses - 1; k >= 0; --k) {
         uint32_t before = 0, tot = 0;
         for (uint32_t v = 0; v < 16u; ++v) {
             before += v < w ? waveTot[v][k] : 0u;
@@ -1183,7 +1188,7 @@ __global__ void __launch_bounds__(1024) rt_tile_order_kernel(const uint8_t* cls,
     for (uint32_t t = t0; t < t1; ++t) {
         const uint32_t c = cls[t];
         uint32_t at = 0;
-        for (uint32_t k = 0; k < 4u; ++k) {
+        for (uint32_t k = 0; k < kTileClasses; ++k) {
             at = c == k ? pos[k] : at;
             pos[k] += c == k ? 1u : 0u;
         }
@@ -1252,13 +1257,59 @@ __global__ void __launch_bounds__(256) rt_tile_mask_kernel(const TraceParams p, 
     }
 }
 
+// ====================================================== tiles kept out of the trace queue
+// A full tile whose sphere list is EMPTY can only see the sky: every sample of every pixel of it is the one constant
+// (0 + 1 * sky) * exposure (K_GEN above).  Where an accumulation starts, this kernel writes -- into buffers of the accumulation's own,
+// not the mask tables, which rt_unit_tile_masks may rebuild for another picture -- flags[tile] = 1 iff the tile's list header is 0,
+// info[0] += the number of flagged tiles (zeroed by the caller) and info[1..3] = the constant sample, formed by the V3 expressions
+// of the miss transition and finishPath, so that a -0 channel, a NaN or an infinity keeps the bits the traced path gives it.
+// rt_tile_class_kernel puts the flagged tiles last in work order, the host then leaves them out of the queue, and the tile-aware
+// accumulation below adds the constant for them instead of reading the sample buffer.
+__global__ void __launch_bounds__(256) rt_sky_tiles_kernel(const TraceParams p, const uint16_t* __restrict__ lists, uint32_t nFull,
+                                                           uint8_t* __restrict__ flags, uint32_t* __restrict__ info) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool empty = t < nFull && lists[(size_t)kTileSphereHalfs * t] == 0u;
+    if (t < nFull) flags[t] = empty ? 1u : 0u;
+    const uint32_t n = (uint32_t)__popcll(__ballot(empty));
+    if ((threadIdx.x & 63u) == 0u && n != 0u) atomicAdd(&info[0], n);
+    if (t == 0u) {
+        const V3 sky = v3(p.sky_emit[0], p.sky_emit[1], p.sky_emit[2]);
+        const V3 skyRad = v3(0.f, 0.f, 0.f) + v3(1.f, 1.f, 1.f) * sky;
+        const float expo = p.exposure;
+        info[1] = __float_as_uint(skyRad.x * expo);
+        info[2] = __float_as_uint(skyRad.y * expo);
+        info[3] = __float_as_uint(skyRad.z * expo);
+    }
+}
+// After a launch whose queue left flagged tiles out: what the trace kernel would have added to the counters for those tiles' planes
+// -- one traversal and one segment per path ([0], [1]) and, where the kernel is one that finishes such planes without rays (kSky;
+// else planes = 0: the other kernels keep no tile statistics), one table-taking, direct, ray-less scan per plane ([3], [4], [5]).
+__global__ void __launch_bounds__(64) rt_sky_counters_kernel(unsigned long long* counters, unsigned long long paths, unsigned long long planes) {
+    const uint32_t k = threadIdx.x;
+    if (k < 2u) counters[k] += paths;
+    else if (k >= 3u && k < 6u) counters[k] += planes;
+}
+
 // ============================================================== ordered accumulation (A16)
 // hdr[pixel] += sample(pixel, s) for s = s0 .. s0+spp-1 in that order (spheres-app.cpp:182-183).
-__global__ void __launch_bounds__(256) rt_accumulate_kernel(const float* __restrict__ samples, float* __restrict__ hdr, uint32_t npix,
-                                                            uint32_t spp, uint32_t first = 0, uint32_t count = 0xffffffffu) {
+// kMoments (rt_set_noise_estimate on): the second moments beside it, sq[pixel] += RN(sample^2) for the same planes in the same order
+// (rt_noise.h); hdr and sq are carried in registers and written once, and the hdr arithmetic is the same statements, so the strip
+// has the same bits either way.
+// kTiles: a pixel of a flagged tile (rt_sky_tiles_kernel) does not read the sample buffer -- whose planes of that tile the trace
+// launch may not have written -- but performs the same `count` sequential adds of the constant sample skyC.  A tile is one wave:
+// the branch is wave-uniform.
+template <bool kMoments, bool kTiles>
+RT_DEV void accumulate_body(const float* __restrict__ samples, float* __restrict__ hdr, float* __restrict__ sq, uint32_t npix, uint32_t spp,
+                            uint32_t first, uint32_t count, const uint8_t* __restrict__ skyFlags, const float* __restrict__ skyC) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
     float r = hdr[3 * (size_t)pix], g = hdr[3 * (size_t)pix + 1], b = hdr[3 * (size_t)pix + 2];
+    float qr = 0.f, qg = 0.f, qb = 0.f;
+    if (kMoments) {
+        qr = sq[3 * (size_t)pix];
+        qg = sq[3 * (size_t)pix + 1];
+        qb = sq[3 * (size_t)pix + 2];
+    }
     // tiled buffer [tile of 64 pixels][sample][pixel in tile] (path_coordinates): the 64 lanes of a wave read 768
     // contiguous bytes per sample plane; eight planes in flight, the adds stay sequential in s.  first / count: the planes
     // [first, first + count) of the buffer's spp (render-ahead batching adds the planes of one call at a time).
@@ -1267,6 +1318,20 @@ __global__ void __launch_bounds__(256) rt_accumulate_kernel(const float* __restr
     const float3* sp = reinterpret_cast<const float3*>(samples) + (size_t)tile * 64u * spp + (pix - (tile << 6));
     uint32_t s = first < spp ? first : spp;
     const uint32_t end = count > spp - s ? spp : s + count;
+    if (kTiles && tile < nFull && skyFlags[tile] != 0u) {
+        const float cx = skyC[0], cy = skyC[1], cz = skyC[2];
+        const float cxx = cx * cx, cyy = cy * cy, czz = cz * cz;  // rounded first, added second (rt_noise.h)
+        for (; s < end; ++s) {
+            r += cx;
+            g += cy;
+            b += cz;
+            if (kMoments) {
+                qr = qr + cxx;
+                qg = qg + cyy;
+                qb = qb + czz;
+            }
+        }
+    }
     for (; s + 8 <= end; s += 8) {
         float3 v[8];
 #pragma unroll
@@ -1276,6 +1341,12 @@ __global__ void __launch_bounds__(256) rt_accumulate_kernel(const float* __restr
             r += v[k].x;
             g += v[k].y;
             b += v[k].z;
+            if (kMoments) {
+                // the contract (rt_noise.h): the square rounds to binary32 FIRST, the add rounds second -- never an fmaf
+                qr = qr + (v[k].x * v[k].x);
+                qg = qg + (v[k].y * v[k].y);
+                qb = qb + (v[k].z * v[k].z);
+            }
         }
     }
     for (; s < end; ++s) {
@@ -1283,57 +1354,41 @@ __global__ void __launch_bounds__(256) rt_accumulate_kernel(const float* __restr
         r += v.x;
         g += v.y;
         b += v.z;
+        if (kMoments) {
+            qr = qr + (v.x * v.x);  // two roundings, as above
+            qg = qg + (v.y * v.y);
+            qb = qb + (v.z * v.z);
+        }
     }
     hdr[3 * (size_t)pix] = r;
     hdr[3 * (size_t)pix + 1] = g;
     hdr[3 * (size_t)pix + 2] = b;
+    if (kMoments) {
+        sq[3 * (size_t)pix] = qr;
+        sq[3 * (size_t)pix + 1] = qg;
+        sq[3 * (size_t)pix + 2] = qb;
+    }
 }
-
-// ... and, with rt_set_noise_estimate on, the second moments beside it: sq[pixel] += RN(sample^2) for the same planes in the same
-// order (rt_noise.h).  Same addressing, same first / count, same eight planes in flight; hdr and sq are carried in registers and
-// written once.  The hdr arithmetic is rt_accumulate_kernel's statement for statement, so the strip has the same bits either way.
+__global__ void __launch_bounds__(256) rt_accumulate_kernel(const float* __restrict__ samples, float* __restrict__ hdr, uint32_t npix,
+                                                            uint32_t spp, uint32_t first = 0, uint32_t count = 0xffffffffu) {
+    accumulate_body<false, false>(samples, hdr, nullptr, npix, spp, first, count, nullptr, nullptr);
+}
 __global__ void __launch_bounds__(256) rt_accumulate_moments_kernel(const float* __restrict__ samples, float* __restrict__ hdr,
                                                                     float* __restrict__ sq, uint32_t npix, uint32_t spp, uint32_t first = 0,
                                                                     uint32_t count = 0xffffffffu) {
-    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= npix) return;
-    float r = hdr[3 * (size_t)pix], g = hdr[3 * (size_t)pix + 1], b = hdr[3 * (size_t)pix + 2];
-    float qr = sq[3 * (size_t)pix], qg = sq[3 * (size_t)pix + 1], qb = sq[3 * (size_t)pix + 2];
-    const uint32_t nFull = npix >> 6, tile = pix >> 6;
-    const uint32_t stride = tile < nFull ? 64u : npix - (nFull << 6);
-    const float3* sp = reinterpret_cast<const float3*>(samples) + (size_t)tile * 64u * spp + (pix - (tile << 6));
-    uint32_t s = first < spp ? first : spp;
-    const uint32_t end = count > spp - s ? spp : s + count;
-    for (; s + 8 <= end; s += 8) {
-        float3 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = sp[(size_t)(s + k) * stride];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            r += v[k].x;
-            g += v[k].y;
-            b += v[k].z;
-            // the contract (rt_noise.h): the square rounds to binary32 FIRST, the add rounds second -- never an fmaf
-            qr = qr + (v[k].x * v[k].x);
-            qg = qg + (v[k].y * v[k].y);
-            qb = qb + (v[k].z * v[k].z);
-        }
-    }
-    for (; s < end; ++s) {
-        const float3 v = sp[(size_t)s * stride];
-        r += v.x;
-        g += v.y;
-        b += v.z;
-        qr = qr + (v.x * v.x);  // two roundings, as above
-        qg = qg + (v.y * v.y);
-        qb = qb + (v.z * v.z);
-    }
-    hdr[3 * (size_t)pix] = r;
-    hdr[3 * (size_t)pix + 1] = g;
-    hdr[3 * (size_t)pix + 2] = b;
-    sq[3 * (size_t)pix] = qr;
-    sq[3 * (size_t)pix + 1] = qg;
-    sq[3 * (size_t)pix + 2] = qb;
+    accumulate_body<true, false>(samples, hdr, sq, npix, spp, first, count, nullptr, nullptr);
+}
+// ... and their tile-aware forms, launched whenever the running accumulation has flags
+__global__ void __launch_bounds__(256) rt_accumulate_tiles_kernel(const float* __restrict__ samples, float* __restrict__ hdr, uint32_t npix,
+                                                                  uint32_t spp, uint32_t first, uint32_t count,
+                                                                  const uint8_t* __restrict__ skyFlags, const float* __restrict__ skyC) {
+    accumulate_body<false, true>(samples, hdr, nullptr, npix, spp, first, count, skyFlags, skyC);
+}
+__global__ void __launch_bounds__(256) rt_accumulate_moments_tiles_kernel(const float* __restrict__ samples, float* __restrict__ hdr,
+                                                                          float* __restrict__ sq, uint32_t npix, uint32_t spp, uint32_t first,
+                                                                          uint32_t count, const uint8_t* __restrict__ skyFlags,
+                                                                          const float* __restrict__ skyC) {
+    accumulate_body<true, true>(samples, hdr, sq, npix, spp, first, count, skyFlags, skyC);
 }
 
 // ================================================================ noise estimate (rt_noise.h)

@@ -372,6 +372,12 @@ int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint
  * tile's sphere list is empty (csrc/rt_kernels.h kSky), in the last rt_render that launched a trace kernel of its own; they are part
  * of scans[2] above.  0 with RT_SKY_SKIP=0. */
 int rt_unit_sky_planes(rt_ctx* ctx, uint64_t* planes);
+/* Full tiles the last rt_render that launched a trace kernel of its own kept OUT of its queue because their sphere list is empty: the
+ * launch covered only the other tiles, the accumulation added the constant sky sample for these, and the counters above were given
+ * these tiles' share by the host.  0 whenever every tile was queued: the tiles' number had not reached the host yet (it is copied
+ * asynchronously where the tables are built and never waited for, so the first rt_render of a picture reports 0), RT_SKY_EXCLUDE=0,
+ * RT_SKY_SKIP=0, RT_TILE_ORDER=0, too few tiles for a work order, a partial last tile, frame pipelining. */
+int rt_unit_sky_excluded(rt_ctx* ctx, uint32_t* tiles);
 /* ... the same lists evaluated on the host from the same source (both limits given).  entry_of_sphere (by original sphere index, may be
  * null): the scan entry of each sphere.  Needs no GPU. */
 int rt_unit_tile_spheres_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t mask_limit,

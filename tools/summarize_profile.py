@@ -20,24 +20,32 @@ json.dump(bench, open(prefix + "_bench_line" + suffix + ".json", "w"), indent=1)
 json.dump(last_json_line(os.path.join(src, "bench_kt.json")), open(prefix + "_bench_under_rocprof" + suffix + ".json", "w"), indent=1)
 ks = glob.glob(os.path.join(src, "kt", "*", "*kernel_stats.csv"))[0]
 shutil.copy(ks, prefix + "_bench_kernel_stats" + suffix + ".csv")
+# A process's FIRST step builds the per-picture tables and queues every tile; from the second step on the launches leave the
+# empty-list tiles out.  The summary describes the steady state: of every pass only the LAST dispatch of a kernel
+# counts (the PMC passes run one warm-up step and one timed step), and the launch duration is the mean over the kernel trace's
+# dispatches after the first.
 raw = {"trace": {}, "accumulate": {}}
-rows_per_counter = {}
+launches = None
 for f in glob.glob(os.path.join(src, "pmc_*", "*", "*counter_collection.csv")):
+    per = {"trace": {}, "accumulate": {}}  # kind -> dispatch id -> counter -> sum over the rows of that dispatch
     for r in csv.DictReader(open(f)):
         k = "trace" if "rt_trace_kernel" in r["Kernel_Name"] else ("accumulate" if "rt_accumulate" in r["Kernel_Name"] else None)
         if k:
-            raw[k][r["Counter_Name"]] = raw[k].get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
-            if k == "trace":
-                rows_per_counter.setdefault(r["Counter_Name"], set()).add(r.get("Dispatch_Id", r.get("Correlation_Id", "0")))
-t = raw["trace"]
-launches = max(len(v) for v in rows_per_counter.values())  # dispatches of the trace kernel in one PMC pass (bench --steps 1 --warmup 0: one)
-assert all(len(v) == launches for v in rows_per_counter.values()), "PMC passes saw different numbers of trace launches"
-for k in raw:
-    raw[k] = {c: v / launches for c, v in raw[k].items()}  # per launch
+            d = per[k].setdefault(int(r.get("Dispatch_Id", r.get("Correlation_Id", "0"))), {})
+            d[r["Counter_Name"]] = d.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
+    assert per["trace"], "no trace launch in " + f
+    assert launches in (None, len(per["trace"])), "PMC passes saw different numbers of trace launches"
+    launches = len(per["trace"])
+    for k in per:
+        if per[k]:
+            raw[k].update(per[k][max(per[k])])
 t = raw["trace"]
 stats = {r["Name"]: r for r in csv.DictReader(open(ks))}
 trace_name = [n for n in stats if "rt_trace_kernel" in n][0]
-launch_ms = float(stats[trace_name]["AverageNs"]) * 1e-6
+kt = glob.glob(os.path.join(src, "kt", "*", "*kernel_trace.csv"))
+durs = [(int(r["Dispatch_Id"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) for r in csv.DictReader(open(kt[0])) if "rt_trace_kernel" in r["Kernel_Name"]] if kt else []
+durs = [d for _, d in sorted(durs)]
+launch_ms = (sum(durs[1:]) / len(durs[1:]) * 1e-6) if len(durs) > 1 else float(stats[trace_name]["AverageNs"]) * 1e-6
 # FETCH_SIZE / WRITE_SIZE are in KiB per MI355X_MICROARCH.md; FETCH_SIZE doubled per its gfx950 correction (an upper bound here)
 fetch_b = t.get("FETCH_SIZE", 0.0) * 1024.0 * 2.0
 write_b = t.get("WRITE_SIZE", 0.0) * 1024.0
@@ -46,8 +54,8 @@ cyc = t["GRBM_GUI_ACTIVE"] / xcds  # GRBM_GUI_ACTIVE is summed over the 8 XCDs
 CYC_PER_VALU = 2.164  # SIMD cycles per wave-wide VOP2 instruction at the best measured rate (profiles/r01_valu_rate*_microbench.jsonl)
 import bench as _bench
 derived = {
-    "launches_in_pmc_pass": 1, "raw_counters_are": "per launch (sums over the pass / %d trace launches)" % launches,
-    "launch_ms_rocprof_avg": launch_ms,
+    "launches_in_pmc_pass": 1, "trace_launches_per_pass": launches, "raw_counters_are": "of the last of the %d trace launches of each pass (steady state: the first launch of a process queues every tile)" % launches,
+    "launch_ms_rocprof_avg": launch_ms, "launch_ms_is": "mean over the kernel trace's %d launches after the first" % max(len(durs) - 1, 0),
     "hbm_fetch_bytes": fetch_b, "hbm_write_bytes": write_b, "hbm_bytes_per_launch": fetch_b + write_b,
     "note_traffic": "WRITE_SIZE is the per-sample buffer: paths x 12 B algorithmic (C2: 122.88e6 x 12 = 1.4746e9 B). FETCH_SIZE is in KiB and doubled per the guide's gfx950 correction (an upper bound for the narrow table reads here).",
     "valu_insts_per_launch": t["SQ_INSTS_VALU"], "salu_insts_per_launch": t["SQ_INSTS_SALU"], "lds_insts_per_launch": t["SQ_INSTS_LDS"],
@@ -77,7 +85,7 @@ if profiled_hash != _bench.kernel_sources_hash():
 _cfg = _bench.CONFIGS[bench["config"]["name"]]
 out = {"kernel_sources_sha256": profiled_hash,
        "workload_key": {"n_gpus": bench["n_gpus"], "W": _cfg["W"], "H": _cfg["H"], "spp": bench["config"]["spp"], "config": bench["config"]["name"]},
-       "command": "tools/profile_round.sh: rocprofv3 --kernel-trace --stats (durations) and four separate rocprofv3 --pmc passes (FETCH_SIZE | WRITE_SIZE | SQ group | SQ+MFMA+GRBM group) over python3 bench.py; summarised by tools/summarize_profile.py",
+       "command": "tools/profile_round.sh: rocprofv3 --kernel-trace --stats (durations) and four separate rocprofv3 --pmc passes (FETCH_SIZE | WRITE_SIZE | SQ group | SQ+MFMA+GRBM group) over python3 bench.py --steps 1 --warmup 1; summarised by tools/summarize_profile.py",
        "workload": bench["config"]["workload"], "kernel": trace_name, "raw_counters": raw, "derived_trace_kernel": derived}
 prev = prefix + "_pmc_summary" + suffix + ".json"
 if os.path.exists(prev):
