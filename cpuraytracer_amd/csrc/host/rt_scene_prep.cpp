@@ -84,6 +84,43 @@ bool AllFinite(const rt_sphere* sp, uint32_t n, uint32_t* which) {
     return true;
 }
 
+const char* MaterialFault(const rt_material& m) {
+    if (m.type > 3u) return "type";
+    if (m.tex_type > 1u) return "tex_type";
+    const bool glass = m.type == RT_MAT_DIELECTRIC_TRANSPARENT, emissive = m.type == RT_MAT_EMISSIVE;
+    if (!emissive && !std::isfinite(m.smoothness)) return "smoothness";
+    if (glass && !std::isfinite(m.ior)) return "ior";
+    if (emissive && !std::isfinite(m.luminance)) return "luminance";
+    if (glass) return nullptr;  // a glass sphere has no texture
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(m.rgb0[k])) return "rgb0";
+    if (m.tex_type != RT_TEX_CHECKER) return nullptr;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(m.rgb1[k])) return "rgb1";
+    // (int)(tiling * u) with u = 0.5 n + 0.5, |n| within a few ulp of 1: the product stays inside int (NaN fails the comparison)
+    if (!(std::fabs(m.tiling) <= 1073741824.0f)) return "tiling";
+    return nullptr;
+}
+
+bool MaterialsInDomain(const rt_material* mats, uint32_t n, uint32_t* which, const char** field) {
+    for (uint32_t k = 0; k < n; ++k)
+        if (const char* f = MaterialFault(mats[k])) {
+            if (which) *which = k;
+            if (field) *field = f;
+            return false;
+        }
+    return true;
+}
+
+std::string MaterialFaultMessage(const char* who, const std::string& what, const rt_material& m, const char* field) {
+    std::string why;
+    if (!std::strcmp(field, "type")) why = "type = " + std::to_string(m.type) + " (rt_material_type is 0..3)";
+    else if (!std::strcmp(field, "tex_type")) why = "tex_type = " + std::to_string(m.tex_type) + " (rt_texture_type is 0..1)";
+    else if (!std::strcmp(field, "tiling")) why = "tiling is not finite or beyond 2^30 in magnitude";
+    else why = std::string(field) + " is not finite";
+    return std::string(who) + ": the material of " + what + " is outside the material domain: " + why;
+}
+
 // Conservative bounding sphere of a set of spheres, in the filter's (C, |C|^2 - Rf^2) form.
 static F4 BoundOf(const rt_sphere* sp, const std::vector<uint32_t>& ids, float* normOut, float marginK) {
     if (ids.empty()) return MakeF4(0.f, 0.f, 0.f, 1e30f);  // never a candidate

@@ -94,6 +94,16 @@ struct PreparedScene {
 // A centre or a radius that is not finite: no bound can be built from it (the callers refuse the scene).
 bool AllFinite(const rt_sphere* sp, uint32_t n, uint32_t* which);
 
+// The material domain (include/rt_api.h at rt_material): type <= 3, tex_type <= 1, every field the record's type READS finite
+// (smoothness: types 0-2; ior: type 2; luminance: type 3; rgb0: types 0, 1, 3; rgb1 and tiling: under a checker texture on types
+// 0, 1, 3), and |tiling| <= 2^30 under a checker texture.  Fields the type does not read are not inspected.  nullptr: the
+// record is inside the domain; else the name of its first offending field.
+const char* MaterialFault(const rt_material& m);
+// ... over a table: false, *which = the first offending record and *field = MaterialFault of it
+bool MaterialsInDomain(const rt_material* mats, uint32_t n, uint32_t* which, const char** field);
+// What the callers refuse a record with: "<who>: <what> is outside the material domain: <field> ..." (what: "sphere 7", "sky")
+std::string MaterialFaultMessage(const char* who, const std::string& what, const rt_material& m, const char* field);
+
 void BuildLayout(const rt_sphere* spheres, uint32_t n, const PrepOptions& opt, SceneLayout& L);
 void BuildShadowGrid(const rt_sphere* spheres, const SceneLayout& L, const float lightDir[3], uint32_t maxCells, ShadowGrid& G);
 

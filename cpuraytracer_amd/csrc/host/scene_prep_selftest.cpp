@@ -3,6 +3,7 @@
 // centres, light lists of every length -- and checks the STRUCTURE of what PrepareScene returns: lengths, permutations, prefix
 // tables, the range of every 16-bit id.  Whether the scan's bounds are conservative is not its business (the fuzz tests own that);
 // of the shadow indices it checks the plain inclusion: every sphere's exact footprint lies in cells that list it.
+// The material domain (MaterialFault): one offender per clause, the first offender of a table, unread fields left alone.
 // Exit status 0 and one line per scene, or the first failed condition and status 1.  Also built with AddressSanitizer and
 // UBSan (make scene_prep_selftest_san): the index arithmetic of the builders then runs under both.
 #include <cmath>
@@ -228,6 +229,79 @@ int CheckScene(const std::vector<rt_sphere>& sp, const std::vector<rt_material>&
     return L.gridOn ? 1 : (L.nLevels > 1 ? 2 : 0);
 }
 
+// The material domain of include/rt_api.h: every clause refuses its offender under the right field name, records that only
+// carry NaN where their type does not read are inside, and a table reports its FIRST offender.
+void CheckMaterialDomain() {
+    g_scene = "material domain";
+    g_lights = "";
+    const float nan = std::nanf(""), inf = INFINITY;
+    auto rec = [](uint32_t type, uint32_t tex) {
+        rt_material m;
+        std::memset(&m, 0, sizeof(m));
+        m.type = type; m.tex_type = tex;
+        m.smoothness = 16.f; m.ior = 1.5f; m.tiling = 4.f; m.luminance = 100.f;
+        for (int c = 0; c < 3; ++c) { m.rgb0[c] = 0.5f; m.rgb1[c] = 0.25f; }
+        return m;
+    };
+    auto faultIs = [](const rt_material& m, const char* field) {
+        const char* f = MaterialFault(m);
+        return field ? (f && !std::strcmp(f, field)) : f == nullptr;
+    };
+    for (uint32_t type = 0; type < 4; ++type)
+        for (uint32_t tex = 0; tex < 2; ++tex) CHECK(faultIs(rec(type, tex), nullptr));
+    { rt_material m = rec(4, 0); CHECK(faultIs(m, "type")); m.type = 0xffffffffu; CHECK(faultIs(m, "type")); }
+    { rt_material m = rec(1, 2); CHECK(faultIs(m, "tex_type")); }
+    for (uint32_t type = 0; type < 3; ++type) { rt_material m = rec(type, 0); m.smoothness = type == 1 ? inf : nan; CHECK(faultIs(m, "smoothness")); }
+    { rt_material m = rec(2, 0); m.ior = nan; CHECK(faultIs(m, "ior")); m.ior = -inf; CHECK(faultIs(m, "ior")); }
+    { rt_material m = rec(3, 0); m.luminance = inf; CHECK(faultIs(m, "luminance")); }
+    for (uint32_t type : {0u, 1u, 3u}) {
+        rt_material m = rec(type, 0);
+        m.rgb0[type % 3] = nan;
+        CHECK(faultIs(m, "rgb0"));
+        m = rec(type, 1);
+        m.rgb1[2] = inf;
+        CHECK(faultIs(m, "rgb1"));
+        m = rec(type, 0);
+        m.rgb1[0] = nan; m.tiling = nan;  // const texture: neither is read
+        CHECK(faultIs(m, nullptr));
+        for (float t : {nan, inf, -inf, std::nextafterf(1073741824.0f, inf), -3.0e9f}) {
+            m = rec(type, 1);
+            m.tiling = t;
+            CHECK(faultIs(m, "tiling"));
+        }
+        for (float t : {1073741824.0f, -1073741824.0f, 0.f, -50.f, 1e6f}) {
+            m = rec(type, 1);
+            m.tiling = t;
+            CHECK(faultIs(m, nullptr));
+        }
+    }
+    {   // what a type does not read is not inspected
+        rt_material m = rec(0, 0);
+        m.ior = nan; m.luminance = nan; m.tiling = inf;
+        CHECK(faultIs(m, nullptr));
+        m = rec(2, 1);  // a glass sphere has no texture: tex_type must still be a texture kind, the texture's fields are unread
+        m.tiling = 3.0e9f; m.luminance = nan;
+        for (int c = 0; c < 3; ++c) m.rgb0[c] = m.rgb1[c] = nan;
+        CHECK(faultIs(m, nullptr));
+        m = rec(3, 0);
+        m.smoothness = nan; m.ior = inf;
+        CHECK(faultIs(m, nullptr));
+    }
+    {   // a table: the first offender, with its field; untouched outputs when there is none
+        std::vector<rt_material> tab(7, rec(0, 1));
+        uint32_t which = 99;
+        const char* field = "untouched";
+        CHECK(MaterialsInDomain(tab.data(), 7, &which, &field) && which == 99 && !std::strcmp(field, "untouched"));
+        tab[5].type = 9;
+        tab[3].tiling = nan;
+        CHECK(!MaterialsInDomain(tab.data(), 7, &which, &field) && which == 3 && !std::strcmp(field, "tiling"));
+        CHECK(!MaterialsInDomain(tab.data(), 7, nullptr, nullptr));
+        const std::string msg = MaterialFaultMessage("rt_scene_upload", "sphere 3", tab[3], field);
+        CHECK(msg.find("sphere 3") != std::string::npos && msg.find("tiling") != std::string::npos);
+    }
+    std::printf("ok material domain\n");
+}
+
 }  // namespace
 
 int main() {
@@ -252,6 +326,7 @@ int main() {
     g_scene = "all scenes";
     g_lights = "";
     CHECK(seen[0] && seen[1] && seen[2]);
+    CheckMaterialDomain();
     std::printf("scene_prep_selftest: ok\n");
     return 0;
 }

@@ -1025,6 +1025,10 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     uint32_t bad = 0;  // (refused before any side effect: pending frames stay pending, the previous scene stays)
     if (!rtprep::AllFinite(spheres, n, &bad))
         return Fail(RT_ERR_INVALID_ARG, "rt_scene_upload: sphere " + std::to_string(bad) + " has a centre or a radius that is not finite");
+    const char* field = nullptr;  // the material domain (rt_api.h at rt_material; the rule itself is host/rt_scene_prep.cpp's)
+    if (!rtprep::MaterialsInDomain(materials, n, &bad, &field))
+        return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_scene_upload", "sphere " + std::to_string(bad), materials[bad], field));
+    if ((field = rtprep::MaterialFault(*sky)) != nullptr) return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_scene_upload", "the sky", *sky, field));
     RT_HIP(hipSetDevice(ctx->device));
     int rc;
     if ((rc = BatchFlush(ctx)) != RT_OK) return rc;  // pending frames were asked of the scene that is being replaced
@@ -1907,6 +1911,7 @@ int rt_unit_camera_rays(rt_ctx* ctx, const rt_camera* camera, const float* uv_of
 int rt_unit_scatter(rt_ctx* ctx, const rt_material* material, const rt_light* sun, const float view_origin[3], const float* in,
                     uint32_t n, float* out) {
     if (!ctx || !material || !sun || !view_origin || !in || !out) return Fail(RT_ERR_INVALID_ARG, "rt_unit_scatter: invalid argument");
+    if (const char* field = rtprep::MaterialFault(*material)) return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_unit_scatter", "the record", *material, field));
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     TmpDev<float> dIn, dOut;

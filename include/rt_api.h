@@ -60,7 +60,19 @@ enum rt_texture_type {
 };
 
 /* Material + its (single) texture, flattened.  Colours are the values the
- * reference holds after XMLoadColor(XMCOLOR) (texture.cpp:5,16-17): byte * (1/255). */
+ * reference holds after XMLoadColor(XMCOLOR) (texture.cpp:5,16-17): byte * (1/255).
+ *
+ * The material domain -- what rt_scene_upload (every sphere's record and the sky's) and rt_unit_scatter accept; anything else is
+ * RT_ERR_INVALID_ARG with a message naming the sphere (or "the sky") and the field:
+ *   - type <= 3 and tex_type <= 1 (the enums above);
+ *   - the fields the record's type reads are finite: smoothness for types 0, 1, 2; ior for type 2; luminance for type 3; rgb0
+ *     for types 0, 1, 3; rgb1 and tiling only under a checker texture, on types 0, 1, 3 (a glass sphere has no texture).  Fields
+ *     the type does not read are NOT inspected: callers leave them unset;
+ *   - under a checker texture |tiling| <= 2^30: CheckerTexture::Evaluate (texture.cpp:20-33) forms (int)(tiling * u) with
+ *     u = 0.5 n + 0.5, |n| within a few ulp of 1, and beyond int that conversion is undefined in C++ (x86 and gfx950 give
+ *     different values).
+ * Colours off the byte grid are accepted: they lie outside the parity contract with the reference (which can only hold bytes)
+ * and take the 48-byte records on the device. */
 typedef struct rt_material {
     uint32_t type;       /* rt_material_type                                         */
     uint32_t tex_type;   /* rt_texture_type (opaque: albedo, metal: reflectance)     */
@@ -153,6 +165,8 @@ int rt_set_workspace_limit(rt_ctx* ctx, uint64_t bytes);
  * n_lights == 0: Shade then returns zero and no shadow ray is cast).  Every light answers its any-hit shadow query through
  * an exact footprint index of its own; a light below the horizon of a surface contributes nDotL = 0 exactly as in
  * the reference.  One light (the reference's scene) runs the single-light kernel path unchanged. */
+/* materials and sky: inside the material domain (rt_material above).  Like a sphere that is not finite, a record outside it is
+ * refused before any side effect: the previous scene and pending frames stay as they were. */
 #define RT_MAX_LIGHTS 8
 int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* materials, uint32_t n,
                     const rt_camera* camera, const rt_light* lights, uint32_t n_lights, const rt_material* sky,
@@ -330,7 +344,7 @@ int rt_unit_camera_rays(rt_ctx* ctx, const rt_camera* camera, const float* uv_of
  * material record.  in: ray direction 3, hit pos 3, hit normal 3, three uniforms consumed in call order (12 floats);
  * out: scattered flag, attenuation 3, scattered direction 3, draws consumed, Emit+Shade 3 (11 floats). */
 int rt_unit_scatter(rt_ctx* ctx, const rt_material* material, const rt_light* sun, const float view_origin[3],
-                    const float* in, uint32_t n, float* out);  /* uses the context's sampler flags */
+                    const float* in, uint32_t n, float* out);  /* uses the context's sampler flags; the record must be inside the material domain */
 /* Host-only view of the clustered storage rt_scene_upload builds for the scan (groups of four spheres with a
  * conservative bounding sphere each).  orig: 4 entries per group, 0xffffffff = padding;
  * bounds: Cx, Cy, Cz, |C|^2 - Rf^2 per group.  cap_groups == 0 only queries *n_groups.  Needs no GPU. */

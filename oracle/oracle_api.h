@@ -30,6 +30,9 @@ int orc_build_scene(const char* name, uint64_t seed, float aspect, float apertur
                     rt_sphere* spheres, rt_material* materials, uint32_t* n, rt_camera* camera, rt_light* sun,
                     rt_material* sky, float* exposure_scale);
 
+/* Materials and the sky must lie inside the material domain of include/rt_api.h (at rt_material), as for rt_scene_upload: a record
+ * outside it is refused (1) with a message naming the sphere (or "the sky") and the field.  The single-material unit entries
+ * below refuse the same records: orc_unit_scatter returns -1, orc_unit_emit_shade writes NaN, the others return 1. */
 int orc_scene_upload(orc_ctx* ctx, const rt_sphere* spheres, const rt_material* materials, uint32_t n,
                      const rt_camera* camera, const rt_light* lights, uint32_t n_lights, const rt_material* sky, float exposure_scale);
 int orc_render(orc_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t s0, uint32_t s1, uint32_t max_depth,
@@ -88,6 +91,9 @@ int orc_unit_texture_eval(const rt_material* m, const float* uv, uint32_t n, flo
  * orc_use_reference_halton_counters(1)): the uniforms are ignored, the material draws HaltonSample(counter++, base) from its own
  * counters, which start at 0 and run on through the n hits; draws consumed reads 0. */
 int orc_unit_scatter_n(const rt_material* m, const float* in17, uint32_t n, int use_counters, float* out11);
+/* orc_unit_emit_shade for n hits (pos 3, normal 3, uv 2) against ONE material object, one light record (unoccluded) and one view
+ * origin -> 3 floats per hit */
+int orc_unit_emit_shade_n(const rt_material* m, const rt_light* light, const float view_origin[3], const float* hits8, uint32_t n, float* out3);
 /* Emit + Shade of sphere `sphere_index` of the uploaded scene for n given hits (pos 3, normal 3, uv 2), with the uploaded light
  * list in list order and the list scan over the uploaded spheres as every light's occlusion test */
 int orc_unit_emit_shade_scene(orc_ctx* ctx, uint32_t sphere_index, const float view_origin[3], const float* hits8, uint32_t n, float* out3);

@@ -1,6 +1,7 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY.  C ABI over rt_oracle.{h,cpp}; see oracle_api.h.
 #include "oracle_api.h"
 
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -15,6 +16,32 @@ struct orc_ctx {
 static thread_local std::string g_err;
 static int Fail(const char* msg) {
     g_err = msg;
+    return 1;
+}
+
+// The material domain of include/rt_api.h (at rt_material), restated here so that the oracle accepts exactly the scenes the device
+// library accepts: nullptr, or the name of the record's first offending field.
+static const char* MaterialFault(const rt_material& m) {
+    if (m.type > 3u) return "type";
+    if (m.tex_type > 1u) return "tex_type";
+    const bool glass = m.type == RT_MAT_DIELECTRIC_TRANSPARENT, emissive = m.type == RT_MAT_EMISSIVE;
+    if (!emissive && !std::isfinite(m.smoothness)) return "smoothness";
+    if (glass && !std::isfinite(m.ior)) return "ior";
+    if (emissive && !std::isfinite(m.luminance)) return "luminance";
+    if (glass) return nullptr;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(m.rgb0[k])) return "rgb0";
+    if (m.tex_type != RT_TEX_CHECKER) return nullptr;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(m.rgb1[k])) return "rgb1";
+    if (!(std::fabs(m.tiling) <= 1073741824.0f)) return "tiling";  // (int)(tiling * u) stays inside int; NaN fails too
+    return nullptr;
+}
+// 0, or 1 with the error set: "<who>: the material of <what> is outside the material domain: field <field>"
+static int RefuseMaterial(const char* who, const std::string& what, const rt_material& m) {
+    const char* f = MaterialFault(m);
+    if (!f) return 0;
+    g_err = std::string(who) + ": the material of " + what + " is outside the material domain: field " + f;
     return 1;
 }
 
@@ -48,6 +75,9 @@ int orc_build_scene(const char* name, uint64_t seed, float aspect, float apertur
 int orc_scene_upload(orc_ctx* ctx, const rt_sphere* spheres, const rt_material* materials, uint32_t n, const rt_camera* camera,
                      const rt_light* lights, uint32_t n_lights, const rt_material* sky, float exposure_scale) {
     if (!ctx || !spheres || !materials || !camera || (!lights && n_lights != 0) || !sky || n == 0) return Fail("orc_scene_upload: invalid argument");
+    for (uint32_t k = 0; k < n; ++k)
+        if (RefuseMaterial("orc_scene_upload", "sphere " + std::to_string(k), materials[k])) return 1;
+    if (RefuseMaterial("orc_scene_upload", "the sky", *sky)) return 1;
     FlatScene fs;
     fs.spheres.assign(spheres, spheres + n);
     fs.materials.assign(materials, materials + n);
@@ -242,6 +272,7 @@ int orc_unit_scatter(const rt_material* m, const float ray_dir[3], const float p
                      const float draws[3], float out_atten[3], float out_dir[3], uint32_t* n_draws) {
     // Build the one material; feed draws through a scripted stream by temporarily overriding
     // the path stream with a recorder: xoshiro cannot be scripted, so use the scripted hook.
+    if (RefuseMaterial("orc_unit_scatter", "the record", *m)) return -1;
     FlatScene fs;
     fs.spheres.push_back({0.f, 0.f, 0.f, 1.f});
     fs.materials.push_back(*m);
@@ -269,6 +300,10 @@ int orc_unit_scatter(const rt_material* m, const float ray_dir[3], const float p
 
 void orc_unit_emit_shade(const rt_material* m, const rt_light* sun, const float view_origin[3], const float pos[3],
                          const float normal[3], const float uv[2], float out_local[3]) {
+    if (RefuseMaterial("orc_unit_emit_shade", "the record", *m)) {
+        out_local[0] = out_local[1] = out_local[2] = NAN;
+        return;
+    }
     FlatScene fs;
     fs.spheres.push_back({0.f, 0.f, 0.f, 1.f});
     fs.materials.push_back(*m);
@@ -325,6 +360,8 @@ int orc_unit_texture_eval(const rt_material* m, const float* uv, uint32_t n, flo
     if (!m || !uv || !out4) return Fail("orc_unit_texture_eval: null argument");
     rt_material rec = *m;
     rec.type = RT_MAT_DIELECTRIC_OPAQUE;  // GetAlbedo is the texture's Evaluate
+    rec.smoothness = 0.f;
+    if (RefuseMaterial("orc_unit_texture_eval", "the record", rec)) return 1;
     SpheresApp app;
     OneMaterialScene(rec, app);
     for (uint32_t k = 0; k < n; ++k) {
@@ -337,6 +374,7 @@ int orc_unit_texture_eval(const rt_material* m, const float* uv, uint32_t n, flo
 int orc_unit_scatter_n(const rt_material* m, const float* in17, uint32_t n, int use_counters, float* out11) {
     if (!m || !in17 || !out11) return Fail("orc_unit_scatter_n: null argument");
     if (use_counters && !Random::ReferenceHaltonCounters()) return Fail("orc_unit_scatter_n: counter mode is off");
+    if (RefuseMaterial("orc_unit_scatter_n", "the record", *m)) return 1;
     SpheresApp app;
     OneMaterialScene(*m, app);
     const Material* mat = app.MaterialOf(0);
@@ -356,6 +394,23 @@ int orc_unit_scatter_n(const rt_material* m, const float* in17, uint32_t n, int 
         o[4] = outRay.origin.x; o[5] = outRay.origin.y; o[6] = outRay.origin.z;
         o[7] = outRay.direction.x; o[8] = outRay.direction.y; o[9] = outRay.direction.z;
         o[10] = (float)used;
+    }
+    return 0;
+}
+
+int orc_unit_emit_shade_n(const rt_material* m, const rt_light* light, const float view_origin[3], const float* hits8, uint32_t n, float* out3) {
+    if (!m || !light || !view_origin || !hits8 || !out3) return Fail("orc_unit_emit_shade_n: null argument");
+    if (RefuseMaterial("orc_unit_emit_shade_n", "the record", *m)) return 1;
+    SpheresApp app;
+    OneMaterialScene(*m, app);
+    std::vector<std::unique_ptr<Light>> lights;
+    lights.push_back(std::make_unique<DirectionalLight>(*light, [](const Ray&) { return false; }));
+    const Material* mat = app.MaterialOf(0);
+    const XMVECTOR vo = XMVectorSet(view_origin[0], view_origin[1], view_origin[2], 1.f);
+    for (uint32_t k = 0; k < n; ++k) {
+        const Payload hit = HitOf(hits8 + 8 * (size_t)k);
+        const XMVECTOR local = mat->Emit(hit) + mat->Shade(hit, lights, vo);
+        out3[3 * (size_t)k] = local.x; out3[3 * (size_t)k + 1] = local.y; out3[3 * (size_t)k + 2] = local.z;
     }
     return 0;
 }

@@ -137,6 +137,7 @@ def lib():
         L.orc_unit_camera_rays.argtypes = [C.POINTER(RtCamera), C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_unit_texture_eval.argtypes = [C.POINTER(RtMaterial), C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_unit_scatter_n.argtypes = [C.POINTER(RtMaterial), C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+        L.orc_unit_emit_shade_n.argtypes = [C.POINTER(RtMaterial), C.POINTER(RtLight), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_unit_emit_shade_scene.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_xoshiro_seed.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
         L.orc_xoshiro_draws.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -324,6 +325,18 @@ def scatter_n(material, in17, use_counters=False):
     out = np.zeros((q.shape[0], 11), dtype=np.float32)
     m = RtMaterial.from_buffer_copy(bytes(material))
     _check(lib().orc_unit_scatter_n(C.byref(m), q.ctypes.data, q.shape[0], 1 if use_counters else 0, out.ctypes.data))
+    return out
+
+
+def emit_shade_n(material, light, view_origin, hits8):
+    """Emit + unoccluded Shade of ONE material object under one light record and one view origin for [n, 8] hits (pos, normal,
+    uv) -> [n, 3] (oracle_api.h orc_unit_emit_shade_n)"""
+    q = np.ascontiguousarray(hits8, dtype=np.float32).reshape(-1, 8)
+    vo = np.ascontiguousarray(view_origin, dtype=np.float32).reshape(3)
+    out = np.zeros((q.shape[0], 3), dtype=np.float32)
+    m = RtMaterial.from_buffer_copy(bytes(material))
+    l = RtLight.from_buffer_copy(bytes(light))
+    _check(lib().orc_unit_emit_shade_n(C.byref(m), C.byref(l), vo.ctypes.data, q.ctypes.data, q.shape[0], out.ctypes.data))
     return out
 
 
