@@ -61,6 +61,7 @@ EXPORTS = [
     "rt_render_features", "rt_feature_samples", "rt_download_features", "rt_copy_features_to_device", "rt_clear_features",
     "rt_unit_features_host",
     "rt_unit_shadow_index_host", "rt_unit_shadow_query_host", "rt_unit_shadow",
+    "rt_unit_launch_plan",
 ]
 
 _lib = None
@@ -155,6 +156,8 @@ def load():
                                                 C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rt_unit_shadow_query_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtLight), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rt_unit_shadow.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    if hasattr(L, "rt_unit_launch_plan"):
+        L.rt_unit_launch_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     _lib = L
     return L
 

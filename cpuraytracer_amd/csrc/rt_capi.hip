@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/rt_api.h"
+#include "host/rt_launch_plan.h"
 #include "host/rt_scene_prep.h"
 #include "rt_kernels.h"
 
@@ -220,367 +221,155 @@ struct rt_ctx {
     DevBuf<rtd::FrameCtl> ctl;
 };
 
-static size_t LdsBytesFor(uint32_t n, uint32_t nPadded, bool mats) {
-    (void)n;  // radius and material tables are stored per scan entry (clustered order), like the scan table
-    return (size_t)nPadded * (16 + 4) + (mats ? (size_t)nPadded * 48 : 0) + (size_t)nPadded * 4;
+// ---- launches.  What a launch IS -- its dynamic LDS image, the TraceParams fields that describe it, its grid, and which of the
+// instantiated variants runs -- is planned by host/rt_launch_plan.cpp, in plain C++ that tests reach without a device
+// (rt_unit_launch_plan).  Here the plan's inputs are gathered from the context, the scene and the environment of the moment, its
+// fields applied and the kernel looked up in the tables below, which expand the one list of variants (rt_trace_variants.h).
+static rtplan::SceneShape ShapeOf(const rtd::TraceParams& tp) {
+    rtplan::SceneShape S;
+    S.n_padded = tp.n_padded;
+    S.n_levels = tp.n_levels;
+    S.top_cnt = tp.level_cnt[tp.n_levels - 1];
+    S.top_off = tp.level_off[tp.n_levels - 1];
+    S.grid = tp.grid_cell_start != nullptr;
+    S.grid_nu = tp.grid_nu, S.grid_nv = tp.grid_nv;
+    S.grid_quant = tp.grid_qrec != nullptr;
+    S.sg_enabled = tp.sg_enabled != 0u;
+    S.sg_nx = tp.sg_nx, S.sg_ny = tp.sg_ny, S.sg_nentries = tp.sg_nentries, S.sg_nglobal = tp.sg_nglobal;
+    S.mats16 = tp.mats16 != nullptr;
+    S.n_lights = tp.n_lights;
+    return S;
 }
-static size_t MfmaOpsBytesFor(uint32_t nGroups) { return (size_t)rtd::mfma_tiles_for(nGroups) * rtd::kOpsPerTile * 4; }
+static rtplan::Settings SettingsOf(const rt_ctx* ctx) {
+    rtplan::Settings C;
+    C.cuCount = (uint32_t)ctx->cuCount, C.blocksPerCu = ctx->blocksPerCu, C.blockThreads = ctx->blockThreads;
+    C.useMfma = ctx->useMfma, C.matsInLds = ctx->matsInLds, C.useRayCache = ctx->useRayCache, C.useStash = ctx->useStash;
+    C.treeInLds = ctx->treeInLds, C.forceGlobal = ctx->forceGlobal;
+    return C;
+}
+static rtplan::Knobs KnobsFromEnv() {  // read at every launch: tests change them between calls
+    rtplan::Knobs K;
+    K.mats16 = EnvU32("RT_MATS16", K.mats16), K.matsL2 = EnvU32("RT_MATS_L2", K.matsL2);
+    K.stashCap = EnvU32("RT_STASH_CAP", K.stashCap), K.stashProcess = EnvU32("RT_STASH_PROCESS", K.stashProcess);
+    K.gridQuant = EnvU32("RT_GRID_QUANT", K.gridQuant), K.gridSgLds = EnvU32("RT_GRID_SG_LDS", K.gridSgLds);
+    K.queueBlock = EnvU32("RT_QUEUE_BLOCK", K.queueBlock), K.queueStatic = EnvU32("RT_QUEUE_STATIC", K.queueStatic);
+    return K;
+}
+static void SetQueue(rtd::TraceParams& tp, const rtplan::QueueCut& q) {
+    tp.queue_block = q.queue_block, tp.static_blocks = q.static_blocks, tp.dyn_begin = q.dyn_begin, tp.dyn_blocks = q.dyn_blocks;
+}
 
-// Which instantiation of rt_trace_kernel a scene gets under this context's settings (also used by the closest-hit unit
-// entry, so that it runs the scan rt_render runs): tree = hierarchy scan <false, ., 2>, flat = matrix-core filter over the
-// groups with every table in LDS <true, ., 1>, else the VALU scan with (ldsTables) or without LDS tables.
-struct TraceVariant {
-    bool tree, flat, ldsTables, grid, gridLds;
-    size_t candBytes, leafBytes;
+using TraceKernelFn = void (*)(rtd::TraceParams);
+using ClosestKernelFn = void (*)(rtd::TraceParams, const float*, uint32_t, float*);
+using FeaturesKernelFn = void (*)(rtd::TraceParams, rtd::FeatureParams);
+static const struct {
+    TraceKernelFn one, lights;  // the single-light kernel and its twin over the light list (rt_kernels.h trace_body)
+} kTraceKernels[] = {
+#define RT_ROW(...) {&rtd::rt_trace_kernel<__VA_ARGS__>, &rtd::rt_trace_kernel_lights<__VA_ARGS__>},
+    RT_TRACE_VARIANTS(RT_ROW)
+#undef RT_ROW
 };
-static TraceVariant ChooseVariant(const rt_ctx* ctx, const rtd::TraceParams& tp) {
-    TraceVariant V{};
-    const size_t lds = LdsBytesFor(tp.n, tp.n_padded, ctx->matsInLds);
-    const bool useLds = !ctx->forceGlobal && lds <= 48 * 1024 && tp.n_padded < 65536;
-    const uint32_t wavesPerBlock = ctx->blockThreads / 64;
-    V.grid = ctx->useMfma && tp.grid_cell_start != nullptr;  // cell-grid scan (the scene was laid out for it at upload): tables in global memory (L2)
-    V.tree = ctx->useMfma && !V.grid && tp.n_levels > 1;  // deeper hierarchy: tables stay in global memory (L2)
-    const uint32_t topCnt = tp.level_cnt[tp.n_levels - 1];
-    // the scene constants' slot comes first in the image, then the per-wave regions
-    V.candBytes = rtd::kConstBytes + (size_t)wavesPerBlock * (V.grid ? rtd::kWaveGridBytes : (V.tree ? rtd::kWaveCandBytes : rtd::kWaveListBytes)) +
-                  (size_t)tp.sg_glob16 * 16;  // ... and the shadow index's global list in front of the tables (rt_params.h sg_glob_slots)
-    // one-sphere bounds, staged next to the scan table: the flat scan's copy has kFlatLeafStride float4 per group (rt_scan.h), the grid's is dense
-    V.leafBytes = (size_t)(tp.n_padded / 4u) * (V.grid ? 4u : rtd::kFlatLeafStride) * 16;
-    V.flat = !V.tree && !V.grid && useLds && ctx->useMfma && (V.candBytes + lds + V.leafBytes + MfmaOpsBytesFor(topCnt)) <= 160 * 1024;
-    V.ldsTables = useLds && !V.tree && !V.grid;
-    // a grid scene whose tables all fit LDS next to the grid scan's work lists (small scenes laid out for the grid: RT_GRID=2)
-    V.gridLds = V.grid && useLds && ctx->matsInLds && ctx->blockThreads == 1024 &&
-                V.candBytes + lds + V.leafBytes + ((size_t)tp.grid_nu * tp.grid_nv + 1) * 2 + 16 <= 128 * 1024;
-    return V;
-}
-
-// The queue of fresh paths (rt_params.h): the first static_blocks blocks of every launched wave are static, the remaining
-// paths are cut into eight shards of whole blocks.
-static void QueueShards(rtd::TraceParams& tp, uint32_t wavesLaunched, uint32_t queueBlock, uint32_t staticBlocks) {
-    tp.queue_block = queueBlock;
-    tp.static_blocks = staticBlocks;
-    const uint64_t total = tp.total_paths, qb = queueBlock;
-    uint64_t begin = (uint64_t)wavesLaunched * qb * staticBlocks;
-    if (begin > total) begin = total;
-    tp.dyn_begin = (uint32_t)begin;
-    tp.dyn_blocks = (uint32_t)((total - begin + qb - 1) / qb);
-}
+#define RT_ROW(LDS, M) &rtd::k_unit_closest<LDS, M>,
+static const ClosestKernelFn kClosestKernels[] = {RT_SCAN_VARIANTS(RT_ROW)};
+#undef RT_ROW
+#define RT_ROW(LDS, M) &rtd::rt_features_kernel<LDS, M>,
+static const FeaturesKernelFn kFeaturesKernels[] = {RT_SCAN_VARIANTS(RT_ROW)};
+#undef RT_ROW
+static_assert(sizeof(kTraceKernels) / sizeof(kTraceKernels[0]) == rtplan::kTraceVariantCount, "one row per variant of the list");
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of (device, function), process-wide: every kernel variant is raised
 // ONCE per device to the 160 KiB a workgroup can have, so that two contexts with different scenes can never disagree about it
 // (a per-context cache of "the last value I set" could skip the call after another context had lowered the limit), and a
-// launch-bound 1-spp frame pays the attribute call only the first time.
-static int RaiseLdsLimit(int device, const void* fn) {
+// launch-bound 1-spp frame pays the attribute call only the first time.  Never lowered, never set to one launch's size.
+static int RaiseLdsLimit(int device, const void* fn, size_t ldsBytes) {
+    if (ldsBytes <= 48 * 1024) return RT_OK;  // what every function may have without asking
     static std::mutex mu;
     static std::set<std::pair<int, const void*>> raised;
     std::lock_guard<std::mutex> lock(mu);
     if (raised.count({device, fn})) return RT_OK;
-    RT_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RT_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rtplan::kLdsPerCu));
     raised.insert({device, fn});
     return RT_OK;
 }
 
-// Launch the megakernel over total paths described by tp.  carryMode 0: ordinary launch.  1: probe -- RT_OK iff this scene
-// and these settings get the kernel variant that implements frame pipelining (nothing is launched).  2: launch that variant
-// (tp.ctl etc. filled by the caller; the queue cursor lives in tp.ctl and is reset by the preparation kernel).
-static int LaunchTrace(rt_ctx* ctx, rtd::TraceParams& tp, int carryMode = 0) {
+// Launch the megakernel over the total_paths paths described by tp.  Mode::Carry: the variant that implements frame pipelining
+// (tp.ctl etc. and the queue fields filled by the caller; the queue cursor lives in tp.ctl and is reset by the preparation kernel).
+static int LaunchTrace(rt_ctx* ctx, rtd::TraceParams& tp, rtplan::Mode mode = rtplan::Mode::Ordinary) {
+    const rtplan::TracePlan P = rtplan::PlanTrace(ShapeOf(tp), SettingsOf(ctx), KnobsFromEnv(), {tp.total_paths, tp.max_depth, mode});
+    if (P.status != RT_OK) return Fail(P.status, P.message);
     tp.shard_heads = ctx->queue.ptr;
     tp.fd_tile = rtd::make_fastdiv(tp.spp_pass ? 64u * tp.spp_pass : 1u);  // path_coordinates' divisors (rt_params.h, FastDiv)
     tp.fd_w = rtd::make_fastdiv(tp.W ? tp.W : 1u);
     tp.fd_rows = rtd::make_fastdiv(tp.rs.block_rows ? tp.rs.block_rows : 1u);
-    tp.mats_in_lds = ctx->matsInLds ? 1u : 0u;
-    // packed materials (decided below, once it is known where the variant reads its materials from).  RT_MATS16: 0 (default) never, 1
-    // from global memory wherever the 48-byte table would be read from there, 2 also staged into LDS by the flat stash variant.
-    // Measured (C2, three interleaved rounds): 48-byte records through L2 9,983 / packed from global memory 9,972 / packed in LDS
-    // with a 56-record stash 9,977 Msamples/s -- the material read is not what a hit waits for; C5: 7,579 -> 7,596; the unpacking adds 62 lane-operations per
-    // sample (+1.3 % of the kernel's VALU instructions, tools/phase_budget.py): same time for more instructions, so it stays off.
-    const bool want16 = tp.mats16 != nullptr && EnvU32("RT_MATS16", 0u) != 0u;
-    tp.mats16_mode = 0u;
-    tp.sg_glob16 = tp.sg_enabled ? rtd::sg_glob_slots(tp.sg_nglobal) : 0u;
-    const size_t lds = LdsBytesFor(tp.n, tp.n_padded, ctx->matsInLds);
-    if (tp.n_padded >= 65536) return Fail(RT_ERR_INVALID_ARG, "scenes beyond 65,000 spheres are not supported by the 16-bit candidate lists");
-    const uint32_t maxBlocks = (uint32_t)ctx->cuCount * ctx->blocksPerCu;
-    // one wave holds 64 paths; do not launch more waves than there is work for
-    const uint64_t wavesNeeded = ((uint64_t)tp.total_paths + 63) / 64;
-    const uint32_t wavesPerBlock = ctx->blockThreads / 64;
-    uint32_t blocks = (uint32_t)((wavesNeeded + wavesPerBlock - 1) / wavesPerBlock);
-    if (blocks > maxBlocks) blocks = maxBlocks;
-    if (blocks == 0) blocks = 1;
-    if (carryMode == 2) blocks = maxBlocks;  // carried paths may outnumber the fresh ones (a flush has none)
-    if (carryMode == 0) {
+    tp.mats_in_lds = P.mats_in_lds, tp.mats16_mode = P.mats16_mode;
+    tp.sg_glob16 = P.sg_glob16, tp.sg_in_lds = P.sg_in_lds, tp.tree_in_lds = P.tree_in_lds, tp.grid_in_lds = P.grid_in_lds;
+    tp.ray_cache_off16 = P.ray_cache_off16, tp.ray_cache_stride16 = P.ray_cache_stride16;
+    tp.stash_cap = P.stash_cap, tp.stash_process = P.stash_process;
+    ctx->lastTraceSky = P.lastTraceSky;
+    if (std::getenv("RT_VERBOSE"))
+        std::fprintf(stderr, "rt_trace launch: tree=%d flat=%d ldsTables=%d blocks=%u threads=%u lds=%zu B (cand %zu, tables %zu, leaf %zu, ops %zu, sg %zu, tree %zu, cache %s, stash %u)\n",
+                     (int)P.tree, (int)P.flat + 2 * (int)P.grid + 4 * (int)P.gridLds, (int)P.ldsTables, P.blocks, ctx->blockThreads, P.ldsBytes, P.candBytes, P.tablesBytes, P.leafBytes,
+                     P.opsBytes, P.sgBytes, P.treeBytes, P.cacheOn ? "yes" : "no", P.stash_cap);
+    if (mode == rtplan::Mode::Ordinary) {
         // queue cursors for this launch (the pipelined path sets them in its preparation kernel)
-        // 128-path blocks; 256 once a wave will take more than ~32 of them anyway (measured: +0.7 % at 1200x800 spp 128, +0.8 % on C4,
-        // +0.9 % on grid10k, neutral at spp 48, -1.7 % at spp 16, where the finer blocks balance the short launch's end better)
-        uint32_t qb = EnvU32("RT_QUEUE_BLOCK", 0u) / 64u * 64u;
-        if (qb == 0u) qb = (uint64_t)tp.total_paths >= 8192ull * blocks * wavesPerBlock ? 2u * rtd::kQueueBlock : rtd::kQueueBlock;
-        QueueShards(tp, blocks * wavesPerBlock, qb, EnvU32("RT_QUEUE_STATIC", 1u));
+        SetQueue(tp, P.queue);
         hipLaunchKernelGGL(rtd::rt_raygen_tables_kernel, dim3(1), dim3(64), 0, ctx->stream, (float2*)nullptr, 0u, 0u, (float2*)nullptr, 0u, 0u, 0u,
                            ctx->queue.ptr, (rtd::FrameCtl*)nullptr);
         RT_HIP(hipGetLastError());
     }
-    // dynamic LDS: per-wave candidate regions + the scene tables when they fit + the filter operand image
-    const TraceVariant V = ChooseVariant(ctx, tp);
-    const bool tree = V.tree, flat = V.flat, ldsTables = V.ldsTables;
-    const uint32_t topCnt = tp.level_cnt[tp.n_levels - 1];
-    const size_t candBytes = V.candBytes, leafBytes = V.leafBytes;
-    bool gridLds = V.gridLds;
-    size_t sgBytes = ((flat || gridLds) && tp.sg_enabled) ? (((size_t)tp.sg_nx * tp.sg_ny + 1 + tp.sg_nentries + tp.sg_nglobal) * 2 + 15) / 16 * 16 : 0;
-    if (candBytes + lds + leafBytes + (flat ? MfmaOpsBytesFor(topCnt) : 0) + sgBytes + (gridLds ? ((size_t)tp.grid_nu * tp.grid_nv + 1) * 2 + 16 : 0) > 160 * 1024) {
-        sgBytes = 0;  // index stays in global memory (L2)
-        if (tp.sg_enabled) gridLds = false;  // ... and the all-in-LDS grid variant needs it there
-    }
-    tp.sg_in_lds = sgBytes ? 1u : 0u;
-    size_t treeBytes = tree ? (size_t)(tp.level_off[tp.n_levels - 1] + topCnt) * 16 : 0;
-    if (!ctx->treeInLds || candBytes + MfmaOpsBytesFor(topCnt) + treeBytes > 160 * 1024) treeBytes = 0;
-    tp.tree_in_lds = treeBytes ? 1u : 0u;
-    const bool grid = V.grid;
-    // (the cells go to LDS in the 1024-thread variants; smaller workgroups -- a knob for experiments -- read them through L2)
-    size_t gridBytes = (grid && ctx->blockThreads == 1024) ? (((size_t)tp.grid_nu * tp.grid_nv + 1) * 2 + 15) / 16 * 16 : 0;
-    if (candBytes + gridBytes > 160 * 1024) gridBytes = 0;  // (cannot happen below 60,000 cells)
-    tp.grid_in_lds = gridBytes ? 1u : 0u;
-    // ... and, RT_GRID_QUANT=1 (experiments; BASELINE configs[4]'s "LDS-tiled sphere list"): in the stash variant with global tables
-    // the QUANTISED one-sphere bounds behind the cells (rt_scan.h GridQuant: the step loop then reads no global memory) when they
-    // leave room for a stash of at least 16 records.  Measured on grid10k (4096^2, spp 64): 40 KB of bounds leave 38 stash records
-    // instead of 63; 7.59 -> 7.10 Gsamples/s, of which -3.8 % is the smaller stash (float4 bounds at 38 records: 7.31) and -2.8 %
-    // the 17 extra operations per tested sphere that unpack the record -- the float4 bounds hit L1 95 % of the time, and what the
-    // L1 serves per cycle was not the limit it looked like (profiles/r04_c5_placement.json).  Default off.
-    size_t gridQBytes = 0;
-    if (grid && !gridLds && gridBytes != 0 && tp.grid_qrec != nullptr && ctx->useStash && carryMode == 0 && ctx->blockThreads == 1024 &&
-        tp.max_depth < 65536u && EnvU32("RT_GRID_QUANT", 0u) != 0u && EnvU32("RT_GRID_SG_LDS", 0u) == 0u && EnvU32("RT_STASH_CAP", 63u) >= 16u) {
-        const size_t qb = ((size_t)tp.n_padded * 4 + 15) / 16 * 16;
-        if (candBytes + gridBytes + qb + (size_t)wavesPerBlock * 16 * rtd::kStashDwords * 4 + 256 <= 160 * 1024) gridQBytes = qb;
-    }
-    // cell-grid scan with its tables in global memory, RT_GRID_SG_LDS=1 (experiments): the shadow index in LDS next to the cells when
-    // that leaves a stash of at least 24 records.  Measured on grid10k: 48.6 KB of index leave 31 records instead of 63: -5 %
-    // (6.47 vs 6.82 Gsamples/s) -- the full stash is worth more than the three dependent L2 reads per shadow query it would save.
-    bool gridSgLds = false;
-    if (grid && !gridLds && gridBytes != 0 && tp.sg_enabled && ctx->useStash && carryMode == 0 && ctx->blockThreads == 1024 && tp.max_depth < 65536u &&
-        EnvU32("RT_GRID_SG_LDS", 0u) != 0u) {
-        const size_t sgb = (((size_t)tp.sg_nx * tp.sg_ny + 1 + tp.sg_nentries + tp.sg_nglobal) * 2 + 15) / 16 * 16;
-        const size_t used = candBytes + gridBytes + sgb;
-        if (used + (size_t)wavesPerBlock * 24 * rtd::kStashDwords * 4 + 256 <= 160 * 1024) {
-            gridSgLds = true;
-            sgBytes = sgb;
-        }
-    }
-    size_t ldsBytes = candBytes + ((ldsTables || gridLds) ? lds : 0) + ((flat || gridLds) ? leafBytes : 0) + ((flat || tree) ? MfmaOpsBytesFor(topCnt) : 0) + sgBytes + treeBytes + gridBytes + gridQBytes;
-    // per-wave caches of prepared paths go last, when there is room left (RT_RAY_CACHE=0 disables them)
-    ldsBytes = (ldsBytes + 15) / 16 * 16;
-    tp.ray_cache_off16 = 0;
-    tp.ray_cache_stride16 = 0;
-    tp.stash_cap = 0;
-    // Hit stash (rt_kernels.h, kStash): the matrix-core variants at 1024 threads regroup their hit processing through a per-wave
-    // stash of up to 63 hit records in the room the path cache would take -- as many records as the LDS left over holds
-    // (RT_STASH=0: the path-cache variants; RT_STASH_CAP: fewer records).  depth shares its register with the scan entry.
-    bool useStash = false, matsL2 = false;
-    {
-        const size_t budget = 160 * 1024 / ctx->blocksPerCu;
-        const uint32_t capEnv = EnvU32("RT_STASH_CAP", 63u);
-        auto capFor = [&](size_t imageBytes) -> uint32_t {  // records per wave that fit behind an image of this size
-            if (budget <= imageBytes) return 0u;
-            const size_t room = (budget - imageBytes) / wavesPerBlock / 16 * 16;
-            uint32_t c = (uint32_t)(room / (rtd::kStashDwords * 4));
-            c = c > 63u ? 63u : c;
-            return c > capEnv ? capEnv : c;
-        };
-        const bool stashKernel = ctx->useStash && carryMode == 0 && (flat || tree || grid) && ctx->blockThreads == 1024 && tp.max_depth < 65536u;
-        uint32_t cap = capFor(ldsBytes);
-        // Flat variant: when the material table's 48 bytes per sphere would buy at least eight more records per wave, the
-        // materials are read through L2 instead (kMatsL2; measured on the cover scene: 44 -> 63 records, +1 %; RT_MATS_L2=0: never).
-        // Decided on the candidate image WITHOUT touching ldsBytes: the smaller image is committed only together with the stash
-        // variant that is built for it (the other flat kernels stage the material table and need its room).
-        if (stashKernel && flat && tp.mats_in_lds && (sgBytes != 0 || !tp.sg_enabled) && EnvU32("RT_MATS_L2", 1u) != 0u) {
-            const size_t matBytes = (size_t)tp.n_padded * 48;
-            const uint32_t cap2 = matBytes <= ldsBytes ? capFor(ldsBytes - matBytes) : 0u;
-            if (cap2 >= cap + 8u && cap2 >= 16u) {
-                matsL2 = true;
-                ldsBytes -= matBytes;
-                cap = cap2;
-                // ... and, RT_MATS16=2, their packed form into the room that leaves, when the stash keeps at least 48 records with it
-                const size_t m16Bytes = (size_t)tp.n_padded * 16;
-                const uint32_t cap3 = capFor(ldsBytes + m16Bytes);
-                if (want16 && EnvU32("RT_MATS16", 0u) >= 2u && cap3 >= 48u) {
-                    tp.mats16_mode = 2u;
-                    ldsBytes += m16Bytes;
-                    cap = cap3;
-                }
-            }
-        }
-        if (stashKernel && cap >= 16u) {
-            useStash = true;
-            tp.stash_cap = cap;
-            const uint32_t procEnv = EnvU32("RT_STASH_PROCESS", 63u);  // experiments: process hits from this many + 1 lanes on
-            tp.stash_process = procEnv < cap ? procEnv : cap;
-            tp.ray_cache_off16 = (uint32_t)(ldsBytes / 16);
-            tp.ray_cache_stride16 = (cap * rtd::kStashDwords * 4 + 15) / 16;
-            ldsBytes += (size_t)wavesPerBlock * tp.ray_cache_stride16 * 16;
-        }
-        if (matsL2 && !useStash) return Fail(RT_ERR_HIP, "internal: materials through L2 without the stash variant");
-        // every other variant that reads its materials from GLOBAL memory takes the packed record from there (one 16-byte read per
-        // hit instead of three); variants with the 48-byte table in LDS keep it
-        const bool matsGlobal = matsL2 || tree || (grid && !gridLds) || !tp.mats_in_lds || (!flat && !ldsTables && !gridLds);
-        if (want16 && tp.mats16_mode == 0u && matsGlobal) tp.mats16_mode = 1u;
-    }
-    if (!useStash && ctx->useRayCache && ldsBytes + (size_t)wavesPerBlock * rtd::kRayCacheBytes <= 160 * 1024 / ctx->blocksPerCu) {
-        tp.ray_cache_off16 = (uint32_t)(ldsBytes / 16);
-        tp.ray_cache_stride16 = rtd::kRayCacheBytes / 16;
-        ldsBytes += (size_t)wavesPerBlock * rtd::kRayCacheBytes;
-    }
-    if (std::getenv("RT_VERBOSE"))
-        std::fprintf(stderr, "rt_trace launch: tree=%d flat=%d ldsTables=%d blocks=%u threads=%u lds=%zu B (cand %zu, tables %zu, leaf %zu, ops %zu, sg %zu, tree %zu, cache %s, stash %u)\n",
-                     (int)tree, (int)flat + 2 * (int)grid + 4 * (int)gridLds, (int)ldsTables, blocks, ctx->blockThreads, ldsBytes, candBytes, ldsTables ? lds : (size_t)0, flat ? leafBytes : (size_t)0,
-                     (flat || tree) ? MfmaOpsBytesFor(topCnt) : (size_t)0, sgBytes, treeBytes, (tp.ray_cache_off16 && !useStash) ? "yes" : "no", tp.stash_cap);
-    // flat variant with the hit-processing tables provably in LDS (typed pointers: no flat loads) when they all fit
-    const bool hitLds = flat && tp.mats_in_lds && (sgBytes != 0 || !tp.sg_enabled);
-    if (carryMode != 0) {
-        const bool ok = hitLds && tp.ray_cache_off16 != 0 && ctx->blockThreads == 1024;
-        if (carryMode == 1) return ok ? RT_OK : RT_ERR_INVALID_ARG;
-        if (!ok) return Fail(RT_ERR_INVALID_ARG, "frame pipelining needs the flat LDS variant of the trace kernel");
-    }
-#define RT_LAUNCH_FN(KERNEL)                                                                                                  \
-    do {                                                                                                                      \
-        const void* fn_ = reinterpret_cast<const void*>(&KERNEL);                                                             \
-        /* the attribute belongs to the FUNCTION on this device, not to the context: raised once to what any launch can ask for, never lowered */ \
-        if (ldsBytes > 48 * 1024 && RaiseLdsLimit(ctx->device, fn_) != RT_OK) return RT_ERR_HIP;                               \
-        hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(ctx->blockThreads), ldsBytes, ctx->stream, tp);                         \
-    } while (0)
-/* the variant with these template arguments: the single-light kernel, or its twin over the light list (rt_kernels.h trace_body) */
-#define RT_LAUNCH_K(...)                                                          \
-    do {                                                                          \
-        if (tp.n_lights == 1u) RT_LAUNCH_FN((rtd::rt_trace_kernel<__VA_ARGS__>)); \
-        else RT_LAUNCH_FN((rtd::rt_trace_kernel_lights<__VA_ARGS__>));            \
-    } while (0)
-#define RT_LAUNCH(LDS, T, M)                                                                        \
-    do {                                                                                            \
-        if (((M) == 1 && hitLds) || ((M) == 2 && tp.tree_in_lds)) {                                 \
-            if (tp.ray_cache_off16) RT_LAUNCH_K(LDS, T, M, true, (M) != 0);  \
-            else RT_LAUNCH_K(LDS, T, M, false, (M) != 0);                    \
-        } else {                                                                                    \
-            if (tp.ray_cache_off16) RT_LAUNCH_K(LDS, T, M, true, false);    \
-            else RT_LAUNCH_K(LDS, T, M, false, false);                      \
-        }                                                                                           \
-    } while (0)
-#define RT_LAUNCH_T(LDS, M)                                            \
-    do {                                                               \
-        if (ctx->blockThreads == 1024) RT_LAUNCH(LDS, 1024, M);        \
-        else if (ctx->blockThreads == 512) RT_LAUNCH(LDS, 512, M);     \
-        else RT_LAUNCH(LDS, 256, M);                                   \
-    } while (0)
-    ctx->lastTraceSky = carryMode == 0 && useStash && !grid && !tree;  // kStash && kScan == 1 && !kCarry
-    if (carryMode == 2) RT_LAUNCH_K(true, 1024, 1, true, true, true);
-    else if (gridLds && useStash && tp.grid_in_lds) RT_LAUNCH_K(true, 1024, 3, true, true, false, true);
-    else if (gridLds && tp.grid_in_lds && tp.ray_cache_off16) RT_LAUNCH_K(true, 1024, 3, true, true);
-    else if (gridLds && tp.grid_in_lds) RT_LAUNCH_K(true, 1024, 3, false, true);
-    else if (grid && gridSgLds && useStash && tp.grid_in_lds) RT_LAUNCH_K(false, 1024, 3, true, true, false, true, false, true);
-    else if (grid && gridSgLds) return Fail(RT_ERR_HIP, "internal: the grid variant with the shadow index in LDS needs the hit stash");
-    else if (grid && ctx->blockThreads == 1024 && useStash && tp.grid_in_lds && gridQBytes != 0) RT_LAUNCH_K(false, 1024, 3, true, true, false, true, false, false, true);
-    else if (grid && gridQBytes != 0) return Fail(RT_ERR_HIP, "internal: quantised grid bounds without the stash variant");
-    else if (grid && ctx->blockThreads == 1024 && useStash && tp.grid_in_lds) RT_LAUNCH_K(false, 1024, 3, true, true, false, true);
-    else if (grid && ctx->blockThreads == 1024 && tp.grid_in_lds && tp.ray_cache_off16) RT_LAUNCH_K(false, 1024, 3, true, true);
-    else if (grid && ctx->blockThreads == 1024 && tp.grid_in_lds) RT_LAUNCH_K(false, 1024, 3, false, true);
-    else if (grid && ctx->blockThreads == 1024) RT_LAUNCH_K(false, 1024, 3, false, false);
-    else if (grid && ctx->blockThreads == 512 && !tp.ray_cache_off16) RT_LAUNCH_K(false, 512, 3, false, false);
-    else if (grid && ctx->blockThreads == 512) RT_LAUNCH_K(false, 512, 3, true, false);
-    else if (grid && !tp.ray_cache_off16) RT_LAUNCH_K(false, 256, 3, false, false);
-    else if (grid) RT_LAUNCH_K(false, 256, 3, true, false);
-    else if (useStash && tree && tp.tree_in_lds) RT_LAUNCH_K(false, 1024, 2, true, true, false, true);
-    else if (useStash && tree) RT_LAUNCH_K(false, 1024, 2, true, false, false, true);
-    else if (useStash && hitLds && matsL2) RT_LAUNCH_K(true, 1024, 1, true, true, false, true, true);
-    else if (useStash && hitLds) RT_LAUNCH_K(true, 1024, 1, true, true, false, true);
-    else if (useStash) RT_LAUNCH_K(true, 1024, 1, true, false, false, true);
-    else if (tree) RT_LAUNCH_T(false, 2);
-    else if (flat) RT_LAUNCH_T(true, 1);
-    else if (ldsTables) RT_LAUNCH_T(true, 0);
-    else RT_LAUNCH_T(false, 0);
-#undef RT_LAUNCH_T
-#undef RT_LAUNCH
-#undef RT_LAUNCH_K
-#undef RT_LAUNCH_FN
+    const int row = rtplan::FindTraceVariant(P.kernel);
+    if (row < 0) return Fail(RT_ERR_HIP, "internal: the launch plan chose a trace kernel variant that is not instantiated");
+    const TraceKernelFn fn = P.kernel.lights ? kTraceKernels[row].lights : kTraceKernels[row].one;
+    if (const int rc = RaiseLdsLimit(ctx->device, reinterpret_cast<const void*>(fn), P.ldsBytes)) return rc;
+    hipLaunchKernelGGL(fn, dim3(P.blocks), dim3(ctx->blockThreads), P.ldsBytes, ctx->stream, tp);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }
 
+// The unit kernels' launch (rtplan::PlanScanOnly): the scan variant rt_render would launch for this scene, 64 rays per wave, LDS
+// image for four waves, hit-processing tables left out.  Returns the row of the kernel in kClosestKernels / kFeaturesKernels.
+static int PlanScanOnlyLaunch(const rt_ctx* ctx, rtd::TraceParams& tp, rtplan::ScanOnlyPlan& P) {
+    P = rtplan::PlanScanOnly(ShapeOf(tp), SettingsOf(ctx));
+    tp.mats_in_lds = 0;
+    tp.sg_in_lds = 0;
+    if (P.kernel.kScan == 3) tp.grid_in_lds = 0;
+    if (P.kernel.kScan == 2) tp.tree_in_lds = P.tree_in_lds;
+    return rtplan::FindScanVariant(P.kernel);
+}
 
-// rt_unit_closest_hit's device part: the scan variant rt_render would launch for this scene, 64 rays per wave (LDS image
-// for four waves, hit-processing tables left out).  Also traces the pilot rays of the tile order.
+// rt_unit_closest_hit's device part.  Also traces the pilot rays of the tile order.
 static int LaunchClosest(rt_ctx* ctx, const float* dRays, uint32_t n, float* dOut) {
-        // the scan variant rt_render would launch for this scene; LDS image for four waves, hit-processing tables left out
-        rtd::TraceParams tp = ctx->base;
-        const TraceVariant V = ChooseVariant(ctx, tp);
-        tp.mats_in_lds = 0;
-        tp.sg_in_lds = 0;
-        const uint32_t topCnt = tp.level_cnt[tp.n_levels - 1];
-        const size_t waves = 256 / 64;
-        size_t ldsBytes = waves * (V.grid ? rtd::kWaveGridBytes : (V.tree ? rtd::kWaveCandBytes : rtd::kWaveListBytes));
-        if (V.grid) {
-            tp.grid_in_lds = 0;
-        } else if (V.tree) {
-            ldsBytes += MfmaOpsBytesFor(topCnt);
-            const size_t treeBytes = (size_t)(tp.level_off[tp.n_levels - 1] + topCnt) * 16;
-            tp.tree_in_lds = (ctx->treeInLds && ldsBytes + treeBytes <= 160 * 1024) ? 1u : 0u;
-            if (tp.tree_in_lds) ldsBytes += treeBytes;
-        } else if (V.flat || V.ldsTables) {
-            ldsBytes += LdsBytesFor(tp.n, tp.n_padded, false);
-            if (V.flat) ldsBytes += V.leafBytes + MfmaOpsBytesFor(topCnt);
-        }
-#define RT_UNIT_CLOSEST(LDS, M)                                                                                        \
-    do {                                                                                                               \
-        const void* fn_ = reinterpret_cast<const void*>(&rtd::k_unit_closest<LDS, M>);                                 \
-        if (ldsBytes > 48 * 1024) RT_HIP(hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes)); \
-        hipLaunchKernelGGL((rtd::k_unit_closest<LDS, M>), dim3((n + 255) / 256), dim3(256), ldsBytes, ctx->stream, tp, dRays, n, dOut); \
-    } while (0)
-        if (V.grid) RT_UNIT_CLOSEST(false, 3);
-        else if (V.tree) RT_UNIT_CLOSEST(false, 2);
-        else if (V.flat) RT_UNIT_CLOSEST(true, 1);
-        else if (V.ldsTables) RT_UNIT_CLOSEST(true, 0);
-        else RT_UNIT_CLOSEST(false, 0);
-#undef RT_UNIT_CLOSEST
-        RT_HIP(hipGetLastError());
+    rtd::TraceParams tp = ctx->base;
+    rtplan::ScanOnlyPlan P;
+    const int row = PlanScanOnlyLaunch(ctx, tp, P);
+    if (row < 0) return Fail(RT_ERR_HIP, "internal: the launch plan chose a scan that is not instantiated");
+    const ClosestKernelFn fn = kClosestKernels[row];
+    if (const int rc = RaiseLdsLimit(ctx->device, reinterpret_cast<const void*>(fn), P.ldsBytes)) return rc;
+    hipLaunchKernelGGL(fn, dim3((n + 255) / 256), dim3(256), P.ldsBytes, ctx->stream, tp, dRays, n, dOut);
+    RT_HIP(hipGetLastError());
     return RT_OK;
 }
 
 // The feature pass (rt_kernels.h rt_features_kernel) over the strip's npix local pixels: the scan variant and the LDS image of
-// LaunchClosest (four waves, hit-processing tables left out), persistent workgroups -- as many as are resident at once.
+// LaunchClosest, persistent workgroups -- as many as are resident at once.
 static int LaunchFeatures(rt_ctx* ctx, rtd::TraceParams& tp, const rtd::FeatureParams& fp) {
-    const TraceVariant V = ChooseVariant(ctx, tp);
-    tp.mats_in_lds = 0;
-    tp.sg_in_lds = 0;
+    rtplan::ScanOnlyPlan P;
+    const int row = PlanScanOnlyLaunch(ctx, tp, P);
+    if (row < 0) return Fail(RT_ERR_HIP, "internal: the launch plan chose a scan that is not instantiated");
     tp.fd_w = rtd::make_fastdiv(tp.W ? tp.W : 1u);
     tp.fd_rows = rtd::make_fastdiv(tp.rs.block_rows ? tp.rs.block_rows : 1u);
-    const uint32_t topCnt = tp.level_cnt[tp.n_levels - 1];
-    const size_t waves = 256 / 64;
-    size_t ldsBytes = waves * (V.grid ? rtd::kWaveGridBytes : (V.tree ? rtd::kWaveCandBytes : rtd::kWaveListBytes));
-    if (V.grid) {
-        tp.grid_in_lds = 0;
-    } else if (V.tree) {
-        ldsBytes += MfmaOpsBytesFor(topCnt);
-        const size_t treeBytes = (size_t)(tp.level_off[tp.n_levels - 1] + topCnt) * 16;
-        tp.tree_in_lds = (ctx->treeInLds && ldsBytes + treeBytes <= 160 * 1024) ? 1u : 0u;
-        if (tp.tree_in_lds) ldsBytes += treeBytes;
-    } else if (V.flat || V.ldsTables) {
-        ldsBytes += LdsBytesFor(tp.n, tp.n_padded, false);
-        if (V.flat) ldsBytes += V.leafBytes + MfmaOpsBytesFor(topCnt);
-    }
-    if (ldsBytes > 160 * 1024) return Fail(RT_ERR_HIP, "internal: the feature pass's LDS image exceeds a workgroup's 160 KiB");
+    const size_t ldsBytes = P.ldsBytes, waves = 256 / 64;
+    if (ldsBytes > rtplan::kLdsPerCu) return Fail(RT_ERR_HIP, "internal: the feature pass's LDS image exceeds a workgroup's 160 KiB");
     const uint32_t nTiles = (fp.npix + 63u) / 64u;
-    size_t perCu = (160 * 1024) / (ldsBytes ? ldsBytes : 1);  // workgroups of this image a CU holds, at most 8 (32 waves)
+    size_t perCu = rtplan::kLdsPerCu / (ldsBytes ? ldsBytes : 1);  // workgroups of this image a CU holds, at most 8 (32 waves)
     perCu = perCu > 8 ? 8 : (perCu < 1 ? 1 : perCu);
     uint32_t blocks = (uint32_t)((nTiles + waves - 1) / waves);
     const uint32_t maxBlocks = (uint32_t)ctx->cuCount * (uint32_t)perCu;
     if (blocks > maxBlocks) blocks = maxBlocks;
     if (blocks == 0) blocks = 1;
-#define RT_FEATURES(LDS, M)                                                                                            \
-    do {                                                                                                               \
-        const void* fn_ = reinterpret_cast<const void*>(&rtd::rt_features_kernel<LDS, M>);                             \
-        if (ldsBytes > 48 * 1024 && RaiseLdsLimit(ctx->device, fn_) != RT_OK) return RT_ERR_HIP;                       \
-        hipLaunchKernelGGL((rtd::rt_features_kernel<LDS, M>), dim3(blocks), dim3(256), ldsBytes, ctx->stream, tp, fp); \
-    } while (0)
-    if (V.grid) RT_FEATURES(false, 3);
-    else if (V.tree) RT_FEATURES(false, 2);
-    else if (V.flat) RT_FEATURES(true, 1);
-    else if (V.ldsTables) RT_FEATURES(true, 0);
-    else RT_FEATURES(false, 0);
-#undef RT_FEATURES
+    const FeaturesKernelFn fn = kFeaturesKernels[row];
+    if (const int rc = RaiseLdsLimit(ctx->device, reinterpret_cast<const void*>(fn), ldsBytes)) return rc;
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), ldsBytes, ctx->stream, tp, fp);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }
@@ -604,7 +393,7 @@ static int BuildTileMasks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
     const uint32_t nFull = npix >> 6;
     const rtd::TraceParams& b = ctx->base;
     const bool wanted = EnvU32("RT_PRIMARY_MASK", 1u) != 0u && nFull != 0u && b.n_levels == 1u && b.level_cnt[0] <= 128u &&
-                        ChooseVariant(ctx, b).flat;
+                        rtplan::ChooseScan(ShapeOf(b), SettingsOf(ctx), 0u).flat;
     if (!wanted) {
         ctx->tileMaskValid = false;
         return RT_OK;
@@ -726,7 +515,7 @@ static void PipelineShards(const rt_ctx* ctx, rtd::TraceParams& tp) {
     // measured (tools/progressive_frames.py, 1-spp frames): 128-path blocks x 1 static beat 64 x 2, 128 x 0, 192 x 1, 256 x 0
     uint32_t qb = EnvU32("RT_PIPE_QUEUE_BLOCK", rtd::kCarryQueueBlock) / 64u * 64u;
     if (qb == 0) qb = 64;
-    QueueShards(tp, PipelineWaves(ctx), qb, EnvU32("RT_PIPE_STATIC_BLOCKS", 1));
+    SetQueue(tp, rtplan::CutQueue(tp.total_paths, PipelineWaves(ctx), qb, EnvU32("RT_PIPE_STATIC_BLOCKS", 1)));
 }
 
 static int PipelineTraceAndCommit(rt_ctx* ctx, rtd::TraceParams& tp, uint32_t npix, bool carry) {
@@ -740,7 +529,7 @@ static int PipelineTraceAndCommit(rt_ctx* ctx, rtd::TraceParams& tp, uint32_t np
     tp.max_carry_age = ctx->pipeDepth;
     tp.min_iters = EnvU32("RT_PIPE_MIN_ITERS", 8);
     tp.counters = ctx->counters.ptr;
-    int rc = LaunchTrace(ctx, tp, 2);
+    int rc = LaunchTrace(ctx, tp, rtplan::Mode::Carry);
     if (rc != RT_OK) return rc;
     hipLaunchKernelGGL(rtd::rt_commit_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->ring.ptr, ctx->hdr.ptr, npix,
                        npix * ctx->pipeSppCap, ctx->pipeRing, ctx->pipeRegions, ctx->ctl.ptr, ctx->pipeSeq, ctx->pipeCommits);
@@ -1345,9 +1134,8 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
     // (the carrying kernel's commit adds no second moments: with rt_set_noise_estimate on every call renders unpipelined)
     bool pipelined = ctx->pipeDepth > 0 && out_stats == nullptr && !ctx->noise;
     if (pipelined) {
-        rtd::TraceParams probe = ctx->base;
-        probe.total_paths = npix;
-        pipelined = LaunchTrace(ctx, probe, 1) == RT_OK && (uint64_t)npix * (s1 - s0) * (ctx->pipeDepth + 2u) < (1ull << 31);
+        pipelined = rtplan::PlanTrace(ShapeOf(ctx->base), SettingsOf(ctx), KnobsFromEnv(), {npix, ctx->base.max_depth, rtplan::Mode::Carry}).pipelines &&
+                    (uint64_t)npix * (s1 - s0) * (ctx->pipeDepth + 2u) < (1ull << 31);
     }
     if (s0 == 1 || ctx->accumulated == 0) PipelineDrop(ctx);  // a new accumulation abandons whatever was in flight
     else if (!pipelined) {
@@ -1976,6 +1764,14 @@ static int PrepareForShadow(const char* who, const rt_sphere* spheres, uint32_t 
     const std::vector<rt_material> mats(n, rt_material{});
     P = rtprep::PrepareScene(spheres, mats.data(), n, lights, n_lights, rtprep::PrepOptions::FromEnv());
     if (P.layout.scan.size() >= 65536) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": scenes beyond 65,535 scan entries are not supported");
+    return RT_OK;
+}
+
+int rt_unit_launch_plan(const uint32_t* cases, uint32_t n, uint32_t* plans) {
+    if ((!cases || !plans) && n != 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_launch_plan: invalid argument");
+    for (uint32_t k = 0; k < n; ++k)
+        if (rtplan::PlanPacked(cases + (size_t)k * rtplan::kCaseWords, plans + (size_t)k * rtplan::kPlanWords) != RT_OK)
+            return Fail(RT_ERR_INVALID_ARG, "rt_unit_launch_plan: case " + std::to_string(k) + " describes no context or scene there can be");
     return RT_OK;
 }
 

@@ -49,7 +49,7 @@ enum : uint32_t { kIdle = 0u, kNeedClosest = 1u, kNeedShadow = 2u, kHaveHit = 3u
 // Hit stash (kStash variants of rt_trace_kernel): one record per closest hit that waits for its hit processing --
 // hit position, ray direction, throughput, radiance, stream state, sample slot, depth | scan entry << 16, traversals.
 // Field k of record r sits at dword k * cap + r of the wave's region: consecutive records, consecutive banks.
-constexpr uint32_t kStashDwords = 19;
+static_assert(kStashDwords == 4 * 3 + 4 + 3, "rt_layout_consts.h: four three-vectors, the stream state, slot, depth | entry, traversals");
 
 // Work-item index -> (column i, global row j, sample s) and the path's slot in the sample buffer: the explicit path
 // list of the unit tests, or the tiled order below over the rows of this shard.  slot = index either way.

@@ -40,8 +40,7 @@ static __device__ unsigned int g_tlHist[1024];  // waves leaving the loop per 25
 #endif
 
 constexpr int kWaveSize = 64;
-constexpr uint32_t kQueueBlock = 128;  // paths a wave takes from the global queue per claim (claimed one block ahead: rt_kernels.h)
-constexpr uint32_t kCarryQueueBlock = 128; // ... in the frame-pipelining kernel (rt_kernels.h): two batches of the path cache
+constexpr uint32_t kCarryQueueBlock = 128; // paths per queue block (rt_layout_consts.h kQueueBlock) in the frame-pipelining kernel (rt_kernels.h): two batches of the path cache
 
 // ---- frame pipelining (progressive use: SpheresApp::OnRender adds ONE sample per frame, spheres-app.cpp:163-184).
 // A 1-spp frame is 0.13 ms of work followed by the tail of its few 51-segment paths; with pipelining the trace kernel of
@@ -102,10 +101,6 @@ struct FrameCtl {            // device control block of one context's pipeline
     uint32_t committed_samples[2];  // samples per pixel in the HDR strip
 };
 constexpr uint32_t kMaxFramesInFlight = 16;  // regions of the sample ring
-// The shadow index's GLOBAL list (spheres whose footprint covers much of the grid: the floor, the big spheres; <= 64) is walked by
-// every query: its spheres and ids sit in LDS in every variant -- 18 bytes each -- so that the walk reads them directly instead of
-// chasing id -> sphere through the tables (two dependent L2 reads per pair of entries in the large-scene variants).
-RT_DEV uint32_t sg_glob_slots(uint32_t nGlobal) { return nGlobal ? nGlobal + (nGlobal * 2u + 15u) / 16u : 0u; }
 
 // Lights 1 .. n_lights-1 of the scene's list (light 0 lives in TraceParams / SceneConsts as before): direction, radiance and
 // the light's own shadow index, in global memory.  Member names equal SceneConsts' so that shade_value / shadow_query take either.
@@ -246,9 +241,7 @@ struct SceneConsts {
     uint32_t prim_direct;   // ... and those resolved directly from the tile's sphere list (counters[4]; counters[3] gets both)
     uint32_t prim_sky;      // ... and, of those, the planes of empty-list tiles finished in K_GEN without rays (kSky; counters[5])
 };
-constexpr uint32_t kSceneConstBytes = 256;                         // SceneConsts at the start of the dynamic LDS image ...
-constexpr uint32_t kConstBytes = kSceneConstBytes + 8 * 256;       // ... followed by the elementary functions' tables (255 words)
-static_assert(sizeof(SceneConsts) <= kSceneConstBytes, "SceneConsts must fit its LDS slot");
+static_assert(sizeof(SceneConsts) <= kSceneConstBytes, "SceneConsts must fit its LDS slot (rt_layout_consts.h)");
 static_assert(kMathTabWords <= 256, "math tables must fit their LDS slot");
 RT_DEV void fill_consts(const TraceParams& p, SceneConsts& k) {
     for (int i = 0; i < 3; ++i) {

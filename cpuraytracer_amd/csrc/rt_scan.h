@@ -202,9 +202,9 @@ constexpr uint32_t kFarDrain = 128;                                     // hiera
 constexpr uint32_t kPoolA = RT_POOL_A;                                  // pooled resolve: (ray, group) items per pass
 constexpr uint32_t kPoolB = RT_POOL_B;                                  // pooled resolve: (ray, sphere) items before a drain
 static_assert(kPoolB > 4 * 64 && (kPoolA * 2 + kPoolB * 2) % 16 == 0, "a round may add 256 entries; the keys behind the pools are 8-byte aligned");
-constexpr uint32_t kWaveListBytes = kPoolA * 2 + kPoolB * 2 + 64 * 8;      // item pools + per-ray best keys = 2816 B per wave
+static_assert(kWaveListBytes == kPoolA * 2 + kPoolB * 2 + 64 * 8, "rt_layout_consts.h: item pools + per-ray best keys per wave");
 static_assert(kTreeExact >= kFarDrain + 4 * 64, "a round may add 256 entries to an exact list that holds up to kFarDrain - 1");
-constexpr uint32_t kWaveCandBytes = kTreeWork * 4 + kTreeExact * 4 + 64 * 8;  // hierarchy scan: 5888 B per wave
+static_assert(kWaveCandBytes == kTreeWork * 4 + kTreeExact * 4 + 64 * 8, "rt_layout_consts.h: the hierarchy scan's lists + keys per wave");
 // Cell-grid scan: (ray, slab) items of up to RT_GRID_FEED slabs per ray and feed pass.  Measured on grid10k (4096^2, spp 64; the
 // list's bytes come out of the hit stash): 4 slabs / 320 items 8,205 Msamples/s, 6 / 384 8,175, 8 / 512 8,383, 8 / 640 8,474,
 // 10 / 640 8,448, 8 / 768 8,326, 12 / 768 8,413, 16 / 1024 8,210; 2 / 320 7,770.  Without the consumers' re-check of the closest hit
@@ -224,12 +224,11 @@ constexpr uint32_t kGridWork = RT_GRID_WORK;
 // 128: 8,193 / 8,208 / 8,228 / 8,068 / 7,956 Msamples/s
 constexpr uint32_t kGridDrain = RT_GRID_DRAIN;
 constexpr uint32_t kGridExact = kGridDrain + 4 * 64;  // a step may add 256 entries to an exact list that holds up to kGridDrain - 1
-constexpr uint32_t kWaveGridBytes = kGridWork * 4 + kGridExact * 4 + 64 * 8;  // grid scan: 4480 B per wave
+static_assert(kWaveGridBytes == kGridWork * 4 + kGridExact * 4 + 64 * 8, "rt_layout_consts.h: the grid scan's lists + keys per wave");
 static_assert(kWaveGridBytes % 16 == 0 && ((kGridWork + kGridExact) * 4) % 8 == 0, "per-wave regions are float4 aligned, the keys behind the lists 8-byte aligned");
 template <int kScan>
 constexpr uint32_t wave_region_bytes() { return kScan == 3 ? kWaveGridBytes : (kScan == 2 ? kWaveCandBytes : kWaveListBytes); }
 constexpr float kMarginRel = kMarginK * 5.9604645e-8f;                 // K * eps
-constexpr uint32_t kRayCacheBytes = 64 * 48;                            // per-wave cache of prepared paths
 // Flat scan: the LDS copy of the one-sphere bounds keeps each group's four float4 at a stride of FIVE (80 bytes).  Phase A
 // reads bound q of (ray, group) items with one ds_read_b128 per q, which the LDS serves in sets of 16 lanes over 64 banks: at a
 // stride of 64 bytes the bank quad of bound q is (4 gid + q) mod 16 -- four values whatever the groups are, so 16 lanes with
@@ -238,7 +237,7 @@ constexpr uint32_t kRayCacheBytes = 64 * 48;                            // per-w
 #ifndef RT_LEAF_STRIDE
 #define RT_LEAF_STRIDE 5
 #endif
-constexpr uint32_t kFlatLeafStride = RT_LEAF_STRIDE;
+static_assert(kFlatLeafStride == RT_LEAF_STRIDE, "rt_layout_consts.h holds the stride the launch plan sizes the copy with");
 #ifndef RT_A2
 #define RT_A2 1  // flat scan, pooled phase A: two (ray, group) items per lane and step
 #endif
@@ -248,7 +247,6 @@ constexpr uint32_t kFlatLeafStride = RT_LEAF_STRIDE;
 #ifndef RT_LIST_WORDS
 #define RT_LIST_WORDS 1  // flat scan: candidate lists are pushed word by word (0: the round-3 loops over 64-bit halves)
 #endif                    // float4 slots per group in the flat scan's LDS copy (4 = dense)
-constexpr uint32_t kOpsPerTile = 8 * 64;                                // dwords of the group operand image per 32-group tile
 
 // Split-bf16 operands.  An f32 value v is carried as h + l with h = bf16(v) and l = bf16(v - h) (both round to
 // nearest even; v - h is exact), so |v - (h + l)| <= 2^-18 |v|, and a product x*y becomes the four exact bf16 products
@@ -281,8 +279,7 @@ RT_DEV uint32_t split_ray_value(float v) {
 // matrix row R = l&31: dwords 0-3 = the b chain's two values (-Cx,-Cy | -Cz,1 for l>>5 = 0 | 1) as (hh, ll) pairs,
 // dwords 4-7 = the a*cc chain's (Cx,Cy | Cz,W) in its three-term form plus the constant slots (below).  Rows are PERMUTED so that the candidate bitmaps decode with two
 // operations: output element e (0..15) of the lane in half h is matrix row (e&3) + 8(e>>2) + 4h, and that row holds
-// group 32 t + 16 h + e.  The image always has an even number of tiles (bitmap words cover two tiles).
-RT_DEV uint32_t mfma_tiles_for(uint32_t nTop) { return (((nTop + 31u) / 32u) + 1u) & ~1u; }
+// group 32 t + 16 h + e.  The image always has an even number of tiles (bitmap words cover two tiles: rt_layout_consts.h mfma_tiles_for).
 RT_DEV void build_mfma_operands(const float4* __restrict__ bounds, uint32_t nGroups, uint32_t nTiles, float* __restrict__ ops, uint32_t tid,
                                 uint32_t nthreads) {
     uint32_t* img = reinterpret_cast<uint32_t*>(ops);

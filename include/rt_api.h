@@ -425,6 +425,33 @@ int rt_unit_shadow_query_host(const rt_sphere* spheres, uint32_t n, const rt_lig
  * lights 1 ..: their records): the same byte per point.  glob_in_lds != 0: the index's global list is walked from a copy of
  * (spheres, ids) in LDS, staged as the trace kernel stages it; 0: from its id list in global memory. */
 int rt_unit_shadow(rt_ctx* ctx, uint32_t light, const float* points, uint32_t n, uint32_t glob_in_lds, uint8_t* out);
+/* What the launcher decides for n trace launches, with no context and no device (csrc/host/rt_launch_plan.h): the LDS image, the
+ * launch parameters that describe it, the grid and the kernel variant.  cases: 28 words each --
+ *   [0] scan entries (n_padded)  [1] hierarchy levels (1..6)  [2] nodes of the top level  [3] first node of the top level
+ *   [4] scene bits: 1 laid out for the cell grid, 2 has quantised bounds, 4 light 0 has a shadow index, 8 has packed materials
+ *   [5] [6] grid cells nu, nv  [7] [8] shadow index cells nx, ny  [9] its entries  [10] its global entries  [11] lights
+ *   [12] CUs  [13] blocks per CU (1..8)  [14] threads per block (a multiple of 64, <= 1024)
+ *   [15] setting bits: 1 RT_SCAN=mfma, 2 RT_MATS_LDS, 4 RT_RAY_CACHE, 8 RT_STASH, 16 RT_TREE_LDS, 32 RT_FORCE_GLOBAL_TABLES
+ *   [16] RT_MATS16  [17] RT_MATS_L2  [18] RT_STASH_CAP  [19] RT_STASH_PROCESS  [20] RT_GRID_QUANT  [21] RT_GRID_SG_LDS  [22] RT_QUEUE_BLOCK
+ *   [23] RT_QUEUE_STATIC  [24] paths  [25] max_depth  [26] 0 = ordinary launch, 1 = the frame-pipelining launch  [27] 0
+ * plans: 28 words each --
+ *   [0] RT_OK or the error code of a refused launch  [1] which refusal: 1 too many scan entries, 2 no pipelining for this scene,
+ *       3..5 internal (materials through L2 / shadow index in LDS / quantised bounds, each without the hit stash); after a refusal
+ *       only [26] and [27] are valid besides
+ *   [2] blocks  [3] dynamic LDS bytes  [4..9] the parts RT_VERBOSE prints: work lists, tables, one-sphere bounds, filter operands,
+ *       shadow index, hierarchy
+ *   [10] bits: 1 hierarchy scan, 2 flat scan, 4 cell-grid scan, 8 ... with every table in LDS, 16 scan tables in LDS, 32 path cache,
+ *        64 the kernel finishes empty-list planes itself, 128 ([26] = 1) the scene gets the pipelining variant
+ *   [11] mats_in_lds  [12] mats16_mode  [13] sg_glob16  [14] sg_in_lds  [15] tree_in_lds  [16] grid_in_lds  [17] ray_cache_off16
+ *   [18] ray_cache_stride16  [19] stash_cap  [20] stash_process  [21] queue_block  [22] static_blocks  [23] dyn_begin  [24] dyn_blocks
+ *       ([21..24]: 0 for the pipelining launch, whose caller sets them)
+ *   [25] the kernel: bit 0 the _lights twin, 1 kLds, 2-3 kThreads (0 = 256, 1 = 512, 2 = 1024), 4-5 kScan, 6 kCache, 7 kHitLds, 8 kCarry,
+ *        9 kStash, 10 kMatsL2, 11 kSgLds, 12 kGridQ, 31 the variant is instantiated
+ *   [26] the unit kernels' scan (rt_unit_closest_hit, rt_render_features): bit 0 kLds, 1-2 kScan, 3 tree_in_lds, 4 instantiated
+ *   [27] ... and their dynamic LDS bytes
+ * A case no context or scene can be ([13], [14], [1] out of range, cells beyond 65,535 a side, unknown bits) is RT_ERR_INVALID_ARG.
+ * Needs no GPU. */
+int rt_unit_launch_plan(const uint32_t* cases, uint32_t n, uint32_t* plans);
 /* The resolve of spheres-app.cpp:196-214 for given HDR triples -> R,G,B bytes */
 int rt_unit_tonemap(rt_ctx* ctx, const float* hdr_rgb, uint32_t n, uint32_t n_samples, uint8_t* out_rgb);
 
