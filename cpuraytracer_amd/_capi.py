@@ -41,6 +41,11 @@ class RtStats(C.Structure):
                 ("local_rows", C.c_uint32), ("passes", C.c_uint32)]
 
 
+class RtDenoiseParams(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("k_normal", C.c_float), ("k_depth", C.c_float), ("k_albedo", C.c_float),
+                ("k_coverage", C.c_float), ("k_colour", C.c_float), ("var_floor", C.c_float)]
+
+
 SPHERE_DTYPE = np.dtype([("cx", "<f4"), ("cy", "<f4"), ("cz", "<f4"), ("r", "<f4")])
 MATERIAL_DTYPE = np.dtype([("type", "<u4"), ("tex_type", "<u4"), ("smoothness", "<f4"), ("ior", "<f4"),
                            ("tiling", "<f4"), ("rgb0", "<f4", (3,)), ("rgb1", "<f4", (3,)), ("luminance", "<f4")])
@@ -62,6 +67,7 @@ EXPORTS = [
     "rt_unit_features_host",
     "rt_unit_shadow_index_host", "rt_unit_shadow_query_host", "rt_unit_shadow",
     "rt_unit_launch_plan",
+    "rt_denoise_default_params", "rt_denoise", "rt_download_denoised", "rt_copy_denoised_to_device", "rt_unit_denoise_host", "rt_unit_denoise_forms",
 ]
 
 _lib = None
@@ -158,6 +164,14 @@ def load():
         L.rt_unit_shadow.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     if hasattr(L, "rt_unit_launch_plan"):
         L.rt_unit_launch_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    if hasattr(L, "rt_denoise"):
+        L.rt_denoise_default_params.argtypes = [C.POINTER(RtDenoiseParams)]
+        L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(RtDenoiseParams), C.POINTER(C.c_double)]
+        L.rt_download_denoised.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_copy_denoised_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_unit_denoise_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RtDenoiseParams),
+                                           C.c_void_p, C.c_void_p]
+        L.rt_unit_denoise_forms.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -165,6 +179,17 @@ def load():
 def check(rc):
     if rc != RT_OK:
         raise RtError(rc, load().rt_last_error().decode())
+
+
+def denoise_params(**fields):
+    """rt_denoise_default_params with the given fields replaced (levels, k_normal, k_depth, k_albedo, k_coverage, k_colour, var_floor)."""
+    p = RtDenoiseParams()
+    check(load().rt_denoise_default_params(C.byref(p)))
+    for k, v in fields.items():
+        if k not in dict(RtDenoiseParams._fields_):
+            raise TypeError("rt_denoise_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
 
 
 def whole_image(H):

@@ -18,6 +18,8 @@ static void Usage() {
               "               [--noise-out file.pfm]   per-pixel standard error of the image (HDR units) as a one-channel PFM, rows top to bottom\n"
               "               [--features-out PREFIX]  first-hit feature buffers of the rendered samples, as means: PREFIX.albedo.pfm and\n"
               "                                PREFIX.normal.pfm (three channels), PREFIX.depth.pfm and PREFIX.coverage.pfm (one channel)\n"
+              "               [--denoise-out file.ppm [--denoise-levels N]]   the picture after the feature-guided a-trous filter (rt_denoise, N = 1..5\n"
+              "                                levels, default 3), written beside --out, which is unchanged; needs --spp >= 2\n"
               "               [--target-error T [--target-fraction F] [--max-spp N]]   render --frame-spp samples at a time until at most the\n"
               "                                fraction F (default 0) of the pixels has a relative error above T, or N (default --spp) is reached\n"
               "               [--noise-floor F]        added to a pixel's r + g + b before the relative error divides by it (default 0.01)");
@@ -27,7 +29,8 @@ int main(int argc, char** argv) {
     AppSettingsT st;
     uint32_t spp = 16;
     int device = 0, gpus = 0;
-    std::string out = "out.ppm", noiseOut, featuresOut;
+    std::string out = "out.ppm", noiseOut, featuresOut, denoiseOut;
+    uint32_t denoiseLevels = 0;  // 0: the default
     float targetError = 0.f;
     double targetFraction = 0.0;
     uint32_t maxSpp = 0;
@@ -57,6 +60,8 @@ int main(int argc, char** argv) {
         else if (k == "--batch") st.framesPerLaunch = (uint32_t)std::atoi(val());
         else if (k == "--noise-out") noiseOut = val();
         else if (k == "--features-out") featuresOut = val();
+        else if (k == "--denoise-out") denoiseOut = val();
+        else if (k == "--denoise-levels") denoiseLevels = (uint32_t)std::atoi(val());
         else if (k == "--target-error") { targetError = (float)std::atof(val()); targetSet = true; }
         else if (k == "--target-fraction") targetFraction = std::atof(val());
         else if (k == "--max-spp") maxSpp = (uint32_t)std::atoi(val());
@@ -75,7 +80,11 @@ int main(int argc, char** argv) {
     }
     if (st.samplesPerFrame == 0 || spp == 0 || st.k_backbufferWidth <= 0 || st.k_backbufferHeight <= 0) { Usage(); return 2; }
     if (spp % st.samplesPerFrame != 0) st.samplesPerFrame = 1;
-    st.noiseEstimate = targetSet || !noiseOut.empty();
+    if (!denoiseOut.empty() && gpus > 0) {
+        std::fprintf(stderr, "spheres: --denoise-out is not available with --gpus: the multi-GPU gather carries neither second moments nor feature strips\n");
+        return 2;
+    }
+    st.noiseEstimate = targetSet || !noiseOut.empty() || !denoiseOut.empty();
     if (st.noiseEstimate && gpus > 0) {
         std::fprintf(stderr, "spheres: --noise-out and --target-error are not available with --gpus: the multi-GPU gather carries no second moments\n");
         return 2;
@@ -124,6 +133,10 @@ int main(int argc, char** argv) {
     }
     if (!featuresOut.empty() && !app.WriteFeaturePFMs(featuresOut)) {
         std::fprintf(stderr, "spheres: cannot write the feature buffers %s.*.pfm: %s\n", featuresOut.c_str(), rt_last_error());
+        return 1;
+    }
+    if (!denoiseOut.empty() && !app.WriteDenoisedPPM(denoiseOut, denoiseLevels)) {
+        std::fprintf(stderr, "spheres: cannot write the denoised picture %s: %s\n", denoiseOut.c_str(), rt_last_error());
         return 1;
     }
     if (targetSet) std::printf("{\"target_error\": %g, \"target_fraction\": %g, \"spp_reached\": %zu}\n", (double)targetError, targetFraction, app.SampleCount());

@@ -1,0 +1,78 @@
+// rt_denoise_host.cpp -- the denoiser's arithmetic (../rt_denoise.h) compiled for the host: rt_unit_denoise_host, the twin the
+// device is compared with bit for bit, and the parameter defaults.  Plain C++ with no HIP header, under the same floating-point
+// contract as the kernels (-ffp-contract=off, IEEE division).  Needs no GPU.
+#include <cstddef>
+#include <vector>
+
+#include "../../../include/rt_api.h"
+#include "../rt_denoise.h"
+#include "rt_error.h"
+
+using rtprep::Fail;
+
+static_assert(sizeof(rt_denoise_params) == sizeof(rtd::DenoiseParams) && offsetof(rt_denoise_params, var_floor) == offsetof(rtd::DenoiseParams, var_floor),
+              "rt_denoise_params is laid out like rtd::DenoiseParams");
+
+extern "C" {
+
+int rt_denoise_default_params(rt_denoise_params* out) {
+    if (!out) return Fail(RT_ERR_INVALID_ARG, "rt_denoise_default_params: null argument");
+    out->levels = 3;
+    out->k_normal = 16.0f;
+    out->k_depth = 400.0f;
+    out->k_albedo = 64.0f;
+    out->k_coverage = 16.0f;
+    out->k_colour = 1.0f;
+    out->var_floor = 1e-6f;
+    return RT_OK;
+}
+
+int rt_unit_denoise_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
+                         const rt_denoise_params* params, float* out_rgb, float* out_var) {
+    if (!hdr || !sq || !feat8 || !out_rgb || !out_var) return Fail(RT_ERR_INVALID_ARG, "rt_unit_denoise_host: null buffer");
+    if (W == 0 || rows == 0 || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_denoise_host: empty or too large strip");
+    rt_denoise_params def;
+    rt_denoise_default_params(&def);
+    if (!params) params = &def;
+    rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
+    if (!rtd::denoise_params_ok(P))
+        return Fail(RT_ERR_INVALID_ARG, "rt_unit_denoise_host: levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    if (n < 2) return Fail(RT_ERR_SEQUENCE, "rt_unit_denoise_host: the noise estimate needs at least 2 samples per pixel");
+    if (m == 0) return Fail(RT_ERR_SEQUENCE, "rt_unit_denoise_host: the feature strips hold no sample");
+    const size_t npix = (size_t)W * rows;
+    std::vector<rtd::DenoiseState> a(npix), b(npix);
+    std::vector<float> g(npix * 8);
+    for (size_t p = 0; p < npix; ++p) rtd::denoise_prepare(hdr + 3 * p, sq + 3 * p, n, feat8 + 8 * p, m, a[p], &g[8 * p]);
+    const rtd::DenoiseState* in = a.data();
+    rtd::DenoiseState* out = b.data();
+    for (uint32_t l = 0; l < P.levels; ++l) {
+        const int64_t step = (int64_t)1 << l;
+        for (int64_t y = 0; y < (int64_t)rows; ++y) {
+            for (int64_t x = 0; x < (int64_t)W; ++x) {
+                const size_t p = (size_t)y * W + (size_t)x;
+                rtd::DenoiseSums S;
+                rtd::denoise_begin(S);
+                for (int ta = 0; ta < 5; ++ta) {
+                    const int64_t qy = y + (ta - 2) * step;
+                    if (qy < 0 || qy >= (int64_t)rows) continue;
+                    for (int tb = 0; tb < 5; ++tb) {
+                        const int64_t qx = x + (tb - 2) * step;
+                        if (qx < 0 || qx >= (int64_t)W) continue;
+                        const size_t q = (size_t)qy * W + (size_t)qx;
+                        rtd::denoise_tap(P, rtd::denoise_h(ta) * rtd::denoise_h(tb), in[p], &g[8 * p], in[q], &g[8 * q], S);
+                    }
+                }
+                rtd::denoise_finish(S, out[p]);
+            }
+        }
+        in = out;
+        out = out == b.data() ? a.data() : b.data();
+    }
+    for (size_t p = 0; p < npix; ++p) {
+        for (int k = 0; k < 3; ++k) out_rgb[3 * p + k] = in[p].c[k];
+        out_var[p] = in[p].v;
+    }
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,42 @@
+// rt_denoise_launch.h -- what rt_capi.hip sees of the denoiser's translation unit (rt_denoise.hip): one launcher over plain
+// pointers.  The kernels live in a unit of their own so that the device code of rt_capi.hip -- the trace variants and their
+// register allocation -- stays what it was (DESIGN.md "Denoise").
+#pragma once
+
+#include <stdint.h>
+
+#include "../rt_denoise.h"
+
+namespace rtdn {
+
+constexpr uint32_t kTileW = 32, kTileH = 8;  // a 256-thread workgroup owns a 32 x 8 pixel tile: a wave is two rows of 32
+constexpr uint32_t kStageLdsLimit = 64u * 1024u;  // the staged form runs where three planes of tile + halo fit this
+enum Form : uint32_t { kFormNone = 0, kFormDirect = 1, kFormStaged = 2 };
+
+// Bytes of LDS the staged form takes at a step: three float4 planes of (32 + 4 step) x (8 + 4 step) pixels.
+inline uint32_t StageBytes(uint32_t step) { return (kTileW + 4u * step) * (kTileH + 4u * step) * 3u * 16u; }
+// The measured cut (profiles/denoise_timing.txt): staging pays at these steps.  RT_DENOISE_STAGE overrides it.
+inline bool StageByDefault(uint32_t step) { return step <= 2u; }
+// stageKnob: -1 unset, 0 never staged, 1 staged wherever the LDS image fits
+inline bool Staged(uint32_t step, int stageKnob) {
+    if (StageBytes(step) > kStageLdsLimit) return false;
+    return stageKnob < 0 ? StageByDefault(step) : stageKnob != 0;
+}
+
+struct Strips {
+    const float* hdr;   // [npix][3]
+    const float* sq;    // [npix][3]
+    const float* feat;  // [npix][8], 16-byte aligned
+    uint32_t n, m;      // samples in hdr / sq, samples in feat
+    uint32_t W, rows;
+    void* state[2];     // [npix] float4 (c.rgb, v), ping and pong
+    void* guide[2];     // [npix] float4 each: (albedo rgb, normal x), (normal y, normal z, depth, coverage)
+    float* den;         // [npix][3] out
+    float* denVar;      // [npix] out
+};
+
+// Enqueues the prepare pass and one a-trous launch per level on the stream (a hipStream_t).  forms[l] = the form level l took.
+// Returns a hipError_t as int (0 = success); nothing is waited for.
+int LaunchDenoise(void* stream, const Strips& s, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]);
+
+}  // namespace rtdn

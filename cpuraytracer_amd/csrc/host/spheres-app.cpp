@@ -246,6 +246,26 @@ bool SpheresApp::WriteFeaturePFMs(const std::string& prefix) const {
     return true;
 }
 
+bool SpheresApp::WriteDenoisedPPM(const std::string& path, uint32_t levels) const {
+    const uint32_t W = (uint32_t)GetBackBufferWidth(), H = (uint32_t)GetBackBufferHeight();
+    const uint32_t rows = m_lastStats.local_rows;
+    if (m_sampleCount == 0) return false;
+    const rt_rowset rs = m_hasRowset ? m_rowset : rt_rowset{0, H, H, 0, 1};
+    if (rt_render_features(m_device, W, H, rs, 1u, (uint32_t)m_sampleCount + 1u, nullptr) != RT_OK) return false;
+    rt_denoise_params params;
+    if (rt_denoise_default_params(&params) != RT_OK) return false;
+    if (levels != 0) params.levels = levels;
+    if (rt_denoise(m_device, &params, nullptr) != RT_OK) return false;
+    std::vector<uint8_t> rgb((size_t)W * rows * 3);
+    if (rt_download_denoised(m_device, nullptr, nullptr, rgb.data()) != RT_OK) return false;
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::fprintf(f, "P6\n%u %u\n255\n", W, rows);
+    const bool ok = std::fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
+    std::fclose(f);
+    return ok;
+}
+
 int SpheresApp::RunUntil(float relError, double fraction, uint32_t maxSpp) noexcept {
     try {
         const uint32_t step = AppSettings.samplesPerFrame;

@@ -67,6 +67,9 @@ public:
     // sample count in binary32 -- as little-endian PFMs, rows top to bottom: prefix.albedo.pfm and prefix.normal.pfm (three channels),
     // prefix.depth.pfm and prefix.coverage.pfm (one channel).
     bool WriteFeaturePFMs(const std::string& prefix) const;
+    // Runs the feature pass over the samples rendered so far, then rt_denoise (the defaults; levels != 0 replaces the number of levels),
+    // and writes the filtered picture's tonemap as a PPM like WritePPM's.  Needs AppSettings.noiseEstimate and at least 2 samples.
+    bool WriteDenoisedPPM(const std::string& path, uint32_t levels) const;
     // Frames of samplesPerFrame samples until at most `fraction` of the pixels have a relative error above relError, or the next
     // frame would pass maxSpp (every frame waits for its summary, so every frame is resolved).  SampleCount() is the spp reached.
     int RunUntil(float relError, double fraction, uint32_t maxSpp) noexcept;

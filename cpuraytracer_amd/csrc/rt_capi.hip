@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/rt_api.h"
+#include "host/rt_denoise_launch.h"
 #include "host/rt_launch_plan.h"
 #include "host/rt_scene_prep.h"
 #include "rt_kernels.h"
@@ -147,6 +148,15 @@ struct rt_ctx {
     DevBuf<float> feat;           // [W*rows*8] sums of albedo rgb, normal xyz, depth, coverage
     DevBuf<uint32_t> featIds;     // [W*rows] id of the sample added last
     DevBuf<float2> featJitter, featLens;  // ray-generation tables of the feature pass
+
+    // denoise (rt_denoise; rt_denoise.h, rt_denoise.hip): a snapshot of the filtered picture in strips of its own
+    bool denValid = false;        // den / denVar / denLdr hold the last rt_denoise's result (voided by rt_scene_upload)
+    uint32_t denW = 0, denRows = 0;
+    uint32_t denForms[rtd::kDenoiseMaxLevels] = {0, 0, 0, 0, 0};  // rtdn::Form of each level of the last rt_denoise
+    DevBuf<float> denState[2];    // [W*rows*4] (c.rgb, v) of a level, ping and pong
+    DevBuf<float> denGuide[2];    // [W*rows*4] each: (albedo rgb, normal x), (normal y, normal z, depth, coverage)
+    DevBuf<float> den, denVar;    // [W*rows*3], [W*rows]
+    DevBuf<uint8_t> denLdr;       // [W*rows*3] the resolve of den with n_samples = 1
 
     // tuning (env: RT_BLOCKS_PER_CU, RT_FORCE_GLOBAL_TABLES)
     uint32_t blocksPerCu = 4;
@@ -746,6 +756,13 @@ void rt_destroy(rt_ctx* ctx) {
     ctx->featIds.Release();
     ctx->featJitter.Release();
     ctx->featLens.Release();
+    for (int k = 0; k < 2; ++k) {
+        ctx->denState[k].Release();
+        ctx->denGuide[k].Release();
+    }
+    ctx->den.Release();
+    ctx->denVar.Release();
+    ctx->denLdr.Release();
     ctx->samples.Release();
     ctx->queue.Release();
     ctx->counters.Release();
@@ -953,6 +970,7 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     ctx->accumulated = 0;
     ctx->sky = *sky;
     ctx->featCount = 0;  // the feature strips belonged to the scene that was replaced
+    ctx->denValid = false;  // ... and so did the denoised picture
     PipelineDrop(ctx);
     return RT_OK;
 }
@@ -1545,6 +1563,93 @@ int rt_clear_features(rt_ctx* ctx) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_clear_features: null ctx");
     ctx->featCount = 0;
     ctx->featCleared = true;
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------- denoise (rt_denoise.h; kernels and launcher: rt_denoise.hip)
+// A reader of hdr, sq and feat that writes strips of its own: no sequencing state of rt_render or rt_render_features changes.
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms) {
+    int rc = NoiseReady(ctx, "rt_denoise", 2);
+    if (rc != RT_OK) return rc;
+    rt_denoise_params def;
+    rt_denoise_default_params(&def);
+    if (!params) params = &def;
+    const rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
+    if (!rtd::denoise_params_ok(P))
+        return Fail(RT_ERR_INVALID_ARG, "rt_denoise: levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    if (ctx->rs.nshards != 1)
+        return Fail(RT_ERR_INVALID_ARG, "rt_denoise: the local rows of a cyclic row set (nshards != 1) are not neighbours in the image");
+    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_denoise: no feature strips (rt_render_features)");
+    if (ctx->featW != ctx->W || ctx->featH != ctx->H || ctx->featRows != ctx->rows || std::memcmp(&ctx->featRs, &ctx->rs, sizeof(rt_rowset)) != 0)
+        return Fail(RT_ERR_SEQUENCE, "rt_denoise: the feature strips are of another image or row set than the picture");
+    const uint32_t W = ctx->W, rows = ctx->rows;
+    if ((rows + rtdn::kTileH - 1u) / rtdn::kTileH > 65535u) return Fail(RT_ERR_INVALID_ARG, "rt_denoise: more than 524,280 rows");
+    const size_t npix = (size_t)W * rows;
+    for (int k = 0; k < 2; ++k)
+        if ((rc = ctx->denState[k].Reserve(npix * 4)) != RT_OK || (rc = ctx->denGuide[k].Reserve(npix * 4)) != RT_OK) return rc;
+    if ((rc = ctx->den.Reserve(npix * 3)) != RT_OK || (rc = ctx->denVar.Reserve(npix)) != RT_OK || (rc = ctx->denLdr.Reserve(npix * 3)) != RT_OK) return rc;
+    int knob = -1;
+    if (const char* e = std::getenv("RT_DENOISE_STAGE")) knob = std::atoi(e) != 0 ? 1 : 0;
+    rtdn::Strips S{};
+    S.hdr = ctx->hdr.ptr;
+    S.sq = ctx->sq.ptr;
+    S.feat = ctx->feat.ptr;
+    S.n = ctx->accumulated;
+    S.m = ctx->featCount;
+    S.W = W;
+    S.rows = rows;
+    for (int k = 0; k < 2; ++k) {
+        S.state[k] = ctx->denState[k].ptr;
+        S.guide[k] = ctx->denGuide[k].ptr;
+    }
+    S.den = ctx->den.ptr;
+    S.denVar = ctx->denVar.ptr;
+    ctx->denValid = false;  // the strips are being rewritten
+    if (out_ms) RT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    const int he = rtdn::LaunchDenoise(ctx->stream, S, P, knob, ctx->denForms);
+    if (he != 0) return Fail(RT_ERR_HIP, std::string("rt_denoise: launch: ") + hipGetErrorString((hipError_t)he));
+    hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3(((uint32_t)npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->den.ptr, ctx->denLdr.ptr, (uint32_t)npix, 1u,
+                       nullptr);
+    RT_HIP(hipGetLastError());
+    if (out_ms) {
+        RT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+        RT_HIP(hipEventSynchronize(ctx->ev[3]));
+        float ms = 0.f;
+        RT_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+        *out_ms = ms;
+    }
+    ctx->denW = W;
+    ctx->denRows = rows;
+    ctx->denValid = true;
+    return RT_OK;
+}
+
+int rt_download_denoised(rt_ctx* ctx, float* rgb, float* var, uint8_t* ldr) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_download_denoised: null ctx");
+    if (!ctx->denValid) return Fail(RT_ERR_SEQUENCE, "rt_download_denoised: nothing denoised");
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->denW * ctx->denRows;
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    if (rgb) RT_HIP(hipMemcpy(rgb, ctx->den.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (var) RT_HIP(hipMemcpy(var, ctx->denVar.ptr, npix * sizeof(float), hipMemcpyDeviceToHost));
+    if (ldr) RT_HIP(hipMemcpy(ldr, ctx->denLdr.ptr, npix * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_copy_denoised_to_device(rt_ctx* ctx, void* dev_rgb, void* dev_var, void* dev_ldr) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_copy_denoised_to_device: null ctx");
+    if (!ctx->denValid) return Fail(RT_ERR_SEQUENCE, "rt_copy_denoised_to_device: nothing denoised");
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->denW * ctx->denRows;
+    if (dev_rgb) RT_HIP(hipMemcpyAsync(dev_rgb, ctx->den.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (dev_var) RT_HIP(hipMemcpyAsync(dev_var, ctx->denVar.ptr, npix * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (dev_ldr) RT_HIP(hipMemcpyAsync(dev_ldr, ctx->denLdr.ptr, npix * 3, hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
+int rt_unit_denoise_forms(rt_ctx* ctx, uint32_t out[5]) {
+    if (!ctx || !out) return Fail(RT_ERR_INVALID_ARG, "rt_unit_denoise_forms: null argument");
+    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) out[l] = ctx->denValid ? ctx->denForms[l] : 0u;
     return RT_OK;
 }
 

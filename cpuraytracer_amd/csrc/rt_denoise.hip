@@ -1,0 +1,154 @@
+// rt_denoise.hip -- the denoiser's kernels and their launcher (DESIGN.md "Denoise"; arithmetic: rt_denoise.h).  A translation unit
+// of its own: rt_capi.hip calls LaunchDenoise (host/rt_denoise_launch.h) and holds none of this device code.
+#include <hip/hip_runtime.h>
+
+#include "host/rt_denoise_launch.h"
+
+namespace rtd {
+
+// One pass over the strip: the state (c.rgb, v) as one float4, the guides as two float4 planes.
+__global__ void __launch_bounds__(256) rt_denoise_prepare_kernel(const float* __restrict__ hdr, const float* __restrict__ sq,
+                                                                 const float4* __restrict__ feat, uint32_t npix, uint32_t n, uint32_t m,
+                                                                 float4* __restrict__ state, float4* __restrict__ g0, float4* __restrict__ g1) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= npix) return;
+    const size_t p = pix;
+    const float h[3] = {hdr[3 * p], hdr[3 * p + 1], hdr[3 * p + 2]};
+    const float q[3] = {sq[3 * p], sq[3 * p + 1], sq[3 * p + 2]};
+    const float4 fa = feat[2 * p], fb = feat[2 * p + 1];
+    const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+    DenoiseState s;
+    float g[8];
+    denoise_prepare(h, q, n, f, m, s, g);
+    state[p] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
+    g0[p] = make_float4(g[0], g[1], g[2], g[3]);
+    g1[p] = make_float4(g[4], g[5], g[6], g[7]);
+}
+
+__device__ __forceinline__ void unpack(const float4 s, const float4 a, const float4 b, DenoiseState& st, float g[8]) {
+    st.c[0] = s.x; st.c[1] = s.y; st.c[2] = s.z; st.v = s.w;
+    g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w;
+    g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
+}
+
+// One level.  Thread (tx, ty) of the 32 x 8 workgroup owns pixel (32 bx + tx, 8 by + ty); its 25 taps lie (a - 2) step rows and
+// (b - 2) step columns away, a outer, b inner; a tap outside the strip is skipped, never clamped.
+//   kStaged: the tile and its 2 step halo go into LDS first as three planes of float4 with contiguous rows (a wave stages two rows
+//            of 32 at a time, and later reads 64 consecutive 16-byte slots per tap); slots of pixels outside the strip are never
+//            written and never read.  One barrier.
+//   else:    the taps are read from global memory: lanes are neighbouring pixels and the offset is uniform, so every read is a
+//            contiguous row segment.
+//   kLast:   the result goes to the packed den / den_var strips instead of the next level's state.
+template <bool kStaged, bool kLast>
+__global__ void __launch_bounds__(256) rt_atrous_kernel(const float4* __restrict__ state, const float4* __restrict__ g0, const float4* __restrict__ g1,
+                                                        uint32_t W, uint32_t rows, uint32_t step, const DenoiseParams P, float4* __restrict__ out,
+                                                        float* __restrict__ den, float* __restrict__ denVar) {
+    extern __shared__ float4 tileLds[];
+    const uint32_t tx = threadIdx.x & (rtdn::kTileW - 1u), ty = threadIdx.x / rtdn::kTileW;
+    const int x0 = (int)(blockIdx.x * rtdn::kTileW), y0 = (int)(blockIdx.y * rtdn::kTileH);
+    const int x = x0 + (int)tx, y = y0 + (int)ty;
+    const int halo = 2 * (int)step;
+    const uint32_t tw = rtdn::kTileW + 4u * step, th = rtdn::kTileH + 4u * step;
+    float4* ldsS = tileLds;
+    float4* ldsA = tileLds + tw * th;
+    float4* ldsB = tileLds + 2u * tw * th;
+    if (kStaged) {
+        for (uint32_t ly = ty; ly < th; ly += rtdn::kTileH) {
+            const int gy = y0 - halo + (int)ly;
+            if (gy < 0 || gy >= (int)rows) continue;
+            for (uint32_t lx = tx; lx < tw; lx += rtdn::kTileW) {
+                const int gx = x0 - halo + (int)lx;
+                if (gx < 0 || gx >= (int)W) continue;
+                const size_t q = (size_t)gy * W + (size_t)gx;
+                const uint32_t slot = ly * tw + lx;
+                ldsS[slot] = state[q];
+                ldsA[slot] = g0[q];
+                ldsB[slot] = g1[q];
+            }
+        }
+        __syncthreads();
+    }
+    if (x >= (int)W || y >= (int)rows) return;
+    const size_t p = (size_t)y * W + (size_t)x;
+    DenoiseState sp;
+    float gp[8];
+    if (kStaged) {
+        const uint32_t slot = (ty + (uint32_t)halo) * tw + tx + (uint32_t)halo;
+        unpack(ldsS[slot], ldsA[slot], ldsB[slot], sp, gp);
+    } else {
+        unpack(state[p], g0[p], g1[p], sp, gp);
+    }
+    DenoiseSums S;
+    denoise_begin(S);
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+        const int dy = (a - 2) * (int)step;
+        const int qy = y + dy;
+        if (qy < 0 || qy >= (int)rows) continue;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) {
+            const int dx = (b - 2) * (int)step;
+            const int qx = x + dx;
+            if (qx < 0 || qx >= (int)W) continue;
+            DenoiseState sq;
+            float gq[8];
+            if (kStaged) {
+                const uint32_t slot = (uint32_t)((int)ty + halo + dy) * tw + (uint32_t)((int)tx + halo + dx);
+                unpack(ldsS[slot], ldsA[slot], ldsB[slot], sq, gq);
+            } else {
+                const size_t q = (size_t)qy * W + (size_t)qx;
+                unpack(state[q], g0[q], g1[q], sq, gq);
+            }
+            denoise_tap(P, denoise_h(a) * denoise_h(b), sp, gp, sq, gq, S);
+        }
+    }
+    DenoiseState r;
+    denoise_finish(S, r);
+    if (kLast) {
+        den[3 * p] = r.c[0];
+        den[3 * p + 1] = r.c[1];
+        den[3 * p + 2] = r.c[2];
+        denVar[p] = r.v;
+    } else {
+        out[p] = make_float4(r.c[0], r.c[1], r.c[2], r.v);
+    }
+}
+
+}  // namespace rtd
+
+namespace rtdn {
+
+int LaunchDenoise(void* stream, const Strips& s, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t npix = s.W * s.rows;
+    float4* state[2] = {static_cast<float4*>(s.state[0]), static_cast<float4*>(s.state[1])};
+    float4* g0 = static_cast<float4*>(s.guide[0]);
+    float4* g1 = static_cast<float4*>(s.guide[1]);
+    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
+    hipLaunchKernelGGL(rtd::rt_denoise_prepare_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, s.hdr, s.sq, reinterpret_cast<const float4*>(s.feat),
+                       npix, s.n, s.m, state[0], g0, g1);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    const dim3 grid((s.W + kTileW - 1u) / kTileW, (s.rows + kTileH - 1u) / kTileH);
+    for (uint32_t l = 0; l < P.levels; ++l) {
+        const uint32_t step = 1u << l;
+        const bool staged = Staged(step, stageKnob), last = l + 1u == P.levels;
+        const size_t lds = staged ? StageBytes(step) : 0;
+        const float4* in = state[l & 1u];
+        float4* out = state[(l + 1u) & 1u];
+        if (staged && last)
+            hipLaunchKernelGGL((rtd::rt_atrous_kernel<true, true>), grid, dim3(256), lds, st, in, g0, g1, s.W, s.rows, step, P, out, s.den, s.denVar);
+        else if (staged)
+            hipLaunchKernelGGL((rtd::rt_atrous_kernel<true, false>), grid, dim3(256), lds, st, in, g0, g1, s.W, s.rows, step, P, out, s.den, s.denVar);
+        else if (last)
+            hipLaunchKernelGGL((rtd::rt_atrous_kernel<false, true>), grid, dim3(256), lds, st, in, g0, g1, s.W, s.rows, step, P, out, s.den, s.denVar);
+        else
+            hipLaunchKernelGGL((rtd::rt_atrous_kernel<false, false>), grid, dim3(256), lds, st, in, g0, g1, s.W, s.rows, step, P, out, s.den, s.denVar);
+        e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+        forms[l] = staged ? kFormStaged : kFormDirect;
+    }
+    return 0;
+}
+
+}  // namespace rtdn

@@ -25,6 +25,7 @@ class HipRenderer:
         check(self._L.rt_create(int(device), C.byref(self._h)))
         self.W = self.rows = 0
         self.feature_W = self.feature_rows = 0
+        self.denoised_W = self.denoised_rows = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -196,6 +197,38 @@ class HipRenderer:
 
     def clear_features(self):
         check(self._L.rt_clear_features(self._h))
+
+    # ---- denoise (rt_api.h "denoise")
+    def denoise(self, params=None, timed=False):
+        """rt_denoise: the feature-guided a-trous filter over the picture, its noise estimate and the feature strips as they are now
+        (noise estimate on, at least 2 samples; feature strips of the same image and row set).  params: an RtDenoiseParams
+        (_capi.denoise_params(levels=..., ...)) or None for the defaults.  timed=True waits and returns the HIP-event time in ms; else
+        the call only enqueues work and returns None."""
+        ms = C.c_double(0.0)
+        check(self._L.rt_denoise(self._h, C.byref(params) if params is not None else None, C.byref(ms) if timed else None))
+        self.denoised_W, self.denoised_rows = self.W, self.rows
+        return ms.value if timed else None
+
+    def download_denoised(self):
+        """The last denoise()'s result: rgb (rows, W, 3) float32, the filtered MEAN colour; var (rows, W) float32, the variance left in
+        it; ldr (rows, W, 3) uint8, its tonemap."""
+        rows, W = self.denoised_rows, self.denoised_W
+        rgb = np.zeros((rows, W, 3), dtype=np.float32)
+        var = np.zeros((rows, W), dtype=np.float32)
+        ldr = np.zeros((rows, W, 3), dtype=np.uint8)
+        check(self._L.rt_download_denoised(self._h, rgb.ctypes.data, var.ctypes.data, ldr.ctypes.data))
+        return {"rgb": rgb, "var": var, "ldr": ldr}
+
+    def copy_denoised_to_device(self, rgb_ptr=None, var_ptr=None, ldr_ptr=None):
+        """rt_copy_denoised_to_device: rgb ((rows, W, 3) float32), var ((rows, W) float32) and ldr ((rows, W, 3) uint8) into caller-owned
+        device memory, asynchronously on the context's stream."""
+        check(self._L.rt_copy_denoised_to_device(self._h, C.c_void_p(rgb_ptr or 0), C.c_void_p(var_ptr or 0), C.c_void_p(ldr_ptr or 0)))
+
+    def denoise_forms(self):
+        """Per level of the last denoise(): 0 not run, 1 taps read from global memory, 2 from a tile staged in LDS."""
+        out = (C.c_uint32 * 5)()
+        check(self._L.rt_unit_denoise_forms(self._h, out))
+        return list(out)
 
     # ---- unit entries
     def unit_halton(self, index, base):

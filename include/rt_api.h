@@ -295,6 +295,48 @@ int rt_copy_features_to_device(rt_ctx* ctx, void* dev_feat8, void* dev_ids);
 /* Forget the feature strips; the next rt_render_features starts an accumulation at any s0. */
 int rt_clear_features(rt_ctx* ctx);
 
+/* ----------------------------------------------------------------- denoise
+ * Feature-guided edge-avoiding a-trous filter of the accumulated picture (DESIGN.md "Denoise"; csrc/rt_denoise.h): the consumer of the
+ * noise estimate and of the feature buffers.  Everything is binary32, only + - * / and comparisons in exactly this order and
+ * association, never fused; division is the correctly rounded one; the one square root is the noise estimate's.
+ * Inputs: hdr, sq after n >= 2 samples; feat after m >= 1 samples; W x rows the strip of a CONTIGUOUS row set (nshards == 1: the
+ * local rows of a cyclic row set are not neighbours in the image).  Per pixel p:
+ *     c0[k] = hdr[k] / (float)n   k = r, g, b       sigma = rt_noise_map's out[0] with floor = 0;  v0 = sigma * sigma
+ *     g[k]  = feat[k] / (float)m  k = 0..7 (albedo 3, normal 3, depth, coverage)
+ * Level l = 0 .. levels-1, step = 1 << l: taps a = 0..4 outer (dy = (a-2) step), b = 0..4 inner (dx = (b-2) step), h = {1/16, 1/4,
+ * 3/8, 1/4, 1/16}; a tap outside the strip is skipped (adds nothing, takes no slot); the sums start at +0; for tap q of pixel p
+ *     dn = gp[3..5]-gq[3..5];  xn = k_normal   * ((dn0*dn0 + dn1*dn1) + dn2*dn2)
+ *     da = gp[0..2]-gq[0..2];  xa = k_albedo   * ((da0*da0 + da1*da1) + da2*da2)
+ *     dz = gp[6]-gq[6];  zm = max(gp[6], gq[6]);   xz = k_depth * ((dz*dz) / (zm*zm + 1e-12f))
+ *     dc = gp[7]-gq[7];        xc = k_coverage * (dc*dc)
+ *     dl = cp - cq;            xl = k_colour   * (((dl0*dl0 + dl1*dl1) + dl2*dl2) / ((vp + vq) + var_floor))
+ *     x  = (((xn + xz) + xa) + xc) + xl;       ww = (h[a]*h[b]) / (1.0f + x)
+ *     sc[k] = sc[k] + ww*cq[k];    sv = sv + (ww*ww)*vq;    sw = sw + ww
+ * and after the 25 taps c'[k] = sc[k] / sw, v' = sv / (sw*sw) (the centre tap makes sw > 0).  c, v at every tap of a level are the
+ * previous level's (two buffers, never in place); the guides never change.  Output: den[p][3] = c and den_var[p] = v after the last
+ * level -- means, not sums.  Pixels whose inputs are all finite are covered; a NaN's sign and payload are not. */
+typedef struct rt_denoise_params {
+    uint32_t levels;                                           /* 1..5; default 3                                      */
+    float k_normal, k_depth, k_albedo, k_coverage, k_colour;   /* defaults 16, 400, 64, 16, 1; each finite and >= 0    */
+    float var_floor;                                           /* default 1e-6f; finite and > 0                        */
+} rt_denoise_params;
+int rt_denoise_default_params(rt_denoise_params* out);  /* needs no GPU */
+/* Filters the strips as they are now into strips of the denoiser's own, and tonemaps the result (the resolve with n_samples = 1) into
+ * an LDR buffer of its own.  params == NULL: the defaults; parameters outside their domain: RT_ERR_INVALID_ARG.  Needs the noise
+ * estimate on and n >= 2 samples accumulated (pending batches are settled as rt_noise_map settles them; planes traced ahead are not in
+ * the strips), and feature strips with at least one sample of the same W, H and row set as the picture: else RT_ERR_SEQUENCE.  A row set
+ * with nshards != 1 is RT_ERR_INVALID_ARG.  Reads hdr, sq and feat; changes none of them, nor ldr, nor any sequencing state: a render
+ * that continues afterwards ends on the bits it would have had.  The result is a snapshot that stays until the next rt_denoise or
+ * rt_scene_upload.  With out_ms == NULL the call only enqueues work on the context's stream; else it waits and returns the HIP-event
+ * time.  env RT_DENOISE_STAGE, read per call: 0 = no level stages its taps in LDS, 1 = every level whose tile and halo fit does (same
+ * bits either way; unset: the measured cut). */
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms);
+/* Copy the result to host.  rgb: W*rows*3 floats; var: W*rows floats; ldr: W*rows*3 bytes.  Any pointer may be NULL.
+ * RT_ERR_SEQUENCE before any rt_denoise (or after rt_scene_upload voided it). */
+int rt_download_denoised(rt_ctx* ctx, float* rgb, float* var, uint8_t* ldr);
+/* Same, device to device into caller-owned device memory.  Asynchronous on the context's stream. */
+int rt_copy_denoised_to_device(rt_ctx* ctx, void* dev_rgb, void* dev_var, void* dev_ldr);
+
 /* Replaces the transform(par) tonemap (spheres-app.cpp:186-214): hdr / n_samples,
  * ACES fit, gamma 1/2.2, XMStoreColor.  n_samples == 0 uses the accumulated count. */
 int rt_resolve(rt_ctx* ctx, uint32_t n_samples);
@@ -407,6 +449,15 @@ int rt_unit_noise_estimate_host(const float* hdr, const float* sq, uint32_t npix
  * materials: by original sphere index (an index >= n_materials is RT_ERR_INVALID_ARG).  Needs no GPU. */
 int rt_unit_features_host(const rt_material* materials, uint32_t n_materials, const rt_material* sky, const float* hits10, uint32_t n,
                           float* out8, uint32_t* out_ids);
+/* The filter of rt_denoise for given strips (hdr, sq: 3 floats per pixel after n samples; feat8: 8 floats per pixel after m samples; W x
+ * rows pixels), from the same source compiled for the host (csrc/rt_denoise.h): out_rgb = 3 floats, out_var = 1 float per pixel.
+ * params == NULL: the defaults.  A null buffer, an empty strip or parameters outside their domain: RT_ERR_INVALID_ARG; n < 2 or m == 0:
+ * RT_ERR_SEQUENCE.  Needs no GPU. */
+int rt_unit_denoise_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
+                         const rt_denoise_params* params, float* out_rgb, float* out_var);
+/* Which form each level of the last rt_denoise took: out[l] = 0 the level did not run, 1 its taps were read from global memory, 2 from
+ * a tile staged in LDS. */
+int rt_unit_denoise_forms(rt_ctx* ctx, uint32_t out[5]);
 /* The shadow index rt_scene_upload would build for light `light` of the list, under the environment of the moment.
  * out_u: [0] 1 = the index is enabled (else nothing more is valid: every shadow ray of this light is answered over every scan
  * entry), [1] nx, [2] ny, [3] elements of cell_start (nx * ny + 1), [4] of entries, [5] of global, [6] scan entries (elements of orig),
