@@ -1211,7 +1211,8 @@ def test_hierarchy_scan_knobs_give_the_same_bits(hip, scenes_mod, monkeypatch, e
 def test_closest_hit_unit_runs_the_production_scan(oracle, scenes_mod, monkeypatch, name, env):
     """rt_unit_closest_hit launches the scan variant rt_render uses for the scene (matrix-core filter + pooled resolve,
     hierarchy descent, or the VALU scan) — A4/A6/A7 unit parity on shipped code: t, original index, position, normal and
-    uv equal the oracle's list scan AND its BvhNode traversal for rays from inside, outside, grazing and missing."""
+    uv equal the oracle's list scan AND its BvhNode traversal for random rays from inside, outside and missing.  (None of them is
+    aimed: silhouette grazers, surface starters, ties and the other directed rays are tests/test_scan_rays.py's.)"""
     from cpuraytracer_amd import HipRenderer
     for k, v in env.items():
         monkeypatch.setenv(k, v)
