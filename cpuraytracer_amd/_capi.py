@@ -46,6 +46,12 @@ class RtDenoiseParams(C.Structure):
                 ("k_coverage", C.c_float), ("k_colour", C.c_float), ("var_floor", C.c_float)]
 
 
+class RtShardParts(C.Structure):
+    """rt_shard_parts: the gathered parts of a row-sharded picture (device pointers) and their shape."""
+    _fields_ = [("hdr", C.c_void_p), ("sq", C.c_void_p), ("feat", C.c_void_p), ("W", C.c_uint32), ("rows_max", C.c_uint32),
+                ("rs", RtRowset), ("n", C.c_uint32), ("m", C.c_uint32)]
+
+
 SPHERE_DTYPE = np.dtype([("cx", "<f4"), ("cy", "<f4"), ("cz", "<f4"), ("r", "<f4")])
 MATERIAL_DTYPE = np.dtype([("type", "<u4"), ("tex_type", "<u4"), ("smoothness", "<f4"), ("ior", "<f4"),
                            ("tiling", "<f4"), ("rgb0", "<f4", (3,)), ("rgb1", "<f4", (3,)), ("luminance", "<f4")])
@@ -68,6 +74,7 @@ EXPORTS = [
     "rt_unit_shadow_index_host", "rt_unit_shadow_query_host", "rt_unit_shadow",
     "rt_unit_launch_plan",
     "rt_denoise_default_params", "rt_denoise", "rt_download_denoised", "rt_copy_denoised_to_device", "rt_unit_denoise_host", "rt_unit_denoise_forms",
+    "rt_copy_moments_to_device", "rt_rowset_locate", "rt_denoise_shards", "rt_unit_denoise_shards_host",
 ]
 
 _lib = None
@@ -172,6 +179,12 @@ def load():
         L.rt_unit_denoise_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RtDenoiseParams),
                                            C.c_void_p, C.c_void_p]
         L.rt_unit_denoise_forms.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    if hasattr(L, "rt_denoise_shards"):
+        L.rt_copy_moments_to_device.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_rowset_locate.argtypes = [RtRowset, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.rt_denoise_shards.argtypes = [C.c_void_p, C.POINTER(RtShardParts), C.POINTER(RtDenoiseParams), C.POINTER(C.c_double)]
+        L.rt_unit_denoise_shards_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtShardParts), C.POINTER(RtDenoiseParams),
+                                                  C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -190,6 +203,12 @@ def denoise_params(**fields):
             raise TypeError("rt_denoise_params has no field %r" % k)
         setattr(p, k, v)
     return p
+
+
+def shard_parts(W, H, world, rows_max, n, m, hdr=None, sq=None, feat=None, block_rows=None, first_row=0):
+    """An rt_shard_parts for a W x H picture cut cyclically into `world` shards of block_rows rows (default BLOCK_ROWS)."""
+    rs = RtRowset(first_row, H, BLOCK_ROWS if block_rows is None else block_rows, 0, world)
+    return RtShardParts(hdr or None, sq or None, feat or None, W, rows_max, rs, n, m)
 
 
 def whole_image(H):

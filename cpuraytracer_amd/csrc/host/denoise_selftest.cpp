@@ -5,17 +5,21 @@
 //   - finite in -> finite out, den_var >= 0;
 //   - levels whose step exceeds the image (only the centre row / column of taps is left) still give every pixel;
 //   - all k == 0, uniform picture: the picture is returned and the variance shrinks;
+//   - the same strips cut into the parts of a random cyclic row set give the contiguous filter's bits (rt_unit_denoise_shards_host over
+//     ../rt_rowset_map.h), whatever the padding rows hold;
 //   - the refusals.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <string>
 #include <vector>
 
 #include "../../../include/rt_api.h"
 #include "../rt_denoise.h"
+#include "../rt_rowset_map.h"
 #include "rt_error.h"
 
 namespace rtprep {
@@ -119,6 +123,40 @@ int main(int argc, char** argv) {
             CHECK(std::isfinite(var[p]) && var[p] >= 0.f, "case %u pixel %zu: variance %g", t, p, var[p]);
         }
         pixels += npix;
+        // the same strips cut into the parts of a cyclic row set (rt_unit_denoise_shards_host): NaN in every padding row, and the buffers
+        // end where the last owned row ends, so under ASan a read of the padding behind it is caught as well
+        {
+            rt_shard_parts sp{};
+            sp.W = W;
+            sp.rs = rt_rowset{(uint32_t)(rng() % 5), rows, (uint32_t)(1 + rng() % 5), 0, (uint32_t)(1 + rng() % 9)};
+            sp.n = s.n;
+            sp.m = s.m;
+            const uint32_t most = rtd::rowset_max_shard_rows(rows, sp.rs.block_rows, sp.rs.nshards);
+            sp.rows_max = most + rng() % 2;
+            size_t used = 0;
+            uint32_t sum = 0;
+            for (uint32_t k = 0; k < sp.rs.nshards; ++k) {
+                const uint32_t own = rtd::rowset_shard_rows(rows, sp.rs.block_rows, sp.rs.nshards, k);
+                CHECK(own <= most, "case %u: shard %u owns %u rows, more than shard 0's %u", t, k, own, most);
+                sum += own;
+                if (own) used = ((size_t)k * sp.rows_max + own) * W;
+            }
+            CHECK(sum == rows, "case %u: the shards own %u of %u rows", t, sum, rows);
+            std::vector<float> ph(used * 3, NAN), pq(used * 3, NAN), pf(used * 8, NAN);
+            for (uint32_t y = 0; y < rows; ++y) {
+                uint32_t k = 0, lr = 0;
+                CHECK(rt_rowset_locate(sp.rs, y, &k, &lr) == RT_OK && k < sp.rs.nshards && lr < sp.rows_max, "case %u: row %u -> (%u, %u)", t, y, k, lr);
+                const size_t dst = ((size_t)k * sp.rows_max + lr) * W, src = (size_t)y * W;
+                CHECK(dst + W <= used, "case %u: row %u lies beyond the owned rows", t, y);
+                for (size_t i = 0; i < (size_t)W * 3; ++i) ph[3 * dst + i] = s.hdr[3 * src + i], pq[3 * dst + i] = s.sq[3 * src + i];
+                for (size_t i = 0; i < (size_t)W * 8; ++i) pf[8 * dst + i] = s.feat[8 * src + i];
+            }
+            std::vector<float> rgb2(npix * 3, NAN), var2(npix, NAN);
+            const int rc2 = rt_unit_denoise_shards_host(ph.data(), pq.data(), pf.data(), &sp, &P, rgb2.data(), var2.data());
+            CHECK(rc2 == RT_OK, "case %u: parts form rc %d (%s)", t, rc2, rtprep::LastError());
+            CHECK(std::memcmp(rgb2.data(), rgb.data(), npix * 12) == 0 && std::memcmp(var2.data(), var.data(), npix * 4) == 0,
+                  "case %u: %u x %u in %u shards of %u-row blocks differs from the contiguous filter", t, W, rows, sp.rs.nshards, sp.rs.block_rows);
+        }
     }
     // the sums of one pixel, directly: sw >= the centre tap's 9/64 whatever the neighbours are
     {

@@ -1,17 +1,82 @@
 // rt_denoise_host.cpp -- the denoiser's arithmetic (../rt_denoise.h) compiled for the host: rt_unit_denoise_host, the twin the
-// device is compared with bit for bit, and the parameter defaults.  Plain C++ with no HIP header, under the same floating-point
-// contract as the kernels (-ffp-contract=off, IEEE division).  Needs no GPU.
+// device is compared with bit for bit, its form over the gathered parts of a row-sharded picture (rt_unit_denoise_shards_host; the
+// mapping is ../rt_rowset_map.h, which rt_rowset_locate exposes), and the parameter defaults.  Plain C++ with no HIP header, under the
+// same floating-point contract as the kernels (-ffp-contract=off, IEEE division).  Needs no GPU.
 #include <cstddef>
+#include <string>
 #include <vector>
 
 #include "../../../include/rt_api.h"
 #include "../rt_denoise.h"
+#include "../rt_rowset_map.h"
+#include "rt_denoise_launch.h"
 #include "rt_error.h"
 
 using rtprep::Fail;
 
 static_assert(sizeof(rt_denoise_params) == sizeof(rtd::DenoiseParams) && offsetof(rt_denoise_params, var_floor) == offsetof(rtd::DenoiseParams, var_floor),
               "rt_denoise_params is laid out like rtd::DenoiseParams");
+
+// The levels over the prepared state a (b: the other buffer) and guides g of a W x rows picture; the last level's state goes out.
+static void RunLevels(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseState>& b, const std::vector<float>& g, uint32_t W, uint32_t rows,
+                      const rtd::DenoiseParams& P, float* out_rgb, float* out_var) {
+    const size_t npix = (size_t)W * rows;
+    const rtd::DenoiseState* in = a.data();
+    rtd::DenoiseState* out = b.data();
+    for (uint32_t l = 0; l < P.levels; ++l) {
+        const int64_t step = (int64_t)1 << l;
+        for (int64_t y = 0; y < (int64_t)rows; ++y) {
+            for (int64_t x = 0; x < (int64_t)W; ++x) {
+                const size_t p = (size_t)y * W + (size_t)x;
+                rtd::DenoiseSums S;
+                rtd::denoise_begin(S);
+                for (int ta = 0; ta < 5; ++ta) {
+                    const int64_t qy = y + (ta - 2) * step;
+                    if (qy < 0 || qy >= (int64_t)rows) continue;
+                    for (int tb = 0; tb < 5; ++tb) {
+                        const int64_t qx = x + (tb - 2) * step;
+                        if (qx < 0 || qx >= (int64_t)W) continue;
+                        const size_t q = (size_t)qy * W + (size_t)qx;
+                        rtd::denoise_tap(P, rtd::denoise_h(ta) * rtd::denoise_h(tb), in[p], &g[8 * p], in[q], &g[8 * q], S);
+                    }
+                }
+                rtd::denoise_finish(S, out[p]);
+            }
+        }
+        in = out;
+        out = out == b.data() ? a.data() : b.data();
+    }
+    for (size_t p = 0; p < npix; ++p) {
+        for (int k = 0; k < 3; ++k) out_rgb[3 * p + k] = in[p].c[k];
+        out_var[p] = in[p].v;
+    }
+}
+
+namespace rtdn {
+
+int CheckShardParts(const char* who_, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P) {
+    const std::string who(who_);
+    if (!parts || !P) return Fail(RT_ERR_INVALID_ARG, who + ": null argument");
+    if (devicePointers && (!parts->hdr || !parts->sq || !parts->feat)) return Fail(RT_ERR_INVALID_ARG, who + ": null parts");
+    const rt_rowset rs = parts->rs;
+    if (parts->W == 0 || rs.num_rows == 0 || rs.nshards == 0 || rs.block_rows == 0)
+        return Fail(RT_ERR_INVALID_ARG, who + ": W, rs.num_rows, rs.nshards and rs.block_rows must not be 0");
+    if ((uint64_t)parts->W * rs.num_rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, who + ": more than 2^31 pixels");
+    if ((rs.num_rows + kTileH - 1u) / kTileH > 65535u) return Fail(RT_ERR_INVALID_ARG, who + ": more than 524,280 rows");
+    if (parts->rows_max < rtd::rowset_max_shard_rows(rs.num_rows, rs.block_rows, rs.nshards))
+        return Fail(RT_ERR_INVALID_ARG, who + ": rows_max is below the rows of the largest shard");
+    if (devicePointers && (reinterpret_cast<uintptr_t>(parts->feat) & 15u) != 0) return Fail(RT_ERR_INVALID_ARG, who + ": feat is not 16-byte aligned");
+    rt_denoise_params def;
+    rt_denoise_default_params(&def);
+    if (!params) params = &def;
+    *P = rtd::DenoiseParams{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
+    if (!rtd::denoise_params_ok(*P)) return Fail(RT_ERR_INVALID_ARG, who + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    if (parts->n < 2) return Fail(RT_ERR_SEQUENCE, who + ": the noise estimate needs at least 2 samples per pixel");
+    if (parts->m == 0) return Fail(RT_ERR_SEQUENCE, who + ": the feature parts hold no sample");
+    return RT_OK;
+}
+
+}  // namespace rtdn
 
 extern "C" {
 
@@ -43,35 +108,37 @@ int rt_unit_denoise_host(const float* hdr, const float* sq, uint32_t n, const fl
     std::vector<rtd::DenoiseState> a(npix), b(npix);
     std::vector<float> g(npix * 8);
     for (size_t p = 0; p < npix; ++p) rtd::denoise_prepare(hdr + 3 * p, sq + 3 * p, n, feat8 + 8 * p, m, a[p], &g[8 * p]);
-    const rtd::DenoiseState* in = a.data();
-    rtd::DenoiseState* out = b.data();
-    for (uint32_t l = 0; l < P.levels; ++l) {
-        const int64_t step = (int64_t)1 << l;
-        for (int64_t y = 0; y < (int64_t)rows; ++y) {
-            for (int64_t x = 0; x < (int64_t)W; ++x) {
-                const size_t p = (size_t)y * W + (size_t)x;
-                rtd::DenoiseSums S;
-                rtd::denoise_begin(S);
-                for (int ta = 0; ta < 5; ++ta) {
-                    const int64_t qy = y + (ta - 2) * step;
-                    if (qy < 0 || qy >= (int64_t)rows) continue;
-                    for (int tb = 0; tb < 5; ++tb) {
-                        const int64_t qx = x + (tb - 2) * step;
-                        if (qx < 0 || qx >= (int64_t)W) continue;
-                        const size_t q = (size_t)qy * W + (size_t)qx;
-                        rtd::denoise_tap(P, rtd::denoise_h(ta) * rtd::denoise_h(tb), in[p], &g[8 * p], in[q], &g[8 * q], S);
-                    }
-                }
-                rtd::denoise_finish(S, out[p]);
-            }
-        }
-        in = out;
-        out = out == b.data() ? a.data() : b.data();
+    RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
+    return RT_OK;
+}
+
+int rt_rowset_locate(rt_rowset rs, uint32_t image_row, uint32_t* shard, uint32_t* local_row) {
+    if (!shard || !local_row) return Fail(RT_ERR_INVALID_ARG, "rt_rowset_locate: null argument");
+    if (rs.block_rows == 0 || rs.nshards == 0) return Fail(RT_ERR_INVALID_ARG, "rt_rowset_locate: block_rows and nshards must not be 0");
+    if (image_row >= rs.num_rows) return Fail(RT_ERR_INVALID_ARG, "rt_rowset_locate: the row lies beyond the row range");
+    rtd::rowset_locate(rs.block_rows, rs.nshards, image_row, *shard, *local_row);
+    return RT_OK;
+}
+
+// The prepare pass reads every pixel through the mapping, as rt_denoise_prepare_shards_kernel does; the levels are the same code.
+int rt_unit_denoise_shards_host(const float* hdr, const float* sq, const float* feat8, const rt_shard_parts* shape, const rt_denoise_params* params,
+                                float* out_rgb, float* out_var) {
+    if (!hdr || !sq || !feat8 || !out_rgb || !out_var) return Fail(RT_ERR_INVALID_ARG, "rt_unit_denoise_shards_host: null buffer");
+    rtd::DenoiseParams P{};
+    const int rc = rtdn::CheckShardParts("rt_unit_denoise_shards_host", shape, params, false, &P);
+    if (rc != RT_OK) return rc;
+    const uint32_t W = shape->W, rows = shape->rs.num_rows;
+    const size_t npix = (size_t)W * rows;
+    std::vector<rtd::DenoiseState> a(npix), b(npix);
+    std::vector<float> g(npix * 8);
+    for (uint32_t y = 0; y < rows; ++y) {
+        uint32_t s, lr;
+        rtd::rowset_locate(shape->rs.block_rows, shape->rs.nshards, y, s, lr);
+        const size_t src = ((size_t)s * shape->rows_max + lr) * W, dst = (size_t)y * W;
+        for (size_t x = 0; x < W; ++x)
+            rtd::denoise_prepare(hdr + 3 * (src + x), sq + 3 * (src + x), shape->n, feat8 + 8 * (src + x), shape->m, a[dst + x], &g[8 * (dst + x)]);
     }
-    for (size_t p = 0; p < npix; ++p) {
-        for (int k = 0; k < 3; ++k) out_rgb[3 * p + k] = in[p].c[k];
-        out_var[p] = in[p].v;
-    }
+    RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
     return RT_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../rt_denoise.h"
+#include "../rt_rowset_map.h"
 
 namespace rtdn {
 
@@ -39,4 +40,21 @@ struct Strips {
 // Returns a hipError_t as int (0 = success); nothing is waited for.
 int LaunchDenoise(void* stream, const Strips& s, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]);
 
+// The parts form (rt_denoise_shards): hdr, sq and feat of Strips are the gathered parts of a row-sharded picture, [nshards] parts of
+// rowsMax x W pixels each, and W x rows is the IMAGE; row j of it is the row of the part that ../rt_rowset_map.h names.
+struct ShardLayout {
+    uint32_t rowsMax, blockRows, nshards;
+};
+// The same launches, the prepare pass reading through the mapping; everything it writes is in image order.
+int LaunchDenoiseShards(void* stream, const Strips& s, const ShardLayout& parts, const rtd::DenoiseParams& P, int stageKnob,
+                        uint32_t forms[rtd::kDenoiseMaxLevels]);
+
 }  // namespace rtdn
+
+// What rt_denoise_shards and rt_unit_denoise_shards_host refuse, checked once (rt_denoise_host.cpp): the shape, the sample counts and
+// the parameters (NULL: the defaults), which are returned in P.  The struct's own pointers are looked at only with devicePointers.
+struct rt_shard_parts;
+struct rt_denoise_params;
+namespace rtdn {
+int CheckShardParts(const char* who, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P);
+}

@@ -1411,6 +1411,14 @@ int rt_download_moments(rt_ctx* ctx, float* sq_rgb) {
     return RT_OK;
 }
 
+int rt_copy_moments_to_device(rt_ctx* ctx, void* dev_sq) {
+    const int rc = NoiseReady(ctx, "rt_copy_moments_to_device", 1);
+    if (rc != RT_OK) return rc;
+    if (!dev_sq) return Fail(RT_ERR_INVALID_ARG, "rt_copy_moments_to_device: null buffer");
+    RT_HIP(hipMemcpyAsync(dev_sq, ctx->sq.ptr, (size_t)ctx->W * ctx->rows * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
 int rt_noise_map(rt_ctx* ctx, float floor, float* out_abs_rel) {
     int rc = NoiseReady(ctx, "rt_noise_map", 2);
     if (rc != RT_OK) return rc;
@@ -1608,6 +1616,55 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms) {
     if (out_ms) RT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
     const int he = rtdn::LaunchDenoise(ctx->stream, S, P, knob, ctx->denForms);
     if (he != 0) return Fail(RT_ERR_HIP, std::string("rt_denoise: launch: ") + hipGetErrorString((hipError_t)he));
+    hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3(((uint32_t)npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->den.ptr, ctx->denLdr.ptr, (uint32_t)npix, 1u,
+                       nullptr);
+    RT_HIP(hipGetLastError());
+    if (out_ms) {
+        RT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+        RT_HIP(hipEventSynchronize(ctx->ev[3]));
+        float ms = 0.f;
+        RT_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+        *out_ms = ms;
+    }
+    ctx->denW = W;
+    ctx->denRows = rows;
+    ctx->denValid = true;
+    return RT_OK;
+}
+
+// The same filter over the gathered parts of a row-sharded picture: only the denoiser's own strips of the context are touched.
+int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise_params* params, double* out_ms) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_denoise_shards: null ctx");
+    rtd::DenoiseParams P{};
+    int rc = rtdn::CheckShardParts("rt_denoise_shards", parts, params, true, &P);
+    if (rc != RT_OK) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    const uint32_t W = parts->W, rows = parts->rs.num_rows;
+    const size_t npix = (size_t)W * rows;
+    for (int k = 0; k < 2; ++k)
+        if ((rc = ctx->denState[k].Reserve(npix * 4)) != RT_OK || (rc = ctx->denGuide[k].Reserve(npix * 4)) != RT_OK) return rc;
+    if ((rc = ctx->den.Reserve(npix * 3)) != RT_OK || (rc = ctx->denVar.Reserve(npix)) != RT_OK || (rc = ctx->denLdr.Reserve(npix * 3)) != RT_OK) return rc;
+    int knob = -1;
+    if (const char* e = std::getenv("RT_DENOISE_STAGE")) knob = std::atoi(e) != 0 ? 1 : 0;
+    rtdn::Strips S{};
+    S.hdr = static_cast<const float*>(parts->hdr);
+    S.sq = static_cast<const float*>(parts->sq);
+    S.feat = static_cast<const float*>(parts->feat);
+    S.n = parts->n;
+    S.m = parts->m;
+    S.W = W;
+    S.rows = rows;
+    for (int k = 0; k < 2; ++k) {
+        S.state[k] = ctx->denState[k].ptr;
+        S.guide[k] = ctx->denGuide[k].ptr;
+    }
+    S.den = ctx->den.ptr;
+    S.denVar = ctx->denVar.ptr;
+    const rtdn::ShardLayout layout{parts->rows_max, parts->rs.block_rows, parts->rs.nshards};
+    ctx->denValid = false;  // the strips are being rewritten
+    if (out_ms) RT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    const int he = rtdn::LaunchDenoiseShards(ctx->stream, S, layout, P, knob, ctx->denForms);
+    if (he != 0) return Fail(RT_ERR_HIP, std::string("rt_denoise_shards: launch: ") + hipGetErrorString((hipError_t)he));
     hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3(((uint32_t)npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->den.ptr, ctx->denLdr.ptr, (uint32_t)npix, 1u,
                        nullptr);
     RT_HIP(hipGetLastError());

@@ -25,6 +25,32 @@ __global__ void __launch_bounds__(256) rt_denoise_prepare_kernel(const float* __
     g1[p] = make_float4(g[4], g[5], g[6], g[7]);
 }
 
+// The same pass over the gathered parts of a row-sharded picture (rt_denoise_shards): a thread owns pixel pix of the IMAGE, finds
+// the part and the local row that hold its row (rt_rowset_map.h) and writes state, g0, g1 in image order, so the levels run on them
+// unchanged.  A row is contiguous inside its part: the lanes of a wave still read contiguous segments.  Rows of a part beyond its
+// shard's own (the gather's padding) belong to no image row and are never read.
+__global__ void __launch_bounds__(256) rt_denoise_prepare_shards_kernel(const float* __restrict__ hdr, const float* __restrict__ sq,
+                                                                        const float4* __restrict__ feat, uint32_t W, uint32_t npix, uint32_t rowsMax,
+                                                                        uint32_t blockRows, uint32_t nshards, uint32_t n, uint32_t m,
+                                                                        float4* __restrict__ state, float4* __restrict__ g0, float4* __restrict__ g1) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= npix) return;
+    const uint32_t y = pix / W, x = pix - y * W;
+    uint32_t shard, lr;
+    rowset_locate(blockRows, nshards, y, shard, lr);
+    const size_t p = ((size_t)shard * rowsMax + lr) * W + x;
+    const float h[3] = {hdr[3 * p], hdr[3 * p + 1], hdr[3 * p + 2]};
+    const float q[3] = {sq[3 * p], sq[3 * p + 1], sq[3 * p + 2]};
+    const float4 fa = feat[2 * p], fb = feat[2 * p + 1];
+    const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+    DenoiseState s;
+    float g[8];
+    denoise_prepare(h, q, n, f, m, s, g);
+    state[pix] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
+    g0[pix] = make_float4(g[0], g[1], g[2], g[3]);
+    g1[pix] = make_float4(g[4], g[5], g[6], g[7]);
+}
+
 __device__ __forceinline__ void unpack(const float4 s, const float4 a, const float4 b, DenoiseState& st, float g[8]) {
     st.c[0] = s.x; st.c[1] = s.y; st.c[2] = s.z; st.v = s.w;
     g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w;
@@ -118,17 +144,12 @@ __global__ void __launch_bounds__(256) rt_atrous_kernel(const float4* __restrict
 
 namespace rtdn {
 
-int LaunchDenoise(void* stream, const Strips& s, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint32_t npix = s.W * s.rows;
+// The levels over the prepared state and guides of a W x rows picture in image order.
+static int LaunchLevels(hipStream_t st, const Strips& s, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
     float4* state[2] = {static_cast<float4*>(s.state[0]), static_cast<float4*>(s.state[1])};
     float4* g0 = static_cast<float4*>(s.guide[0]);
     float4* g1 = static_cast<float4*>(s.guide[1]);
-    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
-    hipLaunchKernelGGL(rtd::rt_denoise_prepare_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, s.hdr, s.sq, reinterpret_cast<const float4*>(s.feat),
-                       npix, s.n, s.m, state[0], g0, g1);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    hipError_t e = hipSuccess;
     const dim3 grid((s.W + kTileW - 1u) / kTileW, (s.rows + kTileH - 1u) / kTileH);
     for (uint32_t l = 0; l < P.levels; ++l) {
         const uint32_t step = 1u << l;
@@ -149,6 +170,30 @@ int LaunchDenoise(void* stream, const Strips& s, const rtd::DenoiseParams& P, in
         forms[l] = staged ? kFormStaged : kFormDirect;
     }
     return 0;
+}
+
+int LaunchDenoise(void* stream, const Strips& s, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t npix = s.W * s.rows;
+    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
+    hipLaunchKernelGGL(rtd::rt_denoise_prepare_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, s.hdr, s.sq, reinterpret_cast<const float4*>(s.feat),
+                       npix, s.n, s.m, static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]), static_cast<float4*>(s.guide[1]));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return LaunchLevels(st, s, P, stageKnob, forms);
+}
+
+int LaunchDenoiseShards(void* stream, const Strips& s, const ShardLayout& parts, const rtd::DenoiseParams& P, int stageKnob,
+                        uint32_t forms[rtd::kDenoiseMaxLevels]) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t npix = s.W * s.rows;
+    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
+    hipLaunchKernelGGL(rtd::rt_denoise_prepare_shards_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, s.hdr, s.sq,
+                       reinterpret_cast<const float4*>(s.feat), s.W, npix, parts.rowsMax, parts.blockRows, parts.nshards, s.n, s.m,
+                       static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]), static_cast<float4*>(s.guide[1]));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return LaunchLevels(st, s, P, stageKnob, forms);
 }
 
 }  // namespace rtdn

@@ -7,6 +7,9 @@ work than the mean, with single rows 0.5 % -- tools/shard_balance_probe.py), eve
 the whole (tiny) scene, and the only exchange step is one gather of the finished strips to rank 0,
 which de-interleaves them.  Each pixel depends only on (global pixel id, s, seed), so the assembled
 image is byte-identical to the single-GPU image.  No other collective exists on the path.
+
+Denoising the sharded picture (PostExchange, denoise_gathered) is again one gather: hdr, second moments and features of every rank's
+strip in one buffer, filtered on rank 0 by rt_denoise_shards, which reads the gathered parts through the row mapping.
 """
 import numpy as np
 
@@ -94,3 +97,72 @@ class StripExchange:
             return None, None
         W, rm, hb = self.W, self.rows_max, self.hdr_bytes
         return ([o[:hb].view(torch.float32).view(rm, W, 3) for o in out], [o[hb:].view(rm, W, 3) for o in out])
+
+
+class PostExchange:
+    """What the denoiser needs of a row-sharded picture, brought to rank 0 in ONE gather: each rank's buffer holds its HDR strip, its
+    strip of second moments (rt_set_noise_estimate) and its feature strip (rt_render_features), all float32 sums, each padded to the
+    largest shard: [rows_max * W * 3 | rows_max * W * 3 | rows_max * W * 8].  On rank 0 the gathered buffers are regrouped -- three
+    strided copies on the device, no pass over the host -- into hdr_parts, sq_parts [world, rows_max, W, 3] and feat_parts
+    [world, rows_max, W, 8], each contiguous and an allocation of its own: exactly the layout rt_shard_parts takes
+    (HipRenderer.denoise_shards, denoise_gathered below).  The padding rows are never read by the filter."""
+
+    def __init__(self, H, W, rank, world, device, block_rows=BLOCK_ROWS):
+        import torch
+        self.H, self.W, self.rank, self.world, self.block_rows, self.device = H, W, rank, world, block_rows, device
+        self.rows = local_rows(H, rank, world, block_rows)
+        self.rows_max = max_local_rows(H, world, block_rows)
+        px = self.rows_max * W
+        self.cut = (3 * px, 6 * px, 14 * px)  # floats: end of hdr, of sq, of feat
+        self.buf = torch.zeros(self.cut[2], dtype=torch.float32, device=device)
+        self.hdr = self.buf[:self.cut[0]].view(self.rows_max, W, 3)
+        self.sq = self.buf[self.cut[0]:self.cut[1]].view(self.rows_max, W, 3)
+        self.feat = self.buf[self.cut[1]:].view(self.rows_max, W, 8)
+        self.hdr_parts = self.sq_parts = self.feat_parts = None
+        if rank == 0:
+            self.all = torch.empty((world, self.cut[2]), dtype=torch.float32, device=device) if world > 1 else self.buf.view(1, -1)
+            self.hdr_parts = torch.empty((world, self.rows_max, W, 3), dtype=torch.float32, device=device)
+            self.sq_parts = torch.empty_like(self.hdr_parts)
+            self.feat_parts = torch.empty((world, self.rows_max, W, 8), dtype=torch.float32, device=device)
+
+    def fill(self, renderer):
+        """This rank's three strips, device to device into the buffer.  Asynchronous on the renderer's stream: where that is not the
+        stream the gather runs on (torch's current one), call renderer.synchronize() before gather()."""
+        renderer.copy_to_device(self.hdr.data_ptr(), None)
+        renderer.copy_moments_to_device(self.sq.data_ptr())
+        renderer.copy_features_to_device(self.feat.data_ptr(), None)
+
+    def gather(self, through_host=False):
+        """-> (hdr_parts, sq_parts, feat_parts) on rank 0, (None, None, None) elsewhere.  through_host: CPU tensors over gloo
+        (rehearsal: ranks that share a device); the parts still end on rank 0's device."""
+        import torch.distributed as dist
+        if self.world > 1:
+            if through_host:
+                import torch
+                src = self.buf.cpu()
+                got = torch.empty((self.world, self.cut[2]), dtype=torch.float32) if self.rank == 0 else None
+                dist.gather(src, [got[s] for s in range(self.world)] if self.rank == 0 else None, dst=0)
+                if self.rank == 0:
+                    self.all.copy_(got)
+            else:
+                dist.gather(self.buf, [self.all[s] for s in range(self.world)] if self.rank == 0 else None, dst=0)
+        if self.rank != 0:
+            return None, None, None
+        shape3, shape8 = (self.world, self.rows_max, self.W, 3), (self.world, self.rows_max, self.W, 8)
+        self.hdr_parts.copy_(self.all[:, :self.cut[0]].reshape(shape3))
+        self.sq_parts.copy_(self.all[:, self.cut[0]:self.cut[1]].reshape(shape3))
+        self.feat_parts.copy_(self.all[:, self.cut[1]:].reshape(shape8))
+        return self.hdr_parts, self.sq_parts, self.feat_parts
+
+
+def denoise_gathered(renderer, xch, n, m, params=None, timed=False):
+    """Rank 0, after xch.gather() of a PostExchange on the renderer's device: rt_denoise_shards over the gathered parts (n samples in
+    hdr and sq, m in feat).  The H x W result is the renderer's download_denoised() / copy_denoised_to_device().  The regrouping copies
+    of gather() ran on torch's current stream: they are waited for here."""
+    import torch
+    if xch.rank != 0 or xch.hdr_parts is None:
+        raise ValueError("denoise_gathered: rank 0 holds the gathered parts")
+    if xch.hdr_parts.is_cuda:
+        torch.cuda.current_stream(xch.hdr_parts.device).synchronize()
+    return renderer.denoise_shards(xch.hdr_parts.data_ptr(), xch.sq_parts.data_ptr(), xch.feat_parts.data_ptr(), xch.W, xch.H, xch.world,
+                                   xch.rows_max, n, m, params=params, timed=timed, block_rows=xch.block_rows)

@@ -126,6 +126,11 @@ class HipRenderer:
         check(self._L.rt_download_moments(self._h, q.ctypes.data))
         return q
 
+    def copy_moments_to_device(self, dev_sq_ptr):
+        """rt_copy_moments_to_device: the sums of squared samples ((rows, W, 3) float32) into caller-owned device memory,
+        asynchronously on the context's stream."""
+        check(self._L.rt_copy_moments_to_device(self._h, C.c_void_p(dev_sq_ptr or 0)))
+
     def noise_map(self, floor=NOISE_FLOOR):
         """(rows, W, 2) float32: absolute and relative standard error of every pixel's mean."""
         out = np.zeros((self.rows, self.W, 2), dtype=np.float32)
@@ -207,6 +212,17 @@ class HipRenderer:
         ms = C.c_double(0.0)
         check(self._L.rt_denoise(self._h, C.byref(params) if params is not None else None, C.byref(ms) if timed else None))
         self.denoised_W, self.denoised_rows = self.W, self.rows
+        return ms.value if timed else None
+
+    def denoise_shards(self, hdr_ptr, sq_ptr, feat_ptr, W, H, world, rows_max, n, m, params=None, timed=False, block_rows=_capi.BLOCK_ROWS):
+        """rt_denoise_shards: the same filter over a W x H picture that `world` shards rendered (cyclic blocks of block_rows rows) and a
+        gather brought to this device: hdr_ptr, sq_ptr ([world][rows_max * W * 3] float32) and feat_ptr ([world][rows_max * W * 8] float32,
+        16-byte aligned) are device memory holding the shards' sums after n and m samples.  Needs no scene and no accumulation in this
+        context; download_denoised() then returns the H x W result.  params and timed as in denoise()."""
+        parts = _capi.shard_parts(W, H, world, rows_max, n, m, hdr_ptr, sq_ptr, feat_ptr, block_rows=block_rows)
+        ms = C.c_double(0.0)
+        check(self._L.rt_denoise_shards(self._h, C.byref(parts), C.byref(params) if params is not None else None, C.byref(ms) if timed else None))
+        self.denoised_W, self.denoised_rows = W, H
         return ms.value if timed else None
 
     def download_denoised(self):

@@ -245,10 +245,14 @@ int rt_clear(rt_ctx* ctx);
  * the switch takes effect at the next accumulation (rt_render with s0 == 1) and changing it voids a running one; default off.
  * rt_clear, a failed pass and rt_scene_upload void sq together with hdr.  Frame batching and render-ahead keep sq in step with hdr.
  * FRAME PIPELINING WITH THE SWITCH ON RENDERS EVERY CALL UNPIPELINED (same results; the fallback large scenes already take): the
- * carrying kernel's commit adds no second moments.  Moments are per context: a multi-GPU gather of sq is the caller's. */
+ * carrying kernel's commit adds no second moments.  Moments are per context: a multi-GPU gather of sq is the caller's, and
+ * rt_copy_moments_to_device is what feeds it (rt_denoise_shards below filters the gathered parts). */
 int rt_set_noise_estimate(rt_ctx* ctx, int on);
 /* Copy sq to host: W*local_rows*3 floats.  RT_ERR_SEQUENCE when the switch is off or nothing is accumulated. */
 int rt_download_moments(rt_ctx* ctx, float* sq_rgb);
+/* Same, device to device into caller-owned device memory (the buffer a gather of the shards sends).  Asynchronous on the context's
+ * stream; pending batches are settled and the errors are as for rt_download_moments. */
+int rt_copy_moments_to_device(rt_ctx* ctx, void* dev_sq);
 /* Per-pixel standard error of the accumulated MEAN after n = the samples in the strip (n >= 2, else RT_ERR_SEQUENCE; also when the
  * switch is off or nothing is accumulated).  binary64, only + - * / and comparisons, in this order (DESIGN.md "Noise estimate"):
  *     for c in r,g,b:  S = (double)hdr[c];  Q = (double)sq[c];  mean_c = S / n
@@ -325,7 +329,7 @@ int rt_denoise_default_params(rt_denoise_params* out);  /* needs no GPU */
  * an LDR buffer of its own.  params == NULL: the defaults; parameters outside their domain: RT_ERR_INVALID_ARG.  Needs the noise
  * estimate on and n >= 2 samples accumulated (pending batches are settled as rt_noise_map settles them; planes traced ahead are not in
  * the strips), and feature strips with at least one sample of the same W, H and row set as the picture: else RT_ERR_SEQUENCE.  A row set
- * with nshards != 1 is RT_ERR_INVALID_ARG.  Reads hdr, sq and feat; changes none of them, nor ldr, nor any sequencing state: a render
+ * with nshards != 1 is RT_ERR_INVALID_ARG (gather the shards and call rt_denoise_shards).  Reads hdr, sq and feat; changes none of them, nor ldr, nor any sequencing state: a render
  * that continues afterwards ends on the bits it would have had.  The result is a snapshot that stays until the next rt_denoise or
  * rt_scene_upload.  With out_ms == NULL the call only enqueues work on the context's stream; else it waits and returns the HIP-event
  * time.  env RT_DENOISE_STAGE, read per call: 0 = no level stages its taps in LDS, 1 = every level whose tile and halo fit does (same
@@ -336,6 +340,28 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms);
 int rt_download_denoised(rt_ctx* ctx, float* rgb, float* var, uint8_t* ldr);
 /* Same, device to device into caller-owned device memory.  Asynchronous on the context's stream. */
 int rt_copy_denoised_to_device(rt_ctx* ctx, void* dev_rgb, void* dev_var, void* dev_ldr);
+/* The same filter over a picture that was rendered in row shards (rt_rowset with nshards > 1, e.g. one shard per GPU) and gathered
+ * onto this context's device: part s holds shard s's hdr, sq and feat strips, each part padded to rows_max rows, the parts back to
+ * back -- the layout an equal-count gather of the shards' strips leaves.  Row j of the W x rs.num_rows image (j counted from
+ * rs.first_row) is local row lr of part s with (s, lr) = rt_rowset_locate(rs, j); the rows lr >= local_rows(s) of a part are the
+ * gather's padding and are never read. */
+typedef struct rt_shard_parts {
+    const void* hdr;   /* device: [nshards][rows_max * W * 3] float32 sums, as the equal-count gather leaves them */
+    const void* sq;    /* device: same shape                                                                    */
+    const void* feat;  /* device: [nshards][rows_max * W * 8] float32 sums; 16-byte aligned                     */
+    uint32_t W, rows_max;
+    rt_rowset rs;      /* first_row, num_rows, block_rows, nshards of the sharding; rs.shard ignored            */
+    uint32_t n, m;     /* samples in hdr / sq (>= 2), samples in feat (>= 1)                                    */
+} rt_shard_parts;
+/* Filters that image into the context's own denoise strips, in image order, and tonemaps it: rt_download_denoised,
+ * rt_copy_denoised_to_device and rt_unit_denoise_forms then serve the result exactly as after rt_denoise.  The arithmetic, the
+ * parameters (NULL: the defaults), RT_DENOISE_STAGE, out_ms and the snapshot's lifetime are rt_denoise's: the result has the bits
+ * rt_denoise gives in one context that rendered the whole image.  The parts are read by a prepare pass of their own, which looks every
+ * row up through the mapping; no assembled copy of the inputs is made.  Needs no scene and no accumulation in ctx, and reads and
+ * changes nothing of the context's render, noise or feature state.  A null pointer; W, rs.num_rows, rs.nshards or rs.block_rows of 0
+ * (or an image beyond 2^31 pixels or 524,280 rows); rows_max below the largest shard's rows; feat not 16-byte aligned; parameters
+ * outside their domain: RT_ERR_INVALID_ARG.  n < 2 or m == 0: RT_ERR_SEQUENCE.  A refused call keeps the previous snapshot. */
+int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise_params* params, double* out_ms);
 
 /* Replaces the transform(par) tonemap (spheres-app.cpp:186-214): hdr / n_samples,
  * ACES fit, gamma 1/2.2, XMStoreColor.  n_samples == 0 uses the accumulated count. */
@@ -357,6 +383,11 @@ int rt_synchronize(rt_ctx* ctx);
 /* Global row index of local row lr under rs (pure host arithmetic; no GPU). */
 uint32_t rt_rowset_local_rows(rt_rowset rs);
 uint32_t rt_rowset_global_row(rt_rowset rs, uint32_t local_row);
+/* The inverse: which shard owns row image_row of the row range (counted from rs.first_row, < rs.num_rows) and which of its local rows
+ * that is; rs.shard is ignored.  rt_rowset_global_row({.., shard = *shard, ..}, *local_row) == rs.first_row + image_row.  A null
+ * pointer, block_rows or nshards of 0, or a row beyond the range: RT_ERR_INVALID_ARG.  Pure host arithmetic; no GPU.  The same
+ * source (csrc/rt_rowset_map.h) is what the kernel of rt_denoise_shards finds its rows with. */
+int rt_rowset_locate(rt_rowset rs, uint32_t image_row, uint32_t* shard, uint32_t* local_row);
 
 /* --------------------------------------------------- unit-level entry points
  * Batched, device-evaluated pieces of the path, so that each reference function
@@ -455,8 +486,14 @@ int rt_unit_features_host(const rt_material* materials, uint32_t n_materials, co
  * RT_ERR_SEQUENCE.  Needs no GPU. */
 int rt_unit_denoise_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
                          const rt_denoise_params* params, float* out_rgb, float* out_var);
-/* Which form each level of the last rt_denoise took: out[l] = 0 the level did not run, 1 its taps were read from global memory, 2 from
- * a tile staged in LDS. */
+/* The filter of rt_denoise_shards for given parts, from the same sources compiled for the host (csrc/rt_rowset_map.h, csrc/rt_denoise.h).
+ * hdr, sq, feat8: host memory in the layout of rt_shard_parts; of *shape the pointers are ignored, everything else is read as
+ * rt_denoise_shards reads it.  out_rgb = 3 floats, out_var = 1 float per pixel of the W x rs.num_rows image, in image order.  The
+ * padding rows are never read.  Refusals as rt_denoise_shards'.  Needs no GPU. */
+int rt_unit_denoise_shards_host(const float* hdr, const float* sq, const float* feat8, const rt_shard_parts* shape, const rt_denoise_params* params,
+                                float* out_rgb, float* out_var);
+/* Which form each level of the last rt_denoise or rt_denoise_shards took: out[l] = 0 the level did not run, 1 its taps were read from
+ * global memory, 2 from a tile staged in LDS. */
 int rt_unit_denoise_forms(rt_ctx* ctx, uint32_t out[5]);
 /* The shadow index rt_scene_upload would build for light `light` of the list, under the environment of the moment.
  * out_u: [0] 1 = the index is enabled (else nothing more is valid: every shadow ray of this light is answered over every scan
