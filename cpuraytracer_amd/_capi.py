@@ -46,6 +46,11 @@ class RtDenoiseParams(C.Structure):
                 ("k_coverage", C.c_float), ("k_colour", C.c_float), ("var_floor", C.c_float)]
 
 
+class RtTemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_uint32), ("use_id", C.c_uint32), ("depth_tol", C.c_float), ("normal_tol", C.c_float),
+                ("coverage_tol", C.c_float)]
+
+
 class RtShardParts(C.Structure):
     """rt_shard_parts: the gathered parts of a row-sharded picture (device pointers) and their shape."""
     _fields_ = [("hdr", C.c_void_p), ("sq", C.c_void_p), ("feat", C.c_void_p), ("W", C.c_uint32), ("rows_max", C.c_uint32),
@@ -75,6 +80,7 @@ EXPORTS = [
     "rt_unit_launch_plan",
     "rt_denoise_default_params", "rt_denoise", "rt_download_denoised", "rt_copy_denoised_to_device", "rt_unit_denoise_host", "rt_unit_denoise_forms",
     "rt_copy_moments_to_device", "rt_rowset_locate", "rt_denoise_shards", "rt_unit_denoise_shards_host",
+    "rt_temporal_default_params", "rt_denoise_temporal", "rt_temporal_reset", "rt_download_temporal", "rt_unit_temporal_host",
 ]
 
 _lib = None
@@ -185,6 +191,15 @@ def load():
         L.rt_denoise_shards.argtypes = [C.c_void_p, C.POINTER(RtShardParts), C.POINTER(RtDenoiseParams), C.POINTER(C.c_double)]
         L.rt_unit_denoise_shards_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtShardParts), C.POINTER(RtDenoiseParams),
                                                   C.c_void_p, C.c_void_p]
+    if hasattr(L, "rt_denoise_temporal"):
+        L.rt_temporal_default_params.argtypes = [C.POINTER(RtTemporalParams)]
+        L.rt_denoise_temporal.argtypes = [C.c_void_p, C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.POINTER(C.c_double)]
+        L.rt_temporal_reset.argtypes = [C.c_void_p]
+        L.rt_download_temporal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_unit_temporal_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtCamera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -203,6 +218,47 @@ def denoise_params(**fields):
             raise TypeError("rt_denoise_params has no field %r" % k)
         setattr(p, k, v)
     return p
+
+
+def temporal_params(**fields):
+    """rt_temporal_default_params with the given fields replaced (max_history, use_id, depth_tol, normal_tol, coverage_tol)."""
+    p = RtTemporalParams()
+    check(load().rt_temporal_default_params(C.byref(p)))
+    for k, v in fields.items():
+        if k not in dict(RtTemporalParams._fields_):
+            raise TypeError("rt_temporal_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def unit_temporal_host(hdr, sq, n, feat8, m, ids, W, H, camera, history=None, params=None, tparams=None, first_row=0):
+    """rt_unit_temporal_host over numpy strips of rows [first_row, first_row + rows) of the W x H image.  history: None (empty) or a dict
+    with camera, state (rows, W, 4), guides (rows, W, 8), ids and len (rows, W).  Returns a dict: rgb, var (den and den_var), target,
+    and state, guides, len, ids, camera -- the last five are the next call's history."""
+    hdr = np.ascontiguousarray(hdr, dtype=np.float32)
+    sq = np.ascontiguousarray(sq, dtype=np.float32)
+    feat8 = np.ascontiguousarray(feat8, dtype=np.float32)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    rows = hdr.size // (3 * W)
+    assert hdr.size == rows * W * 3 and sq.size == hdr.size and feat8.size == rows * W * 8 and ids.size == rows * W
+    out = {"rgb": np.zeros((rows, W, 3), np.float32), "var": np.zeros((rows, W), np.float32), "state": np.zeros((rows, W, 4), np.float32),
+           "guides": np.zeros((rows, W, 8), np.float32), "len": np.zeros((rows, W), np.uint32), "target": np.zeros((rows, W), np.uint32)}
+    cam = RtCamera.from_buffer_copy(bytes(camera))
+    if history is None:
+        hc, hs, hg, hi, hl = None, None, None, None, None
+    else:
+        hc = C.byref(RtCamera.from_buffer_copy(bytes(history["camera"])))
+        keep = [np.ascontiguousarray(history["state"], dtype=np.float32), np.ascontiguousarray(history["guides"], dtype=np.float32),
+                np.ascontiguousarray(history["ids"], dtype=np.uint32), np.ascontiguousarray(history["len"], dtype=np.uint32)]
+        assert keep[0].size == rows * W * 4 and keep[1].size == rows * W * 8 and keep[2].size == rows * W and keep[3].size == rows * W
+        hs, hg, hi, hl = (a.ctypes.data for a in keep)
+    check(load().rt_unit_temporal_host(hdr.ctypes.data, sq.ctypes.data, n, feat8.ctypes.data, m, ids.ctypes.data, W, H, first_row, rows, C.byref(cam), hc,
+                                       hs, hg, hi, hl, C.byref(params) if params is not None else None,
+                                       C.byref(tparams) if tparams is not None else None, out["rgb"].ctypes.data, out["var"].ctypes.data,
+                                       out["state"].ctypes.data, out["guides"].ctypes.data, out["len"].ctypes.data, out["target"].ctypes.data))
+    out["ids"] = ids.reshape(rows, W).copy()
+    out["camera"] = cam
+    return out
 
 
 def shard_parts(W, H, world, rows_max, n, m, hdr=None, sq=None, feat=None, block_rows=None, first_row=0):

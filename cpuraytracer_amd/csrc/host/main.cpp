@@ -20,6 +20,9 @@ static void Usage() {
               "                                PREFIX.normal.pfm (three channels), PREFIX.depth.pfm and PREFIX.coverage.pfm (one channel)\n"
               "               [--denoise-out file.ppm [--denoise-levels N]]   the picture after the feature-guided a-trous filter (rt_denoise, N = 1..5\n"
               "                                levels, default 3), written beside --out, which is unchanged; needs --spp >= 2\n"
+              "               [--orbit-frames K [--orbit-deg D]]   with --denoise-out: K pictures of --spp samples each (seed --seed + f) from a camera\n"
+              "                                that turns D degrees (default 0.5) per picture about the scene's look-at point, each followed by the\n"
+              "                                feature pass and rt_denoise_temporal; the last picture is written\n"
               "               [--target-error T [--target-fraction F] [--max-spp N]]   render --frame-spp samples at a time until at most the\n"
               "                                fraction F (default 0) of the pixels has a relative error above T, or N (default --spp) is reached\n"
               "               [--noise-floor F]        added to a pixel's r + g + b before the relative error divides by it (default 0.01)");
@@ -31,6 +34,9 @@ int main(int argc, char** argv) {
     int device = 0, gpus = 0;
     std::string out = "out.ppm", noiseOut, featuresOut, denoiseOut;
     uint32_t denoiseLevels = 0;  // 0: the default
+    uint32_t orbitFrames = 0;
+    double orbitDeg = 0.5;
+    bool orbitSet = false;
     float targetError = 0.f;
     double targetFraction = 0.0;
     uint32_t maxSpp = 0;
@@ -62,6 +68,8 @@ int main(int argc, char** argv) {
         else if (k == "--features-out") featuresOut = val();
         else if (k == "--denoise-out") denoiseOut = val();
         else if (k == "--denoise-levels") denoiseLevels = (uint32_t)std::atoi(val());
+        else if (k == "--orbit-frames") { orbitFrames = (uint32_t)std::atoi(val()); orbitSet = true; }
+        else if (k == "--orbit-deg") { orbitDeg = std::atof(val()); orbitSet = true; }
         else if (k == "--target-error") { targetError = (float)std::atof(val()); targetSet = true; }
         else if (k == "--target-fraction") targetFraction = std::atof(val());
         else if (k == "--max-spp") maxSpp = (uint32_t)std::atoi(val());
@@ -80,6 +88,11 @@ int main(int argc, char** argv) {
     }
     if (st.samplesPerFrame == 0 || spp == 0 || st.k_backbufferWidth <= 0 || st.k_backbufferHeight <= 0) { Usage(); return 2; }
     if (spp % st.samplesPerFrame != 0) st.samplesPerFrame = 1;
+    if (orbitSet && (denoiseOut.empty() || gpus > 0 || targetSet)) {
+        std::fprintf(stderr, "spheres: --orbit-frames and --orbit-deg need --denoise-out and are not available with --gpus or --target-error\n");
+        return 2;
+    }
+    if (orbitSet && (orbitFrames == 0 || spp < 2 || !(orbitDeg == orbitDeg))) { Usage(); return 2; }
     if (!denoiseOut.empty() && gpus > 0) {
         std::fprintf(stderr, "spheres: --denoise-out is not available with --gpus: the multi-GPU gather carries neither second moments nor feature strips\n");
         return 2;
@@ -125,7 +138,8 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "spheres: %s\n", e.what());
         return 1;
     }
-    const int rc = targetSet ? app.RunUntil(targetError, targetFraction, maxSpp) : app.Run(spp / st.samplesPerFrame);
+    const int rc = orbitSet ? app.RunOrbit(orbitFrames, orbitDeg, spp, denoiseLevels)
+                            : (targetSet ? app.RunUntil(targetError, targetFraction, maxSpp) : app.Run(spp / st.samplesPerFrame));
     if (rc != 0) return rc;
     if (!noiseOut.empty() && !app.WriteNoisePFM(noiseOut)) {
         std::fprintf(stderr, "spheres: cannot write %s: %s\n", noiseOut.c_str(), rt_last_error());
@@ -135,7 +149,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "spheres: cannot write the feature buffers %s.*.pfm: %s\n", featuresOut.c_str(), rt_last_error());
         return 1;
     }
-    if (!denoiseOut.empty() && !app.WriteDenoisedPPM(denoiseOut, denoiseLevels)) {
+    if (orbitSet) {
+        if (!app.WriteTemporalPPM(denoiseOut)) {
+            std::fprintf(stderr, "spheres: cannot write the denoised picture %s: %s\n", denoiseOut.c_str(), rt_last_error());
+            return 1;
+        }
+    } else if (!denoiseOut.empty() && !app.WriteDenoisedPPM(denoiseOut, denoiseLevels)) {
         std::fprintf(stderr, "spheres: cannot write the denoised picture %s: %s\n", denoiseOut.c_str(), rt_last_error());
         return 1;
     }

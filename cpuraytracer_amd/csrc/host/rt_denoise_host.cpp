@@ -9,6 +9,7 @@
 #include "../../../include/rt_api.h"
 #include "../rt_denoise.h"
 #include "../rt_rowset_map.h"
+#include "rt_denoise_host.h"
 #include "rt_denoise_launch.h"
 #include "rt_error.h"
 
@@ -53,6 +54,11 @@ static void RunLevels(std::vector<rtd::DenoiseState>& a, std::vector<rtd::Denois
 }
 
 namespace rtdn {
+
+void RunLevelsHost(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseState>& b, const std::vector<float>& g, uint32_t W, uint32_t rows,
+                   const rtd::DenoiseParams& P, float* out_rgb, float* out_var) {
+    RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
+}
 
 int CheckShardParts(const char* who_, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P) {
     const std::string who(who_);

@@ -1,0 +1,28 @@
+// rt_denoise_host.h -- what the host twins share (rt_denoise_host.cpp, rt_temporal_host.cpp): the levels of the filter over a
+// prepared state, and the temporal parameters' check.  Host C++ only.
+#pragma once
+
+#include <stdint.h>
+
+#include <vector>
+
+#include "../rt_denoise.h"
+#include "../rt_temporal.h"
+
+struct rt_camera;
+struct rt_temporal_params;
+
+namespace rtdn {
+
+// The levels over the prepared state a (b: the other buffer; both are overwritten) and guides g (8 floats per pixel) of a W x rows
+// picture; the last level's state goes out as out_rgb (3 floats per pixel) and out_var.
+void RunLevelsHost(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseState>& b, const std::vector<float>& g, uint32_t W, uint32_t rows,
+                   const rtd::DenoiseParams& P, float* out_rgb, float* out_var);
+
+// tparams (NULL: the defaults) into T; outside their domain: RT_ERR_INVALID_ARG with a message that starts with who.
+int CheckTemporalParams(const char* who, const rt_temporal_params* tparams, rtd::TemporalParams* T);
+
+// The part of a camera record the reprojection reads.
+rtd::TemporalCam CamOf(const rt_camera& c);
+
+}  // namespace rtdn

@@ -7,6 +7,7 @@
 
 #include "../rt_denoise.h"
 #include "../rt_rowset_map.h"
+#include "../rt_temporal.h"
 
 namespace rtdn {
 
@@ -48,6 +49,28 @@ struct ShardLayout {
 // The same launches, the prepare pass reading through the mapping; everything it writes is in image order.
 int LaunchDenoiseShards(void* stream, const Strips& s, const ShardLayout& parts, const rtd::DenoiseParams& P, int stageKnob,
                         uint32_t forms[rtd::kDenoiseMaxLevels]);
+
+// The temporal form (rt_denoise_temporal; ../rt_temporal.h): the prepare pass also reprojects every pixel into the history's camera,
+// gathers the history there, validates and blends, and writes the new history -- one pass.  Level 0 then reads the new history's
+// state and guides where they lie (Strips::state[0] and Strips::guide are not used: state[0] and state[1] are the later levels' ping
+// and pong).  The history is never updated in place: prev and next are different sets of buffers.
+struct TemporalSet {
+    void* state;     // [npix] float4 (c.rgb, v) before the levels
+    void* guide[2];  // [npix] float4 each, as Strips::guide
+    uint32_t* ids;   // [npix]
+    uint32_t* len;   // [npix] frames blended into state (>= 1)
+};
+struct Temporal {
+    const uint32_t* ids;   // [npix] the feature strips' ids of this frame
+    rtd::TemporalGeom geom;
+    rtd::TemporalCam cam, camPrev;
+    rtd::TemporalParams params;
+    bool hasPrev;          // false: an empty history (prev is not read)
+    TemporalSet prev, next;
+    uint32_t* target;      // [npix] out
+};
+int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
+                          uint32_t forms[rtd::kDenoiseMaxLevels]);
 
 }  // namespace rtdn
 

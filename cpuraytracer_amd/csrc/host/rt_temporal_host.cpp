@@ -1,0 +1,119 @@
+// rt_temporal_host.cpp -- temporal accumulation (../rt_temporal.h) compiled for the host: rt_unit_temporal_host, the twin the device
+// is compared with bit for bit -- one frame step (prepare, reproject, gather, validate, blend) plus the levels of
+// rt_unit_denoise_host's filter (rtdn::RunLevelsHost, rt_denoise_host.cpp) -- and the parameter defaults.  Plain C++ with no HIP
+// header, under the same floating-point contract as the kernels (-ffp-contract=off, IEEE division).  Needs no GPU.
+#include <cstddef>
+#include <string>
+#include <vector>
+
+#include "../../../include/rt_api.h"
+#include "../rt_temporal.h"
+#include "rt_denoise_host.h"
+#include "rt_error.h"
+
+using rtprep::Fail;
+
+static_assert(sizeof(rt_temporal_params) == sizeof(rtd::TemporalParams) && offsetof(rt_temporal_params, coverage_tol) == offsetof(rtd::TemporalParams, coverage_tol),
+              "rt_temporal_params is laid out like rtd::TemporalParams");
+
+namespace rtdn {
+
+int CheckTemporalParams(const char* who_, const rt_temporal_params* tparams, rtd::TemporalParams* T) {
+    rt_temporal_params def;
+    rt_temporal_default_params(&def);
+    if (!tparams) tparams = &def;
+    *T = rtd::TemporalParams{tparams->max_history, tparams->use_id, tparams->depth_tol, tparams->normal_tol, tparams->coverage_tol};
+    if (!rtd::temporal_params_ok(*T))
+        return Fail(RT_ERR_INVALID_ARG, std::string(who_) + ": max_history must be 1..64, every tolerance finite and >= 0");
+    return RT_OK;
+}
+
+rtd::TemporalCam CamOf(const rt_camera& c) {
+    rtd::TemporalCam C;
+    rtd::temporal_cam(c.origin, c.x, c.y, c.origin_image_plane, C);
+    return C;
+}
+
+}  // namespace rtdn
+
+extern "C" {
+
+int rt_temporal_default_params(rt_temporal_params* out) {
+    if (!out) return Fail(RT_ERR_INVALID_ARG, "rt_temporal_default_params: null argument");
+    out->max_history = 2;  // (nearest-pixel fetches drift, a longer history loses more than it averages away)
+    out->use_id = 1;
+    out->depth_tol = 0.1f;
+    out->normal_tol = 0.1f;
+    out->coverage_tol = 0.25f;
+    return RT_OK;
+}
+
+int rt_unit_temporal_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W, uint32_t H,
+                          uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
+                          const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
+                          const rt_temporal_params* tparams, float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len,
+                          uint32_t* out_target) {
+    const char* who = "rt_unit_temporal_host";
+    if (!hdr || !sq || !feat8 || !ids || !camera) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+    if (hist_len && (!hist_camera || !hist_state4 || !hist_guides8 || !hist_ids))
+        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a history (hist_len != NULL) needs its camera, state, guides and ids");
+    const rtd::TemporalGeom G{W, H, first_row, num_rows};
+    if (!rtd::temporal_geom_ok(G) || (uint64_t)first_row + num_rows > H || (uint64_t)W * num_rows > (1ull << 31))
+        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": empty or too large strip, or rows beyond the image");
+    rt_denoise_params def;
+    rt_denoise_default_params(&def);
+    if (!params) params = &def;
+    const rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
+    if (!rtd::denoise_params_ok(P))
+        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    rtd::TemporalParams T{};
+    const int rc = rtdn::CheckTemporalParams(who, tparams, &T);
+    if (rc != RT_OK) return rc;
+    if (n < 2) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the noise estimate needs at least 2 samples per pixel");
+    if (m == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the feature strips hold no sample");
+    const size_t npix = (size_t)W * num_rows;
+    const rtd::TemporalCam C = rtdn::CamOf(*camera);
+    const rtd::TemporalCam Cp = hist_len ? rtdn::CamOf(*hist_camera) : C;
+    std::vector<rtd::DenoiseState> a(npix), b(npix);
+    std::vector<float> g(npix * 8);
+    for (uint32_t ly = 0; ly < num_rows; ++ly) {
+        for (uint32_t x = 0; x < W; ++x) {
+            const size_t p = (size_t)ly * W + x;
+            rtd::DenoiseState s;
+            float* gp = &g[8 * p];
+            rtd::denoise_prepare(hdr + 3 * p, sq + 3 * p, n, feat8 + 8 * p, m, s, gp);
+            uint32_t len = 1u, target = rtd::kTemporalNoTarget;
+            uint32_t xi = 0, yi = 0;
+            float dist = 0.f;
+            if (hist_len && rtd::temporal_reproject(G, C, Cp, x, first_row + ly, gp, xi, yi, dist)) {
+                const size_t q = (size_t)(yi - first_row) * W + xi;
+                rtd::DenoiseState sh;
+                for (int k = 0; k < 3; ++k) sh.c[k] = hist_state4[4 * q + k];
+                sh.v = hist_state4[4 * q + 3];
+                const bool ok = rtd::temporal_validate(T, gp, ids[p], dist, hist_guides8 + 8 * q, hist_ids[q], hist_len[q]);
+                len = rtd::temporal_blend(T, ok, s, sh, hist_len[q]);
+                if (ok) target = (uint32_t)q;
+            }
+            a[p] = s;
+            if (out_state4) {
+                for (int k = 0; k < 3; ++k) out_state4[4 * p + k] = s.c[k];
+                out_state4[4 * p + 3] = s.v;
+            }
+            if (out_len) out_len[p] = len;
+            if (out_target) out_target[p] = target;
+        }
+    }
+    if (out_guides8)
+        for (size_t i = 0; i < npix * 8; ++i) out_guides8[i] = g[i];
+    if (out_rgb || out_var) {
+        std::vector<float> rgb(npix * 3), var(npix);
+        rtdn::RunLevelsHost(a, b, g, W, num_rows, P, rgb.data(), var.data());
+        if (out_rgb)
+            for (size_t i = 0; i < npix * 3; ++i) out_rgb[i] = rgb[i];
+        if (out_var)
+            for (size_t i = 0; i < npix; ++i) out_var[i] = var[i];
+    }
+    return RT_OK;
+}
+
+}  // extern "C"

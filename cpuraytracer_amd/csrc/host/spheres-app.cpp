@@ -55,11 +55,13 @@ void SpheresApp::InitCamera() {  // spheres-app.cpp:35-49
     if (AppSettings.scene == "three") {  // SURVEY.md §8(d) C1 camera
         m_camera = std::make_unique<Camera>(XMVectorSet(0.f, 0.f, 0.f, 1.f), XMVectorSet(0.f, 0.f, 1.f, 1.f), AppSettings.k_verticalFov,
                                             AppSettings.AspectRatio(), 1.f, AppSettings.k_aperture);
+        m_lookAt[0] = 0.f, m_lookAt[1] = 0.f, m_lookAt[2] = 1.f;
     } else {
         XMVECTOR camOrigin = XMVectorSet(12.f, 2.f, -2.5f, 1.f);
         XMVECTOR camLookAt = XMVectorSet(0, 1, 0, 1.f);
         m_camera = std::make_unique<Camera>(camOrigin, camLookAt, AppSettings.k_verticalFov, AppSettings.AspectRatio(),
                                             XMVectorGetX(XMVector3Length(camOrigin - camLookAt)), AppSettings.k_aperture);
+        m_lookAt[0] = 0.f, m_lookAt[1] = 1.f, m_lookAt[2] = 0.f;
     }
     m_exposure = -15;
 }
@@ -256,6 +258,73 @@ bool SpheresApp::WriteDenoisedPPM(const std::string& path, uint32_t levels) cons
     if (rt_denoise_default_params(&params) != RT_OK) return false;
     if (levels != 0) params.levels = levels;
     if (rt_denoise(m_device, &params, nullptr) != RT_OK) return false;
+    std::vector<uint8_t> rgb((size_t)W * rows * 3);
+    if (rt_download_denoised(m_device, nullptr, nullptr, rgb.data()) != RT_OK) return false;
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::fprintf(f, "P6\n%u %u\n255\n", W, rows);
+    const bool ok = std::fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
+    std::fclose(f);
+    return ok;
+}
+
+rt_camera OrbitCamera(const rt_camera& camera, double degrees, const float pivot[3]) {
+    const double a = degrees * (3.14159265358979323846 / 180.0);
+    const double c = std::cos(a), s = std::sin(a);
+    rt_camera out = camera;
+    const float* src[4] = {camera.origin, camera.origin_image_plane, camera.x, camera.y};
+    float* dst[4] = {out.origin, out.origin_image_plane, out.x, out.y};
+    for (int k = 0; k < 4; ++k) {
+        const bool point = k < 2;
+        double v[3];
+        for (int j = 0; j < 3; ++j) v[j] = point ? (double)src[k][j] - (double)pivot[j] : (double)src[k][j];
+        const double r[3] = {c * v[0] + s * v[2], v[1], -s * v[0] + c * v[2]};
+        for (int j = 0; j < 3; ++j) dst[k][j] = (float)(point ? r[j] + (double)pivot[j] : r[j]);
+    }
+    return out;
+}
+
+int SpheresApp::RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels) noexcept {
+    try {
+        const uint32_t W = (uint32_t)GetBackBufferWidth(), H = (uint32_t)GetBackBufferHeight();
+        const rt_rowset rs = m_hasRowset ? m_rowset : rt_rowset{0, H, H, 0, 1};
+        std::vector<rt_sphere> spheres;
+        std::vector<rt_material> materials;
+        rt_camera camera;
+        std::vector<rt_light> lights;
+        rt_material sky;
+        float exposureAdjustment;
+        DescribeScene(spheres, materials, camera, lights, sky, exposureAdjustment);
+        rt_denoise_params params;
+        RT_CALL(rt_denoise_default_params(&params));
+        if (levels != 0) params.levels = levels;
+        RT_CALL(rt_temporal_reset(m_device));
+        for (uint32_t f = 0; f < frames; ++f) {
+            const rt_camera turned = OrbitCamera(camera, (double)f * degPerFrame, m_lookAt);
+            RT_CALL(rt_scene_upload(m_device, spheres.data(), materials.data(), (uint32_t)spheres.size(), &turned, lights.data(), (uint32_t)lights.size(), &sky,
+                                    exposureAdjustment));
+            RT_CALL(rt_set_sampler(m_device, AppSettings.samplerFlags));
+            RT_CALL(rt_set_noise_estimate(m_device, 1));
+            RT_CALL(rt_set_frame_pipelining(m_device, 0));
+            RT_CALL(rt_set_frame_batch(m_device, 1u));
+            m_uploaded = true;
+            RT_CALL(rt_render(m_device, W, H, rs, 1u, 1u + spp, (uint32_t)AppSettings.k_recursionDepth, AppSettings.renderSeed + f, &m_lastStats));
+            m_sampleCount = spp;
+            RT_CALL(rt_resolve(m_device, spp));
+            m_lastStats.ms_resolve = rt_last_resolve_ms(m_device);
+            RT_CALL(rt_render_features(m_device, W, H, rs, 1u, 1u + spp, nullptr));
+            RT_CALL(rt_denoise_temporal(m_device, &params, nullptr, nullptr));
+        }
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "spheres: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
+bool SpheresApp::WriteTemporalPPM(const std::string& path) const {
+    const uint32_t W = (uint32_t)GetBackBufferWidth();
+    const uint32_t rows = m_lastStats.local_rows;
     std::vector<uint8_t> rgb((size_t)W * rows * 3);
     if (rt_download_denoised(m_device, nullptr, nullptr, rgb.data()) != RT_OK) return false;
     FILE* f = std::fopen(path.c_str(), "wb");

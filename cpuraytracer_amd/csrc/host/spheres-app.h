@@ -32,6 +32,10 @@ struct AppSettingsT {
     float noiseFloor = 0.01f;     // floor of the relative error (rt_noise_map)
 };
 
+// The record turned by `degrees` about the vertical (y) axis through `pivot`: origin and origin_image_plane turn about the pivot, x and
+// y as vectors; evaluated in binary64 and rounded once to binary32 (scenes.orbit_camera in Python does the same arithmetic).
+rt_camera OrbitCamera(const rt_camera& camera, double degrees, const float pivot[3]);
+
 class RayTracingApp {  // app.h:5-30 without the window
 public:
     virtual ~RayTracingApp() = default;
@@ -73,6 +77,12 @@ public:
     // Frames of samplesPerFrame samples until at most `fraction` of the pixels have a relative error above relError, or the next
     // frame would pass maxSpp (every frame waits for its summary, so every frame is resolved).  SampleCount() is the spp reached.
     int RunUntil(float relError, double fraction, uint32_t maxSpp) noexcept;
+    // `frames` pictures of `spp` samples each (samples 1 .. spp, render seed renderSeed + f) from a camera that has turned f * degPerFrame
+    // degrees about the vertical axis through the scene's look-at point (OrbitCamera); every frame is an upload, a render, the feature
+    // pass and rt_denoise_temporal (the defaults; levels != 0 replaces the number of levels), so the history follows the camera.
+    // WritePPM then writes the last frame, WriteTemporalPPM its temporally accumulated and filtered picture.
+    int RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels) noexcept;
+    bool WriteTemporalPPM(const std::string& path) const;
     const std::vector<XMVECTOR>& Hdr() const { return m_backbufferHdr; }
     const std::vector<XMCOLOR>& Ldr() const { return m_backbufferLdr; }
     size_t SampleCount() const { return m_sampleCount; }
@@ -101,6 +111,7 @@ private:
     std::vector<std::unique_ptr<Light>> m_lights;
     std::unique_ptr<BvhNode> m_bvh;
     std::unique_ptr<Material> m_skyMaterial;
+    float m_lookAt[3] = {0.f, 0.f, 0.f};  // InitCamera's look-at point: the pivot of RunOrbit
     float m_exposure = 0.f;
     size_t m_sampleCount = 0;
     bool m_uploaded = false;

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/rt_api.h"
+#include "host/rt_denoise_host.h"
 #include "host/rt_denoise_launch.h"
 #include "host/rt_launch_plan.h"
 #include "host/rt_scene_prep.h"
@@ -157,6 +158,20 @@ struct rt_ctx {
     DevBuf<float> denGuide[2];    // [W*rows*4] each: (albedo rgb, normal x), (normal y, normal z, depth, coverage)
     DevBuf<float> den, denVar;    // [W*rows*3], [W*rows]
     DevBuf<uint8_t> denLdr;       // [W*rows*3] the resolve of den with n_samples = 1
+
+    // temporal accumulation (rt_denoise_temporal; rt_temporal.h): the history, state of its own that rt_scene_upload keeps.  Two sets
+    // used ping-pong -- a call reads set tmpCur and writes the other, which then becomes tmpCur -- and never updated in place.
+    struct TemporalSet {
+        DevBuf<float> state, guide[2];  // [W*rows*4] each
+        DevBuf<uint32_t> ids, len;      // [W*rows]
+    };
+    bool tmpValid = false;        // set tmpCur holds a history of the picture below, taken with tmpCam
+    uint32_t tmpCur = 0;
+    uint32_t tmpW = 0, tmpH = 0;
+    rt_rowset tmpRs{};
+    rtd::TemporalCam tmpCam{};
+    TemporalSet tmpSet[2];
+    DevBuf<uint32_t> tmpTarget;   // [W*rows] of the last call
 
     // tuning (env: RT_BLOCKS_PER_CU, RT_FORCE_GLOBAL_TABLES)
     uint32_t blocksPerCu = 4;
@@ -763,6 +778,14 @@ void rt_destroy(rt_ctx* ctx) {
     ctx->den.Release();
     ctx->denVar.Release();
     ctx->denLdr.Release();
+    for (auto& t : ctx->tmpSet) {
+        t.state.Release();
+        t.guide[0].Release();
+        t.guide[1].Release();
+        t.ids.Release();
+        t.len.Release();
+    }
+    ctx->tmpTarget.Release();
     ctx->samples.Release();
     ctx->queue.Release();
     ctx->counters.Release();
@@ -1678,6 +1701,112 @@ int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise
     ctx->denW = W;
     ctx->denRows = rows;
     ctx->denValid = true;
+    return RT_OK;
+}
+
+// rt_denoise with the temporal step in its prepare pass (rt_temporal.h).  The history is the context's: set tmpCur is read, the other
+// set is written and becomes tmpCur once everything is enqueued.  Every refusal comes before the first change.
+int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, double* out_ms) {
+    int rc = NoiseReady(ctx, "rt_denoise_temporal", 2);
+    if (rc != RT_OK) return rc;
+    rt_denoise_params def;
+    rt_denoise_default_params(&def);
+    if (!params) params = &def;
+    const rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
+    if (!rtd::denoise_params_ok(P))
+        return Fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    rtd::TemporalParams T{};
+    if ((rc = rtdn::CheckTemporalParams("rt_denoise_temporal", tparams, &T)) != RT_OK) return rc;
+    if (ctx->rs.nshards != 1)
+        return Fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: the local rows of a cyclic row set (nshards != 1) are not neighbours in the image");
+    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_denoise_temporal: no feature strips (rt_render_features)");
+    if (ctx->featW != ctx->W || ctx->featH != ctx->H || ctx->featRows != ctx->rows || std::memcmp(&ctx->featRs, &ctx->rs, sizeof(rt_rowset)) != 0)
+        return Fail(RT_ERR_SEQUENCE, "rt_denoise_temporal: the feature strips are of another image or row set than the picture");
+    const uint32_t W = ctx->W, rows = ctx->rows;
+    if ((rows + rtdn::kTileH - 1u) / rtdn::kTileH > 65535u) return Fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: more than 524,280 rows");
+    const rtd::TemporalGeom G{W, ctx->H, ctx->rs.first_row, rows};
+    if (!rtd::temporal_geom_ok(G) || rows != ctx->rs.num_rows)
+        return Fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: a picture wider or taller than 2^24, or a strip that is not its row range");
+    const size_t npix = (size_t)W * rows;
+    const bool hasPrev = ctx->tmpValid && ctx->tmpW == W && ctx->tmpH == ctx->H && std::memcmp(&ctx->tmpRs, &ctx->rs, sizeof(rt_rowset)) == 0;
+    if (!hasPrev) ctx->tmpValid = false;  // (a Reserve below may let the old sets go: they were of another picture)
+    for (auto& t : ctx->tmpSet)
+        if ((rc = t.state.Reserve(npix * 4)) != RT_OK || (rc = t.guide[0].Reserve(npix * 4)) != RT_OK || (rc = t.guide[1].Reserve(npix * 4)) != RT_OK ||
+            (rc = t.ids.Reserve(npix)) != RT_OK || (rc = t.len.Reserve(npix)) != RT_OK)
+            return rc;
+    if ((rc = ctx->tmpTarget.Reserve(npix)) != RT_OK) return rc;
+    for (int k = 0; k < 2; ++k)
+        if ((rc = ctx->denState[k].Reserve(npix * 4)) != RT_OK) return rc;
+    if ((rc = ctx->den.Reserve(npix * 3)) != RT_OK || (rc = ctx->denVar.Reserve(npix)) != RT_OK || (rc = ctx->denLdr.Reserve(npix * 3)) != RT_OK) return rc;
+    int knob = -1;
+    if (const char* e = std::getenv("RT_DENOISE_STAGE")) knob = std::atoi(e) != 0 ? 1 : 0;
+    rtdn::Strips S{};
+    S.hdr = ctx->hdr.ptr;
+    S.sq = ctx->sq.ptr;
+    S.feat = ctx->feat.ptr;
+    S.n = ctx->accumulated;
+    S.m = ctx->featCount;
+    S.W = W;
+    S.rows = rows;
+    for (int k = 0; k < 2; ++k) S.state[k] = ctx->denState[k].ptr;
+    S.den = ctx->den.ptr;
+    S.denVar = ctx->denVar.ptr;
+    const rtd::TraceParams& b = ctx->base;
+    rtdn::Temporal Q{};
+    Q.ids = ctx->featIds.ptr;
+    Q.geom = G;
+    rtd::temporal_cam(b.cam_o, b.cam_x, b.cam_y, b.cam_oip, Q.cam);
+    Q.camPrev = hasPrev ? ctx->tmpCam : Q.cam;
+    Q.params = T;
+    Q.hasPrev = hasPrev;
+    const uint32_t cur = ctx->tmpCur & 1u, nxt = cur ^ 1u;
+    const auto setOf = [](rt_ctx::TemporalSet& t) { return rtdn::TemporalSet{t.state.ptr, {t.guide[0].ptr, t.guide[1].ptr}, t.ids.ptr, t.len.ptr}; };
+    Q.prev = setOf(ctx->tmpSet[cur]);
+    Q.next = setOf(ctx->tmpSet[nxt]);
+    Q.target = ctx->tmpTarget.ptr;
+    ctx->denValid = false;  // the strips are being rewritten
+    ctx->tmpValid = false;  // ... and so is the history, until everything is enqueued
+    if (out_ms) RT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    const int he = rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms);
+    if (he != 0) return Fail(RT_ERR_HIP, std::string("rt_denoise_temporal: launch: ") + hipGetErrorString((hipError_t)he));
+    hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3(((uint32_t)npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->den.ptr, ctx->denLdr.ptr, (uint32_t)npix, 1u,
+                       nullptr);
+    RT_HIP(hipGetLastError());
+    if (out_ms) {
+        RT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+        RT_HIP(hipEventSynchronize(ctx->ev[3]));
+        float ms = 0.f;
+        RT_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+        *out_ms = ms;
+    }
+    ctx->denW = W;
+    ctx->denRows = rows;
+    ctx->denValid = true;
+    ctx->tmpCur = nxt;
+    ctx->tmpW = W;
+    ctx->tmpH = ctx->H;
+    ctx->tmpRs = ctx->rs;
+    ctx->tmpCam = Q.cam;
+    ctx->tmpValid = true;
+    return RT_OK;
+}
+
+int rt_temporal_reset(rt_ctx* ctx) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_temporal_reset: null ctx");
+    ctx->tmpValid = false;
+    return RT_OK;
+}
+
+int rt_download_temporal(rt_ctx* ctx, float* state4, uint32_t* len, uint32_t* target) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_download_temporal: null ctx");
+    if (!ctx->tmpValid) return Fail(RT_ERR_SEQUENCE, "rt_download_temporal: the history is empty");
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->tmpW * ctx->tmpRs.num_rows;
+    const rt_ctx::TemporalSet& t = ctx->tmpSet[ctx->tmpCur & 1u];
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    if (state4) RT_HIP(hipMemcpy(state4, t.state.ptr, npix * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    if (len) RT_HIP(hipMemcpy(len, t.len.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (target) RT_HIP(hipMemcpy(target, ctx->tmpTarget.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

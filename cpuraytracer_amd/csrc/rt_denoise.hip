@@ -57,6 +57,71 @@ __device__ __forceinline__ void unpack(const float4 s, const float4 a, const flo
     g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
 }
 
+// The temporal form of the prepare pass (rt_temporal.h): a thread owns pixel pix of the strip, prepares it through the unchanged
+// denoise_prepare, reprojects it into the history's camera, reads the history's pixel there -- one gathered read of a float4 state, two
+// float4 guide planes, an id and a length; neighbouring lanes are neighbouring pixels, so under small motion the gather is a row
+// segment shifted by a few pixels -- validates, blends and writes the blended state, the guides, the id, the length and the target
+// into the NEXT history set.  The current-frame reads and every write are contiguous row segments.  Nothing of the set that is read
+// is written: a pixel reads other pixels' history.  q < npix by temporal_reproject's bounds (xi < W, yi - first_row < num_rows).
+struct TemporalArgs {
+    const float* __restrict__ hdr;
+    const float* __restrict__ sq;
+    const float4* __restrict__ feat;
+    const uint32_t* __restrict__ ids;
+    uint32_t npix, n, m, hasPrev;
+    TemporalGeom G;
+    TemporalCam C, Cp;
+    TemporalParams T;
+    const float4* __restrict__ hS;
+    const float4* __restrict__ hG0;
+    const float4* __restrict__ hG1;
+    const uint32_t* __restrict__ hId;
+    const uint32_t* __restrict__ hLen;
+    float4* __restrict__ oS;
+    float4* __restrict__ oG0;
+    float4* __restrict__ oG1;
+    uint32_t* __restrict__ oId;
+    uint32_t* __restrict__ oLen;
+    uint32_t* __restrict__ target;
+};
+
+__global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const TemporalArgs A) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    const size_t p = pix;
+    const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
+    const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
+    const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
+    const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+    const uint32_t id = A.ids[p];
+    DenoiseState s;
+    float g[8];
+    denoise_prepare(h, q3, A.n, f, A.m, s, g);
+    uint32_t len = 1u, target = kTemporalNoTarget;
+    if (A.hasPrev) {
+        const uint32_t ly = pix / A.G.W, x = pix - ly * A.G.W;
+        uint32_t xi = 0, yi = 0;
+        float dist = 0.f;
+        if (temporal_reproject(A.G, A.C, A.Cp, x, A.G.first_row + ly, g, xi, yi, dist)) {
+            const uint32_t q = (yi - A.G.first_row) * A.G.W + xi;
+            const float4 hs = A.hS[q], ha = A.hG0[q], hb = A.hG1[q];
+            const uint32_t idh = A.hId[q], lenh = A.hLen[q];
+            DenoiseState sh;
+            float gh[8];
+            unpack(hs, ha, hb, sh, gh);
+            const bool ok = temporal_validate(A.T, g, id, dist, gh, idh, lenh);
+            len = temporal_blend(A.T, ok, s, sh, lenh);
+            if (ok) target = q;
+        }
+    }
+    A.oS[p] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
+    A.oG0[p] = make_float4(g[0], g[1], g[2], g[3]);
+    A.oG1[p] = make_float4(g[4], g[5], g[6], g[7]);
+    A.oId[p] = id;
+    A.oLen[p] = len;
+    A.target[p] = target;
+}
+
 // One level.  Thread (tx, ty) of the 32 x 8 workgroup owns pixel (32 bx + tx, 8 by + ty); its 25 taps lie (a - 2) step rows and
 // (b - 2) step columns away, a outer, b inner; a tap outside the strip is skipped, never clamped.
 //   kStaged: the tile and its 2 step halo go into LDS first as three planes of float4 with contiguous rows (a wave stages two rows
@@ -145,17 +210,17 @@ __global__ void __launch_bounds__(256) rt_atrous_kernel(const float4* __restrict
 namespace rtdn {
 
 // The levels over the prepared state and guides of a W x rows picture in image order.
-static int LaunchLevels(hipStream_t st, const Strips& s, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
+// (first: level 0's input -- state[0] itself, or the temporal form's new history, which no level may overwrite)
+static int LaunchLevels(hipStream_t st, const Strips& s, const float4* first, const float4* g0, const float4* g1, const rtd::DenoiseParams& P, int stageKnob,
+                        uint32_t forms[rtd::kDenoiseMaxLevels]) {
     float4* state[2] = {static_cast<float4*>(s.state[0]), static_cast<float4*>(s.state[1])};
-    float4* g0 = static_cast<float4*>(s.guide[0]);
-    float4* g1 = static_cast<float4*>(s.guide[1]);
     hipError_t e = hipSuccess;
     const dim3 grid((s.W + kTileW - 1u) / kTileW, (s.rows + kTileH - 1u) / kTileH);
     for (uint32_t l = 0; l < P.levels; ++l) {
         const uint32_t step = 1u << l;
         const bool staged = Staged(step, stageKnob), last = l + 1u == P.levels;
         const size_t lds = staged ? StageBytes(step) : 0;
-        const float4* in = state[l & 1u];
+        const float4* in = l == 0 ? first : state[l & 1u];
         float4* out = state[(l + 1u) & 1u];
         if (staged && last)
             hipLaunchKernelGGL((rtd::rt_atrous_kernel<true, true>), grid, dim3(256), lds, st, in, g0, g1, s.W, s.rows, step, P, out, s.den, s.denVar);
@@ -180,7 +245,8 @@ int LaunchDenoise(void* stream, const Strips& s, const rtd::DenoiseParams& P, in
                        npix, s.n, s.m, static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]), static_cast<float4*>(s.guide[1]));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    return LaunchLevels(st, s, P, stageKnob, forms);
+    return LaunchLevels(st, s, static_cast<const float4*>(s.state[0]), static_cast<const float4*>(s.guide[0]), static_cast<const float4*>(s.guide[1]), P, stageKnob,
+                        forms);
 }
 
 int LaunchDenoiseShards(void* stream, const Strips& s, const ShardLayout& parts, const rtd::DenoiseParams& P, int stageKnob,
@@ -193,7 +259,43 @@ int LaunchDenoiseShards(void* stream, const Strips& s, const ShardLayout& parts,
                        static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]), static_cast<float4*>(s.guide[1]));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    return LaunchLevels(st, s, P, stageKnob, forms);
+    return LaunchLevels(st, s, static_cast<const float4*>(s.state[0]), static_cast<const float4*>(s.guide[0]), static_cast<const float4*>(s.guide[1]), P, stageKnob,
+                        forms);
+}
+
+int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
+                          uint32_t forms[rtd::kDenoiseMaxLevels]) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t npix = s.W * s.rows;
+    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
+    rtd::TemporalArgs A{};
+    A.hdr = s.hdr;
+    A.sq = s.sq;
+    A.feat = reinterpret_cast<const float4*>(s.feat);
+    A.ids = t.ids;
+    A.npix = npix;
+    A.n = s.n;
+    A.m = s.m;
+    A.hasPrev = t.hasPrev ? 1u : 0u;
+    A.G = t.geom;
+    A.C = t.cam;
+    A.Cp = t.camPrev;
+    A.T = t.params;
+    A.hS = static_cast<const float4*>(t.prev.state);
+    A.hG0 = static_cast<const float4*>(t.prev.guide[0]);
+    A.hG1 = static_cast<const float4*>(t.prev.guide[1]);
+    A.hId = t.prev.ids;
+    A.hLen = t.prev.len;
+    A.oS = static_cast<float4*>(t.next.state);
+    A.oG0 = static_cast<float4*>(t.next.guide[0]);
+    A.oG1 = static_cast<float4*>(t.next.guide[1]);
+    A.oId = t.next.ids;
+    A.oLen = t.next.len;
+    A.target = t.target;
+    hipLaunchKernelGGL(rtd::rt_denoise_prepare_temporal_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, A);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return LaunchLevels(st, s, A.oS, A.oG0, A.oG1, P, stageKnob, forms);
 }
 
 }  // namespace rtdn

@@ -26,6 +26,7 @@ class HipRenderer:
         self.W = self.rows = 0
         self.feature_W = self.feature_rows = 0
         self.denoised_W = self.denoised_rows = 0
+        self.temporal_W = self.temporal_rows = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -224,6 +225,35 @@ class HipRenderer:
         check(self._L.rt_denoise_shards(self._h, C.byref(parts), C.byref(params) if params is not None else None, C.byref(ms) if timed else None))
         self.denoised_W, self.denoised_rows = W, H
         return ms.value if timed else None
+
+    # ---- temporal accumulation (rt_api.h "temporal accumulation")
+    def denoise_temporal(self, params=None, tparams=None, timed=False):
+        """rt_denoise_temporal: denoise() with the previous call's pre-filter state reprojected into the uploaded scene's camera,
+        validated against the guides and blended in before the levels.  The history survives upload() -- a camera move is an upload
+        -- and starts empty after temporal_reset() or when the picture's size or row set changes; on an empty history the result is
+        denoise()'s.  tparams: an RtTemporalParams (_capi.temporal_params(max_history=..., ...)) or None for the defaults; params and
+        timed as in denoise().  download_denoised() serves the result."""
+        ms = C.c_double(0.0)
+        check(self._L.rt_denoise_temporal(self._h, C.byref(params) if params is not None else None,
+                                          C.byref(tparams) if tparams is not None else None, C.byref(ms) if timed else None))
+        self.denoised_W, self.denoised_rows = self.W, self.rows
+        self.temporal_W, self.temporal_rows = self.W, self.rows
+        return ms.value if timed else None
+
+    def temporal_reset(self):
+        """rt_temporal_reset: drop the history; the next denoise_temporal() starts from an empty one."""
+        check(self._L.rt_temporal_reset(self._h))
+
+    def download_temporal(self):
+        """The history as the last denoise_temporal() left it: state (rows, W, 4) float32, the blended (c.rgb, v) that went into level 0;
+        len (rows, W) uint32, the frames blended into it; target (rows, W) uint32, the history pixel each pixel was blended with
+        (local row * W + column; 0xffffffff: rejected)."""
+        rows, W = self.temporal_rows, self.temporal_W
+        state = np.zeros((rows, W, 4), dtype=np.float32)
+        ln = np.zeros((rows, W), dtype=np.uint32)
+        target = np.zeros((rows, W), dtype=np.uint32)
+        check(self._L.rt_download_temporal(self._h, state.ctypes.data, ln.ctypes.data, target.ctypes.data))
+        return {"state": state, "len": ln, "target": target}
 
     def download_denoised(self):
         """The last denoise()'s result: rgb (rows, W, 3) float32, the filtered MEAN colour; var (rows, W) float32, the variance left in

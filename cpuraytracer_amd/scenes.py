@@ -3,6 +3,7 @@
 Returns the rt_api.h records as numpy structured arrays + ctypes structs, ready for HipRenderer.upload.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -51,3 +52,25 @@ def build_scene(name="cover", seed=1, width=1200, height=800, vfov=-1.0, apertur
     if rc != 0:
         raise RuntimeError("rth_build_scene(%r) failed with %d" % (name, rc))
     return Scene(sph[:n.value].copy(), mat[:n.value].copy(), cam, sun, sky, exp.value, name, seed)
+
+
+def orbit_camera(camera, degrees, pivot=(0.0, 0.0, 0.0)):
+    """The camera record turned by `degrees` about the vertical (y) axis through `pivot`: origin and origin_image_plane rotate about the
+    pivot, x and y rotate as vectors; aperture and focal length stay.  A pure function of the record: evaluated in binary64 and rounded
+    once to binary32.  Returns a new RtCamera."""
+    a = float(degrees) * (math.pi / 180.0)
+    c, s = math.cos(a), math.sin(a)  # libm's, as the spheres CLI's OrbitCamera takes them
+    piv = np.asarray(pivot, dtype=np.float64)
+
+    def turn(v):
+        return np.array([c * v[0] + s * v[2], v[1], -s * v[0] + c * v[2]], dtype=np.float64)
+
+    out = _capi.RtCamera.from_buffer_copy(bytes(camera))
+    for name, point in (("origin", True), ("origin_image_plane", True), ("x", False), ("y", False)):
+        src = getattr(camera, name)
+        v = np.array([src[0], src[1], src[2]], dtype=np.float64)
+        r = turn(v - piv) + piv if point else turn(v)
+        dst = getattr(out, name)
+        for k in range(3):
+            dst[k] = np.float32(r[k])
+    return out

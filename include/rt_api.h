@@ -363,6 +363,51 @@ typedef struct rt_shard_parts {
  * outside their domain: RT_ERR_INVALID_ARG.  n < 2 or m == 0: RT_ERR_SEQUENCE.  A refused call keeps the previous snapshot. */
 int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise_params* params, double* out_ms);
 
+/* ----------------------------------------------------------------- temporal accumulation
+ * The temporal half of the denoiser (DESIGN.md "Temporal accumulation"; csrc/rt_temporal.h): the prepare pass's state (c.rgb, v) of the
+ * previous call -- the HISTORY -- is reprojected into the current camera, validated against the guides and blended into this call's
+ * state before the levels run.  Binary32 only, + - * / and comparisons in exactly this order, never fused, correctly rounded division
+ * and square root (sqrt_rn), dot(a, b) = (a0*b0 + a1*b1) + a2*b2.  For pixel (x, y) of the image (y = rs.first_row + local row), with
+ * c, v, g as rt_denoise prepares them, id the feature strips' id, C the current camera, C' the history's, w = C.origin_image_plane -
+ * C.origin (w' likewise), and ch, vh, gh, idh, lenh the history's pixel:
+ *     u = ((float)x + 0.5f) / (float)W;   vv = ((float)y + 0.5f) / (float)H;   nx = 2.f*u - 1.f;   ny = -2.f*vv + 1.f
+ *     d[k] = (w[k] + nx*C.x[k]) + ny*C.y[k];      cov = g[7]
+ *     cov > 0:  z = g[6] / cov;  s = z / sqrt_rn(dot(d,d));  P[k] = C.origin[k] + s*d[k];  q[k] = P[k] - C'.origin[k];
+ *               dist = sqrt_rn(dot(q,q))          else: q = d (the sky is reprojected by its direction)
+ *     zw = dot(q,w') / dot(w',w');                                                       reject unless zw > 0
+ *     px = (dot(q,C'.x) / dot(C'.x,C'.x)) / zw;   py = (dot(q,C'.y) / dot(C'.y,C'.y)) / zw
+ *     fx = ((px + 1.f) * 0.5f) * (float)W;        fy = ((1.f - py) * 0.5f) * (float)H
+ *     reject unless 0 <= fx < W and first_row <= fy < first_row + num_rows;   xi = (uint32)fx;  yi = (uint32)fy
+ * The history's pixel is the one at (xi, yi) -- nearest pixel, no interpolation.  The pixel is accepted when all of these hold:
+ *     lenh >= 1;   id == idh (with use_id);   |cov - gh[7]| <= coverage_tol;   dn = g[3..5] - gh[3..5], dot(dn,dn) <= normal_tol;
+ *     cov > 0:  gh[7] > 0, and with zh = gh[6]/gh[7], dz = dist - zh, zm = max(dist, zh):  dz*dz <= (depth_tol*depth_tol) * (zm*zm)
+ *     cov == 0: gh[7] == 0
+ * Accepted: L = (float)min(lenh, max_history - 1), a = 1.f / (L + 1.f), c'[k] = a*c[k] + (1.f - a)*ch[k],
+ * v' = (a*a)*v + ((1.f - a)*(1.f - a))*vh, len' = min(lenh, max_history - 1) + 1, target = (yi - first_row)*W + xi.
+ * Rejected (a NaN in any test rejects): c' = c, v' = v, len' = 1, target = 0xffffffff.  (c', v') is the input of level 0 and, with g, id
+ * and len', the new history; C becomes the history's camera. */
+typedef struct rt_temporal_params {
+    uint32_t max_history;   /* 1..64, default 2; 1 = never blend                 */
+    uint32_t use_id;        /* default 1                                          */
+    float depth_tol;        /* default 0.1f;  finite, >= 0                        */
+    float normal_tol;       /* default 0.1f;  finite, >= 0                        */
+    float coverage_tol;     /* default 0.25f; finite, >= 0                        */
+} rt_temporal_params;
+int rt_temporal_default_params(rt_temporal_params* out);  /* needs no GPU */
+/* rt_denoise with the temporal step in its prepare pass.  Preconditions, refusals, params, out_ms, RT_DENOISE_STAGE and the snapshot
+ * (rt_download_denoised, rt_copy_denoised_to_device, rt_unit_denoise_forms) are rt_denoise's; tparams == NULL: the defaults, outside
+ * their domain: RT_ERR_INVALID_ARG; so is a picture wider or taller than 2^24.  The current camera is the uploaded scene's.  Changes
+ * none of hdr, sq, feat, the ids or ldr, nor any sequencing state.  The history is state of its own: it survives rt_scene_upload (a
+ * camera move is an upload; keeping object ids stable across uploads is the caller's business, use_id = 0 otherwise), is dropped by
+ * rt_temporal_reset and rt_destroy, and a call whose W, H or row set differ from the history's starts from an empty one -- on an
+ * empty history the call gives rt_denoise's bits.  A refused call keeps history and snapshot.  rt_denoise and rt_denoise_shards
+ * neither read nor change the history. */
+int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, double* out_ms);
+int rt_temporal_reset(rt_ctx* ctx);
+/* The history as the last rt_denoise_temporal left it: state4 = W*rows*4 floats (c'.rgb, v'), len and target = W*rows words each.  Any
+ * pointer may be NULL.  RT_ERR_SEQUENCE while the history is empty. */
+int rt_download_temporal(rt_ctx* ctx, float* state4, uint32_t* len, uint32_t* target);
+
 /* Replaces the transform(par) tonemap (spheres-app.cpp:186-214): hdr / n_samples,
  * ACES fit, gamma 1/2.2, XMStoreColor.  n_samples == 0 uses the accumulated count. */
 int rt_resolve(rt_ctx* ctx, uint32_t n_samples);
@@ -492,7 +537,19 @@ int rt_unit_denoise_host(const float* hdr, const float* sq, uint32_t n, const fl
  * padding rows are never read.  Refusals as rt_denoise_shards'.  Needs no GPU. */
 int rt_unit_denoise_shards_host(const float* hdr, const float* sq, const float* feat8, const rt_shard_parts* shape, const rt_denoise_params* params,
                                 float* out_rgb, float* out_var);
-/* Which form each level of the last rt_denoise or rt_denoise_shards took: out[l] = 0 the level did not run, 1 its taps were read from
+/* One frame step of rt_denoise_temporal plus the levels, from the same sources compiled for the host (csrc/rt_temporal.h,
+ * csrc/rt_denoise.h), over plain arrays and two camera records: hdr, sq, feat8, ids the strip of rows [first_row, first_row + num_rows)
+ * of the W x H image after n and m samples; camera the current record, hist_camera the history's; hist_state4 (4 floats per pixel),
+ * hist_guides8 (8), hist_ids and hist_len the history's strips -- hist_len == NULL is an empty history, and the other four are then not
+ * read.  Out, each where the pointer is not null: out_rgb (3 floats per pixel) and out_var = den and den_var; out_state4, out_guides8,
+ * out_len = the new history (its ids are `ids`, its camera `camera`); out_target.  params, tparams == NULL: the defaults.  Refusals as
+ * rt_unit_denoise_host's and rt_denoise_temporal's.  Needs no context and no GPU. */
+int rt_unit_temporal_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W, uint32_t H,
+                          uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
+                          const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
+                          const rt_temporal_params* tparams, float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len,
+                          uint32_t* out_target);
+/* Which form each level of the last rt_denoise, rt_denoise_shards or rt_denoise_temporal took: out[l] = 0 the level did not run, 1 its taps were read from
  * global memory, 2 from a tile staged in LDS. */
 int rt_unit_denoise_forms(rt_ctx* ctx, uint32_t out[5]);
 /* The shadow index rt_scene_upload would build for light `light` of the list, under the environment of the moment.
