@@ -22,6 +22,7 @@
 #include "host/rt_denoise_launch.h"
 #include "host/rt_launch_plan.h"
 #include "host/rt_scene_prep.h"
+#include "host/rt_sequence.h"
 #include "rt_kernels.h"
 
 using rtprep::EnvU32;
@@ -99,8 +100,11 @@ struct rt_ctx {
     size_t ldsPerBlockMax = 0;
     uint64_t workspaceLimit = 8ull << 30;
 
+    // how rt_render calls are sequenced (host/rt_sequence.h): has-scene, the mode settings, the running accumulation, the pending batch
+    // and the planes traced ahead.  Read freely here; changed only through rtseq's events and step reports.
+    rtseq::State seq;
+
     // scene
-    bool hasScene = false;
     uint32_t n = 0;
     DevBuf<float4> scan, tree, leaf;
     DevBuf<uint32_t> orig;
@@ -121,14 +125,10 @@ struct rt_ctx {
     bool mats16Ok = false;
     rtd::TraceParams base{};  // scene part filled at upload
 
-    // accumulation state
-    uint32_t W = 0, H = 0, rows = 0;
-    rt_rowset rs{};
-    uint32_t accumulated = 0;  // samples accumulated so far (next s0 must be accumulated + 1)
+    // accumulation: the strips of seq's running accumulation
     uint32_t sampler = 0;      // RT_SAMPLER_* flags of the next / running accumulation (rt_set_sampler)
     DevBuf<float> hdr;         // [W*rows*3]
-    bool noise = false;        // rt_set_noise_estimate: the next / running accumulation keeps second moments
-    DevBuf<float> sq;          // [W*rows*3] sums of squared samples, valid with hdr while noise is on (rt_noise.h)
+    DevBuf<float> sq;          // [W*rows*3] sums of squared samples, valid with hdr while seq.noise is on (rt_noise.h)
     DevBuf<float> noiseMap;    // [W*rows*2] output of rt_noise_map
     DevBuf<uint32_t> noiseRed; // [kNoiseMaxThresholds + 1] counts and maximum of rt_noise_summary
     DevBuf<uint8_t> ldr;       // [W*rows*3]
@@ -144,8 +144,8 @@ struct rt_ctx {
     bool featCleared = false;     // rt_clear_features was called: the next rt_render_features may start at any s0
     uint32_t featCount = 0;       // samples per pixel in the strips (0: nothing accumulated)
     uint32_t featNext = 0;        // the s0 that continues the accumulation (the previous call's s1)
-    uint32_t featW = 0, featH = 0, featRows = 0;
-    rt_rowset featRs{};
+    rtseq::PictureKey featPic;    // the picture the strips are of ...
+    uint32_t featRows = 0;        // ... and its local rows
     DevBuf<float> feat;           // [W*rows*8] sums of albedo rgb, normal xyz, depth, coverage
     DevBuf<uint32_t> featIds;     // [W*rows] id of the sample added last
     DevBuf<float2> featJitter, featLens;  // ray-generation tables of the feature pass
@@ -167,8 +167,7 @@ struct rt_ctx {
     };
     bool tmpValid = false;        // set tmpCur holds a history of the picture below, taken with tmpCam
     uint32_t tmpCur = 0;
-    uint32_t tmpW = 0, tmpH = 0;
-    rt_rowset tmpRs{};
+    rtseq::PictureKey tmpPic;
     rtd::TemporalCam tmpCam{};
     TemporalSet tmpSet[2];
     DevBuf<uint32_t> tmpTarget;   // [W*rows] of the last call
@@ -188,8 +187,7 @@ struct rt_ctx {
     bool useTileOrder = true;  // RT_TILE_ORDER=0 keeps the image order
     bool tileKeyValid = false;    // the key below describes what tileOrderValid / skyFlagsValid say there is
     bool tileOrderValid = false;
-    uint32_t tileW = 0, tileH = 0;  // ... and the image and strip they were built for (with the scene and the lists, all they depend on)
-    rt_rowset tileRs{};
+    rtseq::PictureKey tilePic;    // ... and the picture they were built for (with the scene and the lists, all they depend on)
     uint32_t tileListLimit = 0, tileListSpheres = 0;  // the lists' limits the flags were taken under (0, 0: no flags)
     // Empty-list tiles kept out of the trace queue (rt_kernels.h rt_sky_tiles_kernel).  The flags share the order's key and lifetime;
     // with them the order ends with exactly the flagged tiles.  Their number reaches the host through pinned memory and an event that
@@ -209,34 +207,21 @@ struct rt_ctx {
     DevBuf<uint8_t> tileClass;
     // candidate masks of the tiles' primary rays (BuildTileMasks; rt_tile_mask.h): valid for the same (scene, image, strip)
     bool tileMaskValid = false;
-    uint32_t maskW = 0, maskH = 0, maskLimit = 0, maskTiles = 0;
+    rtseq::PictureKey maskPic;
+    uint32_t maskLimit = 0, maskTiles = 0;
     uint32_t maskSpheres = 0;    // sphere-list limit the tables were built with (0: no lists)
     bool skySkip = true;         // RT_SKY_SKIP, read with the knobs above: empty-list tiles are finished without rays (rt_kernels.h kSky)
-    rt_rowset maskRs{};
     DevBuf<uint32_t> tileMasks;  // kTileMaskWords per full tile
     DevBuf<uint16_t> tileSpheres;  // kTileSphereHalfs per full tile (built together with the masks)
     uint64_t freshScans = 0;     // blocks of 64 fresh paths launched by the last rt_render that ran passes (rt_unit_tile_masks)
 
-    // frame pipelining (rt_set_frame_pipelining; rt_params.h): regions of a sample ring, two continuation buffers
-    uint32_t pipeDepth = 0;     // calls a path may be carried across (0 = off)
+    // frame pipelining (rt_set_frame_pipelining; rt_params.h): regions of a sample ring, two continuation buffers (seq.pipeDepth: the
+    // calls a path may be carried across)
     bool pipeOpen = false;      // pipelined calls have been submitted since the last flush
     uint32_t pipeSeq = 0;       // sequence number of the newest region
     uint32_t pipeSppCap = 0, pipeNpix = 0, pipeRing = 0;  // geometry of the ring: samples per region, pixels, regions
     uint32_t pipeInSel = 0;     // which continuation buffer the next trace kernel reads
     uint32_t pipeCommits = 0;   // commit kernels launched since the pipeline started (FrameCtl: which entry is current)
-    // frame batching (rt_set_frame_batch): stats-less rt_render calls wait here until batchFrames sample planes are pending
-    uint32_t batchFrames = 1;
-    bool pendOn = false;
-    uint32_t pendW = 0, pendH = 0, pendS0 = 0, pendS1 = 0, pendDepth = 0;
-    rt_rowset pendRs{};
-    uint64_t pendSeed = 0;
-    // render-ahead (rt_set_frame_lookahead): sample planes [aheadBase, aheadBase + aheadSpp) of the running accumulation sit in the
-    // sample buffer, traced by ONE launch; planes below aheadNext have been added to the strip
-    uint32_t lookahead = 1;
-    bool aheadValid = false;
-    uint32_t aheadW = 0, aheadH = 0, aheadBase = 0, aheadSpp = 0, aheadNext = 0, aheadDepth = 0;
-    rt_rowset aheadRs{};
-    uint64_t aheadSeed = 0;
     uint32_t pipeMaxDepth = 0;  // max_depth and seed of the running pipeline (a flush re-launches with them)
     uint64_t pipeSeed = 0;
     rtd::RegionTable pipeRegions{};
@@ -412,7 +397,7 @@ static uint32_t TileSphereLimitFromEnv() {
     const uint32_t v = EnvU32("RT_PRIMARY_SPHERES", rtd::kTileSphereLimitDefault);
     return v > rtd::kTileSphereMax ? rtd::kTileSphereMax : v;
 }
-static int BuildTileMasks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t npix) {
+static int BuildTileMasks(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t npix) {
     const uint32_t limit = EnvU32("RT_PRIMARY_MASK_LIMIT", rtd::kTileMaskLimitDefault);
     const uint32_t sphLimit = TileSphereLimitFromEnv();
     const uint32_t nFull = npix >> 6;
@@ -423,27 +408,23 @@ static int BuildTileMasks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
         ctx->tileMaskValid = false;
         return RT_OK;
     }
-    if (ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && ctx->maskLimit == limit && ctx->maskSpheres == sphLimit &&
-        std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0)
-        return RT_OK;
+    if (ctx->tileMaskValid && ctx->maskPic == pic && ctx->maskLimit == limit && ctx->maskSpheres == sphLimit) return RT_OK;
     ctx->tileMaskValid = false;
     int rc;
     if ((rc = ctx->tileMasks.Reserve((size_t)nFull * rtd::kTileMaskWords)) != RT_OK) return rc;
     if (sphLimit != 0u && (rc = ctx->tileSpheres.Reserve((size_t)nFull * rtd::kTileSphereHalfs)) != RT_OK) return rc;
     rtd::TraceParams tp = b;
-    tp.W = W;
-    tp.H = H;
-    tp.rs = rs;
+    tp.W = pic.W;
+    tp.H = pic.H;
+    tp.rs = pic.rs;
     hipLaunchKernelGGL(rtd::rt_tile_mask_kernel, dim3((nFull + 3) / 4), dim3(256), 0, ctx->stream, tp, nFull, limit, ctx->tileMasks.ptr,
                        sphLimit, sphLimit != 0u ? ctx->tileSpheres.ptr : nullptr);
     RT_HIP(hipGetLastError());
     ctx->tileMaskValid = true;
-    ctx->maskW = W;
-    ctx->maskH = H;
+    ctx->maskPic = pic;
     ctx->maskLimit = limit;
     ctx->maskSpheres = sphLimit;
     ctx->maskTiles = nFull;
-    ctx->maskRs = rs;
     return RT_OK;
 }
 
@@ -455,7 +436,7 @@ static int BuildTileMasks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
 static void DropTileOrder(rt_ctx* ctx) {
     ctx->tileKeyValid = ctx->tileOrderValid = ctx->skyFlagsValid = false;
     ctx->skyCountPending = ctx->skyCountKnown = false;
-    ctx->aheadValid = false;  // (planes traced ahead by a truncated launch are only complete together with the flags)
+    (void)rtseq::TileTablesDropped(ctx->seq);  // (planes traced ahead go with the flags: nothing beyond the sequencer's own state)
 }
 static void SkyCountPoll(rt_ctx* ctx) {
     if (!ctx->skyCountPending) return;
@@ -470,16 +451,14 @@ static void SkyCountPoll(rt_ctx* ctx) {
         ctx->skyCountPending = false;  // a real error: the count stays unknown, and the error is left for the call that follows to report
     }
 }
-static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t npix) {
+static int BuildTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t npix) {
     // order and flags are a function of the scene (camera included), the image size, the strip and the lists' limits: a new
     // accumulation of the same picture -- a progressive restart, the next frame of a turntable with an unchanged scene -- keeps them
     const uint32_t nFull = npix >> 6;
     const bool lists = ctx->tileMaskValid && ctx->maskSpheres != 0u && nFull != 0u;  // (BuildTileMasks has just run for this picture)
     const bool wantFlags = lists && ctx->skySkip && ctx->skyExclude;
     const uint32_t keyLimit = wantFlags ? ctx->maskLimit : 0u, keySpheres = wantFlags ? ctx->maskSpheres : 0u;
-    if (ctx->tileKeyValid && ctx->tileW == W && ctx->tileH == H && std::memcmp(&ctx->tileRs, &rs, sizeof(rs)) == 0 &&
-        ctx->tileListLimit == keyLimit && ctx->tileListSpheres == keySpheres)
-        return RT_OK;
+    if (ctx->tileKeyValid && ctx->tilePic == pic && ctx->tileListLimit == keyLimit && ctx->tileListSpheres == keySpheres) return RT_OK;
     DropTileOrder(ctx);
     int rc;
     if (wantFlags) {
@@ -500,9 +479,9 @@ static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
         if ((rc = ctx->tileClass.Reserve(nFull)) != RT_OK) return rc;
         if ((rc = ctx->tileOrder.Reserve(nFull)) != RT_OK) return rc;
         rtd::TraceParams tp = ctx->base;
-        tp.W = W;
-        tp.H = H;
-        tp.rs = rs;
+        tp.W = pic.W;
+        tp.H = pic.H;
+        tp.rs = pic.rs;
         tp.s0 = 1;
         tp.sampler = ctx->sampler;
         tp.jitter_tab = nullptr;
@@ -510,7 +489,7 @@ static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
         hipLaunchKernelGGL(rtd::rt_pilot_rays_kernel, dim3((nPilot + 255) / 256), dim3(256), 0, ctx->stream, tp, nFull, ctx->pilotRays.ptr);
         RT_HIP(hipGetLastError());
         if ((rc = LaunchClosest(ctx, ctx->pilotRays.ptr, nPilot, ctx->pilotHits.ptr)) != RT_OK) return rc;
-        hipLaunchKernelGGL(rtd::rt_tile_class_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->pilotHits.ptr, nFull, W,
+        hipLaunchKernelGGL(rtd::rt_tile_class_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->pilotHits.ptr, nFull, pic.W,
                            ctx->matType.ptr, ctx->tileClass.ptr, wantFlags ? ctx->skyFlags.ptr : (const uint8_t*)nullptr);
         hipLaunchKernelGGL(rtd::rt_tile_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->tileClass.ptr, nFull, ctx->tileOrder.ptr);
         RT_HIP(hipGetLastError());
@@ -522,9 +501,7 @@ static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
         }
     }
     ctx->tileKeyValid = true;
-    ctx->tileW = W;
-    ctx->tileH = H;
-    ctx->tileRs = rs;
+    ctx->tilePic = pic;
     ctx->tileListLimit = keyLimit;
     ctx->tileListSpheres = keySpheres;
     return RT_OK;
@@ -535,6 +512,8 @@ static int BuildTileOrder(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
 // continuation buffers used alternately, and three launches per call: preparation + ray-generation tables, the carrying
 // trace kernel, the commit kernel.  Nothing here waits for the device.
 static void PipelineDrop(rt_ctx* ctx) { ctx->pipeOpen = false; }  // carried paths and uncommitted regions are abandoned
+// What an event of the sequencer voided outside its own state (rtseq::kInFlight ...): dropped here, in one place.
+static void DropVoided(rt_ctx* ctx, uint32_t voids);
 static uint32_t PipelineWaves(const rt_ctx* ctx) { return (uint32_t)ctx->cuCount * ctx->blocksPerCu * (ctx->blockThreads / 64); }
 static void PipelineShards(const rt_ctx* ctx, rtd::TraceParams& tp) {
     // measured (tools/progressive_frames.py, 1-spp frames): 128-path blocks x 1 static beat 64 x 2, 128 x 0, 192 x 1, 256 x 0
@@ -551,7 +530,7 @@ static int PipelineTraceAndCommit(rt_ctx* ctx, rtd::TraceParams& tp, uint32_t np
     tp.cont_out_n = ctx->contN[ctx->pipeInSel ^ 1u].ptr;
     tp.carry = carry ? 1u : 0u;
     tp.region_seq = ctx->pipeSeq;
-    tp.max_carry_age = ctx->pipeDepth;
+    tp.max_carry_age = ctx->seq.pipeDepth;
     tp.min_iters = EnvU32("RT_PIPE_MIN_ITERS", 8);
     tp.counters = ctx->counters.ptr;
     int rc = LaunchTrace(ctx, tp, rtplan::Mode::Carry);
@@ -564,7 +543,7 @@ static int PipelineTraceAndCommit(rt_ctx* ctx, rtd::TraceParams& tp, uint32_t np
     return RT_OK;
 }
 
-// Run every carried path to its end and commit every region: afterwards the HDR strip holds ctx->accumulated samples.
+// Run every carried path to its end and commit every region: afterwards the HDR strip holds seq.accumulated samples.
 static int PipelineFlush(rt_ctx* ctx) {
     if (!ctx->pipeOpen) return RT_OK;
     const uint32_t npix = ctx->pipeNpix;
@@ -574,9 +553,9 @@ static int PipelineFlush(rt_ctx* ctx) {
     hipLaunchKernelGGL(rtd::rt_raygen_tables_kernel, dim3(1), dim3(256), 0, ctx->stream, (float2*)nullptr, 0u, 0u, (float2*)nullptr, 0u, 0u,
                        ctx->sampler, ctx->queue.ptr, ctx->ctl.ptr);
     RT_HIP(hipGetLastError());
-    tp.W = ctx->W;
-    tp.H = ctx->H;
-    tp.rs = ctx->rs;
+    tp.W = ctx->seq.pic.W;
+    tp.H = ctx->seq.pic.H;
+    tp.rs = ctx->seq.pic.rs;
     tp.s0 = 1;
     tp.spp_pass = 1;
     tp.npix_local = npix;
@@ -586,7 +565,7 @@ static int PipelineFlush(rt_ctx* ctx) {
     tp.samples = ctx->ring.ptr;
     int rc = PipelineTraceAndCommit(ctx, tp, npix, false);
     ctx->pipeOpen = false;
-    if (rc != RT_OK) ctx->accumulated = 0;
+    if (rc != RT_OK) DropVoided(ctx, rtseq::StepFailed(ctx->seq));
     return rc;
 }
 
@@ -594,7 +573,7 @@ static int PipelineFlush(rt_ctx* ctx) {
 static int PipelineRender(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t npix, uint32_t s0, uint32_t s1, uint32_t max_depth,
                           uint64_t seed) {
     const uint32_t spp = s1 - s0;
-    const uint32_t nRing = ctx->pipeDepth + 2u;
+    const uint32_t nRing = ctx->seq.pipeDepth + 2u;
     int rc;
     if (ctx->pipeOpen && (ctx->pipeNpix != npix || spp > ctx->pipeSppCap || ctx->pipeRing != nRing || ctx->pipeMaxDepth != max_depth ||
                           ctx->pipeSeed != seed)) {
@@ -619,7 +598,7 @@ static int PipelineRender(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
         rtd::FrameCtl init{};
         init.oldest_open = 0xffffffffu;
         init.committed_seq[0] = ctx->pipeSeq;              // everything up to here is in the strip already
-        init.committed_samples[0] = ctx->accumulated;
+        init.committed_samples[0] = ctx->seq.accumulated;
         ctx->pipeCommits = 0;
         RT_HIP(hipMemcpyAsync(ctx->ctl.ptr, &init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
         RT_HIP(hipStreamSynchronize(ctx->stream));       // `init` is a stack object; once per pipeline start
@@ -819,20 +798,29 @@ void rt_destroy(rt_ctx* ctx) {
 
 static int BatchFlush(rt_ctx* ctx);  // frame batching (rt_set_frame_batch), next to rt_render
 
+// Before an event that asks for it (rtseq::kSettle...): render the pending batch (kPending), then finish the frames in flight (kInFlight).
+static int Settle(rt_ctx* ctx, uint32_t what) {
+    int rc = (what & rtseq::kPending) ? BatchFlush(ctx) : RT_OK;
+    if (rc == RT_OK && (what & rtseq::kInFlight)) rc = PipelineFlush(ctx);
+    return rc;
+}
+static void DropVoided(rt_ctx* ctx, uint32_t voids) {
+    if (voids & rtseq::kInFlight) PipelineDrop(ctx);
+    if (voids & rtseq::kTileOrder) DropTileOrder(ctx);
+    if (voids & rtseq::kFeatures) ctx->featCount = 0;
+    if (voids & rtseq::kDenoised) ctx->denValid = false;
+}
+
 int rt_set_stream(rt_ctx* ctx, void* hip_stream) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_set_stream: null ctx");
-    {   // pending frames and frames in flight belong to the old stream: settle them there first
-        RT_HIP(hipSetDevice(ctx->device));
-        const int rcb = BatchFlush(ctx);
-        if (rcb != RT_OK) return rcb;
-        const int rcf = PipelineFlush(ctx);
-        if (rcf != RT_OK) return rcf;
-    }
-    ctx->aheadValid = false;  // (planes traced ahead were produced on the old stream)
-    // (... and so were the order, the flags and the copy of their count, which must not land in the pinned word after a newer one's:
-    // the one place that waits for it, and only when a picture's tables were built and never rendered from again)
+    RT_HIP(hipSetDevice(ctx->device));
+    const int rcs = Settle(ctx, rtseq::kSettleBeforeStream);  // on the old stream
+    if (rcs != RT_OK) return rcs;
+    const uint32_t voids = rtseq::StreamReplaced(ctx->seq);
+    // (the copy of the flags' count must not land in the pinned word after a newer one's: the one place that waits for it, and only
+    // when a picture's tables were built and never rendered from again)
     if (ctx->skyCountPending) RT_HIP(hipEventSynchronize(ctx->skyEv));
-    DropTileOrder(ctx);
+    DropVoided(ctx, voids);
     ctx->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx->ownStream;
     return RT_OK;
 }
@@ -860,7 +848,7 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     if ((field = rtprep::MaterialFault(*sky)) != nullptr) return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_scene_upload", "the sky", *sky, field));
     RT_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = BatchFlush(ctx)) != RT_OK) return rc;  // pending frames were asked of the scene that is being replaced
+    if ((rc = Settle(ctx, rtseq::kSettleBeforeScene)) != RT_OK) return rc;
     rtprep::PrepOptions opt = rtprep::PrepOptions::FromEnv();
     opt.treeTop = ctx->treeTop;  // (fixed at rt_create)
     opt.shadowGrid = ctx->useShadowGrid;
@@ -988,23 +976,18 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     b.focal = camera->focal_length;
     b.exposure = exposure_scale;
     ctx->n = n;
-    ctx->hasScene = true;
-    ctx->aheadValid = false;
-    ctx->accumulated = 0;
     ctx->sky = *sky;
-    ctx->featCount = 0;  // the feature strips belonged to the scene that was replaced
-    ctx->denValid = false;  // ... and so did the denoised picture
-    PipelineDrop(ctx);
+    DropVoided(ctx, rtseq::SceneReplaced(ctx->seq));
     return RT_OK;
 }
 
 int rt_set_frame_pipelining(rt_ctx* ctx, uint32_t depth) {
     if (!ctx || depth > rtd::kMaxFramesInFlight - 2u) return Fail(RT_ERR_INVALID_ARG, "rt_set_frame_pipelining: depth must be 0..14");
     RT_HIP(hipSetDevice(ctx->device));
-    int rc = BatchFlush(ctx);
+    int rc = Settle(ctx, rtseq::kPending);
     if (rc != RT_OK) return rc;
-    rc = PipelineFlush(ctx);
-    ctx->pipeDepth = depth;
+    rc = Settle(ctx, rtseq::kInFlight);  // (failed or not, nothing is in flight any more: the depth is stored)
+    DropVoided(ctx, rtseq::PipeliningSettingChanged(ctx->seq, depth));
     return rc;
 }
 
@@ -1012,7 +995,7 @@ int rt_committed_samples(rt_ctx* ctx, uint32_t* out) {
     if (!ctx || !out) return Fail(RT_ERR_INVALID_ARG, "rt_committed_samples: null argument");
     RT_HIP(hipSetDevice(ctx->device));
     RT_HIP(hipStreamSynchronize(ctx->stream));
-    *out = ctx->accumulated;
+    *out = ctx->seq.accumulated;
     if (ctx->pipeOpen) {
         rtd::FrameCtl c{};
         RT_HIP(hipMemcpy(&c, ctx->ctl.ptr, sizeof(c), hipMemcpyDeviceToHost));
@@ -1023,41 +1006,24 @@ int rt_committed_samples(rt_ctx* ctx, uint32_t* out) {
 
 int rt_set_sampler(rt_ctx* ctx, uint32_t flags) {
     if (!ctx || (flags & ~(RT_SAMPLER_COSINE_HEMISPHERE | RT_SAMPLER_SQRT_DISK)) != 0u) return Fail(RT_ERR_INVALID_ARG, "rt_set_sampler: unknown flag");
-    if (flags != ctx->sampler) {
-        ctx->pendOn = false;   // (pending frames of the old mapping are dropped with the accumulation they belonged to)
-        ctx->accumulated = 0;  // samples of two mappings do not mix: the next rt_render starts over
-        PipelineDrop(ctx);
-        DropTileOrder(ctx);  // the pilot rays use the lens mapping
-        ctx->featCount = 0;           // ... and so do the feature pass's primary rays
-    }
+    if (flags != ctx->sampler) DropVoided(ctx, rtseq::SamplerChanged(ctx->seq));
     ctx->sampler = flags;
     return RT_OK;
 }
 
 int rt_set_noise_estimate(rt_ctx* ctx, int on) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_set_noise_estimate: null ctx");
-    const bool want = on != 0;
-    if (want != ctx->noise) {
-        ctx->pendOn = false;   // as rt_set_sampler: pending frames go with the accumulation they belonged to
-        ctx->aheadValid = false;
-        ctx->accumulated = 0;  // a strip of moments cannot start in the middle: the next rt_render starts over
-        PipelineDrop(ctx);
-    }
-    ctx->noise = want;
+    DropVoided(ctx, rtseq::NoiseToggled(ctx->seq, on != 0));
     return RT_OK;
 }
 
 int rt_clear(rt_ctx* ctx) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_clear: null ctx");
-    ctx->pendOn = false;
-    ctx->aheadValid = false;
-    PipelineDrop(ctx);
-    ctx->accumulated = 0;
+    DropVoided(ctx, rtseq::Cleared(ctx->seq));
     return RT_OK;
 }
 
-static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t s0, uint32_t s1, uint32_t max_depth, uint64_t seed,
-                     rt_stats* out_stats, uint32_t aheadEnd = 0);
+static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, uint32_t aheadEnd = 0);
 
 // The ordered accumulation of the planes [first, first + count) of the sample buffer: with rt_set_noise_estimate on, the kernel that
 // also adds their squares to the strip of second moments (same hdr bits); off, the plain one.
@@ -1066,13 +1032,13 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
 static void LaunchAccumulate(rt_ctx* ctx, uint32_t npix, uint32_t spp, uint32_t first, uint32_t count) {
     if (ctx->skyFlagsValid) {
         const float* skyC = reinterpret_cast<const float*>(ctx->skyInfo.ptr + 1);  // (the constant sample follows the count)
-        if (ctx->noise)
+        if (ctx->seq.noise)
             hipLaunchKernelGGL(rtd::rt_accumulate_moments_tiles_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr,
                                ctx->hdr.ptr, ctx->sq.ptr, npix, spp, first, count, ctx->skyFlags.ptr, skyC);
         else
             hipLaunchKernelGGL(rtd::rt_accumulate_tiles_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr,
                                ctx->hdr.ptr, npix, spp, first, count, ctx->skyFlags.ptr, skyC);
-    } else if (ctx->noise)
+    } else if (ctx->seq.noise)
         hipLaunchKernelGGL(rtd::rt_accumulate_moments_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr, ctx->hdr.ptr,
                            ctx->sq.ptr, npix, spp, first, count);
     else
@@ -1082,159 +1048,126 @@ static void LaunchAccumulate(rt_ctx* ctx, uint32_t npix, uint32_t spp, uint32_t 
 
 // Frame batching: render the pending sample planes with ONE launch (no statistics, nothing waits for the device).
 static int BatchFlush(rt_ctx* ctx) {
-    if (!ctx->pendOn) return RT_OK;
-    ctx->pendOn = false;
-    return RenderNow(ctx, ctx->pendW, ctx->pendH, ctx->pendRs, ctx->pendS0, ctx->pendS1, ctx->pendDepth, ctx->pendSeed, nullptr);
+    if (!ctx->seq.pend.on) return RT_OK;
+    return RenderNow(ctx, rtseq::PendingTaken(ctx->seq), nullptr);
 }
 
-// The readers (rt_resolve, rt_download, rt_copy_to_device) hand out the COMMITTED strip while a batch that continues it is
-// pending.  A pending batch that does not continue it -- nothing is committed yet, or its first call had s0 == 1 and so starts a
-// new accumulation, possibly of another size: the caller's picture is the new one, and ctx->W / ctx->rows still describe the old
-// strip -- is rendered first.
-static bool PendingMustRender(const rt_ctx* ctx) { return ctx->pendOn && (ctx->accumulated == 0 || ctx->pendS0 == 1u); }
+// The readers (rtseq::PendingMustRender has the rule): nothing committed yet, or the pending frames START a new accumulation -- they
+// are what there is to show, and seq.pic / seq.rows still describe the old strip.
+static int RenderPendingForReader(rt_ctx* ctx) { return rtseq::PendingMustRender(ctx->seq) ? BatchFlush(ctx) : RT_OK; }
 
 int rt_set_frame_batch(rt_ctx* ctx, uint32_t frames) {
     if (!ctx || frames == 0 || frames > 4096) return Fail(RT_ERR_INVALID_ARG, "rt_set_frame_batch: frames must be 1..4096");
     RT_HIP(hipSetDevice(ctx->device));
-    const int rc = BatchFlush(ctx);
-    ctx->batchFrames = frames;
+    const int rc = Settle(ctx, rtseq::kSettleBeforeBatchSetting);  // (failed or not, nothing is pending any more: the size is stored)
+    DropVoided(ctx, rtseq::BatchSettingChanged(ctx->seq, frames));
     return rc;
 }
 
 int rt_set_frame_lookahead(rt_ctx* ctx, uint32_t frames) {
     if (!ctx || frames == 0 || frames > 4096) return Fail(RT_ERR_INVALID_ARG, "rt_set_frame_lookahead: frames must be 1..4096");
-    ctx->lookahead = frames;
-    ctx->aheadValid = false;
+    DropVoided(ctx, rtseq::LookaheadSettingChanged(ctx->seq, frames));
     return RT_OK;
 }
 
+// What the call does is the sequencer's to say (rtseq::PlanRender: plain, batched, render-ahead; pipelining is decided in RenderNow,
+// where the launch plan is at hand); here its steps are carried out in order.
 int rt_render(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t s0, uint32_t s1, uint32_t max_depth, uint64_t seed,
               rt_stats* out_stats) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_render: null ctx");
-    if (ctx->lookahead > 1 && ctx->batchFrames <= 1 && ctx->pipeDepth == 0 && out_stats == nullptr && ctx->hasScene && W != 0 && H != 0 && s0 != 0 && s1 > s0) {
-        // render-ahead: the planes of this call may have been traced by an earlier call's launch -- then they are only ADDED
-        // (in sample order, as always); else this call's launch traces its own planes and the next `lookahead` ones with them
-        if (ctx->aheadValid && ctx->aheadW == W && ctx->aheadH == H && std::memcmp(&ctx->aheadRs, &rs, sizeof(rs)) == 0 && ctx->aheadDepth == max_depth &&
-            ctx->aheadSeed == seed && s0 == ctx->aheadNext && s1 <= ctx->aheadBase + ctx->aheadSpp && ctx->accumulated + 1 == s0) {
-            RT_HIP(hipSetDevice(ctx->device));
-            const uint32_t npix = ctx->W * ctx->rows;
-            LaunchAccumulate(ctx, npix, ctx->aheadSpp, s0 - ctx->aheadBase, s1 - s0);
-            RT_HIP(hipGetLastError());
-            ctx->aheadNext = s1;
-            ctx->accumulated += s1 - s0;
-            return RT_OK;
+    rtseq::Call call;
+    call.pic = {W, H, rs};
+    call.rows = rtprep::RowsetRowsWithin(rs, H);
+    call.s0 = s0, call.s1 = s1, call.max_depth = max_depth, call.seed = seed;
+    call.wants_stats = out_stats != nullptr;
+    const rtseq::Steps steps = rtseq::PlanRender(ctx->seq, call);
+    for (uint32_t k = 0; k < steps.n; ++k) {
+        const rtseq::Step& step = steps.v[k];
+        int rc = RT_OK;
+        switch (step.kind) {
+            case rtseq::StepKind::AddAhead:  // the planes were traced by an earlier call's launch: one small kernel
+                RT_HIP(hipSetDevice(ctx->device));
+                LaunchAccumulate(ctx, ctx->seq.pic.W * ctx->seq.rows, ctx->seq.ahead.spp, step.first, step.count);
+                RT_HIP(hipGetLastError());
+                rtseq::AheadAdded(ctx->seq, step);
+                break;
+            case rtseq::StepKind::Record: rtseq::Recorded(ctx->seq, call); break;
+            case rtseq::StepKind::RenderPending: rc = BatchFlush(ctx); break;
+            case rtseq::StepKind::RenderNow: rc = RenderNow(ctx, call, out_stats, step.aheadEnd); break;
+            case rtseq::StepKind::Refuse:
+                rtseq::RenderBegins(ctx->seq);
+                rc = Fail(step.refusal.status, step.refusal.message);
+                break;
         }
-        const uint32_t want = s1 - s0 > ctx->lookahead ? s1 - s0 : ctx->lookahead;
-        return RenderNow(ctx, W, H, rs, s0, s1, max_depth, seed, nullptr, s0 + want);
+        if (rc != RT_OK) return rc;
     }
-    if (ctx->batchFrames > 1 && out_stats == nullptr && ctx->pipeDepth == 0 && ctx->hasScene && W != 0 && H != 0 && s0 != 0 && s1 > s0) {
-        // a pending batch this call does not continue is rendered first, as the calls were made
-        if (ctx->pendOn && !(ctx->pendW == W && ctx->pendH == H && std::memcmp(&ctx->pendRs, &rs, sizeof(rs)) == 0 && ctx->pendDepth == max_depth &&
-                             ctx->pendSeed == seed && ctx->pendS1 == s0)) {
-            const int rcf = BatchFlush(ctx);
-            if (rcf != RT_OK) return rcf;
-        }
-        if (!ctx->pendOn) {
-            // only a call that RenderNow would accept as the start or the continuation of an accumulation is deferred
-            const uint32_t rows = rtprep::RowsetRowsWithin(rs, H);
-            const bool sameStrip = ctx->W == W && ctx->H == H && ctx->rows == rows && std::memcmp(&ctx->rs, &rs, sizeof(rs)) == 0;
-            const bool starts = s0 == 1, continues = ctx->accumulated != 0 && sameStrip && s0 == ctx->accumulated + 1;
-            if (rows != 0 && (starts || continues)) {
-                ctx->pendOn = true;
-                ctx->pendW = W; ctx->pendH = H; ctx->pendRs = rs; ctx->pendS0 = s0; ctx->pendDepth = max_depth; ctx->pendSeed = seed;
-            }
-        }
-        if (ctx->pendOn) {
-            ctx->pendS1 = s1;
-            if (ctx->pendS1 - ctx->pendS0 >= ctx->batchFrames) return BatchFlush(ctx);
-            return RT_OK;
-        }
-    }
-    const int rcb = BatchFlush(ctx);  // a call with statistics (or one that cannot be deferred) settles the pending batch first
-    if (rcb != RT_OK) return rcb;
-    return RenderNow(ctx, W, H, rs, s0, s1, max_depth, seed, out_stats);
+    return RT_OK;
 }
 
 // aheadEnd (render-ahead, rt_set_frame_lookahead): trace the planes [s0, aheadEnd) with this call's ONE launch, add only [s0, s1)
-// to the strip and keep the rest in the sample buffer for the calls that continue (0: trace [s0, s1) only).
-static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t s0, uint32_t s1, uint32_t max_depth, uint64_t seed,
-                     rt_stats* out_stats, uint32_t aheadEnd) {
-    ctx->aheadValid = false;  // whatever was traced ahead belongs to the calls before this one
-    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_render: no scene uploaded");
-    if (W == 0 || H == 0 || s0 == 0 || s1 <= s0) return Fail(RT_ERR_INVALID_ARG, "rt_render: empty image or sample range");
-    const uint32_t rows = rtprep::RowsetRowsWithin(rs, H);
-    if (rows == 0) return Fail(RT_ERR_INVALID_ARG, "rt_render: bad row set");
-    const uint64_t npix64 = (uint64_t)W * rows;
-    if (npix64 > (1ull << 31) || (uint64_t)W * H > 0xffffffffull) return Fail(RT_ERR_INVALID_ARG, "rt_render: image too large");
+// to the strip and keep the rest in the sample buffer for the calls that continue (0: trace [s0, s1) only).  The sequencer admits
+// the call and cuts it into passes; the tables, the launches, the events and the statistics are here.
+static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, uint32_t aheadEnd) {
+    rtseq::State& seq = ctx->seq;
+    rtseq::RenderBegins(seq);
+    const rtseq::Refusal bad = rtseq::CheckCall(seq, call);
+    if (bad.status != RT_OK) return Fail(bad.status, bad.message);
+    const uint32_t W = call.pic.W, H = call.pic.H, rows = call.rows, s0 = call.s0, s1 = call.s1, max_depth = call.max_depth;
+    const rt_rowset rs = call.pic.rs;
+    const uint64_t seed = call.seed;
     RT_HIP(hipSetDevice(ctx->device));
-    const uint32_t npix = (uint32_t)npix64;
+    const uint32_t npix = W * rows;
     SkyCountPoll(ctx);  // (before any table is rebuilt: the call that builds the flags never sees their number, whatever the timing)
 
-    const bool sameStrip = ctx->W == W && ctx->H == H && ctx->rows == rows && std::memcmp(&ctx->rs, &rs, sizeof(rs)) == 0;
-    // frame pipelining: only calls that ask for no statistics may leave work in flight; anything else first settles it
-    // (the carrying kernel's commit adds no second moments: with rt_set_noise_estimate on every call renders unpipelined)
-    bool pipelined = ctx->pipeDepth > 0 && out_stats == nullptr && !ctx->noise;
-    if (pipelined) {
-        pipelined = rtplan::PlanTrace(ShapeOf(ctx->base), SettingsOf(ctx), KnobsFromEnv(), {npix, ctx->base.max_depth, rtplan::Mode::Carry}).pipelines &&
-                    (uint64_t)npix * (s1 - s0) * (ctx->pipeDepth + 2u) < (1ull << 31);
-    }
-    if (s0 == 1 || ctx->accumulated == 0) PipelineDrop(ctx);  // a new accumulation abandons whatever was in flight
-    else if (!pipelined) {
+    const bool pipelined = rtseq::MayPipeline(seq, call) &&
+                           rtplan::PlanTrace(ShapeOf(ctx->base), SettingsOf(ctx), KnobsFromEnv(), {npix, ctx->base.max_depth, rtplan::Mode::Carry}).pipelines;
+    const uint32_t abandoned = rtseq::AccumulationStarting(seq, call);
+    DropVoided(ctx, abandoned);
+    if (!abandoned && !pipelined) {  // anything but a pipelined call first settles what is in flight
         int rcf = PipelineFlush(ctx);
         if (rcf != RT_OK) return rcf;
     }
-    if (s0 == 1 || ctx->accumulated == 0) {
-        if (s0 != 1) return Fail(RT_ERR_SEQUENCE, "rt_render: first call of an accumulation must start at s0 == 1");
-        int rc;
-        if ((rc = ctx->hdr.Reserve((size_t)npix * 3)) != RT_OK) return rc;
-        if ((rc = ctx->ldr.Reserve((size_t)npix * 3)) != RT_OK) return rc;
-        RT_HIP(hipMemsetAsync(ctx->hdr.ptr, 0, (size_t)npix * 3 * sizeof(float), ctx->stream));  // app.cpp:112-119
-        if (ctx->noise) {
-            if ((rc = ctx->sq.Reserve((size_t)npix * 3)) != RT_OK) return rc;
-            RT_HIP(hipMemsetAsync(ctx->sq.ptr, 0, (size_t)npix * 3 * sizeof(float), ctx->stream));
+    rtseq::Refusal why;
+    switch (rtseq::Admit(seq, call, &why)) {
+        case rtseq::Admission::Refused: return Fail(why.status, why.message);
+        case rtseq::Admission::Continues: break;
+        case rtseq::Admission::Starts: {
+            int rc;
+            if ((rc = ctx->hdr.Reserve((size_t)npix * 3)) != RT_OK) return rc;
+            if ((rc = ctx->ldr.Reserve((size_t)npix * 3)) != RT_OK) return rc;
+            RT_HIP(hipMemsetAsync(ctx->hdr.ptr, 0, (size_t)npix * 3 * sizeof(float), ctx->stream));  // app.cpp:112-119
+            if (seq.noise) {
+                if ((rc = ctx->sq.Reserve((size_t)npix * 3)) != RT_OK) return rc;
+                RT_HIP(hipMemsetAsync(ctx->sq.ptr, 0, (size_t)npix * 3 * sizeof(float), ctx->stream));
+            }
+            rtseq::AccumulationStarted(seq, call);
+            ctx->skySkip = EnvU32("RT_SKY_SKIP", 1u) != 0u;  // (no mask table depends on it; the unit entries that rebuild tables leave it alone)
+            ctx->skyExclude = EnvU32("RT_SKY_EXCLUDE", 1u) != 0u;
+            if ((rc = BuildTileMasks(ctx, call.pic, npix)) != RT_OK) return rc;
+            if ((rc = BuildTileOrder(ctx, call.pic, npix)) != RT_OK) return rc;  // (after the masks: it flags the tiles whose list is empty)
         }
-        ctx->W = W;
-        ctx->H = H;
-        ctx->rows = rows;
-        ctx->rs = rs;
-        ctx->accumulated = 0;
-        ctx->skySkip = EnvU32("RT_SKY_SKIP", 1u) != 0u;  // (no mask table depends on it; the unit entries that rebuild tables leave it alone)
-        ctx->skyExclude = EnvU32("RT_SKY_EXCLUDE", 1u) != 0u;
-        if ((rc = BuildTileMasks(ctx, W, H, rs, npix)) != RT_OK) return rc;
-        if ((rc = BuildTileOrder(ctx, W, H, rs, npix)) != RT_OK) return rc;  // (after the masks: it flags the tiles whose list is empty)
-    } else if (!sameStrip || s0 != ctx->accumulated + 1) {
-        return Fail(RT_ERR_SEQUENCE, "rt_render: sample range or row set does not continue the accumulation");
     }
 
     if (pipelined) {
         ctx->skyExcluded = 0;  // (the carrying kernel's launch queues every tile)
         int rcp = PipelineRender(ctx, W, H, rs, npix, s0, s1, max_depth, seed);
         if (rcp != RT_OK) {
-            ctx->accumulated = 0;
-            PipelineDrop(ctx);
+            DropVoided(ctx, rtseq::StepFailed(seq));
             return rcp;
         }
-        ctx->accumulated += s1 - s0;
+        rtseq::Rendered(seq, call, 0, 0);
         return RT_OK;
     }
 
-    // split [s0, s1) into passes whose sample buffer fits the workspace limit
-    const uint64_t bytesPerSpp = (uint64_t)npix * 12;
-    uint64_t sppMax = ctx->workspaceLimit / bytesPerSpp;
-    const uint64_t sppPathCap = ((1ull << 31) - 1) / npix;  // total_paths stays below 2^31
-    if (sppMax > sppPathCap) sppMax = sppPathCap;
-    if (sppMax == 0) return Fail(RT_ERR_OUT_OF_MEMORY, "rt_render: workspace limit below one sample per pixel");
-    const uint32_t sppTotal = s1 - s0;
-    if (aheadEnd <= s1 || (uint64_t)(aheadEnd - s0) > sppMax || pipelined) aheadEnd = 0;  // the planes traced ahead must share one pass
-    const uint32_t sppTrace = aheadEnd ? aheadEnd - s0 : sppTotal;
-    uint32_t sppPass = (uint32_t)(sppMax < sppTrace ? sppMax : sppTrace);
+    // [s0, s1) in passes whose sample buffer fits the workspace limit
+    rtseq::PassSplit split = rtseq::SplitPasses(npix, s0, s1, aheadEnd, ctx->workspaceLimit);
+    if (split.refused.status != RT_OK) return Fail(split.refused.status, split.refused.message);
     int rc;
     // The default limit is a snapshot of the free memory at rt_create; another context or the caller's allocator may have
     // taken memory since.  A smaller sample buffer only means more passes (bit-identical: the accumulation stays sequential
-    // in s), so halve the pass until the buffer fits before giving up.
-    while ((rc = ctx->samples.Reserve((size_t)npix * sppPass * 3)) != RT_OK) {
-        if (rc != RT_ERR_OUT_OF_MEMORY || sppPass == 1u) return rc;
-        sppPass = (sppPass + 1u) / 2u;
+    // in s), so shrink the pass until the buffer fits before giving up.
+    while ((rc = ctx->samples.Reserve((size_t)npix * split.sppPass * 3)) != RT_OK) {
+        if (rc != RT_ERR_OUT_OF_MEMORY || !rtseq::ShrinkPass(split)) return rc;
     }
 
     // Passes run back to back on the stream: trace(k) -> accumulate(k) -> trace(k+1) are ordered by the stream itself
@@ -1244,20 +1177,21 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
     auto runPasses = [&]() -> int {
         int rc;
         ctx->freshScans = 0;
-        const uint32_t sEnd = aheadEnd ? aheadEnd : s1;
         // Empty-list tiles stay out of the queue when their number had arrived when this call began (never waited for), they are the order's tail, the
         // kernel would finish them without rays anyway (sky_skip below) and no partial tile follows the full ones in path-index
         // space.  Their share of the counters is added behind each launch; their samples are the accumulation's constant (LaunchAccumulate).
         const uint32_t nFull = npix >> 6;
-        const bool listsHere = ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0 && ctx->maskSpheres != 0u;
+        // (the tables must be the ones of THIS accumulation's picture: rt_unit_tile_masks may have rebuilt them for another since)
+        const bool masksHere = ctx->tileMaskValid && ctx->maskPic == call.pic;
+        const bool listsHere = masksHere && ctx->maskSpheres != 0u;
         const uint32_t nSky = (ctx->skyFlagsValid && ctx->skyCountKnown && ctx->tileOrderValid && listsHere && ctx->skySkip && (npix & 63u) == 0u &&
                                ctx->skyEmpty < nFull)
                                   ? ctx->skyEmpty
                                   : 0u;
         RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 6 * sizeof(unsigned long long), ctx->stream));
         ctx->skyExcluded = nSky;
-        for (uint32_t s = s0; s < sEnd; s += sppPass) {
-            const uint32_t spp = (sEnd - s) < sppPass ? (sEnd - s) : sppPass;
+        for (rtseq::Pass pass = rtseq::FirstPass(split); pass.spp != 0; pass = rtseq::NextPass(split, pass)) {
+            const uint32_t s = pass.s, spp = pass.spp;
             rtd::TraceParams tp = ctx->base;
             tp.W = W;
             tp.H = H;
@@ -1271,10 +1205,9 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
             tp.seed = seed;
             tp.path_list = nullptr;
             tp.tile_order = ctx->tileOrderValid ? ctx->tileOrder.ptr : nullptr;
-            // (the table must be the one of THIS accumulation's picture: rt_unit_tile_masks may have rebuilt it for another since)
-            tp.tile_masks = (ctx->tileMaskValid && ctx->maskW == W && ctx->maskH == H && std::memcmp(&ctx->maskRs, &rs, sizeof(rs)) == 0) ? ctx->tileMasks.ptr : nullptr;
-            tp.tile_spheres = (tp.tile_masks != nullptr && ctx->maskSpheres != 0u) ? ctx->tileSpheres.ptr : nullptr;
-            tp.sky_skip = (tp.tile_spheres != nullptr && ctx->skySkip) ? 1u : 0u;
+            tp.tile_masks = masksHere ? ctx->tileMasks.ptr : nullptr;
+            tp.tile_spheres = listsHere ? ctx->tileSpheres.ptr : nullptr;
+            tp.sky_skip = (listsHere && ctx->skySkip) ? 1u : 0u;
             ctx->freshScans += ((uint64_t)tp.total_paths + 63u) / 64u;  // (all tiles: the statistics do not know about the shorter queue)
             if (nSky != 0u) tp.total_paths = (nFull - nSky) * 64u * spp;
             tp.samples = ctx->samples.ptr;
@@ -1309,7 +1242,7 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
                 RT_HIP(hipGetLastError());
             }
             RT_HIP(hipEventRecord(ev[1], ctx->stream));
-            LaunchAccumulate(ctx, npix, spp, 0u, aheadEnd ? sppTotal : spp);
+            LaunchAccumulate(ctx, npix, spp, pass.add_first, pass.add_count);
             RT_HIP(hipGetLastError());
             RT_HIP(hipEventRecord(ev[2], ctx->stream));
             ++passes;
@@ -1317,16 +1250,11 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
         return RT_OK;
     };
     if ((rc = runPasses()) != RT_OK) {
-        // some passes may already have been added to hdr: the accumulation is void, the next call must restart at s0 == 1
-        ctx->accumulated = 0;
+        DropVoided(ctx, rtseq::StepFailed(seq));  // some passes may already have been added to hdr
         return rc;
     }
-    ctx->accumulated += sppTotal;
-    if (aheadEnd && ctx->samples.ptr && passes == 1) {  // the planes [s1, aheadEnd) wait in the sample buffer
-        ctx->aheadValid = true;
-        ctx->aheadW = W; ctx->aheadH = H; ctx->aheadRs = rs; ctx->aheadDepth = max_depth; ctx->aheadSeed = seed;
-        ctx->aheadBase = s0; ctx->aheadSpp = sppTrace; ctx->aheadNext = s1;
-    }
+    rtseq::Rendered(seq, call, split.aheadEnd, split.sppTrace);
+    const uint32_t sppTotal = s1 - s0;
 
     if (out_stats) {
         // Without a stats request the call stays asynchronous on the stream (progressive 1-spp frames are launch bound:
@@ -1357,14 +1285,11 @@ static int RenderNow(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t
 
 int rt_resolve(rt_ctx* ctx, uint32_t n_samples) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_resolve: null ctx");
-    if (PendingMustRender(ctx)) {  // nothing committed yet, or the pending frames START a new accumulation: they are what there is to show
-        const int rcb = BatchFlush(ctx);
-        if (rcb != RT_OK) return rcb;
-    }
-    if (ctx->accumulated == 0) return Fail(RT_ERR_SEQUENCE, "rt_resolve: nothing accumulated");
+    if (const int rcb = RenderPendingForReader(ctx)) return rcb;
+    if (ctx->seq.accumulated == 0) return Fail(RT_ERR_SEQUENCE, "rt_resolve: nothing accumulated");
     RT_HIP(hipSetDevice(ctx->device));
-    const uint32_t n = n_samples ? n_samples : ctx->accumulated;
-    const uint32_t npix = ctx->W * ctx->rows;
+    const uint32_t n = n_samples ? n_samples : ctx->seq.accumulated;
+    const uint32_t npix = ctx->seq.pic.W * ctx->seq.rows;
     RT_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
     // with frames in flight the strip holds FrameCtl::committed_samples samples, a number only the device knows
     const uint32_t* devCount = (ctx->pipeOpen && n_samples == 0) ? &ctx->ctl.ptr->committed_samples[ctx->pipeCommits & 1u] : nullptr;
@@ -1383,13 +1308,10 @@ double rt_last_resolve_ms(rt_ctx* ctx) { return ctx ? ctx->lastResolveMs : 0.0; 
 
 int rt_download(rt_ctx* ctx, float* hdr_rgb, uint8_t* ldr_rgb) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_download: null ctx");
-    if (PendingMustRender(ctx)) {
-        const int rcb = BatchFlush(ctx);
-        if (rcb != RT_OK) return rcb;
-    }
-    if (ctx->accumulated == 0) return Fail(RT_ERR_SEQUENCE, "rt_download: nothing rendered");
+    if (const int rcb = RenderPendingForReader(ctx)) return rcb;
+    if (ctx->seq.accumulated == 0) return Fail(RT_ERR_SEQUENCE, "rt_download: nothing rendered");
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->W * ctx->rows;
+    const size_t npix = (size_t)ctx->seq.pic.W * ctx->seq.rows;
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (hdr_rgb) RT_HIP(hipMemcpy(hdr_rgb, ctx->hdr.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (ldr_rgb) RT_HIP(hipMemcpy(ldr_rgb, ctx->ldr.ptr, npix * 3, hipMemcpyDeviceToHost));
@@ -1398,13 +1320,10 @@ int rt_download(rt_ctx* ctx, float* hdr_rgb, uint8_t* ldr_rgb) {
 
 int rt_copy_to_device(rt_ctx* ctx, void* dev_hdr_rgb, void* dev_ldr_rgb) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_copy_to_device: null ctx");
-    if (PendingMustRender(ctx)) {
-        const int rcb = BatchFlush(ctx);
-        if (rcb != RT_OK) return rcb;
-    }
-    if (ctx->accumulated == 0) return Fail(RT_ERR_SEQUENCE, "rt_copy_to_device: nothing rendered");
+    if (const int rcb = RenderPendingForReader(ctx)) return rcb;
+    if (ctx->seq.accumulated == 0) return Fail(RT_ERR_SEQUENCE, "rt_copy_to_device: nothing rendered");
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->W * ctx->rows;
+    const size_t npix = (size_t)ctx->seq.pic.W * ctx->seq.rows;
     if (dev_hdr_rgb) RT_HIP(hipMemcpyAsync(dev_hdr_rgb, ctx->hdr.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     if (dev_ldr_rgb) RT_HIP(hipMemcpyAsync(dev_ldr_rgb, ctx->ldr.ptr, npix * 3, hipMemcpyDeviceToDevice, ctx->stream));
     return RT_OK;
@@ -1414,13 +1333,10 @@ int rt_copy_to_device(rt_ctx* ctx, void* dev_hdr_rgb, void* dev_ldr_rgb) {
 // Like the other readers: a pending batch that starts the picture is rendered first; planes traced ahead never reached the strips.
 static int NoiseReady(rt_ctx* ctx, const char* who, uint32_t minSamples) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
-    if (!ctx->noise) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": rt_set_noise_estimate is off");
-    if (PendingMustRender(ctx)) {
-        const int rcb = BatchFlush(ctx);
-        if (rcb != RT_OK) return rcb;
-    }
-    if (ctx->accumulated == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": nothing accumulated");
-    if (ctx->accumulated < minSamples) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the estimate needs at least 2 samples per pixel");
+    if (!ctx->seq.noise) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": rt_set_noise_estimate is off");
+    if (const int rcb = RenderPendingForReader(ctx)) return rcb;
+    if (ctx->seq.accumulated == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": nothing accumulated");
+    if (ctx->seq.accumulated < minSamples) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the estimate needs at least 2 samples per pixel");
     RT_HIP(hipSetDevice(ctx->device));
     return RT_OK;
 }
@@ -1430,7 +1346,7 @@ int rt_download_moments(rt_ctx* ctx, float* sq_rgb) {
     if (rc != RT_OK) return rc;
     if (!sq_rgb) return Fail(RT_ERR_INVALID_ARG, "rt_download_moments: null buffer");
     RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(sq_rgb, ctx->sq.ptr, (size_t)ctx->W * ctx->rows * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(sq_rgb, ctx->sq.ptr, (size_t)ctx->seq.pic.W * ctx->seq.rows * 3 * sizeof(float), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -1438,7 +1354,7 @@ int rt_copy_moments_to_device(rt_ctx* ctx, void* dev_sq) {
     const int rc = NoiseReady(ctx, "rt_copy_moments_to_device", 1);
     if (rc != RT_OK) return rc;
     if (!dev_sq) return Fail(RT_ERR_INVALID_ARG, "rt_copy_moments_to_device: null buffer");
-    RT_HIP(hipMemcpyAsync(dev_sq, ctx->sq.ptr, (size_t)ctx->W * ctx->rows * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    RT_HIP(hipMemcpyAsync(dev_sq, ctx->sq.ptr, (size_t)ctx->seq.pic.W * ctx->seq.rows * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     return RT_OK;
 }
 
@@ -1446,9 +1362,9 @@ int rt_noise_map(rt_ctx* ctx, float floor, float* out_abs_rel) {
     int rc = NoiseReady(ctx, "rt_noise_map", 2);
     if (rc != RT_OK) return rc;
     if (!out_abs_rel) return Fail(RT_ERR_INVALID_ARG, "rt_noise_map: null buffer");
-    const uint32_t npix = ctx->W * ctx->rows;
+    const uint32_t npix = ctx->seq.pic.W * ctx->seq.rows;
     if ((rc = ctx->noiseMap.Reserve((size_t)npix * 2)) != RT_OK) return rc;
-    hipLaunchKernelGGL(rtd::rt_noise_map_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->hdr.ptr, ctx->sq.ptr, npix, ctx->accumulated,
+    hipLaunchKernelGGL(rtd::rt_noise_map_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->hdr.ptr, ctx->sq.ptr, npix, ctx->seq.accumulated,
                        floor, reinterpret_cast<float2*>(ctx->noiseMap.ptr));
     RT_HIP(hipGetLastError());
     RT_HIP(hipStreamSynchronize(ctx->stream));
@@ -1461,14 +1377,14 @@ int rt_noise_summary(rt_ctx* ctx, float floor, const float* thresholds, uint32_t
     if (rc != RT_OK) return rc;
     if (n_thr > rtd::kNoiseMaxThresholds || (n_thr != 0 && (!thresholds || !out_counts)))
         return Fail(RT_ERR_INVALID_ARG, "rt_noise_summary: at most 8 thresholds, with their buffers");
-    const uint32_t npix = ctx->W * ctx->rows;
+    const uint32_t npix = ctx->seq.pic.W * ctx->seq.rows;
     rtd::NoiseThresholds thr{};
     thr.n = n_thr;
     for (uint32_t k = 0; k < n_thr; ++k) thr.t[k] = thresholds[k];
     if ((rc = ctx->noiseRed.Reserve(rtd::kNoiseMaxThresholds + 1)) != RT_OK) return rc;
     RT_HIP(hipMemsetAsync(ctx->noiseRed.ptr, 0, (rtd::kNoiseMaxThresholds + 1) * sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL(rtd::rt_noise_summary_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->hdr.ptr, ctx->sq.ptr, npix,
-                       ctx->accumulated, floor, thr, ctx->noiseRed.ptr);
+                       ctx->seq.accumulated, floor, thr, ctx->noiseRed.ptr);
     RT_HIP(hipGetLastError());
     RT_HIP(hipStreamSynchronize(ctx->stream));
     uint32_t red[rtd::kNoiseMaxThresholds + 1];
@@ -1484,7 +1400,7 @@ int rt_noise_summary(rt_ctx* ctx, float floor, const float* thresholds, uint32_t
 int rt_render_features(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t s0, uint32_t s1, double* out_ms) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_render_features: null ctx");
     if (W == 0 || H == 0 || s0 == 0 || s1 <= s0) return Fail(RT_ERR_INVALID_ARG, "rt_render_features: empty image or sample range");
-    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_render_features: no scene uploaded");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_render_features: no scene uploaded");
     const uint32_t rows = rtprep::RowsetRowsWithin(rs, H);
     if (rows == 0) return Fail(RT_ERR_INVALID_ARG, "rt_render_features: bad row set");
     const uint64_t npix64 = (uint64_t)W * rows;
@@ -1493,8 +1409,8 @@ int rt_render_features(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
     if ((uint64_t)s1 + W + H > 0xffffffffull) return Fail(RT_ERR_INVALID_ARG, "rt_render_features: sample range too large");
     RT_HIP(hipSetDevice(ctx->device));
     const uint32_t npix = (uint32_t)npix64;
-    const bool sameStrip = ctx->featW == W && ctx->featH == H && ctx->featRows == rows && std::memcmp(&ctx->featRs, &rs, sizeof(rs)) == 0;
-    const bool continues = ctx->featCount != 0 && sameStrip && s0 == ctx->featNext;
+    const rtseq::PictureKey pic{W, H, rs};
+    const bool continues = ctx->featCount != 0 && ctx->featPic == pic && s0 == ctx->featNext;
     // (a call that starts at 1 always starts over; one that could continue does; after rt_clear_features any s0 starts)
     const bool starts = s0 == 1 || (ctx->featCleared && !continues);
     if (!starts && !continues) return Fail(RT_ERR_SEQUENCE, "rt_render_features: sample range or row set does not continue the accumulation");
@@ -1504,10 +1420,8 @@ int rt_render_features(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
         ctx->featCount = 0;
         if ((rc = ctx->feat.Reserve((size_t)npix * rtd::kFeatureChannels)) != RT_OK) return rc;
         if ((rc = ctx->featIds.Reserve(npix)) != RT_OK) return rc;
-        ctx->featW = W;
-        ctx->featH = H;
+        ctx->featPic = pic;
         ctx->featRows = rows;
-        ctx->featRs = rs;
     }
     const uint32_t spp = s1 - s0;
     const uint32_t k0 = s0 + rs.first_row;
@@ -1573,7 +1487,7 @@ int rt_download_features(rt_ctx* ctx, float* feat8, uint32_t* ids) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_download_features: null ctx");
     if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_download_features: nothing accumulated");
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->featW * ctx->featRows;
+    const size_t npix = (size_t)ctx->featPic.W * ctx->featRows;
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (feat8) RT_HIP(hipMemcpy(feat8, ctx->feat.ptr, npix * rtd::kFeatureChannels * sizeof(float), hipMemcpyDeviceToHost));
     if (ids) RT_HIP(hipMemcpy(ids, ctx->featIds.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1584,7 +1498,7 @@ int rt_copy_features_to_device(rt_ctx* ctx, void* dev_feat8, void* dev_ids) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_copy_features_to_device: null ctx");
     if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_copy_features_to_device: nothing accumulated");
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->featW * ctx->featRows;
+    const size_t npix = (size_t)ctx->featPic.W * ctx->featRows;
     if (dev_feat8) RT_HIP(hipMemcpyAsync(dev_feat8, ctx->feat.ptr, npix * rtd::kFeatureChannels * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     if (dev_ids) RT_HIP(hipMemcpyAsync(dev_ids, ctx->featIds.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     return RT_OK;
@@ -1598,49 +1512,68 @@ int rt_clear_features(rt_ctx* ctx) {
 }
 
 // ---------------------------------------------------------------- denoise (rt_denoise.h; kernels and launcher: rt_denoise.hip)
-// A reader of hdr, sq and feat that writes strips of its own: no sequencing state of rt_render or rt_render_features changes.
-int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms) {
-    int rc = NoiseReady(ctx, "rt_denoise", 2);
+// Readers of hdr, sq and feat that write strips of their own: no sequencing state of rt_render or rt_render_features changes.  The
+// three entries share what follows and differ in where their inputs come from and in the rtdn::Launch* they call; their messages
+// carry their own name in front, and every refusal comes before the first change of state.
+static int DenoiseParamsReady(rt_ctx* ctx, const char* who, const rt_denoise_params* params, rtd::DenoiseParams* P) {
+    const int rc = NoiseReady(ctx, who, 2);
     if (rc != RT_OK) return rc;
     rt_denoise_params def;
     rt_denoise_default_params(&def);
     if (!params) params = &def;
-    const rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
-    if (!rtd::denoise_params_ok(P))
-        return Fail(RT_ERR_INVALID_ARG, "rt_denoise: levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
-    if (ctx->rs.nshards != 1)
-        return Fail(RT_ERR_INVALID_ARG, "rt_denoise: the local rows of a cyclic row set (nshards != 1) are not neighbours in the image");
-    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_denoise: no feature strips (rt_render_features)");
-    if (ctx->featW != ctx->W || ctx->featH != ctx->H || ctx->featRows != ctx->rows || std::memcmp(&ctx->featRs, &ctx->rs, sizeof(rt_rowset)) != 0)
-        return Fail(RT_ERR_SEQUENCE, "rt_denoise: the feature strips are of another image or row set than the picture");
-    const uint32_t W = ctx->W, rows = ctx->rows;
-    if ((rows + rtdn::kTileH - 1u) / rtdn::kTileH > 65535u) return Fail(RT_ERR_INVALID_ARG, "rt_denoise: more than 524,280 rows");
+    *P = rtd::DenoiseParams{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
+    if (!rtd::denoise_params_ok(*P))
+        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    return RT_OK;
+}
+// "The picture is ready for the filter": the context's accumulation is a row range with feature strips of the same picture.
+static int DenoisePictureReady(const rt_ctx* ctx, const char* who) {
+    if (ctx->seq.pic.rs.nshards != 1)
+        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": the local rows of a cyclic row set (nshards != 1) are not neighbours in the image");
+    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": no feature strips (rt_render_features)");
+    if (ctx->featPic != ctx->seq.pic) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the feature strips are of another image or row set than the picture");
+    if ((ctx->seq.rows + rtdn::kTileH - 1u) / rtdn::kTileH > 65535u) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": more than 524,280 rows");
+    return RT_OK;
+}
+// "Reserve and describe the strips" of a W x rows picture: the filter's own (guides: the guide strips too; the temporal step has its
+// history's), and the RT_DENOISE_STAGE knob.  The inputs are the caller's to fill.
+static int DenoiseStrips(rt_ctx* ctx, uint32_t W, uint32_t rows, bool guides, rtdn::Strips* S, int* knob) {
     const size_t npix = (size_t)W * rows;
+    int rc;
     for (int k = 0; k < 2; ++k)
-        if ((rc = ctx->denState[k].Reserve(npix * 4)) != RT_OK || (rc = ctx->denGuide[k].Reserve(npix * 4)) != RT_OK) return rc;
+        if ((rc = ctx->denState[k].Reserve(npix * 4)) != RT_OK || (guides && (rc = ctx->denGuide[k].Reserve(npix * 4)) != RT_OK)) return rc;
     if ((rc = ctx->den.Reserve(npix * 3)) != RT_OK || (rc = ctx->denVar.Reserve(npix)) != RT_OK || (rc = ctx->denLdr.Reserve(npix * 3)) != RT_OK) return rc;
-    int knob = -1;
-    if (const char* e = std::getenv("RT_DENOISE_STAGE")) knob = std::atoi(e) != 0 ? 1 : 0;
-    rtdn::Strips S{};
-    S.hdr = ctx->hdr.ptr;
-    S.sq = ctx->sq.ptr;
-    S.feat = ctx->feat.ptr;
-    S.n = ctx->accumulated;
-    S.m = ctx->featCount;
-    S.W = W;
-    S.rows = rows;
+    *knob = -1;
+    if (const char* e = std::getenv("RT_DENOISE_STAGE")) *knob = std::atoi(e) != 0 ? 1 : 0;
+    *S = rtdn::Strips{};
+    S->W = W;
+    S->rows = rows;
     for (int k = 0; k < 2; ++k) {
-        S.state[k] = ctx->denState[k].ptr;
-        S.guide[k] = ctx->denGuide[k].ptr;
+        S->state[k] = ctx->denState[k].ptr;
+        if (guides) S->guide[k] = ctx->denGuide[k].ptr;
     }
-    S.den = ctx->den.ptr;
-    S.denVar = ctx->denVar.ptr;
+    S->den = ctx->den.ptr;
+    S->denVar = ctx->denVar.ptr;
+    return RT_OK;
+}
+static void DenoiseInputsOfPicture(const rt_ctx* ctx, rtdn::Strips* S) {
+    S->hdr = ctx->hdr.ptr;
+    S->sq = ctx->sq.ptr;
+    S->feat = ctx->feat.ptr;
+    S->n = ctx->seq.accumulated;
+    S->m = ctx->featCount;
+}
+// "Time, launch the resolve, publish", on either side of the entry's own launch (launched: what it returned, a hipError_t as int).
+static int DenoiseBegin(rt_ctx* ctx, double* out_ms) {
     ctx->denValid = false;  // the strips are being rewritten
     if (out_ms) RT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-    const int he = rtdn::LaunchDenoise(ctx->stream, S, P, knob, ctx->denForms);
-    if (he != 0) return Fail(RT_ERR_HIP, std::string("rt_denoise: launch: ") + hipGetErrorString((hipError_t)he));
-    hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3(((uint32_t)npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->den.ptr, ctx->denLdr.ptr, (uint32_t)npix, 1u,
-                       nullptr);
+    return RT_OK;
+}
+static int DenoiseFinish(rt_ctx* ctx, const char* who, const rtdn::Strips& S, int launched, double* out_ms) {
+    const uint32_t npix = S.W * S.rows;
+    const int he = launched;
+    if (he != 0) return Fail(RT_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString((hipError_t)he));
+    hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->den.ptr, ctx->denLdr.ptr, npix, 1u, nullptr);
     RT_HIP(hipGetLastError());
     if (out_ms) {
         RT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
@@ -1649,10 +1582,22 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms) {
         RT_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
         *out_ms = ms;
     }
-    ctx->denW = W;
-    ctx->denRows = rows;
+    ctx->denW = S.W;
+    ctx->denRows = S.rows;
     ctx->denValid = true;
     return RT_OK;
+}
+
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms) {
+    rtd::DenoiseParams P{};
+    int rc = DenoiseParamsReady(ctx, "rt_denoise", params, &P);
+    if (rc != RT_OK || (rc = DenoisePictureReady(ctx, "rt_denoise")) != RT_OK) return rc;
+    rtdn::Strips S{};
+    int knob;
+    if ((rc = DenoiseStrips(ctx, ctx->seq.pic.W, ctx->seq.rows, true, &S, &knob)) != RT_OK) return rc;
+    DenoiseInputsOfPicture(ctx, &S);
+    if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
+    return DenoiseFinish(ctx, "rt_denoise", S, rtdn::LaunchDenoise(ctx->stream, S, P, knob, ctx->denForms), out_ms);
 }
 
 // The same filter over the gathered parts of a row-sharded picture: only the denoiser's own strips of the context are touched.
@@ -1662,95 +1607,45 @@ int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise
     int rc = rtdn::CheckShardParts("rt_denoise_shards", parts, params, true, &P);
     if (rc != RT_OK) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    const uint32_t W = parts->W, rows = parts->rs.num_rows;
-    const size_t npix = (size_t)W * rows;
-    for (int k = 0; k < 2; ++k)
-        if ((rc = ctx->denState[k].Reserve(npix * 4)) != RT_OK || (rc = ctx->denGuide[k].Reserve(npix * 4)) != RT_OK) return rc;
-    if ((rc = ctx->den.Reserve(npix * 3)) != RT_OK || (rc = ctx->denVar.Reserve(npix)) != RT_OK || (rc = ctx->denLdr.Reserve(npix * 3)) != RT_OK) return rc;
-    int knob = -1;
-    if (const char* e = std::getenv("RT_DENOISE_STAGE")) knob = std::atoi(e) != 0 ? 1 : 0;
     rtdn::Strips S{};
+    int knob;
+    if ((rc = DenoiseStrips(ctx, parts->W, parts->rs.num_rows, true, &S, &knob)) != RT_OK) return rc;
     S.hdr = static_cast<const float*>(parts->hdr);
     S.sq = static_cast<const float*>(parts->sq);
     S.feat = static_cast<const float*>(parts->feat);
     S.n = parts->n;
     S.m = parts->m;
-    S.W = W;
-    S.rows = rows;
-    for (int k = 0; k < 2; ++k) {
-        S.state[k] = ctx->denState[k].ptr;
-        S.guide[k] = ctx->denGuide[k].ptr;
-    }
-    S.den = ctx->den.ptr;
-    S.denVar = ctx->denVar.ptr;
     const rtdn::ShardLayout layout{parts->rows_max, parts->rs.block_rows, parts->rs.nshards};
-    ctx->denValid = false;  // the strips are being rewritten
-    if (out_ms) RT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-    const int he = rtdn::LaunchDenoiseShards(ctx->stream, S, layout, P, knob, ctx->denForms);
-    if (he != 0) return Fail(RT_ERR_HIP, std::string("rt_denoise_shards: launch: ") + hipGetErrorString((hipError_t)he));
-    hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3(((uint32_t)npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->den.ptr, ctx->denLdr.ptr, (uint32_t)npix, 1u,
-                       nullptr);
-    RT_HIP(hipGetLastError());
-    if (out_ms) {
-        RT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-        RT_HIP(hipEventSynchronize(ctx->ev[3]));
-        float ms = 0.f;
-        RT_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-        *out_ms = ms;
-    }
-    ctx->denW = W;
-    ctx->denRows = rows;
-    ctx->denValid = true;
-    return RT_OK;
+    if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
+    return DenoiseFinish(ctx, "rt_denoise_shards", S, rtdn::LaunchDenoiseShards(ctx->stream, S, layout, P, knob, ctx->denForms), out_ms);
 }
 
 // rt_denoise with the temporal step in its prepare pass (rt_temporal.h).  The history is the context's: set tmpCur is read, the other
 // set is written and becomes tmpCur once everything is enqueued.  Every refusal comes before the first change.
 int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, double* out_ms) {
-    int rc = NoiseReady(ctx, "rt_denoise_temporal", 2);
+    rtd::DenoiseParams P{};
+    int rc = DenoiseParamsReady(ctx, "rt_denoise_temporal", params, &P);
     if (rc != RT_OK) return rc;
-    rt_denoise_params def;
-    rt_denoise_default_params(&def);
-    if (!params) params = &def;
-    const rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
-    if (!rtd::denoise_params_ok(P))
-        return Fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
     rtd::TemporalParams T{};
     if ((rc = rtdn::CheckTemporalParams("rt_denoise_temporal", tparams, &T)) != RT_OK) return rc;
-    if (ctx->rs.nshards != 1)
-        return Fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: the local rows of a cyclic row set (nshards != 1) are not neighbours in the image");
-    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_denoise_temporal: no feature strips (rt_render_features)");
-    if (ctx->featW != ctx->W || ctx->featH != ctx->H || ctx->featRows != ctx->rows || std::memcmp(&ctx->featRs, &ctx->rs, sizeof(rt_rowset)) != 0)
-        return Fail(RT_ERR_SEQUENCE, "rt_denoise_temporal: the feature strips are of another image or row set than the picture");
-    const uint32_t W = ctx->W, rows = ctx->rows;
-    if ((rows + rtdn::kTileH - 1u) / rtdn::kTileH > 65535u) return Fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: more than 524,280 rows");
-    const rtd::TemporalGeom G{W, ctx->H, ctx->rs.first_row, rows};
-    if (!rtd::temporal_geom_ok(G) || rows != ctx->rs.num_rows)
+    if ((rc = DenoisePictureReady(ctx, "rt_denoise_temporal")) != RT_OK) return rc;
+    const rtseq::PictureKey& pic = ctx->seq.pic;
+    const uint32_t W = pic.W, rows = ctx->seq.rows;
+    const rtd::TemporalGeom G{W, pic.H, pic.rs.first_row, rows};
+    if (!rtd::temporal_geom_ok(G) || rows != pic.rs.num_rows)
         return Fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: a picture wider or taller than 2^24, or a strip that is not its row range");
     const size_t npix = (size_t)W * rows;
-    const bool hasPrev = ctx->tmpValid && ctx->tmpW == W && ctx->tmpH == ctx->H && std::memcmp(&ctx->tmpRs, &ctx->rs, sizeof(rt_rowset)) == 0;
+    const bool hasPrev = ctx->tmpValid && ctx->tmpPic == pic;
     if (!hasPrev) ctx->tmpValid = false;  // (a Reserve below may let the old sets go: they were of another picture)
     for (auto& t : ctx->tmpSet)
         if ((rc = t.state.Reserve(npix * 4)) != RT_OK || (rc = t.guide[0].Reserve(npix * 4)) != RT_OK || (rc = t.guide[1].Reserve(npix * 4)) != RT_OK ||
             (rc = t.ids.Reserve(npix)) != RT_OK || (rc = t.len.Reserve(npix)) != RT_OK)
             return rc;
     if ((rc = ctx->tmpTarget.Reserve(npix)) != RT_OK) return rc;
-    for (int k = 0; k < 2; ++k)
-        if ((rc = ctx->denState[k].Reserve(npix * 4)) != RT_OK) return rc;
-    if ((rc = ctx->den.Reserve(npix * 3)) != RT_OK || (rc = ctx->denVar.Reserve(npix)) != RT_OK || (rc = ctx->denLdr.Reserve(npix * 3)) != RT_OK) return rc;
-    int knob = -1;
-    if (const char* e = std::getenv("RT_DENOISE_STAGE")) knob = std::atoi(e) != 0 ? 1 : 0;
     rtdn::Strips S{};
-    S.hdr = ctx->hdr.ptr;
-    S.sq = ctx->sq.ptr;
-    S.feat = ctx->feat.ptr;
-    S.n = ctx->accumulated;
-    S.m = ctx->featCount;
-    S.W = W;
-    S.rows = rows;
-    for (int k = 0; k < 2; ++k) S.state[k] = ctx->denState[k].ptr;
-    S.den = ctx->den.ptr;
-    S.denVar = ctx->denVar.ptr;
+    int knob;
+    if ((rc = DenoiseStrips(ctx, W, rows, false, &S, &knob)) != RT_OK) return rc;
+    DenoiseInputsOfPicture(ctx, &S);
     const rtd::TraceParams& b = ctx->base;
     rtdn::Temporal Q{};
     Q.ids = ctx->featIds.ptr;
@@ -1764,28 +1659,11 @@ int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_t
     Q.prev = setOf(ctx->tmpSet[cur]);
     Q.next = setOf(ctx->tmpSet[nxt]);
     Q.target = ctx->tmpTarget.ptr;
-    ctx->denValid = false;  // the strips are being rewritten
-    ctx->tmpValid = false;  // ... and so is the history, until everything is enqueued
-    if (out_ms) RT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-    const int he = rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms);
-    if (he != 0) return Fail(RT_ERR_HIP, std::string("rt_denoise_temporal: launch: ") + hipGetErrorString((hipError_t)he));
-    hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3(((uint32_t)npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->den.ptr, ctx->denLdr.ptr, (uint32_t)npix, 1u,
-                       nullptr);
-    RT_HIP(hipGetLastError());
-    if (out_ms) {
-        RT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-        RT_HIP(hipEventSynchronize(ctx->ev[3]));
-        float ms = 0.f;
-        RT_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-        *out_ms = ms;
-    }
-    ctx->denW = W;
-    ctx->denRows = rows;
-    ctx->denValid = true;
+    ctx->tmpValid = false;  // the history is being rewritten, until everything is enqueued
+    if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
+    if ((rc = DenoiseFinish(ctx, "rt_denoise_temporal", S, rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms), out_ms)) != RT_OK) return rc;
     ctx->tmpCur = nxt;
-    ctx->tmpW = W;
-    ctx->tmpH = ctx->H;
-    ctx->tmpRs = ctx->rs;
+    ctx->tmpPic = pic;
     ctx->tmpCam = Q.cam;
     ctx->tmpValid = true;
     return RT_OK;
@@ -1801,7 +1679,7 @@ int rt_download_temporal(rt_ctx* ctx, float* state4, uint32_t* len, uint32_t* ta
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_download_temporal: null ctx");
     if (!ctx->tmpValid) return Fail(RT_ERR_SEQUENCE, "rt_download_temporal: the history is empty");
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->tmpW * ctx->tmpRs.num_rows;
+    const size_t npix = (size_t)ctx->tmpPic.W * ctx->tmpPic.rs.num_rows;
     const rt_ctx::TemporalSet& t = ctx->tmpSet[ctx->tmpCur & 1u];
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (state4) RT_HIP(hipMemcpy(state4, t.state.ptr, npix * 4 * sizeof(float), hipMemcpyDeviceToHost));
@@ -1887,7 +1765,7 @@ int rt_unit_math(rt_ctx* ctx, uint32_t op, const float* x, const float* y, uint3
 
 int rt_unit_primary_rays(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ijs, uint32_t n, float* out_rays) {
     if (!ctx || !ijs || !out_rays || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_primary_rays: invalid argument");
-    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_primary_rays: no scene uploaded");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_primary_rays: no scene uploaded");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     TmpDev<uint32_t> dIjs;
@@ -1908,7 +1786,7 @@ int rt_unit_primary_rays(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ij
 
 int rt_unit_closest_hit(rt_ctx* ctx, const float* rays, uint32_t n, float* out_hits) {
     if (!ctx || !rays || !out_hits) return Fail(RT_ERR_INVALID_ARG, "rt_unit_closest_hit: invalid argument");
-    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_closest_hit: no scene uploaded");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_closest_hit: no scene uploaded");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     TmpDev<float> dRays, dOut;
@@ -1928,7 +1806,7 @@ int rt_unit_closest_hit(rt_ctx* ctx, const float* rays, uint32_t n, float* out_h
 int rt_unit_trace(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ijs, uint32_t n, uint32_t max_depth, uint64_t seed,
                   float* out_rgb, uint32_t* out_traversals) {
     if (!ctx || !ijs || !out_rgb || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_trace: invalid argument");
-    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_trace: no scene uploaded");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_trace: no scene uploaded");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     TmpDev<uint32_t> dIjs, dTrav;
@@ -2149,7 +2027,7 @@ int rt_unit_shadow_query_host(const rt_sphere* spheres, uint32_t n, const rt_lig
 
 int rt_unit_shadow(rt_ctx* ctx, uint32_t light, const float* points, uint32_t n, uint32_t glob_in_lds, uint8_t* out) {
     if (!ctx || !points || !out) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow: invalid argument");
-    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_shadow: no scene uploaded");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_shadow: no scene uploaded");
     if (light >= std::max(1u, ctx->base.n_lights)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow: the scene has no such light");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
@@ -2169,12 +2047,12 @@ int rt_unit_shadow(rt_ctx* ctx, uint32_t light, const float* points, uint32_t n,
 int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t cap_tiles, uint32_t* n_tiles, uint32_t* words,
                        uint32_t cap_spheres, uint32_t* group_of_sphere, uint64_t scans[2]) {
     if (!ctx || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: invalid argument");
-    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_tile_masks: no scene uploaded");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_tile_masks: no scene uploaded");
     const uint32_t rows = rtprep::UnitStripRows(rs, W, H);
     if (rows == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: bad row set");
     RT_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = BuildTileMasks(ctx, W, H, rs, W * rows)) != RT_OK) return rc;
+    if ((rc = BuildTileMasks(ctx, rtseq::PictureKey{W, H, rs}, W * rows)) != RT_OK) return rc;
     *n_tiles = ctx->tileMaskValid ? ctx->maskTiles : 0u;
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (words && *n_tiles != 0u) {
@@ -2198,12 +2076,12 @@ int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
 
 int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t cap_tiles, uint32_t* n_tiles, uint16_t* lists, uint64_t scans[3]) {
     if (!ctx || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres: invalid argument");
-    if (!ctx->hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_tile_spheres: no scene uploaded");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_tile_spheres: no scene uploaded");
     const uint32_t rows = rtprep::UnitStripRows(rs, W, H);
     if (rows == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres: bad row set");
     RT_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = BuildTileMasks(ctx, W, H, rs, W * rows)) != RT_OK) return rc;
+    if ((rc = BuildTileMasks(ctx, rtseq::PictureKey{W, H, rs}, W * rows)) != RT_OK) return rc;
     *n_tiles = (ctx->tileMaskValid && ctx->maskSpheres != 0u) ? ctx->maskTiles : 0u;
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (lists && *n_tiles != 0u) {

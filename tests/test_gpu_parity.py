@@ -899,6 +899,63 @@ def test_readers_render_a_pending_batch_that_starts_a_new_picture(hip, scenes_mo
         one.close()
 
 
+@pytest.mark.parametrize("W,H", [(64, 32), (72, 30)])  # whole 64-pixel tiles; a partial last tile
+def test_switching_progressive_modes_mid_accumulation_keeps_the_one_shot_strip(scenes_mod, W, H):
+    """One accumulation through every way rt_render sequences its calls, switched while it runs: a batch of 3, a lookahead of 4, a call
+    with statistics, pipelining at depth 2, then the workspace limit at its 1 MiB minimum and calls of 100 samples that need several
+    passes.  After every reader the HDR strip equals, bit for bit, the one-shot render of the same sample count on a second context,
+    and rt_committed_samples is the count the contract of rt_api.h gives.  Public entries only."""
+    from cpuraytracer_amd import HipRenderer
+    sc = scenes_mod.build_scene("three", 1, W, H)
+    ctx, one = HipRenderer(0), HipRenderer(0)
+    depth, seed = 8, 1
+
+    def frame(s, stats=False):
+        return ctx.render(W, H, s, s + 1, depth, seed, stats=stats)
+
+    def read(n, what):
+        assert ctx.committed_samples() == n, what
+        ctx.resolve()
+        hdr = ctx.download(ldr=False)[0]
+        one.render(W, H, 1, 1 + n, depth, seed)
+        assert_same(hdr, one.download(ldr=False)[0], "%s: the strip after %d samples" % (what, n))
+
+    try:
+        ctx.upload(sc)
+        one.upload(sc)
+        ctx.set_frame_batch(3)
+        for s in (1, 2, 3, 4):
+            frame(s)
+        read(3, "batch of 3, one call pending")       # the reader hands out the committed strip and leaves the call pending
+        ctx.set_frame_batch(1)                         # ... which the setter renders
+        ctx.set_frame_lookahead(4)
+        frame(5)                                       # traces planes 5..8, adds plane 5
+        read(5, "lookahead of 4, first call")
+        frame(6)                                       # only adds
+        read(6, "lookahead of 4, second call")
+        st = frame(7, stats=True)                      # a launch of its own; what was traced ahead is dropped
+        assert st.samples == W * H and st.passes == 1
+        read(7, "call with statistics")
+        ctx.set_frame_lookahead(1)
+        ctx.set_frame_pipelining(2)
+        for s in (8, 9, 10):
+            frame(s)
+        c = ctx.committed_samples()
+        assert 7 <= c <= 10                            # up to 2 of the newest calls' planes are in flight (and the last commit with them)
+        read(c, "pipelining at depth 2, mid-stream")
+        ctx.set_frame_pipelining(0)                    # settles what is in flight
+        read(10, "pipelining switched off")
+        ctx.set_workspace_limit(1 << 20)               # 40 (72x30) or 42 (64x32) sample planes
+        ctx.render(W, H, 11, 111, depth, seed, stats=False)
+        read(110, "100 samples under a 1 MiB workspace")
+        st = ctx.render(W, H, 111, 211, depth, seed)
+        assert st.passes > 1 and st.samples == 100 * W * H
+        read(210, "the same again, with statistics")
+    finally:
+        ctx.close()
+        one.close()
+
+
 # ------------------------------------------------------------------ the scene's LIST of lights (material.cpp:4-13)
 def _far_camera(oracle, aspect):
     """A camera high above the scene looking at the horizon: most floor hits lie hundreds of units out, beyond every footprint
