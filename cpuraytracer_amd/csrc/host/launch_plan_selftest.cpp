@@ -11,6 +11,7 @@
 // Exit status 0 only when all hold.  `make launch_plan_selftest_san` builds the same program under AddressSanitizer + UBSan.
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 
 #include "rt_launch_plan.h"
 
@@ -89,6 +90,15 @@ int main() {
         Check(FindScanVariant(U.kernel) >= 0, "the unit kernels' scan is not instantiated", c);
         Check(U.tree_in_lds == 0 || U.kernel.kScan == 2, "tree_in_lds without the hierarchy scan (unit kernels)", c);
         const TracePlan P = PlanTrace(S, C, K, A);
+        {
+            // the launcher's account (rt_unit_last_trace_launch): the case it packs reads back as itself -- PlanPacked on those words
+            // answers with the words of this very plan, refusals included
+            uint32_t in[kCaseWords], viaCase[kPlanWords], direct[kPlanWords];
+            PackCase(S, C, K, A, in);
+            PackPlan(P, U, direct);
+            Check(PlanPacked(in, viaCase) == 0 && std::memcmp(viaCase, direct, sizeof(direct)) == 0, "PlanPacked(PackCase(...)) is not PackPlan(PlanTrace(...))", c);
+            Check(P.status != 0 || direct[25] == KernelWord(P.kernel), "word [25] is not the plan's kernel", c);
+        }
         if (P.status != 0) {
             Check(P.refusal != Refusal::None && P.message != nullptr, "a refusal without its text", c);
             Check(P.refusal != Refusal::MatsL2NoStash, "materials through L2 were decided without the stash they are decided with", c);

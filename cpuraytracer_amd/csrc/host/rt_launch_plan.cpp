@@ -292,14 +292,39 @@ int PlanPacked(const uint32_t* in, uint32_t* out) {
         C.cuCount > 4096u || S.n_levels == 0u || S.n_levels > rtd::kMaxLevels || S.grid_nu > 65535u || S.grid_nv > 65535u || S.sg_nx > 65535u ||
         S.sg_ny > 65535u)
         return RT_ERR_INVALID_ARG;
+    PackPlan(PlanTrace(S, C, K, A), PlanScanOnly(S, C), out);
+    return RT_OK;
+}
+
+uint32_t KernelWord(const TraceKernelId& k) {
+    return (k.lights ? 1u : 0u) | (k.kLds ? 2u : 0u) | (k.kThreads == 1024 ? 2u : (k.kThreads == 512 ? 1u : 0u)) << 2 | (uint32_t)k.kScan << 4 |
+           (k.kCache ? 1u << 6 : 0u) | (k.kHitLds ? 1u << 7 : 0u) | (k.kCarry ? 1u << 8 : 0u) | (k.kStash ? 1u << 9 : 0u) |
+           (k.kMatsL2 ? 1u << 10 : 0u) | (k.kSgLds ? 1u << 11 : 0u) | (k.kGridQ ? 1u << 12 : 0u) | (FindTraceVariant(k) >= 0 ? 1u << 31 : 0u);
+}
+
+void PackCase(const SceneShape& S, const Settings& C, const Knobs& K, const Ask& A, uint32_t* in) {
+    in[0] = S.n_padded, in[1] = S.n_levels, in[2] = S.top_cnt, in[3] = S.top_off;
+    in[4] = (S.grid ? 1u : 0u) | (S.grid_quant ? 2u : 0u) | (S.sg_enabled ? 4u : 0u) | (S.mats16 ? 8u : 0u);
+    in[5] = S.grid_nu, in[6] = S.grid_nv;
+    in[7] = S.sg_nx, in[8] = S.sg_ny, in[9] = S.sg_nentries, in[10] = S.sg_nglobal;
+    in[11] = S.n_lights;
+    in[12] = C.cuCount, in[13] = C.blocksPerCu, in[14] = C.blockThreads;
+    in[15] = (C.useMfma ? 1u : 0u) | (C.matsInLds ? 2u : 0u) | (C.useRayCache ? 4u : 0u) | (C.useStash ? 8u : 0u) | (C.treeInLds ? 16u : 0u) |
+             (C.forceGlobal ? 32u : 0u);
+    in[16] = K.mats16, in[17] = K.matsL2, in[18] = K.stashCap, in[19] = K.stashProcess, in[20] = K.gridQuant, in[21] = K.gridSgLds;
+    in[22] = K.queueBlock, in[23] = K.queueStatic;
+    in[24] = A.total_paths, in[25] = A.max_depth;
+    in[26] = A.mode == Mode::Carry ? 1u : 0u;
+    in[27] = 0u;
+}
+
+void PackPlan(const TracePlan& P, const ScanOnlyPlan& U, uint32_t* out) {
     for (uint32_t w = 0; w < kPlanWords; ++w) out[w] = 0u;
-    const ScanOnlyPlan U = PlanScanOnly(S, C);
     out[26] = (U.kernel.kLds ? 1u : 0u) | (uint32_t)U.kernel.kScan << 1 | U.tree_in_lds << 3 | (FindScanVariant(U.kernel) >= 0 ? 1u << 4 : 0u);
     out[27] = (uint32_t)U.ldsBytes;
-    const TracePlan P = PlanTrace(S, C, K, A);
     out[0] = (uint32_t)P.status;
     out[1] = (uint32_t)P.refusal;
-    if (P.status != RT_OK) return RT_OK;
+    if (P.status != RT_OK) return;
     out[2] = P.blocks, out[3] = (uint32_t)P.ldsBytes;
     out[4] = (uint32_t)P.candBytes, out[5] = (uint32_t)P.tablesBytes, out[6] = (uint32_t)P.leafBytes, out[7] = (uint32_t)P.opsBytes;
     out[8] = (uint32_t)P.sgBytes, out[9] = (uint32_t)P.treeBytes;
@@ -308,11 +333,7 @@ int PlanPacked(const uint32_t* in, uint32_t* out) {
     out[11] = P.mats_in_lds, out[12] = P.mats16_mode, out[13] = P.sg_glob16, out[14] = P.sg_in_lds, out[15] = P.tree_in_lds, out[16] = P.grid_in_lds;
     out[17] = P.ray_cache_off16, out[18] = P.ray_cache_stride16, out[19] = P.stash_cap, out[20] = P.stash_process;
     out[21] = P.queue.queue_block, out[22] = P.queue.static_blocks, out[23] = P.queue.dyn_begin, out[24] = P.queue.dyn_blocks;
-    const TraceKernelId& k = P.kernel;
-    out[25] = (k.lights ? 1u : 0u) | (k.kLds ? 2u : 0u) | (k.kThreads == 1024 ? 2u : (k.kThreads == 512 ? 1u : 0u)) << 2 | (uint32_t)k.kScan << 4 |
-              (k.kCache ? 1u << 6 : 0u) | (k.kHitLds ? 1u << 7 : 0u) | (k.kCarry ? 1u << 8 : 0u) | (k.kStash ? 1u << 9 : 0u) |
-              (k.kMatsL2 ? 1u << 10 : 0u) | (k.kSgLds ? 1u << 11 : 0u) | (k.kGridQ ? 1u << 12 : 0u) | (FindTraceVariant(k) >= 0 ? 1u << 31 : 0u);
-    return RT_OK;
+    out[25] = KernelWord(P.kernel);
 }
 
 }  // namespace rtplan

@@ -95,5 +95,11 @@ ScanOnlyPlan PlanScanOnly(const SceneShape& S, const Settings& C);
 // rt_unit_launch_plan's words (include/rt_api.h documents them)
 constexpr uint32_t kCaseWords = 28, kPlanWords = 28;
 int PlanPacked(const uint32_t* in, uint32_t* out);  // one case; RT_ERR_INVALID_ARG (nothing written) for inputs no context can have
+// The two halves of those words on their own: PlanPacked answers through PackPlan, and the launcher (rt_capi.hip LaunchTrace) keeps
+// the case it planned and the plan it applied through both, for rt_unit_last_trace_launch.  PackCase is the inverse of PlanPacked's
+// reading of a case: PlanPacked(PackCase(S, C, K, A)) == PackPlan(PlanTrace(S, C, K, A), PlanScanOnly(S, C)) for every context.
+uint32_t KernelWord(const TraceKernelId& k);  // word [25]
+void PackCase(const SceneShape& S, const Settings& C, const Knobs& K, const Ask& A, uint32_t* in);
+void PackPlan(const TracePlan& P, const ScanOnlyPlan& U, uint32_t* out);
 
 }  // namespace rtplan

@@ -183,6 +183,11 @@ struct rt_ctx {
     uint32_t treeTop = 128;  // largest top level the matrix-core filter takes (4 tiles of 32); RT_TREE_TOP overrides
     bool forceGlobal = false;
 
+    // the launcher's own account (rt_unit_last_trace_launch): the packed inputs and plan of the most recent LaunchTrace, in the words of
+    // rt_unit_launch_plan, and the launches since rt_create
+    uint32_t lastCaseWords[rtplan::kCaseWords] = {}, lastPlanWords[rtplan::kPlanWords] = {};
+    uint32_t traceLaunches = 0;
+
     // work order of the tiles and the flags of the empty-list tiles (BuildTileOrder): valid for the running accumulation's strip
     bool useTileOrder = true;  // RT_TILE_ORDER=0 keeps the image order
     bool tileKeyValid = false;    // the key below describes what tileOrderValid / skyFlagsValid say there is
@@ -305,7 +310,11 @@ static int RaiseLdsLimit(int device, const void* fn, size_t ldsBytes) {
 // Launch the megakernel over the total_paths paths described by tp.  Mode::Carry: the variant that implements frame pipelining
 // (tp.ctl etc. and the queue fields filled by the caller; the queue cursor lives in tp.ctl and is reset by the preparation kernel).
 static int LaunchTrace(rt_ctx* ctx, rtd::TraceParams& tp, rtplan::Mode mode = rtplan::Mode::Ordinary) {
-    const rtplan::TracePlan P = rtplan::PlanTrace(ShapeOf(tp), SettingsOf(ctx), KnobsFromEnv(), {tp.total_paths, tp.max_depth, mode});
+    const rtplan::SceneShape shape = ShapeOf(tp);
+    const rtplan::Settings settings = SettingsOf(ctx);
+    const rtplan::Knobs knobs = KnobsFromEnv();
+    const rtplan::Ask ask{tp.total_paths, tp.max_depth, mode};
+    const rtplan::TracePlan P = rtplan::PlanTrace(shape, settings, knobs, ask);
     if (P.status != RT_OK) return Fail(P.status, P.message);
     tp.shard_heads = ctx->queue.ptr;
     tp.fd_tile = rtd::make_fastdiv(tp.spp_pass ? 64u * tp.spp_pass : 1u);  // path_coordinates' divisors (rt_params.h, FastDiv)
@@ -333,6 +342,10 @@ static int LaunchTrace(rt_ctx* ctx, rtd::TraceParams& tp, rtplan::Mode mode = rt
     if (const int rc = RaiseLdsLimit(ctx->device, reinterpret_cast<const void*>(fn), P.ldsBytes)) return rc;
     hipLaunchKernelGGL(fn, dim3(P.blocks), dim3(ctx->blockThreads), P.ldsBytes, ctx->stream, tp);
     RT_HIP(hipGetLastError());
+    // what was planned and applied, in rt_unit_launch_plan's words (the plan's own packing: nothing is restated here)
+    rtplan::PackCase(shape, settings, knobs, ask, ctx->lastCaseWords);
+    rtplan::PackPlan(P, rtplan::PlanScanOnly(shape, settings), ctx->lastPlanWords);
+    ++ctx->traceLaunches;
     return RT_OK;
 }
 
@@ -1941,6 +1954,25 @@ int rt_unit_launch_plan(const uint32_t* cases, uint32_t n, uint32_t* plans) {
     for (uint32_t k = 0; k < n; ++k)
         if (rtplan::PlanPacked(cases + (size_t)k * rtplan::kCaseWords, plans + (size_t)k * rtplan::kPlanWords) != RT_OK)
             return Fail(RT_ERR_INVALID_ARG, "rt_unit_launch_plan: case " + std::to_string(k) + " describes no context or scene there can be");
+    return RT_OK;
+}
+
+int rt_unit_last_trace_launch(rt_ctx* ctx, uint32_t case_words[28], uint32_t plan_words[28], uint32_t* launches) {
+    static_assert(rtplan::kCaseWords == 28 && rtplan::kPlanWords == 28, "the words of rt_unit_launch_plan");
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_unit_last_trace_launch: invalid argument");
+    if (launches) *launches = ctx->traceLaunches;
+    if (ctx->traceLaunches == 0) return Fail(RT_ERR_SEQUENCE, "rt_unit_last_trace_launch: this context has launched no trace kernel");
+    if (case_words) std::memcpy(case_words, ctx->lastCaseWords, sizeof(ctx->lastCaseWords));
+    if (plan_words) std::memcpy(plan_words, ctx->lastPlanWords, sizeof(ctx->lastPlanWords));
+    return RT_OK;
+}
+
+int rt_unit_trace_variants(uint32_t* kernel_words, uint32_t cap, uint32_t* n) {
+    if (!n || (!kernel_words && cap != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_trace_variants: invalid argument");
+    *n = (uint32_t)rtplan::kTraceVariantCount;
+    if (cap == 0) return RT_OK;
+    if (cap < *n) return Fail(RT_ERR_INVALID_ARG, "rt_unit_trace_variants: capacity too small");
+    for (int r = 0; r < rtplan::kTraceVariantCount; ++r) kernel_words[r] = rtplan::KernelWord(rtplan::kTraceVariants[r]);
     return RT_OK;
 }
 

@@ -3,6 +3,7 @@
 Plumbing for tests, bench.py and the torch.distributed launcher — the host mirror of the
 reference's class API is C++ (cpuraytracer_amd/csrc/host/).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -14,6 +15,33 @@ from ._capi import RtRowset, RtStats, check, whole_image
 # Default `floor` of the relative noise estimate: added to the pixel's mean (r + g + b, HDR units after exposure, where 1.0 per
 # channel is about display white) so that black pixels have a finite relative error.
 NOISE_FLOOR = 0.01
+
+
+# What the launcher reports of a trace-kernel launch (rt_unit_last_trace_launch): `row` of csrc/rt_trace_variants.h (-1: not in the
+# list), `lights` = the _lights twin ran, the ten template arguments of rt_trace_kernel in their order, the grid (`blocks` workgroups
+# of kThreads), the queue cut of rt_params.h (all 0 for the frame-pipelining launch, whose caller cuts the queue), the calls'
+# `launches` since rt_create, and the raw words of rt_unit_launch_plan: `kernel_word` is plan_words[25].
+TraceLaunch = collections.namedtuple("TraceLaunch", [
+    "row", "lights", "kLds", "kThreads", "kScan", "kCache", "kHitLds", "kCarry", "kStash", "kMatsL2", "kSgLds", "kGridQ",
+    "blocks", "queue_block", "static_blocks", "dyn_begin", "dyn_blocks", "launches", "kernel_word", "case_words", "plan_words"])
+
+
+def trace_variants():
+    """rt_unit_trace_variants: word [25] of every instantiated trace-kernel row, single-light form, in list order.  Needs no GPU."""
+    L = _capi.load()
+    n = C.c_uint32(0)
+    check(L.rt_unit_trace_variants(None, 0, C.byref(n)))
+    words = np.zeros(n.value, dtype=np.uint32)
+    check(L.rt_unit_trace_variants(words.ctypes.data, n.value, C.byref(n)))
+    return [int(w) for w in words]
+
+
+def decode_kernel_word(word):
+    """Word [25] of rt_unit_launch_plan as a dict: lights, the ten template arguments, instantiated (bit 31)."""
+    w = int(word)
+    return {"lights": bool(w & 1), "kLds": bool(w & 2), "kThreads": (256, 512, 1024, 0)[(w >> 2) & 3], "kScan": (w >> 4) & 3,
+            "kCache": bool(w >> 6 & 1), "kHitLds": bool(w >> 7 & 1), "kCarry": bool(w >> 8 & 1), "kStash": bool(w >> 9 & 1),
+            "kMatsL2": bool(w >> 10 & 1), "kSgLds": bool(w >> 11 & 1), "kGridQ": bool(w >> 12 & 1), "instantiated": bool(w >> 31 & 1)}
 
 
 class HipRenderer:
@@ -277,6 +305,31 @@ class HipRenderer:
         return list(out)
 
     # ---- unit entries
+    def last_trace_launch(self):
+        """rt_unit_last_trace_launch as a TraceLaunch: which kernel variant the most recent trace launch of this context ran, its grid
+        and queue cut, and the launcher's packed inputs and plan.  RtError (RT_ERR_SEQUENCE) before the first launch."""
+        case = np.zeros(28, dtype=np.uint32)
+        plan = np.zeros(28, dtype=np.uint32)
+        n = C.c_uint32(0)
+        check(self._L.rt_unit_last_trace_launch(self._h, case.ctypes.data, plan.ctypes.data, C.byref(n)))
+        word = int(plan[25])
+        k = decode_kernel_word(word)
+        rows = trace_variants()
+        single = (word & ~1) | (1 << 31)
+        return TraceLaunch(row=rows.index(single) if (k["instantiated"] and single in rows) else -1, lights=k["lights"], kLds=k["kLds"],
+                           kThreads=k["kThreads"], kScan=k["kScan"], kCache=k["kCache"], kHitLds=k["kHitLds"], kCarry=k["kCarry"],
+                           kStash=k["kStash"], kMatsL2=k["kMatsL2"], kSgLds=k["kSgLds"], kGridQ=k["kGridQ"], blocks=int(plan[2]),
+                           queue_block=int(plan[21]), static_blocks=int(plan[22]), dyn_begin=int(plan[23]), dyn_blocks=int(plan[24]),
+                           launches=n.value, kernel_word=word, case_words=case, plan_words=plan)
+
+    def trace_launches(self):
+        """Trace-kernel launches of this context since rt_create (0 before the first: no error)."""
+        n = C.c_uint32(0)
+        rc = self._L.rt_unit_last_trace_launch(self._h, None, None, C.byref(n))
+        if rc not in (_capi.RT_OK, _capi.RT_ERR_SEQUENCE):
+            check(rc)
+        return n.value
+
     def unit_halton(self, index, base):
         index = np.ascontiguousarray(index, dtype=np.uint32)
         out = np.zeros(index.shape[0], dtype=np.float32)

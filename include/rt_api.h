@@ -597,6 +597,18 @@ int rt_unit_shadow(rt_ctx* ctx, uint32_t light, const float* points, uint32_t n,
  * A case no context or scene can be ([13], [14], [1] out of range, cells beyond 65,535 a side, unknown bits) is RT_ERR_INVALID_ARG.
  * Needs no GPU. */
 int rt_unit_launch_plan(const uint32_t* cases, uint32_t n, uint32_t* plans);
+/* The launcher's own account of the most recent trace-kernel launch of this context, in exactly the words above: case_words = the
+ * inputs it gathered from the uploaded scene, the context's settings and the RT_* knobs of that moment, plan_words = the plan it
+ * applied ([25] the kernel that ran, [21..24] its queue cut, [2] its blocks); either may be null.  Ordinary, path-list and
+ * frame-pipelining launches alike (a render call may make several: the last one counts).  Feeding case_words to rt_unit_launch_plan
+ * returns plan_words.  *launches (may be null) = trace-kernel launches since rt_create.  Before the first launch: RT_ERR_SEQUENCE
+ * (*launches = 0 is still written, the words are not); a null context: RT_ERR_INVALID_ARG (nothing is written).  Waits for nothing: the
+ * words are known when the launch is made. */
+int rt_unit_last_trace_launch(rt_ctx* ctx, uint32_t case_words[28], uint32_t plan_words[28], uint32_t* launches);
+/* The variants of the trace kernel the library instantiates (csrc/rt_trace_variants.h), in list order, each as word [25] above in its
+ * single-light form (bit 0 clear, bit 31 set); every one exists a second time as its _lights twin (bit 0 set).  *n = their number (55);
+ * cap == 0 only queries it, a smaller capacity than *n is RT_ERR_INVALID_ARG.  Needs no GPU. */
+int rt_unit_trace_variants(uint32_t* kernel_words, uint32_t cap, uint32_t* n);
 /* The resolve of spheres-app.cpp:196-214 for given HDR triples -> R,G,B bytes */
 int rt_unit_tonemap(rt_ctx* ctx, const float* hdr_rgb, uint32_t n, uint32_t n_samples, uint8_t* out_rgb);
 

@@ -1181,8 +1181,9 @@ def test_gpu_image_agrees_with_the_reference_halton_counter_estimator(hip, oracl
 
 
 # ------------------------------------------------ launch/layout knobs: every combination gives the same bits
-def _render_with_env(monkeypatch, env, sc, W, H, s1, depth=50, seed=1):
-    """Render on a fresh context created under `env` (the knobs are read at rt_create)."""
+def _render_with_env(monkeypatch, env, sc, W, H, s1, depth=50, seed=1, launch=False):
+    """Render on a fresh context created under `env` (the knobs are read at rt_create).  launch=True: also what the launcher reports
+    of that render's trace launch (HipRenderer.last_trace_launch)."""
     from cpuraytracer_amd import HipRenderer
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -1190,72 +1191,114 @@ def _render_with_env(monkeypatch, env, sc, W, H, s1, depth=50, seed=1):
     try:
         r2.upload(sc)
         st = r2.render(W, H, 1, s1, depth, seed)
+        tl = r2.last_trace_launch()
         r2.resolve()
         hdr, ldr = r2.download()
     finally:
         r2.close()
         for k in env:
             monkeypatch.delenv(k, raising=False)
-    return st, hdr, ldr
+    return (st, hdr, ldr, tl) if launch else (st, hdr, ldr)
 
 
-@pytest.mark.parametrize("env", [
-    {"RT_SHADOW_GRID": "0"},                                   # every shadow ray on the two-state scan fallback
-    {"RT_MATS_LDS": "0"},                                      # material table through L2
-    {"RT_BLOCK_THREADS": "256"},
-    {"RT_BLOCK_THREADS": "512"},
-    {"RT_BLOCK_THREADS": "512", "RT_BLOCKS_PER_CU": "2"},
-    {"RT_BLOCK_THREADS": "256", "RT_BLOCKS_PER_CU": "4"},
-    {"RT_BLOCKS_PER_CU": "2"},                                 # more workgroups than fit: the surplus starts as others end
-    {"RT_SCAN": "valu", "RT_BLOCKS_PER_CU": "2", "RT_SHADOW_GRID": "0"},
-    {"RT_SHADOW_GRID": "0", "RT_MATS_LDS": "0", "RT_RAY_CACHE": "0", "RT_BLOCK_THREADS": "512"},
-    {"RT_TILE_ORDER": "0"},                                    # tiles in image order instead of expensive-first
-    {"RT_SINGLE_DIRECT": "0"},                                 # one-sphere groups through the sphere-level filter like the rest
-    {"RT_QUEUE_BLOCK": "256", "RT_QUEUE_STATIC": "0"},         # queue geometry: bigger blocks, nothing static
-    {"RT_STASH": "0"},                                         # the prepared-path cache variants instead of the hit stash
-    {"RT_STASH": "0", "RT_RAY_CACHE": "0"},                    # neither: idle lanes generate their own paths
-    {"RT_STASH_CAP": "16"}, {"RT_STASH_CAP": "63"},            # smallest and largest stash
-    {"RT_MATS_L2": "0"},                                       # the material table in LDS and a smaller stash (default: through L2)
-    {"RT_GRID": "2"},                                          # the cell-grid scan (tables in LDS) instead of the matrix-core filter
-    {"RT_GRID": "2", "RT_MATS_LDS": "0"},                      # ... with its tables through L2
-    {"RT_GRID": "2", "RT_STASH": "0", "RT_SHADOW_GRID": "0"},
-    {"RT_MATS16": "1"},                                        # the packed 16-byte material records instead of the 48-byte ones through L2
-    {"RT_MATS16": "2"},                                        # the packed records staged into LDS (56-record stash)
-    {"RT_MATS16": "1", "RT_MATS_LDS": "0", "RT_STASH": "0"},
-], ids=lambda e: ",".join("%s=%s" % kv for kv in sorted(e.items())))
-def test_launch_and_layout_knobs_give_the_same_bits(hip, scenes_mod, monkeypatch, env):
+def _row(n):
+    """Kernel word (rt_unit_launch_plan word [25], single light) of row n of csrc/rt_trace_variants.h, from the census' table."""
+    import trace_variant_cases
+    row, _, _, args = trace_variant_cases._ROWS[n]
+    assert row == n
+    return trace_variant_cases.kernel_word(*args)
+
+
+def _env_id(env):
+    return ",".join("%s=%s" % kv for kv in sorted(env.items()))
+
+
+def _assert_kernel(tl, want, env):
+    from cpuraytracer_amd import renderer
+    assert tl.kernel_word == want, "under %s the launch took %s (row %d), not %s" % (
+        env, renderer.decode_kernel_word(tl.kernel_word), tl.row, renderer.decode_kernel_word(want))
+
+
+# The cover scene's default kernel: the flat scan with the hit stash and the materials through L2 (row 16).  Each knob set names the
+# row it is meant to reach: another one where it trades a variant "instead of" the default's, row 16 itself for the knobs of the
+# queue, the shadow rays, the tile order and the packed materials, which change what the same kernel is given.
+_COVER_KNOBS = [
+    ({"RT_SHADOW_GRID": "0"}, 16),                                  # every shadow ray on the two-state scan fallback
+    ({"RT_MATS_LDS": "0"}, 18),                                     # material table through L2: the stash kernel without all its tables in LDS
+    ({"RT_BLOCK_THREADS": "256"}, 39),                              # the path-cache kernels of the smaller workgroups
+    ({"RT_BLOCK_THREADS": "512"}, 35),
+    ({"RT_BLOCK_THREADS": "512", "RT_BLOCKS_PER_CU": "2"}, 36),     # ... half the LDS each: no room for the caches
+    ({"RT_BLOCK_THREADS": "256", "RT_BLOCKS_PER_CU": "4"}, 40),
+    ({"RT_BLOCKS_PER_CU": "2"}, 32),                                # more workgroups than fit: the surplus starts as others end; neither stash nor cache fits
+    ({"RT_SCAN": "valu", "RT_BLOCKS_PER_CU": "2", "RT_SHADOW_GRID": "0"}, 47),
+    ({"RT_SHADOW_GRID": "0", "RT_MATS_LDS": "0", "RT_RAY_CACHE": "0", "RT_BLOCK_THREADS": "512"}, 38),
+    ({"RT_TILE_ORDER": "0"}, 16),                                   # tiles in image order instead of expensive-first
+    ({"RT_SINGLE_DIRECT": "0"}, 16),                                # one-sphere groups through the sphere-level filter like the rest
+    ({"RT_QUEUE_BLOCK": "256", "RT_QUEUE_STATIC": "0"}, 16),        # queue geometry: bigger blocks, nothing static
+    ({"RT_STASH": "0"}, 31),                                        # the prepared-path cache variants instead of the hit stash
+    ({"RT_STASH": "0", "RT_RAY_CACHE": "0"}, 32),                   # neither: idle lanes generate their own paths
+    ({"RT_STASH_CAP": "16"}, 17),                                   # smallest stash: dropping the material table no longer buys eight records, so it stays in LDS
+    ({"RT_STASH_CAP": "63"}, 16),                                   # largest stash (the default)
+    ({"RT_MATS_L2": "0"}, 17),                                      # the material table in LDS and a smaller stash (default: through L2)
+    ({"RT_GRID": "2"}, 1),                                          # the cell-grid scan (tables in LDS) instead of the matrix-core filter
+    ({"RT_GRID": "2", "RT_MATS_LDS": "0"}, 6),                      # ... with its tables through L2
+    ({"RT_GRID": "2", "RT_STASH": "0", "RT_SHADOW_GRID": "0"}, 3),  # ... its path caches do not fit beside cover's tables: neither
+    ({"RT_MATS16": "1"}, 16),                                       # the packed 16-byte material records instead of the 48-byte ones through L2
+    ({"RT_MATS16": "2"}, 16),                                       # the packed records staged into LDS (56-record stash)
+    ({"RT_MATS16": "1", "RT_MATS_LDS": "0", "RT_STASH": "0"}, 33),
+]
+
+
+@pytest.mark.parametrize("env,row", _COVER_KNOBS, ids=[_env_id(e) for e, _ in _COVER_KNOBS])
+def test_launch_and_layout_knobs_give_the_same_bits(hip, scenes_mod, monkeypatch, env, row):
     W, H, s1 = 161, 103, 5  # ragged: the last tile of the sample buffer is 9 pixels wide
     if "RT_TILE_ORDER" in env:
         W, H = 483, 309       # enough tiles (2,331) for the expensive-first work order to be built at all; still ragged
     sc = scenes_mod.build_scene("cover", 1, W, H)
     hip.upload(sc)
     sa = hip.render(W, H, 1, s1, 50, 1)
+    _assert_kernel(hip.last_trace_launch(), _row(16), {})
     hip.resolve()
     a, la = hip.download()
-    sb, b, lb = _render_with_env(monkeypatch, env, sc, W, H, s1)
+    sb, b, lb, tl = _render_with_env(monkeypatch, env, sc, W, H, s1, launch=True)
+    _assert_kernel(tl, _row(row), env)
     assert_same(a, b, "HDR under %s" % env)
     assert_same(la, lb, "LDR under %s" % env)
     assert (sa.traversals, sa.segments, sa.samples) == (sb.traversals, sb.segments, sb.samples)
 
 
-@pytest.mark.parametrize("env", [{"RT_TREE_LDS": "0"}, {"RT_TREE_LDS": "0", "RT_SHADOW_GRID": "0"}, {"RT_BLOCK_THREADS": "512"},
-                                 {"RT_MATS_LDS": "0", "RT_TREE_TOP": "32"}, {"RT_ALWAYS_BIG": "1"},
-                                 {"RT_GRID": "0"}, {"RT_GRID": "0", "RT_TREE_LDS": "0", "RT_STASH": "0"}, {"RT_GRID": "0", "RT_BLOCK_THREADS": "512"},
-                                 {"RT_STASH": "0"}, {"RT_STASH": "0", "RT_RAY_CACHE": "0"}, {"RT_BLOCK_THREADS": "256", "RT_BLOCKS_PER_CU": "2"},
-                                 {"RT_STASH_CAP": "17"}, {"RT_GRID_SG_LDS": "1"}, {"RT_GRID_QUANT": "1"}, {"RT_GRID_QUANT": "1", "RT_STASH_CAP": "24"},
-                                 {"RT_SHADOW_CELLS": "64"}, {"RT_SHADOW_CELLS": "128", "RT_GRID": "0"}, {"RT_SG_SPH": "1"}, {"RT_SG_SPH": "1", "RT_GRID": "0"}, {"RT_MATS16": "1"}, {"RT_MATS16": "1", "RT_GRID": "0"}],
-                         ids=lambda e: ",".join("%s=%s" % kv for kv in sorted(e.items())))
-def test_hierarchy_scan_knobs_give_the_same_bits(hip, scenes_mod, monkeypatch, env):
+# grid10k's default kernel: the cell grid with its tables in global memory, the cells in LDS and the hit stash (row 6).  RT_TREE_LDS,
+# RT_TREE_TOP, RT_SHADOW_CELLS, RT_SG_SPH, RT_STASH_CAP and RT_MATS16 change tables or capacities of the kernel a scene gets anyway.
+# RT_GRID_SG_LDS=1 alone is DECLINED on this scene -- its shadow index (78 x 133 cells, 40,038 entries: 98 KiB) leaves no stash of 24
+# records beside the cells -- and so takes row 6 like the default; under RT_SHADOW_CELLS=32 the index fits and the knob reaches the
+# kernel it exists for (row 4).
+_GRID10K_KNOBS = [
+    ({"RT_TREE_LDS": "0"}, 6), ({"RT_TREE_LDS": "0", "RT_SHADOW_GRID": "0"}, 6), ({"RT_BLOCK_THREADS": "512"}, 11),
+    ({"RT_MATS_LDS": "0", "RT_TREE_TOP": "32"}, 6), ({"RT_ALWAYS_BIG": "1"}, 14),
+    ({"RT_GRID": "0"}, 14), ({"RT_GRID": "0", "RT_TREE_LDS": "0", "RT_STASH": "0"}, 21), ({"RT_GRID": "0", "RT_BLOCK_THREADS": "512"}, 23),
+    ({"RT_STASH": "0"}, 7), ({"RT_STASH": "0", "RT_RAY_CACHE": "0"}, 8), ({"RT_BLOCK_THREADS": "256", "RT_BLOCKS_PER_CU": "2"}, 13),
+    ({"RT_STASH_CAP": "17"}, 6), ({"RT_GRID_SG_LDS": "1"}, 6), ({"RT_GRID_QUANT": "1"}, 5), ({"RT_GRID_QUANT": "1", "RT_STASH_CAP": "24"}, 5),
+    ({"RT_SHADOW_CELLS": "64"}, 6), ({"RT_SHADOW_CELLS": "128", "RT_GRID": "0"}, 14), ({"RT_SG_SPH": "1"}, 6), ({"RT_SG_SPH": "1", "RT_GRID": "0"}, 14),
+    ({"RT_MATS16": "1"}, 6), ({"RT_MATS16": "1", "RT_GRID": "0"}, 14),
+    ({"RT_GRID_SG_LDS": "1", "RT_SHADOW_CELLS": "32"}, 4),
+]
+
+
+@pytest.mark.parametrize("env,row", _GRID10K_KNOBS, ids=[_env_id(e) for e, _ in _GRID10K_KNOBS])
+def test_hierarchy_scan_knobs_give_the_same_bits(hip, scenes_mod, monkeypatch, env, row):
     """grid10k (10,004 spheres: the cell-grid scan by default): the bounds hierarchy instead (RT_GRID=0: 2,504 groups, four levels of
     bounds, through LDS or L2, a narrower top level, the big spheres inside it with RT_ALWAYS_BIG=1), smaller workgroups, the path
     cache instead of the hit stash, neither, a small stash; the quantised one-sphere bounds in LDS (RT_GRID_QUANT=1, rt_scan.h
-    GridQuant); coarser shadow indices than the 256 x 256 cells large scenes get."""
+    GridQuant); the shadow index in LDS (RT_GRID_SG_LDS=1 with an index small enough); coarser shadow indices than the 256 x 256
+    cells large scenes get.  Every set names the kernel it reaches."""
     sc = scenes_mod.build_scene("grid10k", 1, 96, 96)
     hip.upload(sc)
     sa = hip.render(96, 96, 1, 3, 50, 1)
+    _assert_kernel(hip.last_trace_launch(), _row(6), {})
     hip.resolve()
     a, la = hip.download()
-    sb, b, lb = _render_with_env(monkeypatch, env, sc, 96, 96, 3)
+    sb, b, lb, tl = _render_with_env(monkeypatch, env, sc, 96, 96, 3, launch=True)
+    _assert_kernel(tl, _row(row), env)
     assert_same(a, b, "grid10k HDR under %s" % env)
     assert_same(la, lb, "grid10k LDR under %s" % env)
     assert (sa.traversals, sa.segments) == (sb.traversals, sb.segments)
