@@ -23,6 +23,7 @@
 #include "host/rt_launch_plan.h"
 #include "host/rt_scene_prep.h"
 #include "host/rt_sequence.h"
+#include "host/rt_tile_tables.h"
 #include "rt_kernels.h"
 
 using rtprep::EnvU32;
@@ -188,37 +189,26 @@ struct rt_ctx {
     uint32_t lastCaseWords[rtplan::kCaseWords] = {}, lastPlanWords[rtplan::kPlanWords] = {};
     uint32_t traceLaunches = 0;
 
-    // work order of the tiles and the flags of the empty-list tiles (BuildTileOrder): valid for the running accumulation's strip
-    bool useTileOrder = true;  // RT_TILE_ORDER=0 keeps the image order
-    bool tileKeyValid = false;    // the key below describes what tileOrderValid / skyFlagsValid say there is
-    bool tileOrderValid = false;
-    rtseq::PictureKey tilePic;    // ... and the picture they were built for (with the scene and the lists, all they depend on)
-    uint32_t tileListLimit = 0, tileListSpheres = 0;  // the lists' limits the flags were taken under (0, 0: no flags)
-    // Empty-list tiles kept out of the trace queue (rt_kernels.h rt_sky_tiles_kernel).  The flags share the order's key and lifetime;
-    // with them the order ends with exactly the flagged tiles.  Their number reaches the host through pinned memory and an event that
-    // is only ever QUERIED: until it has completed the count is unknown and every launch queues all tiles.
-    bool skyExclude = true;       // RT_SKY_EXCLUDE, read where an accumulation starts
-    bool skyFlagsValid = false;
-    bool skyCountPending = false, skyCountKnown = false;
-    uint32_t skyEmpty = 0;        // flagged tiles, once known
-    bool lastTraceSky = false;    // the last ordinary LaunchTrace took a kernel that finishes empty-list planes itself (rt_kernels.h kSky)
-    uint32_t skyExcluded = 0;     // tiles the last rt_render that launched a trace kernel kept out of its queue (rt_unit_sky_excluded)
-    DevBuf<uint8_t> skyFlags;     // [full tiles]
-    DevBuf<uint32_t> skyInfo;     // [0] flagged tiles, [1..3] the constant sample's bits
-    uint32_t* skyCountHost = nullptr;  // pinned
-    hipEvent_t skyEv = nullptr;
+    // The per-tile tables: candidate masks and sphere lists of the primary rays (BuildTileMasks; rt_tile_mask.h), work order and
+    // empty-list flags (BuildTileOrder), the flagged tiles' count.  What of them is valid, for which picture and limits, and what a
+    // call may use is host/rt_tile_tables.h's to say: read and changed only through rttile's plans, reports and events.
+    rttile::State tiles;
+    DevBuf<uint32_t> tileMasks;    // kTileMaskWords per full tile
+    DevBuf<uint16_t> tileSpheres;  // kTileSphereHalfs per full tile (built together with the masks)
     DevBuf<float> pilotRays, pilotHits;
     DevBuf<uint32_t> tileOrder, matType;
     DevBuf<uint8_t> tileClass;
-    // candidate masks of the tiles' primary rays (BuildTileMasks; rt_tile_mask.h): valid for the same (scene, image, strip)
-    bool tileMaskValid = false;
-    rtseq::PictureKey maskPic;
-    uint32_t maskLimit = 0, maskTiles = 0;
-    uint32_t maskSpheres = 0;    // sphere-list limit the tables were built with (0: no lists)
-    bool skySkip = true;         // RT_SKY_SKIP, read with the knobs above: empty-list tiles are finished without rays (rt_kernels.h kSky)
-    DevBuf<uint32_t> tileMasks;  // kTileMaskWords per full tile
-    DevBuf<uint16_t> tileSpheres;  // kTileSphereHalfs per full tile (built together with the masks)
-    uint64_t freshScans = 0;     // blocks of 64 fresh paths launched by the last rt_render that ran passes (rt_unit_tile_masks)
+    DevBuf<uint8_t> skyFlags;     // [full tiles]
+    DevBuf<uint32_t> skyInfo;     // [0] flagged tiles, [1..3] the constant sample's bits
+    // the count's way to the host (rt_kernels.h rt_sky_tiles_kernel): pinned memory and an event that is only ever QUERIED
+    uint32_t* skyCountHost = nullptr;  // pinned
+    hipEvent_t skyEv = nullptr;
+    // the last render's account, for the unit entries
+    struct TileAccount {
+        bool lastTraceSky = false;  // the last ordinary LaunchTrace took a kernel that finishes empty-list planes itself (rt_kernels.h kSky)
+        uint32_t skyExcluded = 0;   // tiles the last rt_render that launched a trace kernel kept out of its queue (rt_unit_sky_excluded)
+        uint64_t freshScans = 0;    // blocks of 64 fresh paths launched by the last rt_render that ran passes (rt_unit_tile_masks)
+    } tileAcct;
 
     // frame pipelining (rt_set_frame_pipelining; rt_params.h): regions of a sample ring, two continuation buffers (seq.pipeDepth: the
     // calls a path may be carried across)
@@ -324,7 +314,7 @@ static int LaunchTrace(rt_ctx* ctx, rtd::TraceParams& tp, rtplan::Mode mode = rt
     tp.sg_glob16 = P.sg_glob16, tp.sg_in_lds = P.sg_in_lds, tp.tree_in_lds = P.tree_in_lds, tp.grid_in_lds = P.grid_in_lds;
     tp.ray_cache_off16 = P.ray_cache_off16, tp.ray_cache_stride16 = P.ray_cache_stride16;
     tp.stash_cap = P.stash_cap, tp.stash_process = P.stash_process;
-    ctx->lastTraceSky = P.lastTraceSky;
+    ctx->tileAcct.lastTraceSky = P.lastTraceSky;
     if (std::getenv("RT_VERBOSE"))
         std::fprintf(stderr, "rt_trace launch: tree=%d flat=%d ldsTables=%d blocks=%u threads=%u lds=%zu B (cand %zu, tables %zu, leaf %zu, ops %zu, sg %zu, tree %zu, cache %s, stash %u)\n",
                      (int)P.tree, (int)P.flat + 2 * (int)P.grid + 4 * (int)P.gridLds, (int)P.ldsTables, P.blocks, ctx->blockThreads, P.ldsBytes, P.candBytes, P.tablesBytes, P.leafBytes,
@@ -410,19 +400,21 @@ static uint32_t TileSphereLimitFromEnv() {
     const uint32_t v = EnvU32("RT_PRIMARY_SPHERES", rtd::kTileSphereLimitDefault);
     return v > rtd::kTileSphereMax ? rtd::kTileSphereMax : v;
 }
-static int BuildTileMasks(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t npix) {
-    const uint32_t limit = EnvU32("RT_PRIMARY_MASK_LIMIT", rtd::kTileMaskLimitDefault);
-    const uint32_t sphLimit = TileSphereLimitFromEnv();
-    const uint32_t nFull = npix >> 6;
+static rttile::Knobs TileKnobsFromEnv() {
+    rttile::Knobs K;
+    K.primaryMask = EnvU32("RT_PRIMARY_MASK", 1u) != 0u;
+    K.primaryMaskLimit = EnvU32("RT_PRIMARY_MASK_LIMIT", rtd::kTileMaskLimitDefault);
+    K.primarySpheres = TileSphereLimitFromEnv();
+    K.skipSky = EnvU32("RT_SKY_SKIP", 1u) != 0u;
+    K.excludeSky = EnvU32("RT_SKY_EXCLUDE", 1u) != 0u;
+    return K;
+}
+static int BuildTileMasks(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t npix, const rttile::Knobs& knobs) {
     const rtd::TraceParams& b = ctx->base;
-    const bool wanted = EnvU32("RT_PRIMARY_MASK", 1u) != 0u && nFull != 0u && b.n_levels == 1u && b.level_cnt[0] <= 128u &&
-                        rtplan::ChooseScan(ShapeOf(b), SettingsOf(ctx), 0u).flat;
-    if (!wanted) {
-        ctx->tileMaskValid = false;
-        return RT_OK;
-    }
-    if (ctx->tileMaskValid && ctx->maskPic == pic && ctx->maskLimit == limit && ctx->maskSpheres == sphLimit) return RT_OK;
-    ctx->tileMaskValid = false;
+    const bool sceneTakesMasks = b.n_levels == 1u && b.level_cnt[0] <= 128u && rtplan::ChooseScan(ShapeOf(b), SettingsOf(ctx), 0u).flat;
+    const rttile::MaskPlan plan = rttile::PlanMasks(ctx->tiles, pic, npix, knobs, sceneTakesMasks);
+    if (plan.answer != rttile::MaskAnswer::Build) return RT_OK;
+    const uint32_t nFull = plan.nFull, sphLimit = plan.sphLimit;
     int rc;
     if ((rc = ctx->tileMasks.Reserve((size_t)nFull * rtd::kTileMaskWords)) != RT_OK) return rc;
     if (sphLimit != 0u && (rc = ctx->tileSpheres.Reserve((size_t)nFull * rtd::kTileSphereHalfs)) != RT_OK) return rc;
@@ -430,14 +422,10 @@ static int BuildTileMasks(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t np
     tp.W = pic.W;
     tp.H = pic.H;
     tp.rs = pic.rs;
-    hipLaunchKernelGGL(rtd::rt_tile_mask_kernel, dim3((nFull + 3) / 4), dim3(256), 0, ctx->stream, tp, nFull, limit, ctx->tileMasks.ptr,
+    hipLaunchKernelGGL(rtd::rt_tile_mask_kernel, dim3((nFull + 3) / 4), dim3(256), 0, ctx->stream, tp, nFull, plan.limit, ctx->tileMasks.ptr,
                        sphLimit, sphLimit != 0u ? ctx->tileSpheres.ptr : nullptr);
     RT_HIP(hipGetLastError());
-    ctx->tileMaskValid = true;
-    ctx->maskPic = pic;
-    ctx->maskLimit = limit;
-    ctx->maskSpheres = sphLimit;
-    ctx->maskTiles = nFull;
+    rttile::MasksBuilt(ctx->tiles, pic, plan);
     return RT_OK;
 }
 
@@ -446,35 +434,30 @@ static int BuildTileMasks(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t np
 // Runs AFTER BuildTileMasks: where the tiles have sphere lists (and RT_SKY_SKIP and RT_SKY_EXCLUDE are on) the tiles with an empty
 // list are flagged first (rt_sky_tiles_kernel) and sorted behind all others, and their number is copied to pinned host memory
 // behind an event, for the later calls that find it complete (SkyCountPoll) to leave them out of the queue.
+// What is flagged, ordered and copied, and under which key it is kept, is rttile::PlanOrder's answer; a rebuild that fails half way
+// leaves everything dropped (OrderBuilt is reported last).
 static void DropTileOrder(rt_ctx* ctx) {
-    ctx->tileKeyValid = ctx->tileOrderValid = ctx->skyFlagsValid = false;
-    ctx->skyCountPending = ctx->skyCountKnown = false;
+    rttile::Dropped(ctx->tiles);
     (void)rtseq::TileTablesDropped(ctx->seq);  // (planes traced ahead go with the flags: nothing beyond the sequencer's own state)
 }
 static void SkyCountPoll(rt_ctx* ctx) {
-    if (!ctx->skyCountPending) return;
+    if (!rttile::CountToAwait(ctx->tiles)) return;
     const hipError_t e = hipEventQuery(ctx->skyEv);
     if (e == hipSuccess) {
-        ctx->skyCountPending = false;
-        ctx->skyCountKnown = true;
-        ctx->skyEmpty = *ctx->skyCountHost;
+        rttile::CountArrived(ctx->tiles, *ctx->skyCountHost);
     } else if (e == hipErrorNotReady) {
         (void)hipGetLastError();  // "not ready" is an answer, not an error of the calls that follow
     } else {
-        ctx->skyCountPending = false;  // a real error: the count stays unknown, and the error is left for the call that follows to report
+        rttile::CountFailed(ctx->tiles);  // a real error: the count stays unknown, and the error is left for the call that follows to report
     }
 }
 static int BuildTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t npix) {
-    // order and flags are a function of the scene (camera included), the image size, the strip and the lists' limits: a new
-    // accumulation of the same picture -- a progressive restart, the next frame of a turntable with an unchanged scene -- keeps them
-    const uint32_t nFull = npix >> 6;
-    const bool lists = ctx->tileMaskValid && ctx->maskSpheres != 0u && nFull != 0u;  // (BuildTileMasks has just run for this picture)
-    const bool wantFlags = lists && ctx->skySkip && ctx->skyExclude;
-    const uint32_t keyLimit = wantFlags ? ctx->maskLimit : 0u, keySpheres = wantFlags ? ctx->maskSpheres : 0u;
-    if (ctx->tileKeyValid && ctx->tilePic == pic && ctx->tileListLimit == keyLimit && ctx->tileListSpheres == keySpheres) return RT_OK;
-    DropTileOrder(ctx);
+    const rttile::OrderPlan plan = rttile::PlanOrder(ctx->tiles, pic, npix, (uint32_t)ctx->cuCount);
+    if (!plan.rebuild) return RT_OK;
+    (void)rtseq::TileTablesDropped(ctx->seq);  // (the plan dropped order and flags)
+    const uint32_t nFull = plan.nFull;
     int rc;
-    if (wantFlags) {
+    if (plan.flags) {
         if (!ctx->skyEv) RT_HIP(hipEventCreateWithFlags(&ctx->skyEv, hipEventDisableTiming));
         if (!ctx->skyCountHost) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->skyCountHost), sizeof(uint32_t), hipHostMallocDefault));
         if ((rc = ctx->skyFlags.Reserve(nFull)) != RT_OK) return rc;
@@ -483,9 +466,8 @@ static int BuildTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t np
         hipLaunchKernelGGL(rtd::rt_sky_tiles_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->base, ctx->tileSpheres.ptr, nFull,
                            ctx->skyFlags.ptr, ctx->skyInfo.ptr);
         RT_HIP(hipGetLastError());
-        ctx->skyFlagsValid = true;
     }
-    if (ctx->useTileOrder && nFull >= 2u * (uint32_t)ctx->cuCount) {  // (else too little work for the order to matter)
+    if (plan.order) {
         const uint32_t nPilot = nFull * rtd::kPilotsPerTile;
         if ((rc = ctx->pilotRays.Reserve((size_t)nPilot * 6)) != RT_OK) return rc;
         if ((rc = ctx->pilotHits.Reserve((size_t)nPilot * 10)) != RT_OK) return rc;
@@ -503,20 +485,15 @@ static int BuildTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t np
         RT_HIP(hipGetLastError());
         if ((rc = LaunchClosest(ctx, ctx->pilotRays.ptr, nPilot, ctx->pilotHits.ptr)) != RT_OK) return rc;
         hipLaunchKernelGGL(rtd::rt_tile_class_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->pilotHits.ptr, nFull, pic.W,
-                           ctx->matType.ptr, ctx->tileClass.ptr, wantFlags ? ctx->skyFlags.ptr : (const uint8_t*)nullptr);
+                           ctx->matType.ptr, ctx->tileClass.ptr, plan.flags ? ctx->skyFlags.ptr : (const uint8_t*)nullptr);
         hipLaunchKernelGGL(rtd::rt_tile_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->tileClass.ptr, nFull, ctx->tileOrder.ptr);
         RT_HIP(hipGetLastError());
-        ctx->tileOrderValid = true;
-        if (wantFlags) {  // only a launch that has the order can leave the flagged tiles out: without it nobody needs their number
-            RT_HIP(hipMemcpyAsync(ctx->skyCountHost, ctx->skyInfo.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            RT_HIP(hipEventRecord(ctx->skyEv, ctx->stream));
-            ctx->skyCountPending = true;
-        }
     }
-    ctx->tileKeyValid = true;
-    ctx->tilePic = pic;
-    ctx->tileListLimit = keyLimit;
-    ctx->tileListSpheres = keySpheres;
+    if (plan.count) {
+        RT_HIP(hipMemcpyAsync(ctx->skyCountHost, ctx->skyInfo.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(hipEventRecord(ctx->skyEv, ctx->stream));
+    }
+    rttile::OrderBuilt(ctx->tiles, pic, plan);
     return RT_OK;
 }
 
@@ -699,7 +676,7 @@ int rt_create(int device_ordinal, rt_ctx** out) {
         ctx->useRayCache = EnvU32("RT_RAY_CACHE", 1) != 0;
         ctx->useStash = EnvU32("RT_STASH", 1) != 0;
         ctx->treeInLds = EnvU32("RT_TREE_LDS", 1) != 0;
-        ctx->useTileOrder = EnvU32("RT_TILE_ORDER", 1) != 0;
+        ctx->tiles.orderWanted = EnvU32("RT_TILE_ORDER", 1) != 0;
         // what PrepareScene takes from the context, fixed here (its other settings are read at each upload): one reader for
         // rt_create and for the GPU-less layout queries, so that they describe the layout an upload would build
         const rtprep::PrepOptions opt = rtprep::PrepOptions::FromEnv();
@@ -832,7 +809,7 @@ int rt_set_stream(rt_ctx* ctx, void* hip_stream) {
     const uint32_t voids = rtseq::StreamReplaced(ctx->seq);
     // (the copy of the flags' count must not land in the pinned word after a newer one's: the one place that waits for it, and only
     // when a picture's tables were built and never rendered from again)
-    if (ctx->skyCountPending) RT_HIP(hipEventSynchronize(ctx->skyEv));
+    if (rttile::CountToAwait(ctx->tiles)) RT_HIP(hipEventSynchronize(ctx->skyEv));
     DropVoided(ctx, voids);
     ctx->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx->ownStream;
     return RT_OK;
@@ -883,8 +860,8 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     ctx->mats16Ok = P.mats16Ok;
     if (P.mats16Ok && (rc = ctx->mats16.Upload(P.mats16)) != RT_OK) return rc;
     if ((rc = ctx->matType.Upload(P.matType)) != RT_OK) return rc;
-    DropTileOrder(ctx);
-    ctx->tileMaskValid = false;
+    rttile::SceneReplaced(ctx->tiles);  // (their inputs are overwritten: nothing of the tiles' tables is valid)
+    (void)rtseq::TileTablesDropped(ctx->seq);
     // lights 1 .. : one index each, in global memory (256 x 256 cells at most), and their records
     std::vector<rtd::LightRec> recs;
     for (uint32_t k = 1; k < n_lights; ++k) {
@@ -1043,7 +1020,7 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
 // With flags of the empty-list tiles (BuildTileOrder) the tile-aware forms: the flagged tiles' planes are the constant, whether the
 // launch that traced the buffer wrote them or left them out.
 static void LaunchAccumulate(rt_ctx* ctx, uint32_t npix, uint32_t spp, uint32_t first, uint32_t count) {
-    if (ctx->skyFlagsValid) {
+    if (rttile::AccumulateByFlags(ctx->tiles)) {
         const float* skyC = reinterpret_cast<const float*>(ctx->skyInfo.ptr + 1);  // (the constant sample follows the count)
         if (ctx->seq.noise)
             hipLaunchKernelGGL(rtd::rt_accumulate_moments_tiles_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->samples.ptr,
@@ -1154,15 +1131,15 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
                 RT_HIP(hipMemsetAsync(ctx->sq.ptr, 0, (size_t)npix * 3 * sizeof(float), ctx->stream));
             }
             rtseq::AccumulationStarted(seq, call);
-            ctx->skySkip = EnvU32("RT_SKY_SKIP", 1u) != 0u;  // (no mask table depends on it; the unit entries that rebuild tables leave it alone)
-            ctx->skyExclude = EnvU32("RT_SKY_EXCLUDE", 1u) != 0u;
-            if ((rc = BuildTileMasks(ctx, call.pic, npix)) != RT_OK) return rc;
+            const rttile::Knobs knobs = TileKnobsFromEnv();
+            rttile::AccumulationStarts(ctx->tiles, knobs);
+            if ((rc = BuildTileMasks(ctx, call.pic, npix, knobs)) != RT_OK) return rc;
             if ((rc = BuildTileOrder(ctx, call.pic, npix)) != RT_OK) return rc;  // (after the masks: it flags the tiles whose list is empty)
         }
     }
 
     if (pipelined) {
-        ctx->skyExcluded = 0;  // (the carrying kernel's launch queues every tile)
+        ctx->tileAcct.skyExcluded = 0;  // (the carrying kernel's launch queues every tile)
         int rcp = PipelineRender(ctx, W, H, rs, npix, s0, s1, max_depth, seed);
         if (rcp != RT_OK) {
             DropVoided(ctx, rtseq::StepFailed(seq));
@@ -1189,20 +1166,14 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
     uint32_t passes = 0;
     auto runPasses = [&]() -> int {
         int rc;
-        ctx->freshScans = 0;
-        // Empty-list tiles stay out of the queue when their number had arrived when this call began (never waited for), they are the order's tail, the
-        // kernel would finish them without rays anyway (sky_skip below) and no partial tile follows the full ones in path-index
-        // space.  Their share of the counters is added behind each launch; their samples are the accumulation's constant (LaunchAccumulate).
+        ctx->tileAcct.freshScans = 0;
+        // The tables this call's picture may take, and the empty-list tiles that stay out of the queue (rttile::UseFor has the rules).
+        // Their share of the counters is added behind each launch; their samples are the accumulation's constant (LaunchAccumulate).
         const uint32_t nFull = npix >> 6;
-        // (the tables must be the ones of THIS accumulation's picture: rt_unit_tile_masks may have rebuilt them for another since)
-        const bool masksHere = ctx->tileMaskValid && ctx->maskPic == call.pic;
-        const bool listsHere = masksHere && ctx->maskSpheres != 0u;
-        const uint32_t nSky = (ctx->skyFlagsValid && ctx->skyCountKnown && ctx->tileOrderValid && listsHere && ctx->skySkip && (npix & 63u) == 0u &&
-                               ctx->skyEmpty < nFull)
-                                  ? ctx->skyEmpty
-                                  : 0u;
+        const rttile::Use use = rttile::UseFor(ctx->tiles, call.pic, npix);
+        const uint32_t nSky = use.nSky;
         RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 6 * sizeof(unsigned long long), ctx->stream));
-        ctx->skyExcluded = nSky;
+        ctx->tileAcct.skyExcluded = nSky;
         for (rtseq::Pass pass = rtseq::FirstPass(split); pass.spp != 0; pass = rtseq::NextPass(split, pass)) {
             const uint32_t s = pass.s, spp = pass.spp;
             rtd::TraceParams tp = ctx->base;
@@ -1217,11 +1188,11 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
             tp.sampler = ctx->sampler;
             tp.seed = seed;
             tp.path_list = nullptr;
-            tp.tile_order = ctx->tileOrderValid ? ctx->tileOrder.ptr : nullptr;
-            tp.tile_masks = masksHere ? ctx->tileMasks.ptr : nullptr;
-            tp.tile_spheres = listsHere ? ctx->tileSpheres.ptr : nullptr;
-            tp.sky_skip = (listsHere && ctx->skySkip) ? 1u : 0u;
-            ctx->freshScans += ((uint64_t)tp.total_paths + 63u) / 64u;  // (all tiles: the statistics do not know about the shorter queue)
+            tp.tile_order = use.order ? ctx->tileOrder.ptr : nullptr;
+            tp.tile_masks = use.masks ? ctx->tileMasks.ptr : nullptr;
+            tp.tile_spheres = use.lists ? ctx->tileSpheres.ptr : nullptr;
+            tp.sky_skip = use.sky_skip;
+            ctx->tileAcct.freshScans += ((uint64_t)tp.total_paths + 63u) / 64u;  // (all tiles: the statistics do not know about the shorter queue)
             if (nSky != 0u) tp.total_paths = (nFull - nSky) * 64u * spp;
             tp.samples = ctx->samples.ptr;
             tp.trav_out = nullptr;
@@ -1251,7 +1222,7 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
             if (nSky != 0u) {
                 const unsigned long long planes = (unsigned long long)nSky * spp;
                 hipLaunchKernelGGL(rtd::rt_sky_counters_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->counters.ptr, planes * 64ull,
-                                   ctx->lastTraceSky ? planes : 0ull);
+                                   ctx->tileAcct.lastTraceSky ? planes : 0ull);
                 RT_HIP(hipGetLastError());
             }
             RT_HIP(hipEventRecord(ev[1], ctx->stream));
@@ -2084,8 +2055,8 @@ int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
     if (rows == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: bad row set");
     RT_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = BuildTileMasks(ctx, rtseq::PictureKey{W, H, rs}, W * rows)) != RT_OK) return rc;
-    *n_tiles = ctx->tileMaskValid ? ctx->maskTiles : 0u;
+    if ((rc = BuildTileMasks(ctx, rtseq::PictureKey{W, H, rs}, W * rows, TileKnobsFromEnv())) != RT_OK) return rc;
+    *n_tiles = rttile::MaskTiles(ctx->tiles);
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (words && *n_tiles != 0u) {
         if (cap_tiles < *n_tiles) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: capacity too small");
@@ -2100,7 +2071,7 @@ int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
     if (scans) {
         unsigned long long c[4] = {0, 0, 0, 0};
         RT_HIP(hipMemcpy(c, ctx->counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
-        scans[0] = ctx->freshScans;  // host arithmetic: every block of 64 fresh paths of the last rt_render that launched
+        scans[0] = ctx->tileAcct.freshScans;  // host arithmetic: every block of 64 fresh paths of the last rt_render that launched
         scans[1] = c[3];
     }
     return RT_OK;
@@ -2113,8 +2084,8 @@ int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint
     if (rows == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres: bad row set");
     RT_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = BuildTileMasks(ctx, rtseq::PictureKey{W, H, rs}, W * rows)) != RT_OK) return rc;
-    *n_tiles = (ctx->tileMaskValid && ctx->maskSpheres != 0u) ? ctx->maskTiles : 0u;
+    if ((rc = BuildTileMasks(ctx, rtseq::PictureKey{W, H, rs}, W * rows, TileKnobsFromEnv())) != RT_OK) return rc;
+    *n_tiles = rttile::ListTiles(ctx->tiles);
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (lists && *n_tiles != 0u) {
         if (cap_tiles < *n_tiles) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_spheres: capacity too small");
@@ -2123,7 +2094,7 @@ int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint
     if (scans) {
         unsigned long long c[5] = {0, 0, 0, 0, 0};
         RT_HIP(hipMemcpy(c, ctx->counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
-        scans[0] = ctx->freshScans;
+        scans[0] = ctx->tileAcct.freshScans;
         scans[1] = c[3];
         scans[2] = c[4];
     }
@@ -2142,7 +2113,7 @@ int rt_unit_sky_planes(rt_ctx* ctx, uint64_t* planes) {
 
 int rt_unit_sky_excluded(rt_ctx* ctx, uint32_t* tiles) {
     if (!ctx || !tiles) return Fail(RT_ERR_INVALID_ARG, "rt_unit_sky_excluded: invalid argument");
-    *tiles = ctx->skyExcluded;
+    *tiles = ctx->tileAcct.skyExcluded;
     return RT_OK;
 }
 

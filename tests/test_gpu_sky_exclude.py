@@ -230,6 +230,43 @@ def test_resumed_accumulation(hip, monkeypatch, cover, cover_oracle):
 
 
 @pytest.mark.gpu
+def test_tables_rebuilt_for_another_picture_inside_an_accumulation(hip, monkeypatch, cover, cover_oracle):
+    """rt_unit_tile_spheres for 128x64 between the calls 1..3 and 3..5 rebuilds masks and lists for that picture and leaves order,
+    flags and count alone.  The continuing call must then take no table that is not its own picture's: no masks, no lists, no
+    shorter queue (0 tiles kept out) and no ray-less planes -- its launch traces every tile and writes the flagged tiles' planes with
+    the bits of the constant that the tile-aware accumulation still adds for them.  An accumulation started again finds the masks
+    rebuilt for its picture under the order's unchanged key, the count still known: the shorter queue from its first call on."""
+    from cpuraytracer_amd import _capi
+    _knobs(monkeypatch)
+    one = _second_render(hip, cover, W0, H0, 1, 1 + SPP0)
+    assert one.empty > 0 and one.excluded == one.empty
+    hip.render(W0, H0, 1, 3, DEPTH, SEED)
+    assert _excluded(hip) == one.empty
+    other = _list_lengths(hip, 128, 64, _capi.whole_image(64))
+    assert len(other) == 128 * 64 // 64
+    hip.render(W0, H0, 3, 5, DEPTH, SEED)
+    after4 = (_excluded(hip), _sky_planes(hip))
+    print("continued after the rebuild: excluded, ray-less planes = %s" % (after4,))
+    assert after4 == (0, 0)
+    hip.resolve()
+    h, l = hip.download()
+    _same(h, one.hdr, "continued after the rebuild vs one shot (HDR)")
+    _same(l, one.ldr, "continued after the rebuild vs one shot (LDR)")
+    _same(h, cover_oracle[0], "continued after the rebuild vs the oracle (HDR)")
+    _same(l, cover_oracle[1], "continued after the rebuild vs the oracle (LDR)")
+    hip.render(W0, H0, 1, 1 + SPP0, DEPTH, SEED)
+    after5 = (_excluded(hip), _sky_planes(hip))
+    print("started again after the rebuild: excluded, ray-less planes = %s, %d tiles have an empty list" % (after5, one.empty))
+    assert after5 == (one.empty, one.empty * SPP0)
+    hip.resolve()
+    h, l = hip.download()
+    _same(h, one.hdr, "started again after the rebuild vs one shot (HDR)")
+    _same(l, one.ldr, "started again after the rebuild vs one shot (LDR)")
+    _same(h, cover_oracle[0], "started again after the rebuild vs the oracle (HDR)")
+    _same(l, cover_oracle[1], "started again after the rebuild vs the oracle (LDR)")
+
+
+@pytest.mark.gpu
 def test_render_ahead(own, monkeypatch, cover, cover_oracle):
     """rt_set_frame_lookahead(4): the first 1-spp call traces four planes with one launch over the shorter queue, the next three
     calls only add their plane -- the flagged tiles' from the constant, which that launch never wrote."""
