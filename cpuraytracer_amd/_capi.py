@@ -65,6 +65,7 @@ RT_OK = 0
 RT_ERR_NO_DEVICE = 1
 RT_ERR_SEQUENCE = 6
 RT_SAMPLER_COSINE_HEMISPHERE, RT_SAMPLER_SQRT_DISK = 1, 2
+RT_TEMPORAL_FETCH_NEAREST, RT_TEMPORAL_FETCH_BILINEAR = 1, 4
 
 # every symbol include/rt_api.h declares
 EXPORTS = [
@@ -81,6 +82,7 @@ EXPORTS = [
     "rt_denoise_default_params", "rt_denoise", "rt_download_denoised", "rt_copy_denoised_to_device", "rt_unit_denoise_host", "rt_unit_denoise_forms",
     "rt_copy_moments_to_device", "rt_rowset_locate", "rt_denoise_shards", "rt_unit_denoise_shards_host",
     "rt_temporal_default_params", "rt_denoise_temporal", "rt_temporal_reset", "rt_download_temporal", "rt_unit_temporal_host",
+    "rt_temporal_default_params_fetch", "rt_denoise_temporal_fetch", "rt_unit_temporal_host_fetch",
 ]
 
 _lib = None
@@ -203,6 +205,13 @@ def load():
                                             C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtCamera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+    if hasattr(L, "rt_denoise_temporal_fetch"):
+        L.rt_temporal_default_params_fetch.argtypes = [C.c_uint32, C.POINTER(RtTemporalParams)]
+        L.rt_denoise_temporal_fetch.argtypes = [C.c_void_p, C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32, C.POINTER(C.c_double)]
+        L.rt_unit_temporal_host_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtCamera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -234,8 +243,19 @@ def temporal_params(**fields):
     return p
 
 
-def unit_temporal_host(hdr, sq, n, feat8, m, ids, W, H, camera, history=None, params=None, tparams=None, first_row=0):
-    """rt_unit_temporal_host over numpy strips of rows [first_row, first_row + rows) of the W x H image.  history: None (empty) or a dict
+def temporal_params_fetch(fetch, **fields):
+    """rt_temporal_default_params_fetch(fetch) with the given fields replaced."""
+    p = RtTemporalParams()
+    check(load().rt_temporal_default_params_fetch(fetch, C.byref(p)))
+    for k, v in fields.items():
+        if k not in dict(RtTemporalParams._fields_):
+            raise TypeError("rt_temporal_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def unit_temporal_host(hdr, sq, n, feat8, m, ids, W, H, camera, history=None, params=None, tparams=None, first_row=0, fetch=1):
+    """rt_unit_temporal_host_fetch (fetch 1, nearest: rt_unit_temporal_host's bits; 4: bilinear; tparams None: that fetch's defaults) over numpy strips of rows [first_row, first_row + rows) of the W x H image.  history: None (empty) or a dict
     with camera, state (rows, W, 4), guides (rows, W, 8), ids and len (rows, W).  Returns a dict: rgb, var (den and den_var), target,
     and state, guides, len, ids, camera -- the last five are the next call's history."""
     hdr = np.ascontiguousarray(hdr, dtype=np.float32)
@@ -255,10 +275,10 @@ def unit_temporal_host(hdr, sq, n, feat8, m, ids, W, H, camera, history=None, pa
                 np.ascontiguousarray(history["ids"], dtype=np.uint32), np.ascontiguousarray(history["len"], dtype=np.uint32)]
         assert keep[0].size == rows * W * 4 and keep[1].size == rows * W * 8 and keep[2].size == rows * W and keep[3].size == rows * W
         hs, hg, hi, hl = (a.ctypes.data for a in keep)
-    check(load().rt_unit_temporal_host(hdr.ctypes.data, sq.ctypes.data, n, feat8.ctypes.data, m, ids.ctypes.data, W, H, first_row, rows, C.byref(cam), hc,
-                                       hs, hg, hi, hl, C.byref(params) if params is not None else None,
-                                       C.byref(tparams) if tparams is not None else None, out["rgb"].ctypes.data, out["var"].ctypes.data,
-                                       out["state"].ctypes.data, out["guides"].ctypes.data, out["len"].ctypes.data, out["target"].ctypes.data))
+    check(load().rt_unit_temporal_host_fetch(hdr.ctypes.data, sq.ctypes.data, n, feat8.ctypes.data, m, ids.ctypes.data, W, H, first_row, rows, C.byref(cam),
+                                             hc, hs, hg, hi, hl, C.byref(params) if params is not None else None,
+                                             C.byref(tparams) if tparams is not None else None, int(fetch), out["rgb"].ctypes.data, out["var"].ctypes.data,
+                                             out["state"].ctypes.data, out["guides"].ctypes.data, out["len"].ctypes.data, out["target"].ctypes.data))
     out["ids"] = ids.reshape(rows, W).copy()
     out["camera"] = cam
     return out

@@ -20,9 +20,10 @@ static void Usage() {
               "                                PREFIX.normal.pfm (three channels), PREFIX.depth.pfm and PREFIX.coverage.pfm (one channel)\n"
               "               [--denoise-out file.ppm [--denoise-levels N]]   the picture after the feature-guided a-trous filter (rt_denoise, N = 1..5\n"
               "                                levels, default 3), written beside --out, which is unchanged; needs --spp >= 2\n"
-              "               [--orbit-frames K [--orbit-deg D]]   with --denoise-out: K pictures of --spp samples each (seed --seed + f) from a camera\n"
+              "               [--orbit-frames K [--orbit-deg D] [--orbit-fetch nearest|bilinear]]   with --denoise-out: K pictures of --spp samples each (seed --seed + f) from a camera\n"
               "                                that turns D degrees (default 0.5) per picture about the scene's look-at point, each followed by the\n"
-              "                                feature pass and rt_denoise_temporal; the last picture is written\n"
+              "                                feature pass and rt_denoise_temporal; the last picture is written.  --orbit-fetch bilinear\n"
+              "                                interpolates the history (rt_denoise_temporal_fetch with that fetch's defaults); default nearest\n"
               "               [--target-error T [--target-fraction F] [--max-spp N]]   render --frame-spp samples at a time until at most the\n"
               "                                fraction F (default 0) of the pixels has a relative error above T, or N (default --spp) is reached\n"
               "               [--noise-floor F]        added to a pixel's r + g + b before the relative error divides by it (default 0.01)");
@@ -37,6 +38,7 @@ int main(int argc, char** argv) {
     uint32_t orbitFrames = 0;
     double orbitDeg = 0.5;
     bool orbitSet = false;
+    uint32_t orbitFetch = RT_TEMPORAL_FETCH_NEAREST;
     float targetError = 0.f;
     double targetFraction = 0.0;
     uint32_t maxSpp = 0;
@@ -70,6 +72,12 @@ int main(int argc, char** argv) {
         else if (k == "--denoise-levels") denoiseLevels = (uint32_t)std::atoi(val());
         else if (k == "--orbit-frames") { orbitFrames = (uint32_t)std::atoi(val()); orbitSet = true; }
         else if (k == "--orbit-deg") { orbitDeg = std::atof(val()); orbitSet = true; }
+        else if (k == "--orbit-fetch") {
+            const std::string v = val();
+            if (v != "nearest" && v != "bilinear") { Usage(); return 2; }
+            orbitFetch = v == "bilinear" ? RT_TEMPORAL_FETCH_BILINEAR : RT_TEMPORAL_FETCH_NEAREST;
+            orbitSet = true;
+        }
         else if (k == "--target-error") { targetError = (float)std::atof(val()); targetSet = true; }
         else if (k == "--target-fraction") targetFraction = std::atof(val());
         else if (k == "--max-spp") maxSpp = (uint32_t)std::atoi(val());
@@ -89,7 +97,7 @@ int main(int argc, char** argv) {
     if (st.samplesPerFrame == 0 || spp == 0 || st.k_backbufferWidth <= 0 || st.k_backbufferHeight <= 0) { Usage(); return 2; }
     if (spp % st.samplesPerFrame != 0) st.samplesPerFrame = 1;
     if (orbitSet && (denoiseOut.empty() || gpus > 0 || targetSet)) {
-        std::fprintf(stderr, "spheres: --orbit-frames and --orbit-deg need --denoise-out and are not available with --gpus or --target-error\n");
+        std::fprintf(stderr, "spheres: --orbit-frames, --orbit-deg and --orbit-fetch need --denoise-out and are not available with --gpus or --target-error\n");
         return 2;
     }
     if (orbitSet && (orbitFrames == 0 || spp < 2 || !(orbitDeg == orbitDeg))) { Usage(); return 2; }
@@ -138,7 +146,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "spheres: %s\n", e.what());
         return 1;
     }
-    const int rc = orbitSet ? app.RunOrbit(orbitFrames, orbitDeg, spp, denoiseLevels)
+    const int rc = orbitSet ? app.RunOrbit(orbitFrames, orbitDeg, spp, denoiseLevels, orbitFetch)
                             : (targetSet ? app.RunUntil(targetError, targetFraction, maxSpp) : app.Run(spp / st.samplesPerFrame));
     if (rc != 0) return rc;
     if (!noiseOut.empty() && !app.WriteNoisePFM(noiseOut)) {

@@ -22,6 +22,10 @@ void RunLevelsHost(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseSt
 // tparams (NULL: the defaults) into T; outside their domain: RT_ERR_INVALID_ARG with a message that starts with who.
 int CheckTemporalParams(const char* who, const rt_temporal_params* tparams, rtd::TemporalParams* T);
 
+// The same with the fetch chosen: a fetch that is neither RT_TEMPORAL_FETCH_NEAREST nor _BILINEAR is RT_ERR_INVALID_ARG, and NULL takes
+// that fetch's defaults (rt_temporal_default_params_fetch).
+int CheckTemporalParamsFetch(const char* who, const rt_temporal_params* tparams, uint32_t fetch, rtd::TemporalParams* T);
+
 // The part of a camera record the reprojection reads.
 rtd::TemporalCam CamOf(const rt_camera& c);
 

@@ -65,6 +65,7 @@ struct Temporal {
     rtd::TemporalGeom geom;
     rtd::TemporalCam cam, camPrev;
     rtd::TemporalParams params;
+    uint32_t fetch;        // rtd::kTemporalFetchNearest or kTemporalFetchBilinear: which prepare kernel reads the history
     bool hasPrev;          // false: an empty history (prev is not read)
     TemporalSet prev, next;
     uint32_t* target;      // [npix] out

@@ -1,7 +1,8 @@
-// rt_temporal_host.cpp -- temporal accumulation (../rt_temporal.h) compiled for the host: rt_unit_temporal_host, the twin the device
-// is compared with bit for bit -- one frame step (prepare, reproject, gather, validate, blend) plus the levels of
-// rt_unit_denoise_host's filter (rtdn::RunLevelsHost, rt_denoise_host.cpp) -- and the parameter defaults.  Plain C++ with no HIP
-// header, under the same floating-point contract as the kernels (-ffp-contract=off, IEEE division).  Needs no GPU.
+// rt_temporal_host.cpp -- temporal accumulation (../rt_temporal.h) compiled for the host: rt_unit_temporal_host and
+// rt_unit_temporal_host_fetch, the twins the device is compared with bit for bit -- one frame step (prepare, reproject, gather with
+// the nearest or the bilinear fetch, validate, blend) plus the levels of rt_unit_denoise_host's filter (rtdn::RunLevelsHost,
+// rt_denoise_host.cpp) -- and the parameter defaults of either fetch.  Plain C++ with no HIP header, under the same floating-point
+// contract as the kernels (-ffp-contract=off, IEEE division).  Needs no GPU.
 #include <cstddef>
 #include <string>
 #include <vector>
@@ -28,6 +29,14 @@ int CheckTemporalParams(const char* who_, const rt_temporal_params* tparams, rtd
     return RT_OK;
 }
 
+int CheckTemporalParamsFetch(const char* who_, const rt_temporal_params* tparams, uint32_t fetch, rtd::TemporalParams* T) {
+    if (!rtd::temporal_fetch_ok(fetch))
+        return Fail(RT_ERR_INVALID_ARG, std::string(who_) + ": fetch must be RT_TEMPORAL_FETCH_NEAREST (1) or RT_TEMPORAL_FETCH_BILINEAR (4)");
+    rt_temporal_params def;
+    rt_temporal_default_params_fetch(fetch, &def);
+    return CheckTemporalParams(who_, tparams ? tparams : &def, T);
+}
+
 rtd::TemporalCam CamOf(const rt_camera& c) {
     rtd::TemporalCam C;
     rtd::temporal_cam(c.origin, c.x, c.y, c.origin_image_plane, C);
@@ -48,12 +57,24 @@ int rt_temporal_default_params(rt_temporal_params* out) {
     return RT_OK;
 }
 
-int rt_unit_temporal_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W, uint32_t H,
-                          uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
-                          const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
-                          const rt_temporal_params* tparams, float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len,
-                          uint32_t* out_target) {
-    const char* who = "rt_unit_temporal_host";
+int rt_temporal_default_params_fetch(uint32_t fetch, rt_temporal_params* out) {
+    if (!out) return Fail(RT_ERR_INVALID_ARG, "rt_temporal_default_params_fetch: null argument");
+    if (!rtd::temporal_fetch_ok(fetch))
+        return Fail(RT_ERR_INVALID_ARG, "rt_temporal_default_params_fetch: fetch must be RT_TEMPORAL_FETCH_NEAREST (1) or RT_TEMPORAL_FETCH_BILINEAR (4)");
+    rt_temporal_default_params(out);
+    // (docs/EXPERIMENTS.md, the fetch x max_history grid: interpolated taps drift less, so one more frame of history still pays)
+    if (fetch == RT_TEMPORAL_FETCH_BILINEAR) out->max_history = 3;
+    return RT_OK;
+}
+
+}  // extern "C"
+
+// One frame step plus the levels, for either fetch (who: the entry's name for the messages).
+static int TemporalHost(const char* who, const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W,
+                        uint32_t H, uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
+                        const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
+                        const rt_temporal_params* tparams, uint32_t fetch, float* out_rgb, float* out_var, float* out_state4, float* out_guides8,
+                        uint32_t* out_len, uint32_t* out_target) {
     if (!hdr || !sq || !feat8 || !ids || !camera) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null buffer");
     if (hist_len && (!hist_camera || !hist_state4 || !hist_guides8 || !hist_ids))
         return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a history (hist_len != NULL) needs its camera, state, guides and ids");
@@ -67,7 +88,7 @@ int rt_unit_temporal_host(const float* hdr, const float* sq, uint32_t n, const f
     if (!rtd::denoise_params_ok(P))
         return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
     rtd::TemporalParams T{};
-    const int rc = rtdn::CheckTemporalParams(who, tparams, &T);
+    const int rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &T);
     if (rc != RT_OK) return rc;
     if (n < 2) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the noise estimate needs at least 2 samples per pixel");
     if (m == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the feature strips hold no sample");
@@ -85,7 +106,30 @@ int rt_unit_temporal_host(const float* hdr, const float* sq, uint32_t n, const f
             uint32_t len = 1u, target = rtd::kTemporalNoTarget;
             uint32_t xi = 0, yi = 0;
             float dist = 0.f;
-            if (hist_len && rtd::temporal_reproject(G, C, Cp, x, first_row + ly, gp, xi, yi, dist)) {
+            float fx = 0.f, fy = 0.f;
+            if (hist_len && fetch == RT_TEMPORAL_FETCH_BILINEAR) {
+                if (rtd::temporal_reproject_point(G, C, Cp, x, first_row + ly, gp, fx, fy, xi, yi, dist)) {
+                    rtd::TemporalTaps B;
+                    rtd::temporal_taps(fx, fy, xi, yi, B);
+                    rtd::TemporalGather S;
+                    rtd::temporal_gather_begin(S);
+                    for (int k = 0; k < 4; ++k) {
+                        uint32_t q = 0;
+                        const float w = rtd::temporal_tap_weight(B, k);
+                        if (!(rtd::temporal_tap_index(G, B, k, q) && w > 0.f)) continue;
+                        if (!rtd::temporal_validate(T, gp, ids[p], dist, hist_guides8 + 8 * (size_t)q, hist_ids[q], hist_len[q])) continue;
+                        rtd::DenoiseState st;
+                        for (int c = 0; c < 3; ++c) st.c[c] = hist_state4[4 * (size_t)q + c];
+                        st.v = hist_state4[4 * (size_t)q + 3];
+                        rtd::temporal_gather_tap(S, w, st, hist_len[q], q);
+                    }
+                    rtd::DenoiseState sh{};
+                    uint32_t lh = 0u;
+                    const bool ok = rtd::temporal_gather_finish(S, sh, lh);
+                    len = rtd::temporal_blend(T, ok, s, sh, lh);
+                    if (ok) target = S.target;
+                }
+            } else if (hist_len && rtd::temporal_reproject(G, C, Cp, x, first_row + ly, gp, xi, yi, dist)) {
                 const size_t q = (size_t)(yi - first_row) * W + xi;
                 rtd::DenoiseState sh;
                 for (int k = 0; k < 3; ++k) sh.c[k] = hist_state4[4 * q + k];
@@ -114,6 +158,26 @@ int rt_unit_temporal_host(const float* hdr, const float* sq, uint32_t n, const f
             for (size_t i = 0; i < npix; ++i) out_var[i] = var[i];
     }
     return RT_OK;
+}
+
+extern "C" {
+
+int rt_unit_temporal_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W, uint32_t H,
+                          uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
+                          const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
+                          const rt_temporal_params* tparams, float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len,
+                          uint32_t* out_target) {
+    return TemporalHost("rt_unit_temporal_host", hdr, sq, n, feat8, m, ids, W, H, first_row, num_rows, camera, hist_camera, hist_state4, hist_guides8, hist_ids,
+                        hist_len, params, tparams, RT_TEMPORAL_FETCH_NEAREST, out_rgb, out_var, out_state4, out_guides8, out_len, out_target);
+}
+
+int rt_unit_temporal_host_fetch(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W, uint32_t H,
+                                uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
+                                const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
+                                const rt_temporal_params* tparams, uint32_t fetch, float* out_rgb, float* out_var, float* out_state4, float* out_guides8,
+                                uint32_t* out_len, uint32_t* out_target) {
+    return TemporalHost("rt_unit_temporal_host_fetch", hdr, sq, n, feat8, m, ids, W, H, first_row, num_rows, camera, hist_camera, hist_state4, hist_guides8,
+                        hist_ids, hist_len, params, tparams, fetch, out_rgb, out_var, out_state4, out_guides8, out_len, out_target);
 }
 
 }  // extern "C"

@@ -284,7 +284,7 @@ rt_camera OrbitCamera(const rt_camera& camera, double degrees, const float pivot
     return out;
 }
 
-int SpheresApp::RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels) noexcept {
+int SpheresApp::RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels, uint32_t fetch) noexcept {
     try {
         const uint32_t W = (uint32_t)GetBackBufferWidth(), H = (uint32_t)GetBackBufferHeight();
         const rt_rowset rs = m_hasRowset ? m_rowset : rt_rowset{0, H, H, 0, 1};
@@ -313,7 +313,10 @@ int SpheresApp::RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint
             RT_CALL(rt_resolve(m_device, spp));
             m_lastStats.ms_resolve = rt_last_resolve_ms(m_device);
             RT_CALL(rt_render_features(m_device, W, H, rs, 1u, 1u + spp, nullptr));
-            RT_CALL(rt_denoise_temporal(m_device, &params, nullptr, nullptr));
+            if (fetch == RT_TEMPORAL_FETCH_NEAREST)
+                RT_CALL(rt_denoise_temporal(m_device, &params, nullptr, nullptr));
+            else
+                RT_CALL(rt_denoise_temporal_fetch(m_device, &params, nullptr, fetch, nullptr));
         }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "spheres: %s\n", e.what());

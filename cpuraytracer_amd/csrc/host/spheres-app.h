@@ -80,8 +80,9 @@ public:
     // `frames` pictures of `spp` samples each (samples 1 .. spp, render seed renderSeed + f) from a camera that has turned f * degPerFrame
     // degrees about the vertical axis through the scene's look-at point (OrbitCamera); every frame is an upload, a render, the feature
     // pass and rt_denoise_temporal (the defaults; levels != 0 replaces the number of levels), so the history follows the camera.
-    // WritePPM then writes the last frame, WriteTemporalPPM its temporally accumulated and filtered picture.
-    int RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels) noexcept;
+    // WritePPM then writes the last frame, WriteTemporalPPM its temporally accumulated and filtered picture.  fetch: RT_TEMPORAL_FETCH_NEAREST
+    // is that call; RT_TEMPORAL_FETCH_BILINEAR goes through rt_denoise_temporal_fetch with that fetch's defaults.
+    int RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels, uint32_t fetch = RT_TEMPORAL_FETCH_NEAREST) noexcept;
     bool WriteTemporalPPM(const std::string& path) const;
     const std::vector<XMVECTOR>& Hdr() const { return m_backbufferHdr; }
     const std::vector<XMCOLOR>& Ldr() const { return m_backbufferLdr; }

@@ -1606,18 +1606,19 @@ int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise
 
 // rt_denoise with the temporal step in its prepare pass (rt_temporal.h).  The history is the context's: set tmpCur is read, the other
 // set is written and becomes tmpCur once everything is enqueued.  Every refusal comes before the first change.
-int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, double* out_ms) {
+// (who: the entry's name for the messages; fetch: which prepare kernel reads the history, and whose defaults tparams == NULL takes)
+static int DenoiseTemporal(rt_ctx* ctx, const char* who, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms) {
     rtd::DenoiseParams P{};
-    int rc = DenoiseParamsReady(ctx, "rt_denoise_temporal", params, &P);
+    int rc = DenoiseParamsReady(ctx, who, params, &P);
     if (rc != RT_OK) return rc;
     rtd::TemporalParams T{};
-    if ((rc = rtdn::CheckTemporalParams("rt_denoise_temporal", tparams, &T)) != RT_OK) return rc;
-    if ((rc = DenoisePictureReady(ctx, "rt_denoise_temporal")) != RT_OK) return rc;
+    if ((rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &T)) != RT_OK) return rc;
+    if ((rc = DenoisePictureReady(ctx, who)) != RT_OK) return rc;
     const rtseq::PictureKey& pic = ctx->seq.pic;
     const uint32_t W = pic.W, rows = ctx->seq.rows;
     const rtd::TemporalGeom G{W, pic.H, pic.rs.first_row, rows};
     if (!rtd::temporal_geom_ok(G) || rows != pic.rs.num_rows)
-        return Fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: a picture wider or taller than 2^24, or a strip that is not its row range");
+        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a picture wider or taller than 2^24, or a strip that is not its row range");
     const size_t npix = (size_t)W * rows;
     const bool hasPrev = ctx->tmpValid && ctx->tmpPic == pic;
     if (!hasPrev) ctx->tmpValid = false;  // (a Reserve below may let the old sets go: they were of another picture)
@@ -1637,6 +1638,7 @@ int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_t
     rtd::temporal_cam(b.cam_o, b.cam_x, b.cam_y, b.cam_oip, Q.cam);
     Q.camPrev = hasPrev ? ctx->tmpCam : Q.cam;
     Q.params = T;
+    Q.fetch = fetch;
     Q.hasPrev = hasPrev;
     const uint32_t cur = ctx->tmpCur & 1u, nxt = cur ^ 1u;
     const auto setOf = [](rt_ctx::TemporalSet& t) { return rtdn::TemporalSet{t.state.ptr, {t.guide[0].ptr, t.guide[1].ptr}, t.ids.ptr, t.len.ptr}; };
@@ -1645,12 +1647,21 @@ int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_t
     Q.target = ctx->tmpTarget.ptr;
     ctx->tmpValid = false;  // the history is being rewritten, until everything is enqueued
     if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
-    if ((rc = DenoiseFinish(ctx, "rt_denoise_temporal", S, rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms), out_ms)) != RT_OK) return rc;
+    if ((rc = DenoiseFinish(ctx, who, S, rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms), out_ms)) != RT_OK) return rc;
     ctx->tmpCur = nxt;
     ctx->tmpPic = pic;
     ctx->tmpCam = Q.cam;
     ctx->tmpValid = true;
     return RT_OK;
+}
+
+int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, double* out_ms) {
+    return DenoiseTemporal(ctx, "rt_denoise_temporal", params, tparams, RT_TEMPORAL_FETCH_NEAREST, out_ms);
+}
+
+// The same call with the way the history is fetched chosen: 1 runs the kernel above, 4 the bilinear one; the history is one state.
+int rt_denoise_temporal_fetch(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms) {
+    return DenoiseTemporal(ctx, "rt_denoise_temporal_fetch", params, tparams, fetch, out_ms);
 }
 
 int rt_temporal_reset(rt_ctx* ctx) {

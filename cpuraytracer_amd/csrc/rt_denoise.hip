@@ -122,6 +122,73 @@ __global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const 
     A.target[p] = target;
 }
 
+// The bilinear fetch (rt_temporal.h): the same pass, but the history is read at the four pixels around the reprojected point.  The two
+// taps of a row are adjacent (32 bytes per float4 plane) and under small motion a wave's taps are two row segments its lanes share.
+// All four taps' loads are issued before the first is used: a tap outside the strip loads the pixel's own index instead (pix < npix, a
+// contiguous read) and what it loaded is dropped, so no load waits for a test and none leaves the arrays -- a tap inside has q < npix by
+// temporal_tap_index.  Only taps that take part are added (temporal_gather_tap).  Writes as in the nearest kernel.
+__global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_bilinear_kernel(const TemporalArgs A) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    const size_t p = pix;
+    const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
+    const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
+    const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
+    const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+    const uint32_t id = A.ids[p];
+    DenoiseState s;
+    float g[8];
+    denoise_prepare(h, q3, A.n, f, A.m, s, g);
+    uint32_t len = 1u, target = kTemporalNoTarget;
+    if (A.hasPrev) {
+        const uint32_t ly = pix / A.G.W, x = pix - ly * A.G.W;
+        uint32_t xi = 0, yi = 0;
+        float fx = 0.f, fy = 0.f, dist = 0.f;
+        if (temporal_reproject_point(A.G, A.C, A.Cp, x, A.G.first_row + ly, g, fx, fy, xi, yi, dist)) {
+            TemporalTaps B;
+            temporal_taps(fx, fy, xi, yi, B);
+            bool in[4];
+            uint32_t q[4];
+            float4 hs[4], ha[4], hb[4];
+            uint32_t idh[4], lenh[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                q[k] = pix;
+                in[k] = temporal_tap_index(A.G, B, k, q[k]);
+                const uint32_t r = in[k] ? q[k] : pix;
+                hs[k] = A.hS[r];
+                ha[k] = A.hG0[r];
+                hb[k] = A.hG1[r];
+                idh[k] = A.hId[r];
+                lenh[k] = A.hLen[r];
+            }
+            TemporalGather S;
+            temporal_gather_begin(S);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float w = temporal_tap_weight(B, k);
+                if (!(in[k] && w > 0.f)) continue;
+                DenoiseState st;
+                float gh[8];
+                unpack(hs[k], ha[k], hb[k], st, gh);
+                if (!temporal_validate(A.T, g, id, dist, gh, idh[k], lenh[k])) continue;
+                temporal_gather_tap(S, w, st, lenh[k], q[k]);
+            }
+            DenoiseState sh{};
+            uint32_t lh = 0u;
+            const bool ok = temporal_gather_finish(S, sh, lh);
+            len = temporal_blend(A.T, ok, s, sh, lh);
+            if (ok) target = S.target;
+        }
+    }
+    A.oS[p] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
+    A.oG0[p] = make_float4(g[0], g[1], g[2], g[3]);
+    A.oG1[p] = make_float4(g[4], g[5], g[6], g[7]);
+    A.oId[p] = id;
+    A.oLen[p] = len;
+    A.target[p] = target;
+}
+
 // One level.  Thread (tx, ty) of the 32 x 8 workgroup owns pixel (32 bx + tx, 8 by + ty); its 25 taps lie (a - 2) step rows and
 // (b - 2) step columns away, a outer, b inner; a tap outside the strip is skipped, never clamped.
 //   kStaged: the tile and its 2 step halo go into LDS first as three planes of float4 with contiguous rows (a wave stages two rows
@@ -292,7 +359,10 @@ int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, cons
     A.oId = t.next.ids;
     A.oLen = t.next.len;
     A.target = t.target;
-    hipLaunchKernelGGL(rtd::rt_denoise_prepare_temporal_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, A);
+    if (t.fetch == rtd::kTemporalFetchBilinear)
+        hipLaunchKernelGGL(rtd::rt_denoise_prepare_temporal_bilinear_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, A);
+    else
+        hipLaunchKernelGGL(rtd::rt_denoise_prepare_temporal_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, A);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     return LaunchLevels(st, s, A.oS, A.oG0, A.oG1, P, stageKnob, forms);

@@ -116,6 +116,126 @@ RT_DEV uint32_t temporal_blend(const TemporalParams& T, bool accepted, DenoiseSt
     return l + 1u;
 }
 
+// ---- the bilinear fetch (RT_TEMPORAL_FETCH_BILINEAR): the history is read at the four pixels whose centres surround the reprojected
+// point instead of the one pixel that contains it.  Everything above is used as it stands.
+constexpr uint32_t kTemporalFetchNearest = 1, kTemporalFetchBilinear = 4;
+
+RT_DEV bool temporal_fetch_ok(uint32_t fetch) { return fetch == kTemporalFetchNearest || fetch == kTemporalFetchBilinear; }
+
+// temporal_reproject that also yields the point itself, (fx, fy) in pixel units of Cp's picture: the same operations in the same order
+// (kept beside it, not merged into it: the nearest fetch's code stays what it was), so xi, yi, dist and the refusals are its bits.
+RT_DEV bool temporal_reproject_point(const TemporalGeom& G, const TemporalCam& C, const TemporalCam& Cp, uint32_t x, uint32_t y, const float g[8], float& fx,
+                                     float& fy, uint32_t& xi, uint32_t& yi, float& dist) {
+    const float u = ((float)x + 0.5f) / (float)G.W, vv = ((float)y + 0.5f) / (float)G.H;
+    const float nx = 2.f * u - 1.f, ny = -2.f * vv + 1.f;
+    float d[3], q[3];
+    for (int k = 0; k < 3; ++k) d[k] = (C.w[k] + nx * C.x[k]) + ny * C.y[k];
+    const float cov = g[7];
+    dist = 0.f;
+    if (cov > 0.f) {
+        const float z = g[6] / cov;
+        const float s = z / sqrt_rn(temporal_dot(d, d));
+        for (int k = 0; k < 3; ++k) {
+            const float P = C.o[k] + s * d[k];
+            q[k] = P - Cp.o[k];
+        }
+        dist = sqrt_rn(temporal_dot(q, q));
+    } else {
+        for (int k = 0; k < 3; ++k) q[k] = d[k];
+    }
+    const float zw = temporal_dot(q, Cp.w) / temporal_dot(Cp.w, Cp.w);
+    if (!(zw > 0.f)) return false;
+    const float px = (temporal_dot(q, Cp.x) / temporal_dot(Cp.x, Cp.x)) / zw;
+    const float py = (temporal_dot(q, Cp.y) / temporal_dot(Cp.y, Cp.y)) / zw;
+    fx = ((px + 1.f) * 0.5f) * (float)G.W;
+    fy = ((1.f - py) * 0.5f) * (float)G.H;
+    if (!(fx >= 0.f && fx < (float)G.W)) return false;
+    if (!(fy >= (float)G.first_row && fy < (float)(G.first_row + G.num_rows))) return false;
+    xi = (uint32_t)fx;
+    yi = (uint32_t)fy;
+    return true;
+}
+
+// The four taps of an accepted point: pixel centres lie at +0.5, so the point lies between the centres of columns x0 and x0 + 1, tx of
+// the way from the first to the second (0 <= tx <= 1: rx + 0.5f may round up to 1, and that tap (0, .) then weighs 0); rows likewise.  x0 = -1 where the point lies left of column 0's centre and y0 =
+// first_row - 1 above the strip's first centre: those taps are outside.  (fx - (float)xi is exact: xi <= fx < xi + 1 < 2^24.)
+struct TemporalTaps {
+    int32_t x0, y0;  // column and IMAGE row of tap (0, 0)
+    float tx, ty;
+};
+
+RT_DEV void temporal_taps(float fx, float fy, uint32_t xi, uint32_t yi, TemporalTaps& B) {
+    const float rx = fx - (float)xi, ry = fy - (float)yi;
+    if (rx >= 0.5f) {
+        B.x0 = (int32_t)xi;
+        B.tx = rx - 0.5f;
+    } else {
+        B.x0 = (int32_t)xi - 1;
+        B.tx = rx + 0.5f;
+    }
+    if (ry >= 0.5f) {
+        B.y0 = (int32_t)yi;
+        B.ty = ry - 0.5f;
+    } else {
+        B.y0 = (int32_t)yi - 1;
+        B.ty = ry + 0.5f;
+    }
+}
+
+// Tap k = 0..3 is (i, j) = (k & 1, k >> 1): (0,0) (1,0) (0,1) (1,1).
+RT_DEV float temporal_tap_weight(const TemporalTaps& B, int k) {
+    const float wx = (k & 1) ? B.tx : 1.f - B.tx;
+    const float wy = (k >> 1) ? B.ty : 1.f - B.ty;
+    return wx * wy;
+}
+
+// Whether tap k lies inside the strip, and then its index q = (qy - first_row)*W + qx in the history's arrays.
+RT_DEV bool temporal_tap_index(const TemporalGeom& G, const TemporalTaps& B, int k, uint32_t& q) {
+    const int32_t qx = B.x0 + (k & 1), qy = B.y0 + (k >> 1);
+    if (!(qx >= 0 && (uint32_t)qx < G.W)) return false;
+    if (!(qy >= (int32_t)G.first_row && (uint32_t)qy < G.first_row + G.num_rows)) return false;
+    q = ((uint32_t)qy - G.first_row) * G.W + (uint32_t)qx;
+    return true;
+}
+
+// The sums over the taps that take part: inside the strip, w > 0 and temporal_validate -- the caller's business, tap by tap.  A tap
+// that does not take part is never added, so nothing of it (an Inf, a NaN) reaches the result.
+struct TemporalGather {
+    float sc[3], sv, sw, wbest;
+    uint32_t lmin, target;
+};
+
+RT_DEV void temporal_gather_begin(TemporalGather& S) {
+    S.sc[0] = S.sc[1] = S.sc[2] = 0.f;
+    S.sv = 0.f;
+    S.sw = 0.f;
+    S.wbest = 0.f;
+    S.lmin = 0xffffffffu;
+    S.target = kTemporalNoTarget;
+}
+
+// (w > 0 for every tap that gets here, so the first makes itself the target; later ones only with a strictly greater weight)
+RT_DEV void temporal_gather_tap(TemporalGather& S, float w, const DenoiseState& sh, uint32_t lenh, uint32_t q) {
+    for (int k = 0; k < 3; ++k) S.sc[k] = S.sc[k] + w * sh.c[k];
+    S.sv = S.sv + (w * w) * sh.v;
+    S.sw = S.sw + w;
+    S.lmin = lenh < S.lmin ? lenh : S.lmin;
+    if (w > S.wbest) {
+        S.wbest = w;
+        S.target = q;
+    }
+}
+
+// false: no tap took part (rejected).  true: the history's value at the point -- colour sum(w c)/sw, variance sum(w^2 v)/sw^2 (the
+// a-trous's convention, rt_denoise.h denoise_finish), length the shortest of the taps -- for the unchanged temporal_blend.
+RT_DEV bool temporal_gather_finish(const TemporalGather& S, DenoiseState& sh, uint32_t& lenh) {
+    if (!(S.sw > 0.f)) return false;
+    for (int k = 0; k < 3; ++k) sh.c[k] = S.sc[k] / S.sw;
+    sh.v = S.sv / (S.sw * S.sw);
+    lenh = S.lmin;
+    return true;
+}
+
 // max_history 1..64; every tolerance finite and >= 0
 RT_DEV bool temporal_params_ok(const TemporalParams& T) {
     const float t[3] = {T.depth_tol, T.normal_tol, T.coverage_tol};

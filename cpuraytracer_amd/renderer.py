@@ -255,15 +255,17 @@ class HipRenderer:
         return ms.value if timed else None
 
     # ---- temporal accumulation (rt_api.h "temporal accumulation")
-    def denoise_temporal(self, params=None, tparams=None, timed=False):
+    def denoise_temporal(self, params=None, tparams=None, timed=False, fetch=1):
         """rt_denoise_temporal: denoise() with the previous call's pre-filter state reprojected into the uploaded scene's camera,
         validated against the guides and blended in before the levels.  The history survives upload() -- a camera move is an upload
         -- and starts empty after temporal_reset() or when the picture's size or row set changes; on an empty history the result is
         denoise()'s.  tparams: an RtTemporalParams (_capi.temporal_params(max_history=..., ...)) or None for the defaults; params and
-        timed as in denoise().  download_denoised() serves the result."""
+        timed as in denoise().  download_denoised() serves the result.  fetch (rt_denoise_temporal_fetch): 1, nearest, is
+        rt_denoise_temporal's bits; 4, bilinear, interpolates the history from the four pixels around the reprojected point.  tparams
+        None means that fetch's defaults (_capi.temporal_params_fetch)."""
         ms = C.c_double(0.0)
-        check(self._L.rt_denoise_temporal(self._h, C.byref(params) if params is not None else None,
-                                          C.byref(tparams) if tparams is not None else None, C.byref(ms) if timed else None))
+        check(self._L.rt_denoise_temporal_fetch(self._h, C.byref(params) if params is not None else None,
+                                                C.byref(tparams) if tparams is not None else None, int(fetch), C.byref(ms) if timed else None))
         self.denoised_W, self.denoised_rows = self.W, self.rows
         self.temporal_W, self.temporal_rows = self.W, self.rows
         return ms.value if timed else None

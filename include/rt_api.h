@@ -407,6 +407,24 @@ int rt_temporal_reset(rt_ctx* ctx);
 /* The history as the last rt_denoise_temporal left it: state4 = W*rows*4 floats (c'.rgb, v'), len and target = W*rows words each.  Any
  * pointer may be NULL.  RT_ERR_SEQUENCE while the history is empty. */
 int rt_download_temporal(rt_ctx* ctx, float* state4, uint32_t* len, uint32_t* target);
+/* The way the history is fetched, chosen per call.  RT_TEMPORAL_FETCH_NEAREST is everything above.  RT_TEMPORAL_FETCH_BILINEAR reads
+ * the four pixels whose centres surround the reprojected point, so that a sample k calls old is not up to k/2 pixels off.  For a point
+ * the reprojection accepts (fx, fy, xi, yi, dist as above), in the same arithmetic:
+ *   rx = fx - (float)xi (exact);  rx >= 0.5f: x0 = xi, tx = rx - 0.5f;  else: x0 = xi - 1 (may be -1), tx = rx + 0.5f;  ry, y0, ty likewise
+ *   taps in the order (i, j) = (0,0) (1,0) (0,1) (1,1):  qx = x0 + i, qy = y0 + j,  w = (i ? tx : 1.f - tx) * (j ? ty : 1.f - ty)
+ *   a tap takes part iff 0 <= qx < W, first_row <= qy < first_row + num_rows, w > 0.f and it passes the validation above (the current
+ *   pixel against the history's pixel q, with the same dist) -- a tap that does not is never added, so an Inf or NaN there reaches nothing:
+ *     sc[k] = sc[k] + w*ch(q)[k];  sv = sv + (w*w)*vh(q);  sw = sw + w;  lmin = min(lmin, lenh(q))        (sums start at +0)
+ *   accepted iff sw > 0.f: ch[k] = sc[k]/sw, vh = sv/(sw*sw) (the filter's own rule for a weighted mean's variance), lenh = lmin, and the
+ *   blend above; target = the index of the participating tap of the greatest w, the first in tap order on a tie.  Rejected: as above.
+ * The history is the same state whichever fetch wrote it: calls may alternate. */
+enum { RT_TEMPORAL_FETCH_NEAREST = 1, RT_TEMPORAL_FETCH_BILINEAR = 4 };
+/* rt_temporal_default_params for a fetch: 1 gives its values, 4 the same tolerances with max_history = 3 (docs/EXPERIMENTS.md: the
+ * best row of the fetch x max_history grid).  Any other fetch: RT_ERR_INVALID_ARG.  Needs no GPU. */
+int rt_temporal_default_params_fetch(uint32_t fetch, rt_temporal_params* out);
+/* rt_denoise_temporal with the fetch chosen: its preconditions, refusals, snapshot and history lifetime, every refusal before the first
+ * change.  tparams == NULL: that fetch's defaults.  fetch neither 1 nor 4: RT_ERR_INVALID_ARG.  Fetch 1 gives rt_denoise_temporal's bits. */
+int rt_denoise_temporal_fetch(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms);
 
 /* Replaces the transform(par) tonemap (spheres-app.cpp:186-214): hdr / n_samples,
  * ACES fit, gamma 1/2.2, XMStoreColor.  n_samples == 0 uses the accumulated count. */
@@ -549,6 +567,13 @@ int rt_unit_temporal_host(const float* hdr, const float* sq, uint32_t n, const f
                           const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
                           const rt_temporal_params* tparams, float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len,
                           uint32_t* out_target);
+/* rt_unit_temporal_host with the fetch chosen (tparams == NULL: that fetch's defaults; fetch neither 1 nor 4: RT_ERR_INVALID_ARG): the
+ * twin of rt_denoise_temporal_fetch.  Fetch 1 gives rt_unit_temporal_host's bits. */
+int rt_unit_temporal_host_fetch(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W, uint32_t H,
+                                uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
+                                const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
+                                const rt_temporal_params* tparams, uint32_t fetch, float* out_rgb, float* out_var, float* out_state4, float* out_guides8,
+                                uint32_t* out_len, uint32_t* out_target);
 /* Which form each level of the last rt_denoise, rt_denoise_shards or rt_denoise_temporal took: out[l] = 0 the level did not run, 1 its taps were read from
  * global memory, 2 from a tile staged in LDS. */
 int rt_unit_denoise_forms(rt_ctx* ctx, uint32_t out[5]);
