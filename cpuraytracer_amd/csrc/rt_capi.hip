@@ -14,6 +14,8 @@
 #include <string>
 #include <unordered_map>
 #include <array>
+#include <initializer_list>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -48,10 +50,16 @@ namespace {
         }                                                                                                        \
     } while (0)
 
+// Device memory with one owner: freed when its owner goes -- a member of rt_ctx inside `delete ctx` (rt_destroy), a local of a unit
+// entry at its return -- and never copied.
 template <typename T>
 struct DevBuf {
     T* ptr = nullptr;
     size_t count = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { Release(); }
     int Reserve(size_t n) {
         if (n <= count) return RT_OK;
         if (ptr) (void)hipFree(ptr);
@@ -74,12 +82,25 @@ struct DevBuf {
         if (!src.empty()) RT_HIP(hipMemcpy(ptr, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
         return RT_OK;
     }
+    // The unit entries' round trip: room for n elements filled from host memory; and n elements back, once the stream has run dry.
+    int UploadFrom(const T* src, size_t n) {
+        const int rc = Reserve(n);
+        if (rc != RT_OK) return rc;
+        RT_HIP(hipMemcpy(ptr, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return RT_OK;
+    }
+    int DownloadTo(T* dst, size_t n, hipStream_t stream) const {
+        RT_HIP(hipStreamSynchronize(stream));
+        RT_HIP(hipMemcpy(dst, ptr, n * sizeof(T), hipMemcpyDeviceToHost));
+        return RT_OK;
+    }
     void Release() {
         if (ptr) (void)hipFree(ptr);
         ptr = nullptr;
         count = 0;
     }
 };
+static_assert(!std::is_copy_constructible<DevBuf<float>>::value, "a DevBuf is the one owner of its memory");
 
 // A shadow index's three tables (the id lists with one spare element, so that an empty list still has an address).
 int UploadShadowGrid(const rtprep::ShadowGrid& G, DevBuf<uint16_t>& cells, DevBuf<uint16_t>& entries, DevBuf<uint16_t>& global) {
@@ -264,6 +285,83 @@ static void SetQueue(rtd::TraceParams& tp, const rtplan::QueueCut& q) {
     tp.queue_block = q.queue_block, tp.static_blocks = q.static_blocks, tp.dyn_begin = q.dyn_begin, tp.dyn_blocks = q.dyn_blocks;
 }
 
+// ---- how the host's records become launch parameters, each written down once.  P is rtd::TraceParams (light 0, the unit kernels) or
+// rtd::LightRec (lights 1 ..): the member names are equal (rt_params.h).
+// A shadow index's constants; a disabled index leaves them zero.  Where its three tables lie differs by caller and stays there.
+template <typename P>
+static void SetShadowGrid(P& p, const rtprep::ShadowGrid& G) {
+    p.sg_enabled = G.enabled ? 1u : 0u;
+    if (!G.enabled) return;
+    for (int c = 0; c < 3; ++c) {
+        p.sg_e1[c] = G.e1[c];
+        p.sg_e2[c] = G.e2[c];
+    }
+    p.sg_u0 = G.u0, p.sg_v0 = G.v0, p.sg_inv_cell = G.invCell, p.sg_p0sq = G.p0sq;
+    p.sg_nx = G.nx, p.sg_ny = G.ny, p.sg_nglobal = (uint32_t)G.global.size();
+}
+template <typename P>
+static void SetLight(P& p, const rt_light& light) {
+    for (int c = 0; c < 3; ++c) {
+        p.sun_dir[c] = light.direction[c];
+        p.sun_rad[c] = light.luminance * light.color[c];  // m_luminance * m_color, light.cpp:27
+    }
+}
+static void SetCamera(rtd::TraceParams& tp, const rt_camera& camera) {
+    for (int c = 0; c < 3; ++c) {
+        tp.cam_o[c] = camera.origin[c];
+        tp.cam_x[c] = camera.x[c];
+        tp.cam_y[c] = camera.y[c];
+        tp.cam_oip[c] = camera.origin_image_plane[c];
+    }
+    tp.aperture = camera.aperture;
+    tp.focal = camera.focal_length;
+}
+static void SetPicture(rtd::TraceParams& tp, const rtseq::PictureKey& pic) { tp.W = pic.W, tp.H = pic.H, tp.rs = pic.rs; }
+// The parameters of one pass of the trace kernel: the scene (ctx->base, whose work part is zero: no path list, no tile tables, no
+// ray-generation tables, nothing of the pipeline) and the samples [s0, s0 + spp) of the npix local pixels of the picture.  The caller
+// adds what is its own.
+static rtd::TraceParams PassParams(const rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t s0, uint32_t spp, uint32_t npix, uint32_t max_depth,
+                                   uint64_t seed) {
+    rtd::TraceParams tp = ctx->base;
+    SetPicture(tp, pic);
+    tp.s0 = s0;
+    tp.spp_pass = spp;
+    tp.total_paths = npix * spp;
+    tp.npix_local = npix;
+    tp.max_depth = max_depth;
+    tp.sampler = ctx->sampler;
+    tp.seed = seed;
+    tp.counters = ctx->counters.ptr;
+    return tp;
+}
+
+// The time on the stream since hipEventRecord(ctx->ev[first]), in ms: records ev[first + 1] and waits for it.
+static int ElapsedSince(rt_ctx* ctx, int first, double* out_ms) {
+    RT_HIP(hipEventRecord(ctx->ev[first + 1], ctx->stream));
+    RT_HIP(hipEventSynchronize(ctx->ev[first + 1]));
+    float ms = 0.f;
+    RT_HIP(hipEventElapsedTime(&ms, ctx->ev[first], ctx->ev[first + 1]));
+    *out_ms = ms;
+    return RT_OK;
+}
+
+// What a reader hands out: strips of the context, each to the caller's buffer where one is given.  The host form waits for the stream
+// and copies; the device form enqueues on it.
+struct StripCopy {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+static int CopyStrips(rt_ctx* ctx, bool toDevice, std::initializer_list<StripCopy> strips) {
+    if (!toDevice) RT_HIP(hipStreamSynchronize(ctx->stream));
+    for (const StripCopy& s : strips) {
+        if (!s.dst) continue;
+        if (toDevice) RT_HIP(hipMemcpyAsync(s.dst, s.src, s.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        else RT_HIP(hipMemcpy(s.dst, s.src, s.bytes, hipMemcpyDeviceToHost));
+    }
+    return RT_OK;
+}
+
 using TraceKernelFn = void (*)(rtd::TraceParams);
 using ClosestKernelFn = void (*)(rtd::TraceParams, const float*, uint32_t, float*);
 using FeaturesKernelFn = void (*)(rtd::TraceParams, rtd::FeatureParams);
@@ -419,9 +517,7 @@ static int BuildTileMasks(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t np
     if ((rc = ctx->tileMasks.Reserve((size_t)nFull * rtd::kTileMaskWords)) != RT_OK) return rc;
     if (sphLimit != 0u && (rc = ctx->tileSpheres.Reserve((size_t)nFull * rtd::kTileSphereHalfs)) != RT_OK) return rc;
     rtd::TraceParams tp = b;
-    tp.W = pic.W;
-    tp.H = pic.H;
-    tp.rs = pic.rs;
+    SetPicture(tp, pic);
     hipLaunchKernelGGL(rtd::rt_tile_mask_kernel, dim3((nFull + 3) / 4), dim3(256), 0, ctx->stream, tp, nFull, plan.limit, ctx->tileMasks.ptr,
                        sphLimit, sphLimit != 0u ? ctx->tileSpheres.ptr : nullptr);
     RT_HIP(hipGetLastError());
@@ -474,9 +570,7 @@ static int BuildTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t np
         if ((rc = ctx->tileClass.Reserve(nFull)) != RT_OK) return rc;
         if ((rc = ctx->tileOrder.Reserve(nFull)) != RT_OK) return rc;
         rtd::TraceParams tp = ctx->base;
-        tp.W = pic.W;
-        tp.H = pic.H;
-        tp.rs = pic.rs;
+        SetPicture(tp, pic);
         tp.s0 = 1;
         tp.sampler = ctx->sampler;
         tp.jitter_tab = nullptr;
@@ -494,6 +588,26 @@ static int BuildTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t np
         RT_HIP(hipEventRecord(ctx->skyEv, ctx->stream));
     }
     rttile::OrderBuilt(ctx->tiles, pic, plan);
+    return RT_OK;
+}
+
+// The ray-generation tables of the samples [s0, s0 + spp) of a strip of W columns, in the two buffers given (rt_render's or the feature
+// pass's), and tp's account of them: the host half of the indexing contract of rt_params.h -- jitter_tab[s - s0], and lens_tab[k - lens_k0]
+// for k = s + i + j over the strip's rows.  queue, ctl: the pipelined form, whose table kernel also resets the queue cursors and the
+// control block for the carrying trace kernel that follows.
+static int LaunchRaygenTables(rt_ctx* ctx, rtd::TraceParams& tp, DevBuf<float2>& jitter, DevBuf<float2>& lens, uint32_t s0, uint32_t spp, uint32_t W,
+                              const rt_rowset& rs, uint32_t* queue = nullptr, rtd::FrameCtl* ctl = nullptr) {
+    const uint32_t k0 = s0 + rs.first_row;
+    const uint32_t nLens = spp + W + rs.num_rows;
+    const uint32_t nmax = spp > nLens ? spp : nLens;
+    int rc;
+    if ((rc = jitter.Reserve(spp)) != RT_OK || (rc = lens.Reserve(nLens)) != RT_OK) return rc;
+    tp.jitter_tab = jitter.ptr;
+    tp.lens_tab = lens.ptr;
+    tp.lens_k0 = k0;
+    hipLaunchKernelGGL(rtd::rt_raygen_tables_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, jitter.ptr, s0, spp, lens.ptr, k0, nLens,
+                       ctx->sampler, queue, ctl);
+    RT_HIP(hipGetLastError());
     return RT_OK;
 }
 
@@ -522,7 +636,6 @@ static int PipelineTraceAndCommit(rt_ctx* ctx, rtd::TraceParams& tp, uint32_t np
     tp.region_seq = ctx->pipeSeq;
     tp.max_carry_age = ctx->seq.pipeDepth;
     tp.min_iters = EnvU32("RT_PIPE_MIN_ITERS", 8);
-    tp.counters = ctx->counters.ptr;
     int rc = LaunchTrace(ctx, tp, rtplan::Mode::Carry);
     if (rc != RT_OK) return rc;
     hipLaunchKernelGGL(rtd::rt_commit_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->ring.ptr, ctx->hdr.ptr, npix,
@@ -537,22 +650,13 @@ static int PipelineTraceAndCommit(rt_ctx* ctx, rtd::TraceParams& tp, uint32_t np
 static int PipelineFlush(rt_ctx* ctx) {
     if (!ctx->pipeOpen) return RT_OK;
     const uint32_t npix = ctx->pipeNpix;
-    rtd::TraceParams tp = ctx->base;
+    rtd::TraceParams tp = PassParams(ctx, ctx->seq.pic, 1, 1, npix, ctx->pipeMaxDepth, ctx->pipeSeed);
     tp.total_paths = 0;  // nothing fresh: only the carried paths
+    tp.samples = ctx->ring.ptr;
     PipelineShards(ctx, tp);
     hipLaunchKernelGGL(rtd::rt_raygen_tables_kernel, dim3(1), dim3(256), 0, ctx->stream, (float2*)nullptr, 0u, 0u, (float2*)nullptr, 0u, 0u,
                        ctx->sampler, ctx->queue.ptr, ctx->ctl.ptr);
     RT_HIP(hipGetLastError());
-    tp.W = ctx->seq.pic.W;
-    tp.H = ctx->seq.pic.H;
-    tp.rs = ctx->seq.pic.rs;
-    tp.s0 = 1;
-    tp.spp_pass = 1;
-    tp.npix_local = npix;
-    tp.max_depth = ctx->pipeMaxDepth;
-    tp.sampler = ctx->sampler;
-    tp.seed = ctx->pipeSeed;
-    tp.samples = ctx->ring.ptr;
     int rc = PipelineTraceAndCommit(ctx, tp, npix, false);
     ctx->pipeOpen = false;
     if (rc != RT_OK) DropVoided(ctx, rtseq::StepFailed(ctx->seq));
@@ -560,8 +664,7 @@ static int PipelineFlush(rt_ctx* ctx) {
 }
 
 // One pipelined call: samples [s0, s1) of the strip become region pipeSeq + 1 of the ring.
-static int PipelineRender(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t npix, uint32_t s0, uint32_t s1, uint32_t max_depth,
-                          uint64_t seed) {
+static int PipelineRender(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t npix, uint32_t s0, uint32_t s1, uint32_t max_depth, uint64_t seed) {
     const uint32_t spp = s1 - s0;
     const uint32_t nRing = ctx->seq.pipeDepth + 2u;
     int rc;
@@ -598,49 +701,16 @@ static int PipelineRender(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uin
     const uint32_t slot = seq % nRing;
     ctx->pipeRegions.seq[slot] = seq;
     ctx->pipeRegions.spp[slot] = spp;
-    rtd::TraceParams tp = ctx->base;
-    tp.W = W;
-    tp.H = H;
-    tp.rs = rs;
-    tp.s0 = s0;
-    tp.spp_pass = spp;
-    tp.total_paths = npix * spp;
-    tp.npix_local = npix;
-    tp.max_depth = max_depth;
-    tp.sampler = ctx->sampler;
-    tp.seed = seed;
-    tp.path_list = nullptr;
+    rtd::TraceParams tp = PassParams(ctx, pic, s0, spp, npix, max_depth, seed);
     // natural tile order: a frame's long paths are carried into the next kernel anyway, and starting every wave on the most
     // expensive tiles only lengthens the stretch before the first wave runs dry (measured 0.285 vs 0.253 ms per frame)
     tp.tile_order = nullptr;
     tp.samples = ctx->ring.ptr;
     tp.sample_base = slot * npix * ctx->pipeSppCap;
-    tp.trav_out = nullptr;
-    const uint32_t k0 = s0 + rs.first_row;
-    const uint32_t nLens = spp + W + rs.num_rows;
-    if ((rc = ctx->jitterTab.Reserve(spp)) != RT_OK) return rc;
-    if ((rc = ctx->lensTab.Reserve(nLens)) != RT_OK) return rc;
-    tp.jitter_tab = ctx->jitterTab.ptr;
-    tp.lens_tab = ctx->lensTab.ptr;
-    tp.lens_k0 = k0;
-    const uint32_t nmax = spp > nLens ? spp : nLens;
     PipelineShards(ctx, tp);
-    hipLaunchKernelGGL(rtd::rt_raygen_tables_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, ctx->jitterTab.ptr, s0, spp,
-                       ctx->lensTab.ptr, k0, nLens, ctx->sampler, ctx->queue.ptr, ctx->ctl.ptr);
-    RT_HIP(hipGetLastError());
+    if ((rc = LaunchRaygenTables(ctx, tp, ctx->jitterTab, ctx->lensTab, s0, spp, pic.W, pic.rs, ctx->queue.ptr, ctx->ctl.ptr)) != RT_OK) return rc;
     return PipelineTraceAndCommit(ctx, tp, npix, true);
 }
-
-namespace {
-template <typename T>
-struct TmpDev {
-    T* p = nullptr;
-    ~TmpDev() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t Alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T)); }
-};
-}  // namespace
 
 extern "C" {
 
@@ -713,76 +783,15 @@ void rt_destroy(rt_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    ctx->scan.Release();
-    ctx->orig.Release();
-    ctx->tree.Release();
-    ctx->sgCells.Release();
-    ctx->gridCells.Release();
-    ctx->gridQ.Release();
-    ctx->sgEntries.Release();
-    ctx->sgGlobal.Release();
-    ctx->sgSph.Release();
-    for (auto& x : ctx->extraIdx) {
-        x.cells.Release();
-        x.entries.Release();
-        x.global.Release();
-    }
-    ctx->lightRecs.Release();
-    ctx->radius.Release();
-    ctx->mats.Release();
-    ctx->mats16.Release();
-    ctx->hdr.Release();
-    ctx->sq.Release();
-    ctx->noiseMap.Release();
-    ctx->noiseRed.Release();
-    ctx->ldr.Release();
-    ctx->feat.Release();
-    ctx->featIds.Release();
-    ctx->featJitter.Release();
-    ctx->featLens.Release();
-    for (int k = 0; k < 2; ++k) {
-        ctx->denState[k].Release();
-        ctx->denGuide[k].Release();
-    }
-    ctx->den.Release();
-    ctx->denVar.Release();
-    ctx->denLdr.Release();
-    for (auto& t : ctx->tmpSet) {
-        t.state.Release();
-        t.guide[0].Release();
-        t.guide[1].Release();
-        t.ids.Release();
-        t.len.Release();
-    }
-    ctx->tmpTarget.Release();
-    ctx->samples.Release();
-    ctx->queue.Release();
-    ctx->counters.Release();
-    ctx->jitterTab.Release();
-    ctx->lensTab.Release();
-    ctx->leaf.Release();
-    ctx->pilotRays.Release();
-    ctx->pilotHits.Release();
-    ctx->tileOrder.Release();
-    ctx->tileMasks.Release();
-    ctx->tileSpheres.Release();
-    ctx->tileClass.Release();
-    ctx->skyFlags.Release();
-    ctx->skyInfo.Release();
     if (ctx->skyCountHost) (void)hipHostFree(ctx->skyCountHost);
     if (ctx->skyEv) (void)hipEventDestroy(ctx->skyEv);
-    ctx->matType.Release();
-    ctx->ring.Release();
-    ctx->cont[0].Release();
-    ctx->cont[1].Release();
-    ctx->contN[0].Release();
-    ctx->contN[1].Release();
-    ctx->ctl.Release();
     for (auto& ev : ctx->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->passEv)
         if (ev) (void)hipEventDestroy(ev);
     if (ctx->ownStream) (void)hipStreamDestroy(ctx->ownStream);
+    // The buffers free themselves inside `delete ctx` (DevBuf), after the stream is gone: nothing on it can still use them, since it
+    // was synchronised above, and the device they belong to is still the current one.
     delete ctx;
 }
 
@@ -868,20 +877,11 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
         const rtprep::ShadowGrid& G2 = P.extraShadow[k - 1];
         rt_ctx::ExtraLight& X = ctx->extraIdx[k];
         rtd::LightRec R{};
-        for (int c = 0; c < 3; ++c) {
-            R.sun_dir[c] = lights[k].direction[c];
-            R.sun_rad[c] = lights[k].luminance * lights[k].color[c];  // m_luminance * m_color, light.cpp:27
-            R.cam_o[c] = camera->origin[c];
-        }
-        R.sg_enabled = G2.enabled ? 1u : 0u;
+        SetLight(R, lights[k]);
+        for (int c = 0; c < 3; ++c) R.cam_o[c] = camera->origin[c];
+        SetShadowGrid(R, G2);
         if (G2.enabled) {
             if ((rc = UploadShadowGrid(G2, X.cells, X.entries, X.global)) != RT_OK) return rc;
-            for (int c = 0; c < 3; ++c) {
-                R.sg_e1[c] = G2.e1[c];
-                R.sg_e2[c] = G2.e2[c];
-            }
-            R.sg_u0 = G2.u0; R.sg_v0 = G2.v0; R.sg_inv_cell = G2.invCell; R.sg_p0sq = G2.p0sq;
-            R.sg_nx = G2.nx; R.sg_ny = G2.ny; R.sg_nglobal = (uint32_t)G2.global.size();
             R.cell_start = X.cells.ptr; R.entries = X.entries.ptr; R.global = X.global.ptr;
         }
         recs.push_back(R);
@@ -913,24 +913,13 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     }
     b.n_lights = n_lights;
     b.extra_lights = recs.empty() ? nullptr : ctx->lightRecs.ptr;
-    b.sg_enabled = SG.enabled ? 1u : 0u;
+    SetShadowGrid(b, SG);
     if (SG.enabled) {
         b.sg_cell_start = ctx->sgCells.ptr;
         b.sg_entries = ctx->sgEntries.ptr;
         b.sg_global = ctx->sgGlobal.ptr;
         b.sg_sph = P.sgSph.empty() ? nullptr : ctx->sgSph.ptr;
-        b.sg_nx = SG.nx;
-        b.sg_ny = SG.ny;
-        b.sg_nglobal = (uint32_t)SG.global.size();
-        b.sg_nentries = (uint32_t)SG.entries.size();
-        for (int k = 0; k < 3; ++k) {
-            b.sg_e1[k] = SG.e1[k];
-            b.sg_e2[k] = SG.e2[k];
-        }
-        b.sg_u0 = SG.u0;
-        b.sg_v0 = SG.v0;
-        b.sg_inv_cell = SG.invCell;
-        b.sg_p0sq = SG.p0sq;
+        b.sg_nentries = (uint32_t)SG.entries.size();  // (for the list's copy into LDS; a LightRec's index stays in global memory)
     }
     b.scan = ctx->scan.ptr;
     b.orig = ctx->orig.ptr;
@@ -953,17 +942,9 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     b.mats16 = ctx->mats16Ok ? ctx->mats16.ptr : nullptr;
     b.n = n;
     b.n_padded = nPad;
-    for (int k = 0; k < 3; ++k) {
-        b.cam_o[k] = camera->origin[k];
-        b.cam_x[k] = camera->x[k];
-        b.cam_y[k] = camera->y[k];
-        b.cam_oip[k] = camera->origin_image_plane[k];
-        b.sun_dir[k] = sun->direction[k];
-        b.sun_rad[k] = sun->luminance * sun->color[k];  // m_luminance * m_color, light.cpp:27
-        b.sky_emit[k] = sky->luminance * sky->rgb0[k];  // Emissive::Emit, material.cpp:172-175
-    }
-    b.aperture = camera->aperture;
-    b.focal = camera->focal_length;
+    SetCamera(b, *camera);
+    SetLight(b, *sun);
+    for (int k = 0; k < 3; ++k) b.sky_emit[k] = sky->luminance * sky->rgb0[k];  // Emissive::Emit, material.cpp:172-175
     b.exposure = exposure_scale;
     ctx->n = n;
     ctx->sky = *sky;
@@ -1102,7 +1083,7 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
     rtseq::RenderBegins(seq);
     const rtseq::Refusal bad = rtseq::CheckCall(seq, call);
     if (bad.status != RT_OK) return Fail(bad.status, bad.message);
-    const uint32_t W = call.pic.W, H = call.pic.H, rows = call.rows, s0 = call.s0, s1 = call.s1, max_depth = call.max_depth;
+    const uint32_t W = call.pic.W, rows = call.rows, s0 = call.s0, s1 = call.s1, max_depth = call.max_depth;
     const rt_rowset rs = call.pic.rs;
     const uint64_t seed = call.seed;
     RT_HIP(hipSetDevice(ctx->device));
@@ -1140,7 +1121,7 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
 
     if (pipelined) {
         ctx->tileAcct.skyExcluded = 0;  // (the carrying kernel's launch queues every tile)
-        int rcp = PipelineRender(ctx, W, H, rs, npix, s0, s1, max_depth, seed);
+        int rcp = PipelineRender(ctx, call.pic, npix, s0, s1, max_depth, seed);
         if (rcp != RT_OK) {
             DropVoided(ctx, rtseq::StepFailed(seq));
             return rcp;
@@ -1176,18 +1157,7 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
         ctx->tileAcct.skyExcluded = nSky;
         for (rtseq::Pass pass = rtseq::FirstPass(split); pass.spp != 0; pass = rtseq::NextPass(split, pass)) {
             const uint32_t s = pass.s, spp = pass.spp;
-            rtd::TraceParams tp = ctx->base;
-            tp.W = W;
-            tp.H = H;
-            tp.rs = rs;
-            tp.s0 = s;
-            tp.spp_pass = spp;
-            tp.total_paths = npix * spp;
-            tp.npix_local = npix;
-            tp.max_depth = max_depth;
-            tp.sampler = ctx->sampler;
-            tp.seed = seed;
-            tp.path_list = nullptr;
+            rtd::TraceParams tp = PassParams(ctx, call.pic, s, spp, npix, max_depth, seed);
             tp.tile_order = use.order ? ctx->tileOrder.ptr : nullptr;
             tp.tile_masks = use.masks ? ctx->tileMasks.ptr : nullptr;
             tp.tile_spheres = use.lists ? ctx->tileSpheres.ptr : nullptr;
@@ -1195,16 +1165,6 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
             ctx->tileAcct.freshScans += ((uint64_t)tp.total_paths + 63u) / 64u;  // (all tiles: the statistics do not know about the shorter queue)
             if (nSky != 0u) tp.total_paths = (nFull - nSky) * 64u * spp;
             tp.samples = ctx->samples.ptr;
-            tp.trav_out = nullptr;
-            tp.counters = ctx->counters.ptr;
-            // ray-generation tables for this pass: s in [s, s+spp), k = s+i+j over the strip's rows
-            const uint32_t k0 = s + rs.first_row;
-            const uint32_t nLens = spp + W + rs.num_rows;
-            if ((rc = ctx->jitterTab.Reserve(spp)) != RT_OK) return rc;
-            if ((rc = ctx->lensTab.Reserve(nLens)) != RT_OK) return rc;
-            tp.jitter_tab = ctx->jitterTab.ptr;
-            tp.lens_tab = ctx->lensTab.ptr;
-            tp.lens_k0 = k0;
             while (ctx->passEv.size() < 3 * (size_t)(passes + 1)) {
                 hipEvent_t e = nullptr;
                 RT_HIP(hipEventCreate(&e));
@@ -1212,12 +1172,7 @@ static int RenderNow(rt_ctx* ctx, const rtseq::Call& call, rt_stats* out_stats, 
             }
             hipEvent_t* ev = ctx->passEv.data() + 3 * (size_t)passes;
             RT_HIP(hipEventRecord(ev[0], ctx->stream));
-            {
-                const uint32_t nmax = spp > nLens ? spp : nLens;
-                hipLaunchKernelGGL(rtd::rt_raygen_tables_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, ctx->jitterTab.ptr, s,
-                                   spp, ctx->lensTab.ptr, k0, nLens, ctx->sampler);
-                RT_HIP(hipGetLastError());
-            }
+            if ((rc = LaunchRaygenTables(ctx, tp, ctx->jitterTab, ctx->lensTab, s, spp, W, rs)) != RT_OK) return rc;
             if ((rc = LaunchTrace(ctx, tp)) != RT_OK) return rc;
             if (nSky != 0u) {
                 const unsigned long long planes = (unsigned long long)nSky * spp;
@@ -1280,38 +1235,22 @@ int rt_resolve(rt_ctx* ctx, uint32_t n_samples) {
     hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->hdr.ptr, ctx->ldr.ptr, npix, n,
                        devCount);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
-    RT_HIP(hipEventSynchronize(ctx->ev[1]));
-    float ms = 0.f;
-    RT_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    ctx->lastResolveMs = ms;
-    return RT_OK;
+    return ElapsedSince(ctx, 0, &ctx->lastResolveMs);
 }
 
 double rt_last_resolve_ms(rt_ctx* ctx) { return ctx ? ctx->lastResolveMs : 0.0; }
 
-int rt_download(rt_ctx* ctx, float* hdr_rgb, uint8_t* ldr_rgb) {
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_download: null ctx");
+// Each reader once, for both of its forms (who: the entry's name for the messages; CopyStrips has the difference).
+static int ReadPicture(rt_ctx* ctx, const char* who, bool toDevice, void* hdr_rgb, void* ldr_rgb) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
     if (const int rcb = RenderPendingForReader(ctx)) return rcb;
-    if (ctx->seq.accumulated == 0) return Fail(RT_ERR_SEQUENCE, "rt_download: nothing rendered");
+    if (ctx->seq.accumulated == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": nothing rendered");
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->seq.pic.W * ctx->seq.rows;
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    if (hdr_rgb) RT_HIP(hipMemcpy(hdr_rgb, ctx->hdr.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (ldr_rgb) RT_HIP(hipMemcpy(ldr_rgb, ctx->ldr.ptr, npix * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return CopyStrips(ctx, toDevice, {{hdr_rgb, ctx->hdr.ptr, npix * 3 * sizeof(float)}, {ldr_rgb, ctx->ldr.ptr, npix * 3}});
 }
-
-int rt_copy_to_device(rt_ctx* ctx, void* dev_hdr_rgb, void* dev_ldr_rgb) {
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_copy_to_device: null ctx");
-    if (const int rcb = RenderPendingForReader(ctx)) return rcb;
-    if (ctx->seq.accumulated == 0) return Fail(RT_ERR_SEQUENCE, "rt_copy_to_device: nothing rendered");
-    RT_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->seq.pic.W * ctx->seq.rows;
-    if (dev_hdr_rgb) RT_HIP(hipMemcpyAsync(dev_hdr_rgb, ctx->hdr.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (dev_ldr_rgb) RT_HIP(hipMemcpyAsync(dev_ldr_rgb, ctx->ldr.ptr, npix * 3, hipMemcpyDeviceToDevice, ctx->stream));
-    return RT_OK;
-}
+int rt_download(rt_ctx* ctx, float* hdr_rgb, uint8_t* ldr_rgb) { return ReadPicture(ctx, "rt_download", false, hdr_rgb, ldr_rgb); }
+int rt_copy_to_device(rt_ctx* ctx, void* dev_hdr_rgb, void* dev_ldr_rgb) { return ReadPicture(ctx, "rt_copy_to_device", true, dev_hdr_rgb, dev_ldr_rgb); }
 
 // ---------------------------------------------------------------- noise estimate (rt_noise.h)
 // Like the other readers: a pending batch that starts the picture is rendered first; planes traced ahead never reached the strips.
@@ -1325,22 +1264,14 @@ static int NoiseReady(rt_ctx* ctx, const char* who, uint32_t minSamples) {
     return RT_OK;
 }
 
-int rt_download_moments(rt_ctx* ctx, float* sq_rgb) {
-    const int rc = NoiseReady(ctx, "rt_download_moments", 1);
+static int ReadMoments(rt_ctx* ctx, const char* who, bool toDevice, void* sq_rgb) {
+    const int rc = NoiseReady(ctx, who, 1);
     if (rc != RT_OK) return rc;
-    if (!sq_rgb) return Fail(RT_ERR_INVALID_ARG, "rt_download_moments: null buffer");
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(sq_rgb, ctx->sq.ptr, (size_t)ctx->seq.pic.W * ctx->seq.rows * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    if (!sq_rgb) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+    return CopyStrips(ctx, toDevice, {{sq_rgb, ctx->sq.ptr, (size_t)ctx->seq.pic.W * ctx->seq.rows * 3 * sizeof(float)}});
 }
-
-int rt_copy_moments_to_device(rt_ctx* ctx, void* dev_sq) {
-    const int rc = NoiseReady(ctx, "rt_copy_moments_to_device", 1);
-    if (rc != RT_OK) return rc;
-    if (!dev_sq) return Fail(RT_ERR_INVALID_ARG, "rt_copy_moments_to_device: null buffer");
-    RT_HIP(hipMemcpyAsync(dev_sq, ctx->sq.ptr, (size_t)ctx->seq.pic.W * ctx->seq.rows * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    return RT_OK;
-}
+int rt_download_moments(rt_ctx* ctx, float* sq_rgb) { return ReadMoments(ctx, "rt_download_moments", false, sq_rgb); }
+int rt_copy_moments_to_device(rt_ctx* ctx, void* dev_sq) { return ReadMoments(ctx, "rt_copy_moments_to_device", true, dev_sq); }
 
 int rt_noise_map(rt_ctx* ctx, float floor, float* out_abs_rel) {
     int rc = NoiseReady(ctx, "rt_noise_map", 2);
@@ -1408,22 +1339,11 @@ int rt_render_features(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
         ctx->featRows = rows;
     }
     const uint32_t spp = s1 - s0;
-    const uint32_t k0 = s0 + rs.first_row;
-    const uint32_t nLens = spp + W + rs.num_rows;
-    if ((rc = ctx->featJitter.Reserve(spp)) != RT_OK || (rc = ctx->featLens.Reserve(nLens)) != RT_OK) {
-        ctx->featCount = 0;
-        return rc;
-    }
     rtd::TraceParams tp = ctx->base;
-    tp.W = W;
-    tp.H = H;
-    tp.rs = rs;
+    SetPicture(tp, pic);
     tp.s0 = s0;
     tp.sampler = ctx->sampler;
     tp.npix_local = npix;
-    tp.jitter_tab = ctx->featJitter.ptr;
-    tp.lens_tab = ctx->featLens.ptr;
-    tp.lens_k0 = k0;
     rtd::FeatureParams fp{};
     fp.feat = ctx->feat.ptr;
     fp.ids = ctx->featIds.ptr;
@@ -1437,20 +1357,9 @@ int rt_render_features(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
     fp.sky[2] = skyAlbedo.z;
     auto run = [&]() -> int {
         if (out_ms) RT_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-        const uint32_t nmax = spp > nLens ? spp : nLens;
-        hipLaunchKernelGGL(rtd::rt_raygen_tables_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, ctx->featJitter.ptr, s0, spp,
-                           ctx->featLens.ptr, k0, nLens, ctx->sampler);
-        RT_HIP(hipGetLastError());
-        const int rcl = LaunchFeatures(ctx, tp, fp);
-        if (rcl != RT_OK) return rcl;
-        if (out_ms) {
-            RT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-            RT_HIP(hipEventSynchronize(ctx->ev[3]));
-            float ms = 0.f;
-            RT_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-            *out_ms = ms;
-        }
-        return RT_OK;
+        int rcl = LaunchRaygenTables(ctx, tp, ctx->featJitter, ctx->featLens, s0, spp, W, rs);
+        if (rcl != RT_OK || (rcl = LaunchFeatures(ctx, tp, fp)) != RT_OK) return rcl;
+        return out_ms ? ElapsedSince(ctx, 2, out_ms) : RT_OK;
     };
     if ((rc = run()) != RT_OK) {
         ctx->featCount = 0;  // the strips may be half written: the next call must start again
@@ -1467,26 +1376,15 @@ int rt_feature_samples(rt_ctx* ctx, uint32_t* out) {
     return RT_OK;
 }
 
-int rt_download_features(rt_ctx* ctx, float* feat8, uint32_t* ids) {
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_download_features: null ctx");
-    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_download_features: nothing accumulated");
+static int ReadFeatures(rt_ctx* ctx, const char* who, bool toDevice, void* feat8, void* ids) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": nothing accumulated");
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->featPic.W * ctx->featRows;
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    if (feat8) RT_HIP(hipMemcpy(feat8, ctx->feat.ptr, npix * rtd::kFeatureChannels * sizeof(float), hipMemcpyDeviceToHost));
-    if (ids) RT_HIP(hipMemcpy(ids, ctx->featIds.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return CopyStrips(ctx, toDevice, {{feat8, ctx->feat.ptr, npix * rtd::kFeatureChannels * sizeof(float)}, {ids, ctx->featIds.ptr, npix * sizeof(uint32_t)}});
 }
-
-int rt_copy_features_to_device(rt_ctx* ctx, void* dev_feat8, void* dev_ids) {
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_copy_features_to_device: null ctx");
-    if (ctx->featCount == 0) return Fail(RT_ERR_SEQUENCE, "rt_copy_features_to_device: nothing accumulated");
-    RT_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->featPic.W * ctx->featRows;
-    if (dev_feat8) RT_HIP(hipMemcpyAsync(dev_feat8, ctx->feat.ptr, npix * rtd::kFeatureChannels * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (dev_ids) RT_HIP(hipMemcpyAsync(dev_ids, ctx->featIds.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    return RT_OK;
-}
+int rt_download_features(rt_ctx* ctx, float* feat8, uint32_t* ids) { return ReadFeatures(ctx, "rt_download_features", false, feat8, ids); }
+int rt_copy_features_to_device(rt_ctx* ctx, void* dev_feat8, void* dev_ids) { return ReadFeatures(ctx, "rt_copy_features_to_device", true, dev_feat8, dev_ids); }
 
 int rt_clear_features(rt_ctx* ctx) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_clear_features: null ctx");
@@ -1559,13 +1457,8 @@ static int DenoiseFinish(rt_ctx* ctx, const char* who, const rtdn::Strips& S, in
     if (he != 0) return Fail(RT_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString((hipError_t)he));
     hipLaunchKernelGGL(rtd::rt_resolve_kernel, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, ctx->den.ptr, ctx->denLdr.ptr, npix, 1u, nullptr);
     RT_HIP(hipGetLastError());
-    if (out_ms) {
-        RT_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-        RT_HIP(hipEventSynchronize(ctx->ev[3]));
-        float ms = 0.f;
-        RT_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-        *out_ms = ms;
-    }
+    if (out_ms)
+        if (const int rc = ElapsedSince(ctx, 2, out_ms)) return rc;
     ctx->denW = S.W;
     ctx->denRows = S.rows;
     ctx->denValid = true;
@@ -1676,34 +1569,20 @@ int rt_download_temporal(rt_ctx* ctx, float* state4, uint32_t* len, uint32_t* ta
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->tmpPic.W * ctx->tmpPic.rs.num_rows;
     const rt_ctx::TemporalSet& t = ctx->tmpSet[ctx->tmpCur & 1u];
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    if (state4) RT_HIP(hipMemcpy(state4, t.state.ptr, npix * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    if (len) RT_HIP(hipMemcpy(len, t.len.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (target) RT_HIP(hipMemcpy(target, ctx->tmpTarget.ptr, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return CopyStrips(ctx, false, {{state4, t.state.ptr, npix * 4 * sizeof(float)}, {len, t.len.ptr, npix * sizeof(uint32_t)},
+                                   {target, ctx->tmpTarget.ptr, npix * sizeof(uint32_t)}});
 }
 
-int rt_download_denoised(rt_ctx* ctx, float* rgb, float* var, uint8_t* ldr) {
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_download_denoised: null ctx");
-    if (!ctx->denValid) return Fail(RT_ERR_SEQUENCE, "rt_download_denoised: nothing denoised");
+static int ReadDenoised(rt_ctx* ctx, const char* who, bool toDevice, void* rgb, void* var, void* ldr) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    if (!ctx->denValid) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": nothing denoised");
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->denW * ctx->denRows;
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    if (rgb) RT_HIP(hipMemcpy(rgb, ctx->den.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (var) RT_HIP(hipMemcpy(var, ctx->denVar.ptr, npix * sizeof(float), hipMemcpyDeviceToHost));
-    if (ldr) RT_HIP(hipMemcpy(ldr, ctx->denLdr.ptr, npix * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return CopyStrips(ctx, toDevice, {{rgb, ctx->den.ptr, npix * 3 * sizeof(float)}, {var, ctx->denVar.ptr, npix * sizeof(float)}, {ldr, ctx->denLdr.ptr, npix * 3}});
 }
-
+int rt_download_denoised(rt_ctx* ctx, float* rgb, float* var, uint8_t* ldr) { return ReadDenoised(ctx, "rt_download_denoised", false, rgb, var, ldr); }
 int rt_copy_denoised_to_device(rt_ctx* ctx, void* dev_rgb, void* dev_var, void* dev_ldr) {
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_copy_denoised_to_device: null ctx");
-    if (!ctx->denValid) return Fail(RT_ERR_SEQUENCE, "rt_copy_denoised_to_device: nothing denoised");
-    RT_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->denW * ctx->denRows;
-    if (dev_rgb) RT_HIP(hipMemcpyAsync(dev_rgb, ctx->den.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (dev_var) RT_HIP(hipMemcpyAsync(dev_var, ctx->denVar.ptr, npix * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (dev_ldr) RT_HIP(hipMemcpyAsync(dev_ldr, ctx->denLdr.ptr, npix * 3, hipMemcpyDeviceToDevice, ctx->stream));
-    return RT_OK;
+    return ReadDenoised(ctx, "rt_copy_denoised_to_device", true, dev_rgb, dev_var, dev_ldr);
 }
 
 int rt_unit_denoise_forms(rt_ctx* ctx, uint32_t out[5]) {
@@ -1728,34 +1607,26 @@ int rt_unit_halton(rt_ctx* ctx, const uint32_t* index, uint32_t base, uint32_t n
     if (!ctx || !index || !out || base < 2) return Fail(RT_ERR_INVALID_ARG, "rt_unit_halton: invalid argument");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    TmpDev<uint32_t> dIdx;
-    TmpDev<float> dOut;
-    RT_HIP(dIdx.Alloc(n));
-    RT_HIP(dOut.Alloc(n));
-    RT_HIP(hipMemcpy(dIdx.p, index, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(rtd::k_unit_halton, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dIdx.p, base, n, dOut.p);
+    DevBuf<uint32_t> dIdx;
+    DevBuf<float> dOut;
+    int rc;
+    if ((rc = dIdx.UploadFrom(index, n)) != RT_OK || (rc = dOut.Reserve(n)) != RT_OK) return rc;
+    hipLaunchKernelGGL(rtd::k_unit_halton, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dIdx.ptr, base, n, dOut.ptr);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(out, dOut.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return dOut.DownloadTo(out, n, ctx->stream);
 }
 
 int rt_unit_math(rt_ctx* ctx, uint32_t op, const float* x, const float* y, uint32_t n, float* out) {
     if (!ctx || !x || !out || op > 9) return Fail(RT_ERR_INVALID_ARG, "rt_unit_math: invalid argument");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    TmpDev<float> dX, dY, dOut;
-    RT_HIP(dX.Alloc(n));
-    RT_HIP(dY.Alloc(n));
-    RT_HIP(dOut.Alloc(n));
-    RT_HIP(hipMemcpy(dX.p, x, n * sizeof(float), hipMemcpyHostToDevice));
-    if (y) RT_HIP(hipMemcpy(dY.p, y, n * sizeof(float), hipMemcpyHostToDevice));
-    else RT_HIP(hipMemset(dY.p, 0, n * sizeof(float)));
-    hipLaunchKernelGGL(rtd::k_unit_math, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, op, dX.p, dY.p, n, dOut.p);
+    DevBuf<float> dX, dY, dOut;
+    int rc;
+    if ((rc = dX.UploadFrom(x, n)) != RT_OK || (rc = y ? dY.UploadFrom(y, n) : dY.Reserve(n)) != RT_OK || (rc = dOut.Reserve(n)) != RT_OK) return rc;
+    if (!y) RT_HIP(hipMemset(dY.ptr, 0, n * sizeof(float)));
+    hipLaunchKernelGGL(rtd::k_unit_math, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, op, dX.ptr, dY.ptr, n, dOut.ptr);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(out, dOut.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return dOut.DownloadTo(out, n, ctx->stream);
 }
 
 int rt_unit_primary_rays(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ijs, uint32_t n, float* out_rays) {
@@ -1763,20 +1634,17 @@ int rt_unit_primary_rays(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ij
     if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_primary_rays: no scene uploaded");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    TmpDev<uint32_t> dIjs;
-    TmpDev<float> dOut;
-    RT_HIP(dIjs.Alloc((size_t)n * 3));
-    RT_HIP(dOut.Alloc((size_t)n * 6));
-    RT_HIP(hipMemcpy(dIjs.p, ijs, (size_t)n * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    DevBuf<uint32_t> dIjs;
+    DevBuf<float> dOut;
+    int rc;
+    if ((rc = dIjs.UploadFrom(ijs, (size_t)n * 3)) != RT_OK || (rc = dOut.Reserve((size_t)n * 6)) != RT_OK) return rc;
     rtd::TraceParams tp = ctx->base;
     tp.W = W;
     tp.H = H;
     tp.sampler = ctx->sampler;
-    hipLaunchKernelGGL(rtd::k_unit_primary, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, tp, dIjs.p, n, dOut.p);
+    hipLaunchKernelGGL(rtd::k_unit_primary, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, tp, dIjs.ptr, n, dOut.ptr);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(out_rays, dOut.p, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return dOut.DownloadTo(out_rays, (size_t)n * 6, ctx->stream);
 }
 
 int rt_unit_closest_hit(rt_ctx* ctx, const float* rays, uint32_t n, float* out_hits) {
@@ -1784,18 +1652,11 @@ int rt_unit_closest_hit(rt_ctx* ctx, const float* rays, uint32_t n, float* out_h
     if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_closest_hit: no scene uploaded");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    TmpDev<float> dRays, dOut;
-    RT_HIP(dRays.Alloc((size_t)n * 6));
-    RT_HIP(dOut.Alloc((size_t)n * 10));
-    RT_HIP(hipMemcpy(dRays.p, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice));
-    {
-        const int rcl = LaunchClosest(ctx, dRays.p, n, dOut.p);
-        if (rcl != RT_OK) return rcl;
-    }
-    RT_HIP(hipGetLastError());
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(out_hits, dOut.p, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    DevBuf<float> dRays, dOut;
+    int rc;
+    if ((rc = dRays.UploadFrom(rays, (size_t)n * 6)) != RT_OK || (rc = dOut.Reserve((size_t)n * 10)) != RT_OK) return rc;
+    if ((rc = LaunchClosest(ctx, dRays.ptr, n, dOut.ptr)) != RT_OK) return rc;
+    return dOut.DownloadTo(out_hits, (size_t)n * 10, ctx->stream);
 }
 
 int rt_unit_trace(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ijs, uint32_t n, uint32_t max_depth, uint64_t seed,
@@ -1804,60 +1665,33 @@ int rt_unit_trace(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ijs, uint
     if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_trace: no scene uploaded");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    TmpDev<uint32_t> dIjs, dTrav;
-    TmpDev<float> dOut;
-    RT_HIP(dIjs.Alloc((size_t)n * 3));
-    RT_HIP(dTrav.Alloc(n));
-    RT_HIP(dOut.Alloc((size_t)n * 3));
-    RT_HIP(hipMemcpy(dIjs.p, ijs, (size_t)n * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    DevBuf<uint32_t> dIjs, dTrav;
+    DevBuf<float> dOut;
+    int rc;
+    if ((rc = dIjs.UploadFrom(ijs, (size_t)n * 3)) != RT_OK || (rc = dTrav.Reserve(n)) != RT_OK || (rc = dOut.Reserve((size_t)n * 3)) != RT_OK) return rc;
     RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 6 * sizeof(unsigned long long), ctx->stream));
-    rtd::TraceParams tp = ctx->base;
-    tp.W = W;
-    tp.H = H;
-    tp.rs = rt_rowset{0, H, H, 0, 1};
-    tp.s0 = 1;
-    tp.spp_pass = 1;
-    tp.total_paths = n;
-    tp.npix_local = n;
-    tp.max_depth = max_depth;
-    tp.sampler = ctx->sampler;
-    tp.seed = seed;
-    tp.path_list = dIjs.p;
-    tp.jitter_tab = nullptr;
-    tp.lens_tab = nullptr;
-    tp.samples = dOut.p;
-    tp.trav_out = dTrav.p;
-    tp.counters = ctx->counters.ptr;
-    int rc = LaunchTrace(ctx, tp);
-    if (rc != RT_OK) return rc;
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(out_rgb, dOut.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_traversals) RT_HIP(hipMemcpy(out_traversals, dTrav.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    // the n listed paths as a "picture" of n pixels and one sample, over the whole image's rows
+    rtd::TraceParams tp = PassParams(ctx, rtseq::PictureKey{W, H, rt_rowset{0, H, H, 0, 1}}, 1, 1, n, max_depth, seed);
+    tp.path_list = dIjs.ptr;
+    tp.samples = dOut.ptr;
+    tp.trav_out = dTrav.ptr;
+    if ((rc = LaunchTrace(ctx, tp)) != RT_OK) return rc;
+    if ((rc = dOut.DownloadTo(out_rgb, (size_t)n * 3, ctx->stream)) != RT_OK) return rc;
+    return out_traversals ? dTrav.DownloadTo(out_traversals, n, ctx->stream) : RT_OK;
 }
 
 int rt_unit_camera_rays(rt_ctx* ctx, const rt_camera* camera, const float* uv_offset, uint32_t n, float* out_rays) {
     if (!ctx || !camera || !uv_offset || !out_rays) return Fail(RT_ERR_INVALID_ARG, "rt_unit_camera_rays: invalid argument");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    TmpDev<float> dIn, dOut;
-    RT_HIP(dIn.Alloc((size_t)n * 4));
-    RT_HIP(dOut.Alloc((size_t)n * 6));
-    RT_HIP(hipMemcpy(dIn.p, uv_offset, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice));
+    DevBuf<float> dIn, dOut;
+    int rc;
+    if ((rc = dIn.UploadFrom(uv_offset, (size_t)n * 4)) != RT_OK || (rc = dOut.Reserve((size_t)n * 6)) != RT_OK) return rc;
     rtd::TraceParams tp{};
-    for (int k = 0; k < 3; ++k) {
-        tp.cam_o[k] = camera->origin[k];
-        tp.cam_x[k] = camera->x[k];
-        tp.cam_y[k] = camera->y[k];
-        tp.cam_oip[k] = camera->origin_image_plane[k];
-    }
-    tp.aperture = camera->aperture;
-    tp.focal = camera->focal_length;
-    hipLaunchKernelGGL(rtd::k_unit_camera, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, tp, dIn.p, n, dOut.p);
+    SetCamera(tp, *camera);
+    hipLaunchKernelGGL(rtd::k_unit_camera, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, tp, dIn.ptr, n, dOut.ptr);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(out_rays, dOut.p, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return dOut.DownloadTo(out_rays, (size_t)n * 6, ctx->stream);
 }
 
 int rt_unit_scatter(rt_ctx* ctx, const rt_material* material, const rt_light* sun, const float view_origin[3], const float* in,
@@ -1866,41 +1700,30 @@ int rt_unit_scatter(rt_ctx* ctx, const rt_material* material, const rt_light* su
     if (const char* field = rtprep::MaterialFault(*material)) return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_unit_scatter", "the record", *material, field));
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    TmpDev<float> dIn, dOut;
-    TmpDev<rt_material> dMat;
-    RT_HIP(dIn.Alloc((size_t)n * 12));
-    RT_HIP(dOut.Alloc((size_t)n * 11));
-    RT_HIP(dMat.Alloc(1));
-    RT_HIP(hipMemcpy(dIn.p, in, (size_t)n * 12 * sizeof(float), hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(dMat.p, material, sizeof(rt_material), hipMemcpyHostToDevice));
+    DevBuf<float> dIn, dOut;
+    DevBuf<rt_material> dMat;
+    int rc;
+    if ((rc = dIn.UploadFrom(in, (size_t)n * 12)) != RT_OK || (rc = dMat.UploadFrom(material, 1)) != RT_OK || (rc = dOut.Reserve((size_t)n * 11)) != RT_OK) return rc;
     rtd::TraceParams tp{};
-    for (int k = 0; k < 3; ++k) {
-        tp.cam_o[k] = view_origin[k];
-        tp.sun_dir[k] = sun->direction[k];
-        tp.sun_rad[k] = sun->luminance * sun->color[k];
-    }
+    for (int k = 0; k < 3; ++k) tp.cam_o[k] = view_origin[k];
+    SetLight(tp, *sun);
     tp.sampler = ctx->sampler;
-    hipLaunchKernelGGL(rtd::k_unit_scatter, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, tp, dMat.p, dIn.p, n, dOut.p);
+    hipLaunchKernelGGL(rtd::k_unit_scatter, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, tp, dMat.ptr, dIn.ptr, n, dOut.ptr);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(out, dOut.p, (size_t)n * 11 * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return dOut.DownloadTo(out, (size_t)n * 11, ctx->stream);
 }
 
 int rt_unit_tonemap(rt_ctx* ctx, const float* hdr_rgb, uint32_t n, uint32_t n_samples, uint8_t* out_rgb) {
     if (!ctx || !hdr_rgb || !out_rgb || n_samples == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tonemap: invalid argument");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    TmpDev<float> dIn;
-    TmpDev<uint8_t> dOut;
-    RT_HIP(dIn.Alloc((size_t)n * 3));
-    RT_HIP(dOut.Alloc((size_t)n * 3));
-    RT_HIP(hipMemcpy(dIn.p, hdr_rgb, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(rtd::k_unit_tonemap, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dIn.p, n, n_samples, dOut.p);
+    DevBuf<float> dIn;
+    DevBuf<uint8_t> dOut;
+    int rc;
+    if ((rc = dIn.UploadFrom(hdr_rgb, (size_t)n * 3)) != RT_OK || (rc = dOut.Reserve((size_t)n * 3)) != RT_OK) return rc;
+    hipLaunchKernelGGL(rtd::k_unit_tonemap, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dIn.ptr, n, n_samples, dOut.ptr);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(out_rgb, dOut.p, (size_t)n * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return dOut.DownloadTo(out_rgb, (size_t)n * 3, ctx->stream);
 }
 
 // Host-only: the grid walk's row computation, the SAME functions the kernels call (rt_scan.h; RT_DEV is __host__ __device__).
@@ -2003,14 +1826,8 @@ int rt_unit_shadow_query_host(const rt_sphere* spheres, uint32_t n, const rt_lig
     const uint16_t* glob = G.global.empty() ? &none : G.global.data();
     rtd::TraceParams tp{};
     rtd::LightRec R{};
-    for (int c = 0; c < 3; ++c) {
-        tp.sun_dir[c] = R.sun_dir[c] = lights[light].direction[c];
-        tp.sg_e1[c] = R.sg_e1[c] = G.e1[c];
-        tp.sg_e2[c] = R.sg_e2[c] = G.e2[c];
-    }
-    tp.sg_enabled = R.sg_enabled = G.enabled ? 1u : 0u;
-    tp.sg_u0 = R.sg_u0 = G.u0; tp.sg_v0 = R.sg_v0 = G.v0; tp.sg_inv_cell = R.sg_inv_cell = G.invCell; tp.sg_p0sq = R.sg_p0sq = G.p0sq;
-    tp.sg_nx = R.sg_nx = G.nx; tp.sg_ny = R.sg_ny = G.ny; tp.sg_nglobal = R.sg_nglobal = (uint32_t)G.global.size();
+    SetLight(tp, lights[light]), SetLight(R, lights[light]);
+    SetShadowGrid(tp, G), SetShadowGrid(R, G);  // (both forms, filled as rt_scene_upload fills them)
     R.cell_start = cells; R.entries = ents; R.global = glob;
     rtd::SceneConsts K;
     rtd::fill_consts(tp, K);
@@ -2045,17 +1862,14 @@ int rt_unit_shadow(rt_ctx* ctx, uint32_t light, const float* points, uint32_t n,
     if (light >= std::max(1u, ctx->base.n_lights)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow: the scene has no such light");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    TmpDev<float> dIn;
-    TmpDev<uint8_t> dOut;
-    RT_HIP(dIn.Alloc((size_t)n * 3));
-    RT_HIP(dOut.Alloc(n));
-    RT_HIP(hipMemcpy(dIn.p, points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    DevBuf<float> dIn;
+    DevBuf<uint8_t> dOut;
+    int rc;
+    if ((rc = dIn.UploadFrom(points, (size_t)n * 3)) != RT_OK || (rc = dOut.Reserve(n)) != RT_OK) return rc;
     const size_t lds = (size_t)rtd::sg_glob_slots(64u) * 16;  // a global list has 64 entries at most (BuildShadowGrid)
-    hipLaunchKernelGGL(rtd::k_unit_shadow, dim3((n + 255) / 256), dim3(256), lds, ctx->stream, ctx->base, light, glob_in_lds, dIn.p, n, dOut.p);
+    hipLaunchKernelGGL(rtd::k_unit_shadow, dim3((n + 255) / 256), dim3(256), lds, ctx->stream, ctx->base, light, glob_in_lds, dIn.ptr, n, dOut.ptr);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    RT_HIP(hipMemcpy(out, dOut.p, n, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return dOut.DownloadTo(out, n, ctx->stream);
 }
 
 int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t cap_tiles, uint32_t* n_tiles, uint32_t* words,
