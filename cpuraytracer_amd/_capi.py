@@ -79,6 +79,8 @@ EXPORTS = [
     "rt_unit_features_host",
     "rt_unit_shadow_index_host", "rt_unit_shadow_query_host", "rt_unit_shadow",
     "rt_unit_launch_plan", "rt_unit_last_trace_launch", "rt_unit_trace_variants",
+    "rt_unit_trace_lean_variants", "rt_unit_last_trace_far_state", "rt_unit_far_state_plan",
+    "rt_unit_shadow_index_host_tier", "rt_unit_shadow_query_host_tier", "rt_unit_shadow_tier",
     "rt_denoise_default_params", "rt_denoise", "rt_download_denoised", "rt_copy_denoised_to_device", "rt_unit_denoise_host", "rt_unit_denoise_forms",
     "rt_copy_moments_to_device", "rt_rowset_locate", "rt_denoise_shards", "rt_unit_denoise_shards_host",
     "rt_temporal_default_params", "rt_denoise_temporal", "rt_temporal_reset", "rt_download_temporal", "rt_unit_temporal_host",
@@ -182,6 +184,16 @@ def load():
     if hasattr(L, "rt_unit_last_trace_launch"):
         L.rt_unit_last_trace_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.rt_unit_trace_variants.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    if hasattr(L, "rt_unit_last_trace_far_state"):
+        L.rt_unit_trace_lean_variants.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.rt_unit_last_trace_far_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.rt_unit_far_state_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.rt_unit_shadow_index_host_tier.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtLight), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                                     C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                     C.c_void_p]
+        L.rt_unit_shadow_query_host_tier.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtLight), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                     C.c_void_p]
+        L.rt_unit_shadow_tier.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     if hasattr(L, "rt_denoise"):
         L.rt_denoise_default_params.argtypes = [C.POINTER(RtDenoiseParams)]
         L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(RtDenoiseParams), C.POINTER(C.c_double)]

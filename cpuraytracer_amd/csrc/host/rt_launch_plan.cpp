@@ -248,6 +248,13 @@ TracePlan PlanTrace(const SceneShape& S, const Settings& C, const Knobs& K, cons
     return P;
 }
 
+bool FarStateLean(const SceneShape& S, const Ask& A, const TracePlan& P, const FarStateAsk& F) {
+    if (P.status != RT_OK || A.mode != Mode::Ordinary || F.forceFull) return false;
+    if (F.pathList || F.travOut) return false;       // the lean kernels count no traversals per path
+    if (!S.sg_enabled || !F.shadowGrid) return false;  // without an index every shadow ray waits for the scan: that is the far-hit state
+    return FindLeanVariant(P.kernel) >= 0;
+}
+
 ScanOnlyPlan PlanScanOnly(const SceneShape& S, const Settings& C) {
     const ScanChoice V = ChooseScan(S, C, 0u);
     ScanOnlyPlan P{};
@@ -269,31 +276,50 @@ ScanOnlyPlan PlanScanOnly(const SceneShape& S, const Settings& C) {
     return P;
 }
 
-int PlanPacked(const uint32_t* in, uint32_t* out) {
-    SceneShape S;
+namespace {
+
+// a packed case as its four records; false for inputs no context can have
+bool UnpackCase(const uint32_t* in, SceneShape& S, Settings& C, Knobs& K, Ask& A) {
     S.n_padded = in[0], S.n_levels = in[1], S.top_cnt = in[2], S.top_off = in[3];
     S.grid = in[4] & 1u, S.grid_quant = in[4] & 2u, S.sg_enabled = in[4] & 4u, S.mats16 = in[4] & 8u;
     S.grid_nu = in[5], S.grid_nv = in[6];
     S.sg_nx = in[7], S.sg_ny = in[8], S.sg_nentries = in[9], S.sg_nglobal = in[10];
     S.n_lights = in[11];
-    Settings C;
     C.cuCount = in[12], C.blocksPerCu = in[13], C.blockThreads = in[14];
     C.useMfma = in[15] & 1u, C.matsInLds = in[15] & 2u, C.useRayCache = in[15] & 4u, C.useStash = in[15] & 8u, C.treeInLds = in[15] & 16u,
     C.forceGlobal = in[15] & 32u;
-    Knobs K;
     K.mats16 = in[16], K.matsL2 = in[17], K.stashCap = in[18], K.stashProcess = in[19], K.gridQuant = in[20], K.gridSgLds = in[21],
     K.queueBlock = in[22], K.queueStatic = in[23];
-    Ask A;
     A.total_paths = in[24], A.max_depth = in[25];
-    if (in[26] > 1u || in[27] != 0u || (in[4] >> 4) != 0u || (in[15] >> 6) != 0u) return RT_ERR_INVALID_ARG;
+    if (in[26] > 1u || in[27] != 0u || (in[4] >> 4) != 0u || (in[15] >> 6) != 0u) return false;
     A.mode = in[26] ? Mode::Carry : Mode::Ordinary;
     // what rt_create and rt_scene_upload guarantee
     if (C.blocksPerCu == 0u || C.blocksPerCu > 8u || C.blockThreads < 64u || C.blockThreads > 1024u || C.blockThreads % 64u != 0u || C.cuCount == 0u ||
         C.cuCount > 4096u || S.n_levels == 0u || S.n_levels > rtd::kMaxLevels || S.grid_nu > 65535u || S.grid_nv > 65535u || S.sg_nx > 65535u ||
         S.sg_ny > 65535u)
-        return RT_ERR_INVALID_ARG;
+        return false;
+    return true;
+}
+
+}  // namespace
+
+int PlanPacked(const uint32_t* in, uint32_t* out) {
+    SceneShape S;
+    Settings C;
+    Knobs K;
+    Ask A;
+    if (!UnpackCase(in, S, C, K, A)) return RT_ERR_INVALID_ARG;
     PackPlan(PlanTrace(S, C, K, A), PlanScanOnly(S, C), out);
     return RT_OK;
+}
+
+bool FarStateLeanPacked(const uint32_t* in, const FarStateAsk& F) {
+    SceneShape S;
+    Settings C;
+    Knobs K;
+    Ask A;
+    if (!UnpackCase(in, S, C, K, A)) return false;
+    return FarStateLean(S, A, PlanTrace(S, C, K, A), F);
 }
 
 uint32_t KernelWord(const TraceKernelId& k) {

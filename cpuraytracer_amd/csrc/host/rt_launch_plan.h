@@ -83,6 +83,23 @@ struct TracePlan {
 };
 TracePlan PlanTrace(const SceneShape& S, const Settings& C, const Knobs& K, const Ask& A);
 
+// Far-hit state (rt_kernels.h kFarState): whether the planned kernel runs as its row's LEAN function (rt_trace_variants.h
+// RT_TRACE_LEAN_VARIANTS), which answers the shadow ray of a hit point beyond the shadow index inside hit processing and keeps no
+// per-path traversal count.  What is asked of the launch beyond the plan's inputs:
+struct FarStateAsk {
+    bool pathList = false;    // the launch traces an explicit path list (rt_unit_trace) ...
+    bool travOut = false;     // ... or wants per-path traversal counts (TraceParams::trav_out)
+    bool shadowGrid = true;   // the context builds shadow indices (RT_SHADOW_GRID is not 0)
+    bool forceFull = false;   // RT_FAR_STATE=1: the kernels with far-hit state, everywhere (A/B runs, knob tests)
+};
+// Lean: an ordinary picture launch -- no path list, no trav_out -- of a scene whose light 0 has a shadow index, on a row of the lean
+// list, with the knob at rest.  Everything else keeps the full state: a disabled index (a light list without one, RT_SHADOW_GRID=0:
+// every shadow ray then takes the scan, which IS the far-hit state), path lists and rt_unit_trace, the frame-pipelining kernel, the
+// cell-grid and hierarchy scans, the kernels without hit stash.  Does not change the plan: image, grid and kernel word are the row's.
+bool FarStateLean(const SceneShape& S, const Ask& A, const TracePlan& P, const FarStateAsk& F);
+// ... for a packed case of rt_unit_launch_plan (false for a case PlanPacked refuses): rt_unit_far_state_plan
+bool FarStateLeanPacked(const uint32_t* in, const FarStateAsk& F);
+
 // The unit kernels (k_unit_closest, rt_features_kernel): the scan a trace launch would run, 256 threads, the LDS image of four
 // waves with the hit-processing tables left out.
 struct ScanOnlyPlan {

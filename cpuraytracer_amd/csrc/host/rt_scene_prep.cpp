@@ -582,6 +582,22 @@ void BuildLayout(const rt_sphere* signedSp, uint32_t n, const PrepOptions& opt, 
 // 64 x 64 a query of grid10k walked ~15 spheres -- 7 rounds of two dependent L2 reads -- at 256 x 256 (cells of about one
 // footprint) ~5.
 void BuildShadowGrid(const rt_sphere* signedSp, const SceneLayout& L, const float sunDir[3], uint32_t maxCells, ShadowGrid& G) {
+    BuildShadowGridTier(signedSp, L, sunDir, maxCells, 1u, G);
+}
+
+// tier 1: the index above, valid within P0.  tier 2: THE SAME construction -- footprint formula, spill-to-global rule, halving rule --
+// for the hit points beyond P0 (the ground towards the horizon), valid within
+//     P2 = min(4 P0, P1),   P1 = 1.01 max_i(|c_i| + |r_i|) + 1e-30.
+// Why not P1 alone: the footprints are inflated for the reference test's own rounding at the LARGEST point the index answers, by
+// 128 eps P^2 under the root.  A floor of radius 1000 makes P1 about 2000 and every footprint of the cover scene 5.5 units wide where
+// the spheres are 0.2: each covers more than an eighth of the cells, all 480 go to the global list, and the builder gives up (more
+// than 64).  At 4 P0 the inflation is sixteen times the first index's (cover: footprints of 0.42, 20 x 32 cells, the floor alone in
+// the global list), the grid is still a grid, and it reaches beyond every hit a camera near the field can see on such a floor (the
+// horizon from height h on radius R is sqrt(2 R h) away: 63 units from h = 2; cover's P0 is 33, its P2 134).  P1 only caps P2 where the whole scene is smaller than 4 P0: a hit point lies on a sphere, so
+// |p| <= |c| + |r| up to the rounding of t d + o and of the root, for which one per cent is ample; nothing RELIES on that bound --
+// a point beyond P2 is answered by the any-hit over every entry (rt_kernels.h processHit), which is always right and merely slow.
+// Not enabled where P2 <= P0 (no sphere reaches beyond the first index) or where the first index's own reasons apply.
+void BuildShadowGridTier(const rt_sphere* signedSp, const SceneLayout& L, const float sunDir[3], uint32_t maxCells, uint32_t tier, ShadowGrid& G) {
     G = ShadowGrid{};
     uint32_t nSp = 0;
     for (uint32_t o : L.orig)
@@ -617,7 +633,18 @@ void BuildShadowGrid(const rt_sphere* signedSp, const SceneLayout& L, const floa
         if (q.r > 4.0 * med) continue;
         reach = std::max(reach, std::sqrt((double)q.cx * q.cx + (double)q.cy * q.cy + (double)q.cz * q.cz) + q.r);
     }
-    const double P0 = 2.0 * reach + 8.0 * med + 1.0;
+    double P0 = 2.0 * reach + 8.0 * med + 1.0;
+    if (tier >= 2u) {
+        double far = 0;
+        for (size_t e = 0; e < nEnt; ++e) {
+            if (L.orig[e] == 0xffffffffu) continue;
+            const rt_sphere& q = sp[L.orig[e]];
+            far = std::max(far, std::sqrt((double)q.cx * q.cx + (double)q.cy * q.cy + (double)q.cz * q.cz) + q.r);
+        }
+        const double P2 = std::min(4.0 * P0, 1.01 * far + 1e-30);
+        if (!(P2 > P0)) return;
+        P0 = P2;  // from here on the construction is the first index's, for this radius
+    }
     const double eps = 5.9604644775390625e-08;
     struct Foot { double u, v, rho; uint16_t entry; };
     std::vector<Foot> feet;
@@ -680,7 +707,7 @@ void BuildShadowGrid(const rt_sphere* signedSp, const SceneLayout& L, const floa
     size_t total = 0;
     for (const auto& c : cells) total += c.size();
     if (total >= 65535 && maxCells > 64u) {  // too many entries for 16-bit cell starts: the coarser grid
-        BuildShadowGrid(sp, L, sunDir, maxCells / 2u, G);
+        BuildShadowGridTier(sp, L, sunDir, maxCells / 2u, tier, G);
         return;
     }
     if (total >= 65535 || G.global.size() > 64) return;  // pathological: keep the scan
@@ -748,6 +775,8 @@ PreparedScene PrepareScene(const rt_sphere* spheres, const rt_material* material
         BuildShadowGrid(spheres, L, lights[0].direction, L.InGlobalMemory() ? opt.shadowCellsGlobal : opt.shadowCellsLds, P.shadow);
     P.extraShadow.resize(n_lights > 1 ? n_lights - 1 : 0);
     for (uint32_t k = 1; k < n_lights && opt.shadowGrid; ++k) BuildShadowGrid(spheres, L, lights[k].direction, opt.shadowCellsGlobal, P.extraShadow[k - 1]);
+    // light 0's second index, for the hit points beyond the first one's radius: in global memory, like the extra lights'
+    if (P.shadow.enabled) BuildShadowGridTier(spheres, L, lights[0].direction, opt.shadowCellsGlobal, 2u, P.shadowFar);
     // RT_SG_SPH=1 (experiments): the index stays in global memory -- the sphere record of every entry side by side with the ids, so
     // that a walk round is one round trip instead of two.  Measured on grid10k: 7.79 -> 7.66 Gsamples/s (700 KB of duplicated
     // spheres hit the L1 less often than the 160 KB table they are shared from).  Default off.

@@ -87,6 +87,7 @@ struct PreparedScene {
     std::vector<uint32_t> matType;  // material type by ORIGINAL sphere index (rt_tile_order_kernel classifies first hits by it)
     ShadowGrid shadow;                     // the first light's index (not enabled: no lights, switched off, or the scene does not suit)
     std::vector<ShadowGrid> extraShadow;   // one per light 1 .. n_lights - 1
+    ShadowGrid shadowFar;                  // the first light's tier-2 index: hit points with p0sq(shadow) < |p|^2 <= p0sq(shadowFar); not enabled: none
     std::vector<F4> sgSph;                 // PrepOptions::sgSph: the scan record of every entry of `shadow` (+ one that never hits), else empty
     unsigned long long singleMask[2] = {0ull, 0ull};  // layout.singleMask, or zero (PrepOptions::singleDirect)
 };
@@ -106,6 +107,8 @@ std::string MaterialFaultMessage(const char* who, const std::string& what, const
 
 void BuildLayout(const rt_sphere* spheres, uint32_t n, const PrepOptions& opt, SceneLayout& L);
 void BuildShadowGrid(const rt_sphere* spheres, const SceneLayout& L, const float lightDir[3], uint32_t maxCells, ShadowGrid& G);
+// tier 1: the same; tier 2: the index for the hit points beyond tier 1's radius (rt_scene_prep.cpp states its radius and why)
+void BuildShadowGridTier(const rt_sphere* spheres, const SceneLayout& L, const float lightDir[3], uint32_t maxCells, uint32_t tier, ShadowGrid& G);
 
 // spheres: n > 0, all finite (AllFinite).  A layout of 65,536 scan entries or more cannot be indexed by the 16-bit ids of the
 // tables behind it: then only `layout` is filled, and the caller refuses the scene.

@@ -138,6 +138,9 @@ struct rt_ctx {
     };
     ExtraLight extraIdx[RT_MAX_LIGHTS];
     DevBuf<rtd::LightRec> lightRecs;
+    // light 0's second shadow index (rt_params.h far_index): its tables, in global memory like an extra light's; its record is the
+    // last of lightRecs
+    ExtraLight farIdx;
     DevBuf<uint16_t> gridCells;  // cell-grid scan: first scan entry per cell
     DevBuf<uint32_t> gridQ;      // ... and the quantised one-sphere bounds per scan entry (rt_scan.h GridQuant)
     bool useShadowGrid = true;  // RT_SHADOW_GRID=0 keeps every shadow ray on the scan
@@ -209,6 +212,7 @@ struct rt_ctx {
     // rt_unit_launch_plan, and the launches since rt_create
     uint32_t lastCaseWords[rtplan::kCaseWords] = {}, lastPlanWords[rtplan::kPlanWords] = {};
     uint32_t traceLaunches = 0;
+    bool lastTraceLean = false;  // ... and whether it ran its row's kernel without far-hit state (rt_unit_last_trace_far_state)
 
     // The per-tile tables: candidate masks and sphere lists of the primary rays (BuildTileMasks; rt_tile_mask.h), work order and
     // empty-list flags (BuildTileOrder), the flagged tiles' count.  What of them is valid, for which picture and limits, and what a
@@ -379,6 +383,15 @@ static const ClosestKernelFn kClosestKernels[] = {RT_SCAN_VARIANTS(RT_ROW)};
 static const FeaturesKernelFn kFeaturesKernels[] = {RT_SCAN_VARIANTS(RT_ROW)};
 #undef RT_ROW
 static_assert(sizeof(kTraceKernels) / sizeof(kTraceKernels[0]) == rtplan::kTraceVariantCount, "one row per variant of the list");
+// ... and the rows that exist without far-hit state as well (rt_trace_variants.h RT_TRACE_LEAN_VARIANTS), instantiated behind them
+static const struct {
+    TraceKernelFn one, lights;
+} kTraceLeanKernels[] = {
+#define RT_ROW(...) {&rtd::rt_trace_kernel_lean<__VA_ARGS__>, &rtd::rt_trace_kernel_lights_lean<__VA_ARGS__>},
+    RT_TRACE_LEAN_VARIANTS(RT_ROW)
+#undef RT_ROW
+};
+static_assert(sizeof(kTraceLeanKernels) / sizeof(kTraceLeanKernels[0]) == rtplan::kTraceLeanVariantCount, "one row per variant of the lean list");
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of (device, function), process-wide: every kernel variant is raised
 // ONCE per device to the 160 KiB a workgroup can have, so that two contexts with different scenes can never disagree about it
@@ -426,13 +439,21 @@ static int LaunchTrace(rt_ctx* ctx, rtd::TraceParams& tp, rtplan::Mode mode = rt
     }
     const int row = rtplan::FindTraceVariant(P.kernel);
     if (row < 0) return Fail(RT_ERR_HIP, "internal: the launch plan chose a trace kernel variant that is not instantiated");
-    const TraceKernelFn fn = P.kernel.lights ? kTraceKernels[row].lights : kTraceKernels[row].one;
+    // far-hit state or not (host/rt_launch_plan.h FarStateLean; RT_FAR_STATE is read at every launch, like the other knobs)
+    rtplan::FarStateAsk far;
+    far.pathList = tp.path_list != nullptr, far.travOut = tp.trav_out != nullptr;
+    far.shadowGrid = ctx->useShadowGrid, far.forceFull = EnvU32("RT_FAR_STATE", 0) != 0u;
+    const bool lean = rtplan::FarStateLean(shape, ask, P, far);
+    const int leanRow = lean ? rtplan::FindLeanVariant(P.kernel) : -1;
+    const TraceKernelFn fn = lean ? (P.kernel.lights ? kTraceLeanKernels[leanRow].lights : kTraceLeanKernels[leanRow].one)
+                                  : (P.kernel.lights ? kTraceKernels[row].lights : kTraceKernels[row].one);
     if (const int rc = RaiseLdsLimit(ctx->device, reinterpret_cast<const void*>(fn), P.ldsBytes)) return rc;
     hipLaunchKernelGGL(fn, dim3(P.blocks), dim3(ctx->blockThreads), P.ldsBytes, ctx->stream, tp);
     RT_HIP(hipGetLastError());
     // what was planned and applied, in rt_unit_launch_plan's words (the plan's own packing: nothing is restated here)
     rtplan::PackCase(shape, settings, knobs, ask, ctx->lastCaseWords);
     rtplan::PackPlan(P, rtplan::PlanScanOnly(shape, settings), ctx->lastPlanWords);
+    ctx->lastTraceLean = lean;
     ++ctx->traceLaunches;
     return RT_OK;
 }
@@ -886,6 +907,14 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
         }
         recs.push_back(R);
     }
+    const rtprep::ShadowGrid& FG = P.shadowFar;  // (enabled only with light 0's first index, so n_lights >= 1: record n_lights - 1)
+    if (FG.enabled) {
+        rtd::LightRec R{};
+        SetShadowGrid(R, FG);
+        if ((rc = UploadShadowGrid(FG, ctx->farIdx.cells, ctx->farIdx.entries, ctx->farIdx.global)) != RT_OK) return rc;
+        R.cell_start = ctx->farIdx.cells.ptr; R.entries = ctx->farIdx.entries.ptr; R.global = ctx->farIdx.global.ptr;
+        recs.push_back(R);
+    }
     if (!recs.empty() && (rc = ctx->lightRecs.Upload(recs)) != RT_OK) return rc;
     if (SG.enabled && (rc = UploadShadowGrid(SG, ctx->sgCells, ctx->sgEntries, ctx->sgGlobal)) != RT_OK) return rc;
     if (!P.sgSph.empty() && (rc = ctx->sgSph.Upload(P.sgSph)) != RT_OK) return rc;
@@ -914,6 +943,7 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     b.n_lights = n_lights;
     b.extra_lights = recs.empty() ? nullptr : ctx->lightRecs.ptr;
     SetShadowGrid(b, SG);
+    b.far_index = FG.enabled ? 1u : 0u;
     if (SG.enabled) {
         b.sg_cell_start = ctx->sgCells.ptr;
         b.sg_entries = ctx->sgEntries.ptr;
@@ -1781,13 +1811,56 @@ int rt_unit_trace_variants(uint32_t* kernel_words, uint32_t cap, uint32_t* n) {
     return RT_OK;
 }
 
+int rt_unit_last_trace_far_state(rt_ctx* ctx, uint32_t* lean) {
+    if (!ctx || !lean) return Fail(RT_ERR_INVALID_ARG, "rt_unit_last_trace_far_state: invalid argument");
+    if (ctx->traceLaunches == 0) return Fail(RT_ERR_SEQUENCE, "rt_unit_last_trace_far_state: this context has launched no trace kernel");
+    *lean = ctx->lastTraceLean ? 1u : 0u;
+    return RT_OK;
+}
+
+int rt_unit_trace_lean_variants(uint32_t* kernel_words, uint32_t cap, uint32_t* n) {
+    if (!n || (!kernel_words && cap != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_trace_lean_variants: invalid argument");
+    *n = (uint32_t)rtplan::kTraceLeanVariantCount;
+    if (cap == 0) return RT_OK;
+    if (cap < *n) return Fail(RT_ERR_INVALID_ARG, "rt_unit_trace_lean_variants: capacity too small");
+    for (int r = 0; r < rtplan::kTraceLeanVariantCount; ++r) kernel_words[r] = rtplan::KernelWord(rtplan::kTraceLeanVariants[r]);
+    return RT_OK;
+}
+
+int rt_unit_far_state_plan(const uint32_t* case_words, uint32_t path_list, uint32_t trav_out, uint32_t shadow_grid, uint32_t force_full, uint32_t* lean) {
+    if (!case_words || !lean) return Fail(RT_ERR_INVALID_ARG, "rt_unit_far_state_plan: invalid argument");
+    uint32_t plan[rtplan::kPlanWords];
+    if (rtplan::PlanPacked(case_words, plan) != RT_OK) return Fail(RT_ERR_INVALID_ARG, "rt_unit_far_state_plan: the case describes no context or scene there can be");
+    rtplan::FarStateAsk F;
+    F.pathList = path_list != 0u, F.travOut = trav_out != 0u, F.shadowGrid = shadow_grid != 0u, F.forceFull = force_full != 0u;
+    *lean = rtplan::FarStateLeanPacked(case_words, F) ? 1u : 0u;
+    return RT_OK;
+}
+
+// which of light `light`'s indices: tier 1 = the index of rt_unit_shadow_index_host, tier 2 = light 0's second index
+static const rtprep::ShadowGrid* ShadowTier(const char* who, const rtprep::PreparedScene& P, uint32_t light, uint32_t tier) {
+    if (tier == 1u) return light == 0u ? &P.shadow : &P.extraShadow[light - 1u];
+    if (tier == 2u && light == 0u) return &P.shadowFar;
+    Fail(RT_ERR_INVALID_ARG, std::string(who) + ": tier 2 exists for light 0 only; tiers are 1 and 2");
+    return nullptr;
+}
+
 int rt_unit_shadow_index_host(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light, uint32_t out_u[8],
                               float out_f[10], uint32_t cap_cells, uint16_t* cell_start, uint32_t cap_entries, uint16_t* entries,
                               uint32_t cap_global, uint16_t* global, uint32_t cap_orig, uint32_t* orig) {
+    return rt_unit_shadow_index_host_tier(spheres, n, lights, n_lights, light, 1u, out_u, out_f, cap_cells, cell_start, cap_entries, entries, cap_global,
+                                          global, cap_orig, orig);
+}
+
+int rt_unit_shadow_index_host_tier(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light, uint32_t tier,
+                                   uint32_t out_u[8], float out_f[10], uint32_t cap_cells, uint16_t* cell_start, uint32_t cap_entries, uint16_t* entries,
+                                   uint32_t cap_global, uint16_t* global, uint32_t cap_orig, uint32_t* orig) {
     if (!out_u || !out_f) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow_index_host: invalid argument");
     rtprep::PreparedScene P;
     if (const int rc = PrepareForShadow("rt_unit_shadow_index_host", spheres, n, lights, n_lights, light, P)) return rc;
-    const rtprep::ShadowGrid& G = light == 0u ? P.shadow : P.extraShadow[light - 1u];
+    const rtprep::ShadowGrid* Gp = ShadowTier("rt_unit_shadow_index_host_tier", P, light, tier);
+    if (!Gp) return RT_ERR_INVALID_ARG;
+    const rtprep::ShadowGrid& G = *Gp;
     const std::vector<uint32_t>& O = P.layout.orig;
     out_u[0] = G.enabled ? 1u : 0u;
     out_u[1] = G.nx; out_u[2] = G.ny;
@@ -1814,9 +1887,25 @@ int rt_unit_shadow_index_host(const rt_sphere* spheres, uint32_t n, const rt_lig
 // their LightRec -- over the prepared tables where they lie on the host.
 int rt_unit_shadow_query_host(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light,
                               const float* points, uint32_t n_points, uint8_t* out) {
+    return rt_unit_shadow_query_host_tier(spheres, n, lights, n_lights, light, 1u, points, n_points, out);
+}
+
+// tier 2 (light 0): the question as the kernels without far-hit state ask it (rt_kernels.h farShadow): a point beyond the first index
+// is answered by the second one within its radius (bit 2 set, bit 1 clear), else by the any-hit over every entry
+int rt_unit_shadow_query_host_tier(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light, uint32_t tier,
+                                   const float* points, uint32_t n_points, uint8_t* out) {
     if ((!points || !out) && n_points != 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow_query_host: invalid argument");
     rtprep::PreparedScene P;
     if (const int rc = PrepareForShadow("rt_unit_shadow_query_host", spheres, n, lights, n_lights, light, P)) return rc;
+    if (!ShadowTier("rt_unit_shadow_query_host_tier", P, light, tier)) return RT_ERR_INVALID_ARG;
+    const rtprep::ShadowGrid& FG = P.shadowFar;
+    rtd::LightRec FR{};
+    if (tier == 2u && FG.enabled) {
+        SetShadowGrid(FR, FG);
+        FR.cell_start = FG.cellStart.data();
+        FR.entries = FG.entries.empty() ? FG.cellStart.data() : FG.entries.data();  // (an empty list is never read: any address)
+        FR.global = FG.global.empty() ? FG.cellStart.data() : FG.global.data();
+    }
     const rtprep::ShadowGrid& G = light == 0u ? P.shadow : P.extraShadow[light - 1u];
     const float4* scanTab = reinterpret_cast<const float4*>(P.layout.scan.data());
     const uint32_t nPad = (uint32_t)P.layout.scan.size();
@@ -1835,12 +1924,15 @@ int rt_unit_shadow_query_host(const rt_sphere* spheres, uint32_t n, const rt_lig
     for (uint32_t k = 0; k < n_points; ++k) {
         const rtd::V3 pos = rtd::v3(points[3 * (size_t)k], points[3 * (size_t)k + 1], points[3 * (size_t)k + 2]);
         const float pp = rtd::dot3(pos, pos);
-        bool useIndex, occ;
+        bool useIndex, occ, useFar = false;
         if (light == 0u) {
             const rtd::V3 sunDir = rtd::v3(K.sun_dir[0], K.sun_dir[1], K.sun_dir[2]);
             const float aSun = rtd::dot3(sunDir, sunDir);
             useIndex = K.sg_enabled && pp <= K.sg_p0sq;
+            useFar = !useIndex && FR.sg_enabled != 0u && pp <= FR.sg_p0sq;
             occ = useIndex ? rtd::shadow_query(K, scanTab, cells, ents, glob, false, (const float4*)nullptr, (const uint16_t*)nullptr, entrySph, pos, sunDir, aSun)
+                  : useFar ? rtd::shadow_query(FR, scanTab, FR.cell_start, FR.entries, FR.global, false, (const float4*)nullptr, (const uint16_t*)nullptr,
+                                               (const float4*)nullptr, pos, sunDir, aSun)
                            : rtd::any_hit_all(scanTab, nPad, pos, sunDir, aSun);
         } else {
             const rtd::LightRec& Lk = R;
@@ -1851,13 +1943,18 @@ int rt_unit_shadow_query_host(const rt_sphere* spheres, uint32_t n, const rt_lig
                                                (const float4*)nullptr, pos, dirK, aK)
                            : rtd::any_hit_all(scanTab, nPad, pos, dirK, aK);
         }
-        out[k] = (uint8_t)((occ ? 1u : 0u) | (useIndex ? 0u : 2u));
+        out[k] = (uint8_t)((occ ? 1u : 0u) | ((useIndex || useFar) ? 0u : 2u) | (useFar ? 4u : 0u));
     }
     return RT_OK;
 }
 
 int rt_unit_shadow(rt_ctx* ctx, uint32_t light, const float* points, uint32_t n, uint32_t glob_in_lds, uint8_t* out) {
+    return rt_unit_shadow_tier(ctx, light, 1u, points, n, glob_in_lds, out);
+}
+
+int rt_unit_shadow_tier(rt_ctx* ctx, uint32_t light, uint32_t tier, const float* points, uint32_t n, uint32_t glob_in_lds, uint8_t* out) {
     if (!ctx || !points || !out) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow: invalid argument");
+    if (tier != 1u && !(tier == 2u && light == 0u)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow_tier: tier 2 exists for light 0 only; tiers are 1 and 2");
     if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_shadow: no scene uploaded");
     if (light >= std::max(1u, ctx->base.n_lights)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_shadow: the scene has no such light");
     if (n == 0) return RT_OK;
@@ -1867,7 +1964,7 @@ int rt_unit_shadow(rt_ctx* ctx, uint32_t light, const float* points, uint32_t n,
     int rc;
     if ((rc = dIn.UploadFrom(points, (size_t)n * 3)) != RT_OK || (rc = dOut.Reserve(n)) != RT_OK) return rc;
     const size_t lds = (size_t)rtd::sg_glob_slots(64u) * 16;  // a global list has 64 entries at most (BuildShadowGrid)
-    hipLaunchKernelGGL(rtd::k_unit_shadow, dim3((n + 255) / 256), dim3(256), lds, ctx->stream, ctx->base, light, glob_in_lds, dIn.ptr, n, dOut.ptr);
+    hipLaunchKernelGGL(rtd::k_unit_shadow, dim3((n + 255) / 256), dim3(256), lds, ctx->stream, ctx->base, light, glob_in_lds, dIn.ptr, n, dOut.ptr, tier);
     RT_HIP(hipGetLastError());
     return dOut.DownloadTo(out, n, ctx->stream);
 }

@@ -319,8 +319,17 @@ RT_DEV bool claim_block(const TraceParams& p, SceneConsts* ldsK, uint32_t lane, 
 // (rt_trace_kernel_lights: Material::Shade's loop, material.cpp:4-13).  Two entry kernels over one body, so that the single-light
 // kernels' code and register allocation are exactly what they were without the list.
 // kGridQ (cell-grid scan, global tables): the quantised one-sphere bounds are staged into LDS behind the cells (rt_scan.h GridQuant).
-template <bool kLights, bool kLds, int kThreads, int kScan, bool kCache, bool kHitLds, bool kCarry, bool kStash, bool kMatsL2, bool kSgLds, bool kGridQ>
+// kFarState: true = a hit point beyond the shadow index's radius waits one iteration in kNeedShadow and takes a lane of the next scan
+// (one light), carrying pend, nextDir, contAfterShadow and pathScattered across the loop; and every path counts its traversals for
+// trav_out.  false (the flat hit-stash kernels of picture launches, rt_trace_kernel_lean below): such a hit is answered inside
+// processHit -- by light 0's second index (p.far_index), or by the any-hit over every entry -- so that none of that state, nor
+// pathTrav with its stash dword (dword 18 stays in the record, unread and unwritten), lives across an iteration: nextDir is then
+// written by Scatter and read a few lines on, in the same hit processing.  Same arithmetic on the same values, same counts: only where
+// the far shadow ray is answered changes.  (The kFarState == true code is the text it was, so that those kernels keep their code.)
+template <bool kLights, bool kLds, int kThreads, int kScan, bool kCache, bool kHitLds, bool kCarry, bool kStash, bool kMatsL2, bool kSgLds, bool kGridQ,
+          bool kFarState = true>
 __device__ __forceinline__ void trace_body(const TraceParams& p) {
+    static_assert(kFarState || (kLds && kScan == 1 && kStash && !kCarry), "without far-hit state: the flat LDS hit-stash family, no frame pipelining");
     static_assert(!kGridQ || (kScan == 3 && !kLds && kHitLds && !kSgLds), "quantised bounds: the global-tables grid variant");
     static_assert(!kSgLds || (kScan == 3 && !kLds && kHitLds), "shadow index in LDS next to the grid's cells: the global-tables grid variant");
     static_assert(!kMatsL2 || (kHitLds && kStash && kLds), "materials through L2: a flavour of the all-in-LDS stash variants");
@@ -490,7 +499,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         RT_SITE(K_FINISH);
         const float expo = K.exposure;
         *reinterpret_cast<float3*>(p.samples + (size_t)q * 3) = make_float3(rad.x * expo, rad.y * expo, rad.z * expo);
-        if (p.trav_out) p.trav_out[q] = pathTrav;
+        if (kFarState && p.trav_out) p.trav_out[q] = pathTrav;  // (a launch with trav_out takes a kFarState kernel: host/rt_launch_plan.cpp)
         state = kIdle;
 #ifdef RT_TIMELINE
         if (!kCarry && tlDrain != 0ull && gwave < 4096u) {
@@ -502,6 +511,16 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
 #ifdef RT_STAMPS
     unsigned long long thA = 0, thB = 0;
 #endif
+    // kFarState == false: light 0's shadow question for a hit point beyond its first index (|p|^2 = pp > sg_p0sq): the second index
+    // within its radius; beyond that, or where the scene has none, the any-hit over every entry.  All three answer "does any entry
+    // yield an accepted root", which is what the shadow scan answered.
+    auto farShadow = [&](V3 pos, float pp) -> bool {
+        RT_SITE(H_FARHIT);
+        const LightRec* F = far_index_rec(p);
+        if (F != nullptr && pp <= F->sg_p0sq)
+            return shadow_query(*F, scanTab, F->cell_start, F->entries, F->global, false, globSph, globIds, (const float4*)nullptr, pos, sunDir, aSun);
+        return any_hit_all(scanTab, p.n_padded, pos, sunDir, aSun);
+    };
     // Hit processing of one closest hit (scan entry idx at pos) for a lane in state kNeedClosest: Scatter, the shadow
     // query, Emit + Shade, and the path's next state (GetHitColor, spheres-app.cpp:238-257).
     auto processHit = [&](int idx, V3 pos, bool& finished) {
@@ -533,7 +552,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                 if (k == 0u) {
                     occ = (K.sg_enabled && pp <= K.sg_p0sq)
                               ? shadow_query(K, scanTab, sgCell, sgEntries, sgGlobal, p.sg_glob16 != 0u, globSph, globIds, (!kLds && kScan >= 2) ? p.sg_sph : nullptr, pos, sunDir, aSun)
-                              : any_hit_all(scanTab, p.n_padded, pos, sunDir, aSun);
+                              : (kFarState ? any_hit_all(scanTab, p.n_padded, pos, sunDir, aSun) : farShadow(pos, pp));
                     sh = occ ? v3(0.f, 0.f, 0.f) : shade_only(K, m, tex, pos, nrm, mt);
                 } else {
                     const LightRec& Lk = p.extra_lights[k - 1u];
@@ -545,7 +564,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                     sh = occ ? v3(0.f, 0.f, 0.f) : shade_only(Lk, m, tex, pos, nrm, mt);
                 }
                 ++nTrav;
-                ++pathTrav;
+                if (kFarState) ++pathTrav;
                 direct = direct + sh;  // (an occluded light's Shade is XM_Zero, light.cpp:15-18)
             }
             rad = rad + thr * (emitOnly + direct);  // radiance += throughput * (Emit + Shade)
@@ -562,6 +581,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         const bool useIndex = K.sg_enabled && dot3(pos, pos) <= K.sg_p0sq;
         bool occluded = false;
         if (useIndex) occluded = shadow_query(K, scanTab, sgCell, sgEntries, sgGlobal, p.sg_glob16 != 0u, globSph, globIds, (!kLds && kScan >= 2) ? p.sg_sph : nullptr, pos, sunDir, aSun);
+        else if (!kFarState) occluded = farShadow(pos, dot3(pos, pos));
         RT_STAMP(th2);
         // the Blinn-Phong value (two normalisations, two pows) is only needed when the sun is visible or unknown
         shade_value(K, m, tex, pos, nrm, !occluded, local, localOcc, mt);
@@ -573,11 +593,11 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         RT_ACC(cyHit[0], th0, th1);
         RT_ACC(cyHit[1], th1, th2);
         RT_ACC(cyHit[2], th2, th3);
-        if (useIndex) {
+        if (useIndex || !kFarState) {
             RT_SITE(H_INDEXED);
-            // shadow ray answered by the exact footprint index: no second scan for this hit
+            // shadow ray answered by the exact footprint index (or, kFarState == false, in place above): no second scan for this hit
             ++nTrav;  // the shadow ray still counts as a traversal of the scene (matches the oracle's counter)
-            ++pathTrav;
+            if (kFarState) ++pathTrav;
             if (!occluded) rad = rad + thr * local;           // radiance += throughput * (Emit + Shade)
             else if (!scattered) rad = rad + thr * localOcc;  // occluded: throughput * (Emit + 0)
             if (cont) {
@@ -638,7 +658,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                                     __float_as_uint(e[15u * cap])};
                     q = __float_as_uint(e[16u * cap]);
                     depth = __float_as_uint(e[17u * cap]);
-                    pathTrav = __float_as_uint(e[18u * cap]);
+                    if (kFarState) pathTrav = __float_as_uint(e[18u * cap]);
                     state = kHaveHit;
                 }
                 stashCnt -= n;
@@ -647,7 +667,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             const uint64_t hitMask = __ballot(state == kHaveHit);
             const uint32_t nHit = (uint32_t)__popcll(hitMask);
             bool process = nHit > p.stash_process;
-            if (!process && nHit != 0u && __ballot(state == kNeedClosest || state == kNeedShadow) == 0ull) {
+            if (!process && nHit != 0u && __ballot(state == kNeedClosest || (kFarState && state == kNeedShadow)) == 0ull) {
                 if (blkNext == blkEnd && !queueEmpty && !nextBlock()) queueEmpty = true;
                 if (blkNext == blkEnd) {
                     process = true;  // no fresh paths left: the hits are processed as they are
@@ -667,7 +687,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                         e[14u * cap] = __uint_as_float(draws.rng.s2); e[15u * cap] = __uint_as_float(draws.rng.s3);
                         e[16u * cap] = __uint_as_float(q);
                         e[17u * cap] = __uint_as_float(depth);
-                        e[18u * cap] = __uint_as_float(pathTrav);
+                        if (kFarState) e[18u * cap] = __uint_as_float(pathTrav);
                         state = kIdle;
                     }
                     stashCnt = nHit;
@@ -908,7 +928,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         // ------------------------------------------------ one list scan for every live lane
         float tmin = 0.f;
         int idx = -1;
-        const bool live = kStash ? (state == kNeedClosest || state == kNeedShadow) : (state != kIdle);  // (lanes holding a hit wait)
+        const bool live = kStash ? (state == kNeedClosest || (kFarState && state == kNeedShadow)) : (state != kIdle);  // (lanes holding a hit wait)
         if (kMfma) {
             // every lane takes part: lane l also supplies operands for, and filters half the spheres of,
             // the ray owned by lane l^32, whether or not its own ray is live
@@ -936,7 +956,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         }
         if (live) {
             ++nTrav;
-            ++pathTrav;
+            if (kFarState) ++pathTrav;
         }
 
         RT_STAMP(ts2);
@@ -964,7 +984,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             } else {
                 processHit(idx, tmin * rd + ro, finished);  // XMVectorMultiplyAdd(t, dir, origin), ray-tracing.cpp:57
             }
-        } else if (state == kNeedShadow) {
+        } else if (kFarState && state == kNeedShadow) {
             RT_SITE(K_TRANS_SHADOW);
             if (idx < 0) rad = rad + pend;              // sun visible: radiance += throughput * (Emit + Shade)
             else if (!pathScattered) rad = rad + nextDir;  // occluded: radiance += throughput * (Emit + 0)
@@ -1076,6 +1096,17 @@ template <bool kLds, int kThreads, int kScan, bool kCache, bool kHitLds = false,
           bool kSgLds = false, bool kGridQ = false>
 __global__ void __launch_bounds__(kThreads, 1) rt_trace_kernel_lights(const TraceParams p) {
     trace_body<true, kLds, kThreads, kScan, kCache, kHitLds, kCarry, kStash, kMatsL2, kSgLds, kGridQ>(p);
+}
+
+// ... and the flat LDS hit-stash kernels without far-hit state (trace_body, kFarState == false; rt_trace_variants.h RT_TRACE_LEAN_VARIANTS),
+// as entries of their own: the kernels above keep their names and their code
+template <bool kLds, int kThreads, int kScan, bool kCache, bool kHitLds, bool kCarry, bool kStash, bool kMatsL2, bool kSgLds, bool kGridQ>
+__global__ void __launch_bounds__(kThreads, 1) rt_trace_kernel_lean(const TraceParams p) {
+    trace_body<false, kLds, kThreads, kScan, kCache, kHitLds, kCarry, kStash, kMatsL2, kSgLds, kGridQ, false>(p);
+}
+template <bool kLds, int kThreads, int kScan, bool kCache, bool kHitLds, bool kCarry, bool kStash, bool kMatsL2, bool kSgLds, bool kGridQ>
+__global__ void __launch_bounds__(kThreads, 1) rt_trace_kernel_lights_lean(const TraceParams p) {
+    trace_body<true, kLds, kThreads, kScan, kCache, kHitLds, kCarry, kStash, kMatsL2, kSgLds, kGridQ, false>(p);
 }
 
 // ============================================================ ray-generation tables (A1, A9)
@@ -1715,8 +1746,10 @@ __global__ void k_unit_scatter(const TraceParams p, const rt_material* mat, cons
 // The shadow question of the hit processing (processHit above) for given points and light `light` of the scene's list, over the
 // uploaded tables: out = bit 0 occluded | bit 1 answered by any_hit_all (index off, or |p|^2 > sg_p0sq).  globLds: the index's
 // global list from an LDS copy of (spheres, ids), staged as rt_trace_kernel's prologue stages globSph / globIds (dynamic LDS:
-// sg_glob_slots(global entries) float4); else from its id list.
-__global__ void __launch_bounds__(256) k_unit_shadow(const TraceParams p, uint32_t light, uint32_t globLds, const float* pts, uint32_t n, uint8_t* out) {
+// sg_glob_slots(global entries) float4); else from its id list.  tier 2 (light 0 only): the question as the kernels without far-hit state
+// ask it (trace_body farShadow) -- a point beyond the first index goes to the second one within ITS radius: bit 2 set, bit 1 clear.
+__global__ void __launch_bounds__(256) k_unit_shadow(const TraceParams p, uint32_t light, uint32_t globLds, const float* pts, uint32_t n, uint8_t* out,
+                                                     uint32_t tier) {
     extern __shared__ float4 smem[];
     const LightRec* Lk = light != 0u ? p.extra_lights + (light - 1u) : nullptr;
     const bool enabled = (Lk ? Lk->sg_enabled : p.sg_enabled) != 0u;
@@ -1736,12 +1769,15 @@ __global__ void __launch_bounds__(256) k_unit_shadow(const TraceParams p, uint32
     if (k >= n) return;
     const V3 pos = v3(pts[3 * (size_t)k], pts[3 * (size_t)k + 1], pts[3 * (size_t)k + 2]);
     const float pp = dot3(pos, pos);
-    bool useIndex, occ;
+    bool useIndex, occ, useFar = false;
     if (Lk == nullptr) {
         const V3 sunDir = v3(p.sun_dir[0], p.sun_dir[1], p.sun_dir[2]);
         const float aSun = dot3(sunDir, sunDir);
         useIndex = p.sg_enabled && pp <= p.sg_p0sq;
+        const LightRec* F = tier >= 2u ? far_index_rec(p) : nullptr;
+        useFar = !useIndex && F != nullptr && pp <= F->sg_p0sq;
         occ = useIndex ? shadow_query(p, p.scan, p.sg_cell_start, p.sg_entries, p.sg_global, inLds, globSph, globIds, p.sg_sph, pos, sunDir, aSun)
+              : useFar ? shadow_query(*F, p.scan, F->cell_start, F->entries, F->global, false, globSph, globIds, (const float4*)nullptr, pos, sunDir, aSun)
                        : any_hit_all(p.scan, p.n_padded, pos, sunDir, aSun);
     } else {
         const V3 dirK = v3(Lk->sun_dir[0], Lk->sun_dir[1], Lk->sun_dir[2]);
@@ -1750,7 +1786,7 @@ __global__ void __launch_bounds__(256) k_unit_shadow(const TraceParams p, uint32
         occ = useIndex ? shadow_query(*Lk, p.scan, Lk->cell_start, Lk->entries, Lk->global, inLds, globSph, globIds, (const float4*)nullptr, pos, dirK, aK)
                        : any_hit_all(p.scan, p.n_padded, pos, dirK, aK);
     }
-    out[k] = (uint8_t)((occ ? 1u : 0u) | (useIndex ? 0u : 2u));
+    out[k] = (uint8_t)((occ ? 1u : 0u) | ((useIndex || useFar) ? 0u : 2u) | (useFar ? 4u : 0u));
 }
 // Resolve for given HDR triples (tonemap unit test): in 3 floats, out 3 bytes
 __global__ void k_unit_tonemap(const float* hdr, uint32_t n, uint32_t nSamples, uint8_t* out) {

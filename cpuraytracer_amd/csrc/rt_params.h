@@ -216,7 +216,15 @@ struct TraceParams {
     // 1: a full tile whose sphere list is empty is finished in K_GEN without rays (rt_kernels.h kSky); set only beside tile_spheres
     // and never with a path list (RT_SKY_SKIP=0: 0)
     uint32_t sky_skip;
+    // 1: light 0 has a SECOND shadow index (host/rt_scene_prep.cpp BuildShadowGridTier), for the hit points with sg_p0sq < |p|^2 <= its
+    // own sg_p0sq: a record behind the extra lights', extra_lights[n_lights - 1] (far_index_rec below), in global memory like theirs
+    // (only the sg_* members and the three tables are filled).  0: the scene has none.  Read by the kernels without far-hit state
+    // (rt_kernels.h kFarState == false) and by k_unit_shadow.  A 32-bit flag in the structure's tail padding and not a pointer of its
+    // own: the kernel-argument segment keeps its size, and with it every other kernel its code (the hidden arguments lie behind it).
+    uint32_t far_index;
 };
+// light 0's second shadow index, or null
+RT_DEV const LightRec* far_index_rec(const TraceParams& p) { return p.far_index != 0u ? p.extra_lights + (p.n_lights - 1u) : nullptr; }
 
 // The scene and pass constants the hit processing and the ray generation read, copied once per workgroup into LDS
 // (rt_trace_kernel): as kernel arguments they live in SGPRs for the whole persistent loop (~60 of them, spilled to VGPR

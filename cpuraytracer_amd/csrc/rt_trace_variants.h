@@ -4,7 +4,8 @@
 //
 // A row is X(kLds, kThreads, kScan, kCache, kHitLds, kCarry, kStash, kMatsL2, kSgLds, kGridQ), the template arguments of
 // rt_trace_kernel (rt_kernels.h) in their order.  Every row exists twice in the library: for scenes with one light, and as the
-// _lights twin.  55 rows; the order is the order of instantiation and so the order of the kernels in the code object.
+// _lights twin.  55 rows; the order is the order of instantiation and so the order of the kernels in the code object.  Three of the
+// rows exist once more without far-hit state (RT_TRACE_LEAN_VARIANTS below), instantiated behind the 110.
 #pragma once
 
 #include <stdint.h>
@@ -58,6 +59,16 @@
 // LDS tables, VALU scan with global tables.
 #define RT_SCAN_VARIANTS(X) X(false, 3) X(false, 2) X(true, 1) X(true, 0) X(false, 0)
 
+// The rows of RT_TRACE_VARIANTS that exist a second time WITHOUT far-hit state (rt_kernels.h trace_body, kFarState == false:
+// rt_trace_kernel_lean and rt_trace_kernel_lights_lean): the flat LDS hit-stash family -- kLds, kScan == 1, kStash, no frame
+// pipelining; the stash exists at 1024 threads only.  Same tuples, same kernel words: a lean kernel is its row's kernel for picture
+// launches (host/rt_launch_plan.h FarStateLean), not another row, and the launcher reports which of the two ran beside the plan
+// (rt_unit_last_trace_far_state).  Six more functions in the library, behind the 110.
+#define RT_TRACE_LEAN_VARIANTS(X)                                  \
+    X(true, 1024, 1, true, true, false, true, true, false, false)  \
+    X(true, 1024, 1, true, true, false, true, false, false, false) \
+    X(true, 1024, 1, true, false, false, true, false, false, false)
+
 namespace rtplan {
 
 // Which rt_trace_kernel: `lights` picks the _lights twin, the rest are the template arguments.
@@ -82,6 +93,28 @@ constexpr TraceKernelId kTraceVariants[] = {RT_TRACE_VARIANTS(RT_VARIANT_ID)};
 #undef RT_VARIANT_ID
 constexpr int kTraceVariantCount = (int)(sizeof(kTraceVariants) / sizeof(kTraceVariants[0]));
 static_assert(kTraceVariantCount == 55, "55 variants of rt_trace_kernel, each with its _lights twin");
+
+#define RT_VARIANT_ID(LDS, T, M, CACHE, HIT, CARRY, STASH, ML2, SG, GQ) {false, LDS, T, M, CACHE, HIT, CARRY, STASH, ML2, SG, GQ},
+constexpr TraceKernelId kTraceLeanVariants[] = {RT_TRACE_LEAN_VARIANTS(RT_VARIANT_ID)};
+#undef RT_VARIANT_ID
+constexpr int kTraceLeanVariantCount = (int)(sizeof(kTraceLeanVariants) / sizeof(kTraceLeanVariants[0]));
+// position of the variant in the lean list, or -1: it exists with far-hit state only
+constexpr int FindLeanVariant(const TraceKernelId& id) {
+    for (int i = 0; i < kTraceLeanVariantCount; ++i)
+        if (SameVariant(kTraceLeanVariants[i], id)) return i;
+    return -1;
+}
+// the lean list names exactly the flat LDS hit-stash rows without frame pipelining, each of them a row of the list above
+constexpr bool LeanFamily(const TraceKernelId& k) { return k.kLds && k.kScan == 1 && k.kStash && !k.kCarry; }
+constexpr bool LeanListIsTheFamily() {
+    int family = 0;
+    for (int i = 0; i < kTraceVariantCount; ++i) {
+        if (LeanFamily(kTraceVariants[i]) != (FindLeanVariant(kTraceVariants[i]) >= 0)) return false;
+        family += LeanFamily(kTraceVariants[i]) ? 1 : 0;
+    }
+    return family == kTraceLeanVariantCount;
+}
+static_assert(LeanListIsTheFamily(), "RT_TRACE_LEAN_VARIANTS: the flat LDS hit-stash rows of RT_TRACE_VARIANTS, no more and no fewer");
 
 #define RT_SCAN_ID(LDS, M) {LDS, M},
 constexpr ScanKernelId kScanVariants[] = {RT_SCAN_VARIANTS(RT_SCAN_ID)};

@@ -36,6 +36,25 @@ def trace_variants():
     return [int(w) for w in words]
 
 
+def trace_lean_variants():
+    """rt_unit_trace_lean_variants: the words of the rows that exist a second time without far-hit state (a subset of trace_variants())."""
+    L = _capi.load()
+    n = C.c_uint32(0)
+    check(L.rt_unit_trace_lean_variants(None, 0, C.byref(n)))
+    words = np.zeros(n.value, dtype=np.uint32)
+    check(L.rt_unit_trace_lean_variants(words.ctypes.data, n.value, C.byref(n)))
+    return [int(w) for w in words]
+
+
+def far_state_plan(case_words, path_list=False, trav_out=False, shadow_grid=True, force_full=False):
+    """rt_unit_far_state_plan: True when the launch these 28 case words describe takes its row's lean kernel.  Needs no GPU."""
+    case = np.ascontiguousarray(case_words, dtype=np.uint32)
+    assert case.shape == (28,)
+    lean = C.c_uint32(7)
+    check(_capi.load().rt_unit_far_state_plan(case.ctypes.data, int(path_list), int(trav_out), int(shadow_grid), int(force_full), C.byref(lean)))
+    return bool(lean.value)
+
+
 def decode_kernel_word(word):
     """Word [25] of rt_unit_launch_plan as a dict: lights, the ten template arguments, instantiated (bit 31)."""
     w = int(word)
@@ -324,6 +343,13 @@ class HipRenderer:
                            queue_block=int(plan[21]), static_blocks=int(plan[22]), dyn_begin=int(plan[23]), dyn_blocks=int(plan[24]),
                            launches=n.value, kernel_word=word, case_words=case, plan_words=plan)
 
+    def last_trace_far_state(self):
+        """rt_unit_last_trace_far_state: "lean" when the most recent trace launch ran its row's kernel without far-hit state, "full"
+        when it ran the one with it.  RtError (RT_ERR_SEQUENCE) before the first launch."""
+        lean = C.c_uint32(7)
+        check(self._L.rt_unit_last_trace_far_state(self._h, C.byref(lean)))
+        return "lean" if lean.value else "full"
+
     def trace_launches(self):
         """Trace-kernel launches of this context since rt_create (0 before the first: no error)."""
         n = C.c_uint32(0)
@@ -364,6 +390,14 @@ class HipRenderer:
         points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
         out = np.zeros(points.shape[0], dtype=np.uint8)
         check(self._L.rt_unit_shadow(self._h, int(light), points.ctypes.data, points.shape[0], 1 if glob_in_lds else 0, out.ctypes.data))
+        return out
+
+    def unit_shadow_tier(self, tier, points, light=0, glob_in_lds=False):
+        """unit_shadow with the index chosen (rt_unit_shadow_tier): tier 2 answers as the kernels without far-hit state ask -- bit 2 =
+        the answer came from light 0's second index."""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(points.shape[0], dtype=np.uint8)
+        check(self._L.rt_unit_shadow_tier(self._h, int(light), int(tier), points.ctypes.data, points.shape[0], 1 if glob_in_lds else 0, out.ctypes.data))
         return out
 
     def unit_trace(self, W, H, ijs, max_depth, seed):

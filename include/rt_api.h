@@ -634,6 +634,30 @@ int rt_unit_last_trace_launch(rt_ctx* ctx, uint32_t case_words[28], uint32_t pla
  * single-light form (bit 0 clear, bit 31 set); every one exists a second time as its _lights twin (bit 0 set).  *n = their number (55);
  * cap == 0 only queries it, a smaller capacity than *n is RT_ERR_INVALID_ARG.  Needs no GPU. */
 int rt_unit_trace_variants(uint32_t* kernel_words, uint32_t cap, uint32_t* n);
+/* ... and those of them that exist once more WITHOUT far-hit state (csrc/rt_trace_variants.h RT_TRACE_LEAN_VARIANTS): the
+ * same words, a subset of the list above (3: the flat hit-stash rows), each again with its _lights twin -- six functions behind the 110.
+ * A lean kernel is its row's kernel for picture launches, not another row: the plan, its words and word [25] are the row's.  Same
+ * argument rules.  Needs no GPU. */
+int rt_unit_trace_lean_variants(uint32_t* kernel_words, uint32_t cap, uint32_t* n);
+/* Whether the most recent trace-kernel launch of this context ran its row's lean function (*lean = 1) or the one with far-hit state
+ * (0): what rt_unit_last_trace_launch's words cannot say, since both are the same row.  Same refusals as that entry. */
+int rt_unit_last_trace_far_state(rt_ctx* ctx, uint32_t* lean);
+/* The launcher's rule for that choice (csrc/host/rt_launch_plan.h FarStateLean), with no context and no device: *lean = 1 when the
+ * launch that case_words (28 words, as above) describe takes the lean function, given whether it traces an explicit path list, wants
+ * per-path traversal counts (rt_unit_trace does both), whether the context builds shadow indices (RT_SHADOW_GRID is not 0) and whether
+ * RT_FAR_STATE=1 forces the far-hit state.  A case rt_unit_launch_plan refuses as impossible is RT_ERR_INVALID_ARG. */
+int rt_unit_far_state_plan(const uint32_t* case_words, uint32_t path_list, uint32_t trav_out, uint32_t shadow_grid, uint32_t force_full, uint32_t* lean);
+/* The three shadow entries above with the index chosen: tier 1 = the light's index (what the entries above answer), tier 2 (light 0
+ * only; anything else is RT_ERR_INVALID_ARG) = light 0's SECOND index, built like the first for the hit points beyond its radius and
+ * kept in global memory.  rt_unit_shadow_index_host_tier hands out that index's tables (out_f[9] = the square of ITS
+ * radius; out_u[0] = 0: the scene has none).  The two query entries then answer as the kernels without far-hit state ask: the first
+ * index within its radius, the second one within its own (bit 2 set, bit 1 clear), else every scan entry (bit 1 set). */
+int rt_unit_shadow_index_host_tier(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light, uint32_t tier,
+                                   uint32_t out_u[8], float out_f[10], uint32_t cap_cells, uint16_t* cell_start, uint32_t cap_entries, uint16_t* entries,
+                                   uint32_t cap_global, uint16_t* global, uint32_t cap_orig, uint32_t* orig);
+int rt_unit_shadow_query_host_tier(const rt_sphere* spheres, uint32_t n, const rt_light* lights, uint32_t n_lights, uint32_t light, uint32_t tier,
+                                   const float* points, uint32_t n_points, uint8_t* out);
+int rt_unit_shadow_tier(rt_ctx* ctx, uint32_t light, uint32_t tier, const float* points, uint32_t n, uint32_t glob_in_lds, uint8_t* out);
 /* The resolve of spheres-app.cpp:196-214 for given HDR triples -> R,G,B bytes */
 int rt_unit_tonemap(rt_ctx* ctx, const float* hdr_rgb, uint32_t n, uint32_t n_samples, uint8_t* out_rgb);
 
