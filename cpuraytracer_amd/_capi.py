@@ -71,7 +71,7 @@ RT_TEMPORAL_FETCH_NEAREST, RT_TEMPORAL_FETCH_BILINEAR = 1, 4
 EXPORTS = [
     "rt_last_error", "rt_api_version", "rt_create", "rt_destroy", "rt_set_stream", "rt_set_workspace_limit", "rt_set_sampler", "rt_set_frame_pipelining", "rt_set_frame_batch", "rt_set_frame_lookahead", "rt_committed_samples",
     "rt_scene_upload", "rt_render", "rt_clear", "rt_resolve", "rt_last_resolve_ms", "rt_download", "rt_copy_to_device",
-    "rt_synchronize", "rt_rowset_local_rows", "rt_rowset_global_row", "rt_unit_halton", "rt_unit_math",
+    "rt_synchronize", "rt_rowset_local_rows", "rt_rowset_global_row", "rt_unit_halton", "rt_unit_math", "rt_unit_math_host",
     "rt_unit_primary_rays", "rt_unit_closest_hit", "rt_unit_trace", "rt_unit_camera_rays", "rt_unit_scatter", "rt_unit_tonemap", "rt_unit_layout", "rt_unit_layout_info", "rt_unit_grid_rows", "rt_unit_grid_info",
     "rt_unit_tile_masks", "rt_unit_tile_masks_host", "rt_unit_tile_cone", "rt_unit_tile_spheres", "rt_unit_tile_spheres_host", "rt_unit_sky_planes", "rt_unit_sky_excluded",
     "rt_set_noise_estimate", "rt_download_moments", "rt_noise_map", "rt_noise_summary", "rt_unit_noise_estimate_host",
@@ -134,6 +134,8 @@ def load():
     L.rt_rowset_global_row.restype = C.c_uint32
     L.rt_unit_halton.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.rt_unit_math.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    if hasattr(L, "rt_unit_math_host"):  # (older builds of the library in A/B runs: tools/ab_run.sh)
+        L.rt_unit_math_host.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.rt_unit_primary_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     L.rt_unit_closest_hit.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.rt_unit_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64,

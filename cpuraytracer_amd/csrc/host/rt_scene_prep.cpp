@@ -841,6 +841,14 @@ uint32_t rt_rowset_global_row(rt_rowset rs, uint32_t lr) {
     return rs.first_row + (lb * rs.nshards + rs.shard) * rs.block_rows + k;
 }
 
+// Host-only: the elementary functions of rt_device_math.h as this translation unit compiles them (the source the kernels compile)
+int rt_unit_math_host(uint32_t op, const float* x, const float* y, uint32_t n, float* out) {
+    if (!x || !out || op > 3 || (op == 2 && !y)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_math_host: invalid argument");
+    for (uint32_t k = 0; k < n; ++k)
+        out[k] = op == 0 ? rtd::rt_sinf(x[k]) : (op == 1 ? rtd::rt_cosf(x[k]) : (op == 2 ? rtd::rt_powf(x[k], y[k]) : rtd::rt_tanf(x[k])));
+    return RT_OK;
+}
+
 int rt_unit_noise_estimate_host(const float* hdr, const float* sq, uint32_t npix, uint32_t n, float floor, float* out) {
     if (!hdr || !sq || !out) return Fail(RT_ERR_INVALID_ARG, "rt_unit_noise_estimate_host: null argument");
     if (n < 2) return Fail(RT_ERR_SEQUENCE, "rt_unit_noise_estimate_host: the estimate needs at least 2 samples per pixel");

@@ -444,6 +444,11 @@ static int LaunchTrace(rt_ctx* ctx, rtd::TraceParams& tp, rtplan::Mode mode = rt
     far.pathList = tp.path_list != nullptr, far.travOut = tp.trav_out != nullptr;
     far.shadowGrid = ctx->useShadowGrid, far.forceFull = EnvU32("RT_FAR_STATE", 0) != 0u;
     const bool lean = rtplan::FarStateLean(shape, ask, P, far);
+    // The lean kernels hold no radical-inverse fallback: they read the ray-generation tables, which every launch that can be lean
+    // has (rt_render fills them; the one launch without them, rt_unit_trace, has a path list and keeps the far-hit state).  A
+    // launch that broke that would read through a null pointer: refused here, never answered by another kernel.
+    if (lean && (tp.jitter_tab == nullptr || tp.lens_tab == nullptr))
+        return Fail(RT_ERR_HIP, "internal: a trace launch without far-hit state needs the ray-generation tables");
     const int leanRow = lean ? rtplan::FindLeanVariant(P.kernel) : -1;
     const TraceKernelFn fn = lean ? (P.kernel.lights ? kTraceLeanKernels[leanRow].lights : kTraceLeanKernels[leanRow].one)
                                   : (P.kernel.lights ? kTraceKernels[row].lights : kTraceKernels[row].one);

@@ -53,6 +53,39 @@ static_assert(kStashDwords == 4 * 3 + 4 + 3, "rt_layout_consts.h: four three-vec
 
 // Work-item index -> (column i, global row j, sample s) and the path's slot in the sample buffer: the explicit path
 // list of the unit tests, or the tiled order below over the rows of this shard.  slot = index either way.
+// The tiled order's arithmetic for any source of its constants (member names of TraceParams): the kernel arguments, or the copy the
+// kernels without far-hit state read back from LDS (LeanCoords below), which never have a path list.
+template <class P>
+RT_DEV void tiled_coordinates(const P& p, uint32_t q, uint32_t& i, uint32_t& j, uint32_t& s, uint32_t& slot) {
+    // storage order = [tile of 64 local pixels][sample of the pass][pixel in tile] (the last tile is as wide as the
+    // pixels left): a wave's block of 128 consecutive work-items is two sample planes of one tile, so its 12-byte
+    // results fill whole cache lines, and rt_accumulate_kernel reads 768 contiguous bytes per plane.  The WORK order
+    // is the same with the full tiles permuted by tile_order (expensive tiles first, sky last: rt_tile_order_kernel),
+    // so that the 51-segment paths are not the last ones a launch starts; the partial tile stays last.
+    const uint32_t tileSpan = 64u * p.spp_pass;
+    const uint32_t nFull = p.npix_local >> 6;
+    const uint32_t tileW = fastdiv(q, p.fd_tile);
+    uint32_t pl, k;
+    slot = q;
+    if (tileW < nFull) {
+        const uint32_t rem = q - tileW * tileSpan;
+        const uint32_t tile = p.tile_order ? p.tile_order[tileW] : tileW;
+        k = rem >> 6;
+        pl = (tile << 6) + (rem & 63u);
+        slot = tile * tileSpan + rem;
+    } else {
+        RT_SITE(K_PARTIAL);
+        const uint32_t rem = q - nFull * tileSpan;
+        const uint32_t wl = p.npix_local - (nFull << 6);
+        k = rem / wl;
+        pl = (nFull << 6) + (rem - k * wl);
+    }
+    s = p.s0 + k;
+    const uint32_t lr = fastdiv(pl, p.fd_w);
+    i = pl - lr * p.W;
+    j = rowset_global_row(p.rs, lr, p.fd_rows);
+    slot += p.sample_base;  // the call's region of the sample ring (0 without frame pipelining)
+}
 RT_DEV void path_coordinates(const TraceParams& p, uint32_t q, uint32_t& i, uint32_t& j, uint32_t& s, uint32_t& slot) {
     if (p.path_list) {
         RT_SITE(K_PATHLIST);
@@ -61,35 +94,38 @@ RT_DEV void path_coordinates(const TraceParams& p, uint32_t q, uint32_t& i, uint
         s = p.path_list[3 * q + 2];
         slot = q;
     } else {
-        // storage order = [tile of 64 local pixels][sample of the pass][pixel in tile] (the last tile is as wide as the
-        // pixels left): a wave's block of 128 consecutive work-items is two sample planes of one tile, so its 12-byte
-        // results fill whole cache lines, and rt_accumulate_kernel reads 768 contiguous bytes per plane.  The WORK order
-        // is the same with the full tiles permuted by tile_order (expensive tiles first, sky last: rt_tile_order_kernel),
-        // so that the 51-segment paths are not the last ones a launch starts; the partial tile stays last.
-        const uint32_t tileSpan = 64u * p.spp_pass;
-        const uint32_t nFull = p.npix_local >> 6;
-        const uint32_t tileW = fastdiv(q, p.fd_tile);
-        uint32_t pl, k;
-        slot = q;
-        if (tileW < nFull) {
-            const uint32_t rem = q - tileW * tileSpan;
-            const uint32_t tile = p.tile_order ? p.tile_order[tileW] : tileW;
-            k = rem >> 6;
-            pl = (tile << 6) + (rem & 63u);
-            slot = tile * tileSpan + rem;
-        } else {
-            RT_SITE(K_PARTIAL);
-            const uint32_t rem = q - nFull * tileSpan;
-            const uint32_t wl = p.npix_local - (nFull << 6);
-            k = rem / wl;
-            pl = (nFull << 6) + (rem - k * wl);
-        }
-        s = p.s0 + k;
-        const uint32_t lr = fastdiv(pl, p.fd_w);
-        i = pl - lr * p.W;
-        j = rowset_global_row(p.rs, lr, p.fd_rows);
-        slot += p.sample_base;  // the call's region of the sample ring (0 without frame pipelining)
+        tiled_coordinates(p, q, i, j, s, slot);
     }
+}
+// What tiled_coordinates and the fresh-plane code read of a launch, read back from LDS (rt_params.h, "the launch constants of the
+// kernels without far-hit state"): a and b are chunks 0 and 1.  kUniform: as scalars (the wave-uniform control code of K_GEN_TILE);
+// else as each lane's own temporaries (the per-lane index arithmetic, where an SGPR source would halve the VALU rate).
+struct LeanCoords {
+    const uint32_t* tile_order;
+    const uint32_t* tile_masks;
+    const uint16_t* tile_spheres;
+    FastDiv fd_tile, fd_w, fd_rows;
+    uint32_t npix_local, spp_pass, sample_base, sky_skip, W, s0;
+    uint64_t seed;
+    rt_rowset rs;
+};
+template <bool kUniform>
+RT_DEV LeanCoords lean_coords(const SceneConsts& K, const uint32_t* a, const uint32_t* b) {
+    auto w = [](const uint32_t* at) -> uint32_t { return kUniform ? lds_uniform(at) : *at; };
+    LeanCoords c;
+    c.tile_order = lds_global<const uint32_t>(a + kLeanPlaneTileOrder, kUniform);
+    c.tile_masks = lds_global<const uint32_t>(a + kLeanPlaneTileMasks, kUniform);
+    c.tile_spheres = lds_global<const uint16_t>(a + kLeanPlaneTileSpheres, kUniform);
+    c.fd_tile = FastDiv{w(a + kLeanPlaneFdTile), w(a + kLeanPlaneFdTile + 1)};
+    c.fd_w = FastDiv{w(a + kLeanPlaneFdW), w(a + kLeanPlaneFdW + 1)};
+    c.fd_rows = FastDiv{w(b + kLeanQueueFdRows), w(b + kLeanQueueFdRows + 1)};
+    c.npix_local = w(a + kLeanPlaneNpix); c.spp_pass = w(a + kLeanPlaneSpp); c.sample_base = w(a + kLeanPlaneSampleBase);
+    c.sky_skip = w(a + kLeanPlaneSkySkip);
+    c.W = w(&K.W); c.s0 = w(&K.s0);
+    c.seed = (uint64_t)w(a + kLeanPlaneSeed) | (uint64_t)w(a + kLeanPlaneSeed + 1) << 32;
+    c.rs.first_row = w(b + kLeanQueueRsFirst); c.rs.num_rows = 0u; c.rs.block_rows = w(b + kLeanQueueRsBlockRows);
+    c.rs.shard = w(b + kLeanQueueRsShard); c.rs.nshards = w(b + kLeanQueueRsNshards);
+    return c;
 }
 
 // Scene tables as the scan and the hit processing read them: LDS copies when the launch staged them, else global (L2).
@@ -266,7 +302,17 @@ RT_DEV uint32_t dry_shards(SceneConsts* ldsK) {
 RT_DEV void mark_dry(SceneConsts* ldsK, uint32_t lane, uint32_t k) {
     if (lane == 0) __hip_atomic_fetch_or(&ldsK->dry_mask, 1u << k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-RT_DEV bool claim_block(const TraceParams& p, SceneConsts* ldsK, uint32_t lane, uint32_t qb, uint32_t& blkNext, uint32_t& blkEnd,
+// (P: the kernel arguments, or the lean kernels' LeanQueue read back from LDS -- the queue's members under TraceParams' names)
+struct LeanQueue {
+    uint32_t* shard_heads;
+    uint32_t total_paths, dyn_begin, dyn_blocks, queue_block;
+};
+RT_DEV LeanQueue lean_queue(const uint32_t* b) {
+    return LeanQueue{lds_global<uint32_t>(b + kLeanQueueHeads), lds_uniform(b + kLeanQueueTotal), lds_uniform(b + kLeanQueueDynBegin),
+                     lds_uniform(b + kLeanQueueDynBlocks), lds_uniform(b + kLeanQueueBlock)};
+}
+template <class P>
+RT_DEV bool claim_block(const P& p, SceneConsts* ldsK, uint32_t lane, uint32_t qb, uint32_t& blkNext, uint32_t& blkEnd,
                         uint32_t& shard) {
     RT_SITE(K_CLAIM);
     uint32_t dry = dry_shards(ldsK);
@@ -346,6 +392,14 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
     // [0, kConstBytes): the scene constants; then the per-wave regions; then the tables
     SceneConsts* ldsK = reinterpret_cast<SceneConsts*>(smem);
     if (threadIdx.x == 0) fill_consts(p, *ldsK);
+    // kFarState == false: the launch constants the loop reads go to LDS as well (rt_params.h) and are read back where they are used;
+    // `leanHot` is a fixed address, chunk(k) costs one more LDS read for its offset
+    constexpr bool kLean = !kFarState;
+    static_assert(!kLean || kThreads / kWaveSize >= (int)kLeanChunks, "one hit-stash region per chunk of lean launch constants");
+    const uint32_t* ldsWords = reinterpret_cast<const uint32_t*>(smem);
+    const uint32_t* leanHot = ldsWords + kLeanHotOffset / 4u;
+    if (kLean && threadIdx.x == 0) fill_lean_consts(p, reinterpret_cast<uint32_t*>(smem));
+    auto chunk = [&](uint32_t k) -> const uint32_t* { return ldsWords + (leanHot[kLeanHotTail] + k * leanHot[kLeanHotStride]); };
     // the elementary functions' tables behind the constants (log | exp2 | sincos, as MathTabs indexes them)
     unsigned long long* ldsMath = reinterpret_cast<unsigned long long*>(smem + kSceneConstBytes / 16);
     {
@@ -408,7 +462,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
     uint32_t carried = 0;  // kCarry: paths this wave carries out (wave-uniform)
     uint32_t itersHere = 0;  // kCarry: iterations of this wave in this launch
     const uint32_t gwave = blockIdx.x * (kThreads / kWaveSize) + threadIdx.x / kWaveSize;  // this wave's index in the grid
-    const uint32_t kBlk = p.queue_block;  // paths per queue block (a multiple of 64)
+    const uint32_t kBlk = kLean ? 0u : p.queue_block;  // paths per queue block (a multiple of 64); lean: read where a block is taken
     bool contAfterShadow = false, pathScattered = false;
     uint32_t nTrav = 0, nSeg = 0;
 
@@ -448,9 +502,10 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         // the wave's first block(s) of fresh paths are static: block `gwave`; the shards start behind those.  (The carrying
         // kernel uses half-size blocks: a wave can only start paths as lanes fall idle, so a wave whose lanes are held by long
         // paths should own little unstarted work when the queue runs dry -- it must start all of it before it may leave.)
-        const uint32_t b0 = gwave * (kBlk * p.static_blocks);
+        const uint32_t span = p.queue_block * p.static_blocks;  // (before the loop: the kernel arguments in every kernel)
+        const uint32_t b0 = gwave * span;
         blkNext = b0 < p.total_paths ? b0 : p.total_paths;
-        blkEnd = (b0 + kBlk * p.static_blocks) < p.total_paths ? (b0 + kBlk * p.static_blocks) : p.total_paths;
+        blkEnd = (b0 + span) < p.total_paths ? (b0 + span) : p.total_paths;
     }
     // per-wave region behind the tables: the prepared-path cache, or (kStash) the hit stash, p.ray_cache_stride16 float4 per wave
     float4* rayCache = kCache ? smem + p.ray_cache_off16 + (threadIdx.x / kWaveSize) * p.ray_cache_stride16 : nullptr;
@@ -472,33 +527,44 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
     // previous one was taken: the atomic's round trip (two of them with the look, ~4 us under load, 117 times per wave on
     // C2) ran under the work on a whole block instead of stalling the wave.  A claim that came back beyond the shard's end
     // falls through to a fresh look.
-    auto nextBlock = [&]() -> bool {
-        RT_SITE(K_NEXTBLOCK);
+    // (Q: the queue's constants under TraceParams' names and the block size -- the kernel arguments, or, without far-hit state, what
+    // lean_queue reads back from LDS once per block of 128 paths)
+    auto takeBlock = [&](const auto& Q, uint32_t qb) -> bool {
         bool got = false;
         if (pendShard < kQueueShards) {
             const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)pendCount);
             const uint32_t b = c * kQueueShards + pendShard;
-            if (b < p.dyn_blocks) {
-                blkNext = p.dyn_begin + b * kBlk;
-                blkEnd = (blkNext + kBlk) < p.total_paths ? (blkNext + kBlk) : p.total_paths;
+            if (b < Q.dyn_blocks) {
+                blkNext = Q.dyn_begin + b * qb;
+                blkEnd = (blkNext + qb) < Q.total_paths ? (blkNext + qb) : Q.total_paths;
                 got = true;
             } else {
                 mark_dry(ldsK, lane, pendShard);
                 pendShard = kQueueShards;  // that shard is dry
             }
         }
-        if (!got && !claim_block(p, ldsK, lane, kBlk, blkNext, blkEnd, pendShard)) return false;
+        if (!got && !claim_block(Q, ldsK, lane, qb, blkNext, blkEnd, pendShard)) return false;
         // (not in the frame-pipelining kernel: a wave must start everything it owns before it may carry out)
         if (kCarry) pendShard = kQueueShards;
         if (pendShard < kQueueShards && ((dry_shards(ldsK) >> pendShard) & 1u)) pendShard = kQueueShards;
-        if (pendShard < kQueueShards && lane == 0) pendCount = atomicAdd(p.shard_heads + kShardStrideWords * pendShard, 1u);  // claim ahead
+        if (pendShard < kQueueShards && lane == 0) pendCount = atomicAdd(Q.shard_heads + kShardStrideWords * pendShard, 1u);  // claim ahead
         return true;
+    };
+    auto nextBlock = [&]() -> bool {
+        RT_SITE(K_NEXTBLOCK);
+        if constexpr (kLean) {
+            const LeanQueue Q = lean_queue(chunk(1));
+            return takeBlock(Q, Q.queue_block);
+        } else {
+            return takeBlock(p, kBlk);
+        }
     };
     // A finished path: GetHitColor * exposureAdjustment, spheres-app.cpp:183; one 12-byte store
     auto finishPath = [&]() {
         RT_SITE(K_FINISH);
         const float expo = K.exposure;
-        *reinterpret_cast<float3*>(p.samples + (size_t)q * 3) = make_float3(rad.x * expo, rad.y * expo, rad.z * expo);
+        float* const samples = kLean ? lds_global<float>(leanHot + kLeanHotSamples, false) : p.samples;
+        *reinterpret_cast<float3*>(samples + (size_t)q * 3) = make_float3(rad.x * expo, rad.y * expo, rad.z * expo);
         if (kFarState && p.trav_out) p.trav_out[q] = pathTrav;  // (a launch with trav_out takes a kFarState kernel: host/rt_launch_plan.cpp)
         state = kIdle;
 #ifdef RT_TIMELINE
@@ -516,10 +582,14 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
     // yield an accepted root", which is what the shadow scan answered.
     auto farShadow = [&](V3 pos, float pp) -> bool {
         RT_SITE(H_FARHIT);
-        const LightRec* F = far_index_rec(p);
+        // (reached only without far-hit state: the scene's light records and entry count come out of LDS, chunk 2)
+        const uint32_t* rare = chunk(2);
+        const LightRec* F = lds_uniform(rare + kLeanRareFarIndex) != 0u
+                                ? lds_global<const LightRec>(rare + kLeanRareExtraLights) + (lds_uniform(rare + kLeanRareNLights) - 1u)
+                                : nullptr;
         if (F != nullptr && pp <= F->sg_p0sq)
             return shadow_query(*F, scanTab, F->cell_start, F->entries, F->global, false, globSph, globIds, (const float4*)nullptr, pos, sunDir, aSun);
-        return any_hit_all(scanTab, p.n_padded, pos, sunDir, aSun);
+        return any_hit_all(scanTab, lds_uniform(rare + kLeanRareNPadded), pos, sunDir, aSun);
     };
     // Hit processing of one closest hit (scan entry idx at pos) for a lane in state kNeedClosest: Scatter, the shadow
     // query, Emit + Shade, and the path's next state (GetHitColor, spheres-app.cpp:238-257).
@@ -528,15 +598,19 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         const float4 S = scanTab[idx];
         const float radius = radTab[idx];  // radius and material tables are in scan-entry (clustered) order
         // the packed 16-byte record where the launch provides it: from LDS (kMatsL2 variants, mode 2) or from global memory (mode 1)
-        const Mat m = (kMatsL2 && p.mats16_mode == 2u) ? load_material16(mat16Lds, idx)
-                                                        : (p.mats16_mode == 1u ? load_material16(p.mats16, idx) : load_material(matTab, idx));
+        const uint32_t hotFlags = kLean ? lds_uniform(leanHot + kLeanHotFlags) : 0u;
+        const uint32_t mats16Mode = kLean ? (hotFlags & 255u) : p.mats16_mode;
+        const bool globInLds = kLean ? (hotFlags & 256u) != 0u : p.sg_glob16 != 0u;
+        const uint4* const mats16 = kLean ? lds_global<const uint4>(leanHot + kLeanHotMats16, false) : p.mats16;
+        const Mat m = (kMatsL2 && mats16Mode == 2u) ? load_material16(mat16Lds, idx)
+                                                     : (mats16Mode == 1u ? load_material16(mats16, idx) : load_material(matTab, idx));
         const V3 center = v3(S.x, S.y, S.z);
         const V3 nrm = div3_signed(pos - center, radius);  // ray-tracing.cpp:62 (true divide by the SIGNED radius: r < 0 turns the normal inward)
         V3 atten, local, localOcc, tex;
         RT_STAMP(th0);
         const bool scattered = scatter_only(m, rd, nrm, draws, atten, nextDir, tex, mt, K.sampler);  // Scatter first: it draws (spheres-app.cpp:246)
         RT_STAMP(th1);
-        const bool cont = (depth < p.max_depth) && scattered;  // spheres-app.cpp:247
+        const bool cont = (depth < (kLean ? leanHot[kLeanHotMaxDepth] : p.max_depth)) && scattered;  // spheres-app.cpp:247
         if (kLights) {
             // Material::Shade over the scene's LIST of lights (material.cpp:4-13): directLighting = 0, += light->Shade(...) in list
             // order; every light casts its shadow ray (one traversal each), answered by the light's own footprint index -- or, for
@@ -546,21 +620,24 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             shade_value(K, m, tex, pos, nrm, false, emitOnly, localOcc, mt);  // Emit + 0
             V3 direct = v3(0.f, 0.f, 0.f);
             const float pp = dot3(pos, pos);
-            for (uint32_t k = 0; k < p.n_lights; ++k) {
+            const uint32_t nLights = kLean ? lds_uniform(chunk(2) + kLeanRareNLights) : p.n_lights;
+            const LightRec* const extraLights = kLean ? lds_global<const LightRec>(chunk(2) + kLeanRareExtraLights) : p.extra_lights;
+            const uint32_t nPadded = kLean ? lds_uniform(chunk(2) + kLeanRareNPadded) : p.n_padded;
+            for (uint32_t k = 0; k < nLights; ++k) {
                 bool occ;
                 V3 sh;
                 if (k == 0u) {
                     occ = (K.sg_enabled && pp <= K.sg_p0sq)
-                              ? shadow_query(K, scanTab, sgCell, sgEntries, sgGlobal, p.sg_glob16 != 0u, globSph, globIds, (!kLds && kScan >= 2) ? p.sg_sph : nullptr, pos, sunDir, aSun)
-                              : (kFarState ? any_hit_all(scanTab, p.n_padded, pos, sunDir, aSun) : farShadow(pos, pp));
+                              ? shadow_query(K, scanTab, sgCell, sgEntries, sgGlobal, globInLds, globSph, globIds, (!kLds && kScan >= 2) ? p.sg_sph : nullptr, pos, sunDir, aSun)
+                              : (kFarState ? any_hit_all(scanTab, nPadded, pos, sunDir, aSun) : farShadow(pos, pp));
                     sh = occ ? v3(0.f, 0.f, 0.f) : shade_only(K, m, tex, pos, nrm, mt);
                 } else {
-                    const LightRec& Lk = p.extra_lights[k - 1u];
+                    const LightRec& Lk = extraLights[k - 1u];
                     const V3 dirK = v3(Lk.sun_dir[0], Lk.sun_dir[1], Lk.sun_dir[2]);
                     const float aK = dot3(dirK, dirK);
                     occ = (Lk.sg_enabled && pp <= Lk.sg_p0sq)
                               ? shadow_query(Lk, scanTab, Lk.cell_start, Lk.entries, Lk.global, false, globSph, globIds, (const float4*)nullptr, pos, dirK, aK)
-                              : any_hit_all(scanTab, p.n_padded, pos, dirK, aK);
+                              : any_hit_all(scanTab, nPadded, pos, dirK, aK);
                     sh = occ ? v3(0.f, 0.f, 0.f) : shade_only(Lk, m, tex, pos, nrm, mt);
                 }
                 ++nTrav;
@@ -580,7 +657,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         }
         const bool useIndex = K.sg_enabled && dot3(pos, pos) <= K.sg_p0sq;
         bool occluded = false;
-        if (useIndex) occluded = shadow_query(K, scanTab, sgCell, sgEntries, sgGlobal, p.sg_glob16 != 0u, globSph, globIds, (!kLds && kScan >= 2) ? p.sg_sph : nullptr, pos, sunDir, aSun);
+        if (useIndex) occluded = shadow_query(K, scanTab, sgCell, sgEntries, sgGlobal, globInLds, globSph, globIds, (!kLds && kScan >= 2) ? p.sg_sph : nullptr, pos, sunDir, aSun);
         else if (!kFarState) occluded = farShadow(pos, dot3(pos, pos));
         RT_STAMP(th2);
         // the Blinn-Phong value (two normalisations, two pows) is only needed when the sun is visible or unknown
@@ -598,6 +675,21 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             // shadow ray answered by the exact footprint index (or, kFarState == false, in place above): no second scan for this hit
             ++nTrav;  // the shadow ray still counts as a traversal of the scene (matches the oracle's counter)
             if (kFarState) ++pathTrav;
+            if (kLean) {
+                // The same update without branches.  The addend is chosen by a select and the SUM is what the predicate keeps or
+                // drops -- an occluded lane that scattered keeps its radiance untouched, it does not add +0 (rad can be -0 only in
+                // theory, but the bits are the contract).  A path that ends here is stored by finishPath from rad and q alone, so
+                // its throughput, ray and depth may take the values of a continuing path: nothing reads them again.
+                const bool add = !occluded || !scattered;
+                const V3 sum = rad + thr * v3(occluded ? localOcc.x : local.x, occluded ? localOcc.y : local.y, occluded ? localOcc.z : local.z);
+                rad = v3(add ? sum.x : rad.x, add ? sum.y : rad.y, add ? sum.z : rad.z);
+                thr = thr * atten;
+                ro = pos;
+                rd = nextDir;
+                ++depth;
+                finished = !cont;
+                return;
+            }
             if (!occluded) rad = rad + thr * local;           // radiance += throughput * (Emit + Shade)
             else if (!scattered) rad = rad + thr * localOcc;  // occluded: throughput * (Emit + 0)
             if (cont) {
@@ -631,6 +723,13 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         RT_SITE(K_ITER);
         RT_STAMP(ts0);
         uint32_t primTile = 0xffffffffu;  // wave-uniform: the tile whose mask this iteration's scan takes (none)
+        // kOneExit (the kernels without far-hit state): the loop has ONE exit, at its end, and no `continue` -- an iteration with nothing to scan skips the scan and the
+        // transitions through a wave-uniform `if` and the wave leaves when `leanAgain` is false.  With the exit in the middle of
+        // the body (the text the other kernels keep) the compiler linearises the loop as one with a divergent exit: a break mask
+        // accumulated every iteration, the scan and the transitions under a saved exec mask, and 22 register copies for the loop's
+        // phi nodes at its head.  Same iterations, same work in each.
+        constexpr bool kOneExit = kLean;
+        bool leanSkippedSky = false, leanNoScan = false, leanAgain = true;
         // ------------------------------------------------ refill idle lanes (ballot + prefix)
         // New paths come from a per-wave cache of 64 prepared paths in LDS: when it runs empty ALL 64 lanes generate
         // the next 64 paths of the wave's queue block at once (index arithmetic, stream seeding, Camera::GetRay with
@@ -640,7 +739,8 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         uint64_t idleMask = __ballot(state == kIdle);
         if (kStash) {
             float* stash = reinterpret_cast<float*>(rayCache);
-            const uint32_t cap = p.stash_cap;  // <= 63 records of kStashDwords dwords
+            // <= 63 records of kStashDwords dwords (lean: a lane's temporary out of LDS, used in its address arithmetic only)
+            const uint32_t cap = kLean ? leanHot[kLeanHotStashCap] : p.stash_cap;
             // (1) idle lanes take stashed hits (newest first)
             if (stashCnt != 0u && idleMask != 0ull) {
                 RT_SITE(K_POP);
@@ -650,15 +750,32 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                 if (state == kIdle && r < n) {
                     RT_SITE(K_POP_LANE);
                     const float* e = stash + (stashCnt - 1u - r);
-                    ro = v3(e[0], e[cap], e[2u * cap]);
-                    rd = v3(e[3u * cap], e[4u * cap], e[5u * cap]);
-                    thr = v3(e[6u * cap], e[7u * cap], e[8u * cap]);
-                    rad = v3(e[9u * cap], e[10u * cap], e[11u * cap]);
-                    draws.rng = Rng{__float_as_uint(e[12u * cap]), __float_as_uint(e[13u * cap]), __float_as_uint(e[14u * cap]),
-                                    __float_as_uint(e[15u * cap])};
-                    q = __float_as_uint(e[16u * cap]);
-                    depth = __float_as_uint(e[17u * cap]);
-                    if (kFarState) pathTrav = __float_as_uint(e[18u * cap]);
+                    if constexpr (kLean) {
+                        // field after field by stepping a 32-bit LDS address: with the cap a lane's temporary, e[k * cap] would be a
+                        // 64-bit multiply-add per field
+                        float f[kStashDwords - 1u];
+                        for (uint32_t k = 0; k < kStashDwords - 1u; ++k) {
+                            f[k] = *e;
+                            e += cap;
+                        }
+                        ro = v3(f[0], f[1], f[2]);
+                        rd = v3(f[3], f[4], f[5]);
+                        thr = v3(f[6], f[7], f[8]);
+                        rad = v3(f[9], f[10], f[11]);
+                        draws.rng = Rng{__float_as_uint(f[12]), __float_as_uint(f[13]), __float_as_uint(f[14]), __float_as_uint(f[15])};
+                        q = __float_as_uint(f[16]);
+                        depth = __float_as_uint(f[17]);
+                    } else {
+                        ro = v3(e[0], e[cap], e[2u * cap]);
+                        rd = v3(e[3u * cap], e[4u * cap], e[5u * cap]);
+                        thr = v3(e[6u * cap], e[7u * cap], e[8u * cap]);
+                        rad = v3(e[9u * cap], e[10u * cap], e[11u * cap]);
+                        draws.rng = Rng{__float_as_uint(e[12u * cap]), __float_as_uint(e[13u * cap]), __float_as_uint(e[14u * cap]),
+                                        __float_as_uint(e[15u * cap])};
+                        q = __float_as_uint(e[16u * cap]);
+                        depth = __float_as_uint(e[17u * cap]);
+                        if (kFarState) pathTrav = __float_as_uint(e[18u * cap]);
+                    }
                     state = kHaveHit;
                 }
                 stashCnt -= n;
@@ -666,7 +783,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             // (2) process the hits when (nearly) every lane holds one; with fewer and nothing to scan, make room for 64 fresh paths
             const uint64_t hitMask = __ballot(state == kHaveHit);
             const uint32_t nHit = (uint32_t)__popcll(hitMask);
-            bool process = nHit > p.stash_process;
+            bool process = nHit > (kLean ? lds_uniform(leanHot + kLeanHotStashProcess) : p.stash_process);
             if (!process && nHit != 0u && __ballot(state == kNeedClosest || (kFarState && state == kNeedShadow)) == 0ull) {
                 if (blkNext == blkEnd && !queueEmpty && !nextBlock()) queueEmpty = true;
                 if (blkNext == blkEnd) {
@@ -679,15 +796,25 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                     if (state == kHaveHit) {
                         RT_SITE(K_PUSH_LANE);
                         float* e = stash + prefix_count(hitMask);
-                        e[0] = ro.x; e[cap] = ro.y; e[2u * cap] = ro.z;
-                        e[3u * cap] = rd.x; e[4u * cap] = rd.y; e[5u * cap] = rd.z;
-                        e[6u * cap] = thr.x; e[7u * cap] = thr.y; e[8u * cap] = thr.z;
-                        e[9u * cap] = rad.x; e[10u * cap] = rad.y; e[11u * cap] = rad.z;
-                        e[12u * cap] = __uint_as_float(draws.rng.s0); e[13u * cap] = __uint_as_float(draws.rng.s1);
-                        e[14u * cap] = __uint_as_float(draws.rng.s2); e[15u * cap] = __uint_as_float(draws.rng.s3);
-                        e[16u * cap] = __uint_as_float(q);
-                        e[17u * cap] = __uint_as_float(depth);
-                        if (kFarState) e[18u * cap] = __uint_as_float(pathTrav);
+                        if constexpr (kLean) {
+                            const float f[kStashDwords - 1u] = {ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, thr.x, thr.y, thr.z, rad.x, rad.y, rad.z,
+                                                                __uint_as_float(draws.rng.s0), __uint_as_float(draws.rng.s1), __uint_as_float(draws.rng.s2),
+                                                                __uint_as_float(draws.rng.s3), __uint_as_float(q), __uint_as_float(depth)};
+                            for (uint32_t k = 0; k < kStashDwords - 1u; ++k) {  // (stepping the address: as in the pop)
+                                *e = f[k];
+                                e += cap;
+                            }
+                        } else {
+                            e[0] = ro.x; e[cap] = ro.y; e[2u * cap] = ro.z;
+                            e[3u * cap] = rd.x; e[4u * cap] = rd.y; e[5u * cap] = rd.z;
+                            e[6u * cap] = thr.x; e[7u * cap] = thr.y; e[8u * cap] = thr.z;
+                            e[9u * cap] = rad.x; e[10u * cap] = rad.y; e[11u * cap] = rad.z;
+                            e[12u * cap] = __uint_as_float(draws.rng.s0); e[13u * cap] = __uint_as_float(draws.rng.s1);
+                            e[14u * cap] = __uint_as_float(draws.rng.s2); e[15u * cap] = __uint_as_float(draws.rng.s3);
+                            e[16u * cap] = __uint_as_float(q);
+                            e[17u * cap] = __uint_as_float(depth);
+                            if (kFarState) e[18u * cap] = __uint_as_float(pathTrav);
+                        }
                         state = kIdle;
                     }
                     stashCnt = nHit;
@@ -713,28 +840,39 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                 if (blkNext != blkEnd) {
                     RT_SITE(K_GEN);
 #ifdef RT_TIMELINE
-                    if (blkNext % kBlk == 0u) {
-                        tlLastClaim = __builtin_amdgcn_s_memrealtime();
-                        ++tlBlocks;
-                        tlLastBlock = blkNext / kBlk;
+                    {
+                        const uint32_t tlBlk = kLean ? lds_uniform(chunk(1) + kLeanQueueBlock) : kBlk;  // (kBlk is 0 in a lean kernel)
+                        if (blkNext % tlBlk == 0u) {
+                            tlLastClaim = __builtin_amdgcn_s_memrealtime();
+                            ++tlBlocks;
+                            tlLastBlock = blkNext / tlBlk;
+                        }
                     }
 #endif
                     const uint32_t nGen = (blkEnd - blkNext) < (uint32_t)kWaveSize ? (blkEnd - blkNext) : (uint32_t)kWaveSize;
                     if (kPrim) {
+                        // (lean: this plane's constants as scalars out of LDS; else the kernel arguments themselves)
+                        const uint32_t* const leanA = kLean ? chunk(0) : nullptr;
+                        const uint32_t* const leanB = kLean ? chunk(1) : nullptr;
+                        auto planeConsts = [&]() -> decltype(auto) {
+                            if constexpr (kLean) return lean_coords<true>(K, leanA, leanB);
+                            else return (p);
+                        };
+                        decltype(auto) pc = planeConsts();
                         // one full tile at one sample (path_coordinates: tile spans are multiples of 64), and the tile has a mask
-                        if (p.tile_masks != nullptr && nGen == (uint32_t)kWaveSize && (blkNext & 63u) == 0u) {
+                        if (pc.tile_masks != nullptr && nGen == (uint32_t)kWaveSize && (blkNext & 63u) == 0u) {
                             RT_SITE(K_GEN_TILE);
-                            const uint32_t tw = fastdiv(blkNext, p.fd_tile);
-                            if (tw < (p.npix_local >> 6)) {
-                                const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p.tile_order ? p.tile_order[tw] : tw));
-                                const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_masks[kTileMaskWords * tile + 4u]);
+                            const uint32_t tw = fastdiv(blkNext, pc.fd_tile);
+                            if (tw < (pc.npix_local >> 6)) {
+                                const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pc.tile_order ? pc.tile_order[tw] : tw));
+                                const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)pc.tile_masks[kTileMaskWords * tile + 4u]);
                                 if (flags & 1u) {
                                     primTile = tile;
-                                    if (p.tile_spheres != nullptr) {
-                                        const uint32_t nList = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_spheres[(size_t)kTileSphereHalfs * tile]);
+                                    if (pc.tile_spheres != nullptr) {
+                                        const uint32_t nList = (uint32_t)__builtin_amdgcn_readfirstlane((int)pc.tile_spheres[(size_t)kTileSphereHalfs * tile]);
                                         // bit 31: the tile has a sphere list as well (tile < 2^25: the strip has at most 2^31 pixels)
                                         if (nList != kTileSphereNone) primTile = tile | 0x80000000u;
-                                        if (kSky && nList == 0u && p.sky_skip != 0u) {
+                                        if (kSky && nList == 0u && pc.sky_skip != 0u) {
                                             // An EMPTY list: the list holds every sphere a primary ray of the tile can have a root in
                                             // (rt_tile_mask.h), so all 64 paths miss on their first scan and end as
                                             // (0 + 1 * sky) * exposure -- K_TRANS_MISS and finishPath, whatever the jitter and the lens
@@ -742,7 +880,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                                             // expressions, same bits; one traversal and one segment per path, one direct scan per
                                             // plane) without rays, scan or transition.  Every lane stays idle: back to the top of the
                                             // loop, which pops what the stash holds and comes here again for the paths behind them.
-                                            const uint32_t tileSpan = 64u * p.spp_pass;
+                                            const uint32_t tileSpan = 64u * pc.spp_pass;
                                             const uint32_t rem = blkNext - tw * tileSpan;
                                             const uint32_t inTile = (tileSpan - rem) >> 6, inBlock = (blkEnd - blkNext) >> 6;
                                             const uint32_t nSky = inTile < inBlock ? inTile : inBlock;  // >= 1
@@ -751,10 +889,12 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                                             const float expo = K.exposure;
                                             const float3 smp = make_float3(skyRad.x * expo, skyRad.y * expo, skyRad.z * expo);
                                             // path_coordinates' slot of path blkNext + lane (no path list here: the launch sets sky_skip)
-                                            const uint32_t slot = tile * tileSpan + rem + p.sample_base + lane;
+                                            const uint32_t slot = tile * tileSpan + rem + pc.sample_base + lane;
+                                            float* const samples = kLean ? lds_global<float>(leanHot + kLeanHotSamples) : p.samples;
                                             for (uint32_t k = 0; k < nSky; ++k) {
-                                                *reinterpret_cast<float3*>(p.samples + (size_t)(slot + 64u * k) * 3) = smp;
-                                                if (p.trav_out) p.trav_out[slot + 64u * k] = 1u;  // (no launch with tile tables sets trav_out today)
+                                                *reinterpret_cast<float3*>(samples + (size_t)(slot + 64u * k) * 3) = smp;
+                                                // (no launch with tile tables sets trav_out today, and none without far-hit state ever does)
+                                                if (kFarState && p.trav_out) p.trav_out[slot + 64u * k] = 1u;
                                             }
                                             nTrav += nSky;
                                             nSeg += nSky;
@@ -763,19 +903,29 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                                                 __hip_atomic_fetch_add(&ldsK->prim_sky, nSky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                             }
                                             blkNext += 64u * nSky;
-                                            continue;
+                                            if (kOneExit) leanSkippedSky = true;  // (every lane is idle: nothing below runs)
+                                            else continue;
                                         }
                                     }
                                 }
                             }
                         }
                     }
-                    if (lane < nGen) {
+                    if (lane < nGen && !(kOneExit && leanSkippedSky)) {
                         RT_SITE(K_GEN_LANE);
                         uint32_t i, j, sN;
-                        path_coordinates(p, blkNext + lane, i, j, sN, q);
-                        draws.rng = rng_seed(p.seed, j * p.W + i, sN);
-                        gen_primary_ray(K, i, j, sN, ro, rd);
+                        if constexpr (kLean) {
+                            // every constant of the index arithmetic is the lane's own temporary out of LDS; no path list, and the
+                            // launch provides the ray-generation tables (rt_capi.hip LaunchTrace)
+                            const LeanCoords c = lean_coords<false>(K, chunk(0), chunk(1));
+                            tiled_coordinates(c, blkNext + lane, i, j, sN, q);
+                            draws.rng = rng_seed(c.seed, j * c.W + i, sN);
+                            gen_primary_ray<true>(K, i, j, sN, ro, rd);
+                        } else {
+                            path_coordinates(p, blkNext + lane, i, j, sN, q);
+                            draws.rng = rng_seed(p.seed, j * p.W + i, sN);
+                            gen_primary_ray(K, i, j, sN, ro, rd);
+                        }
                         thr = v3(1.f, 1.f, 1.f);
                         rad = v3(0.f, 0.f, 0.f);
                         depth = 0;
@@ -785,7 +935,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
                         tlBorn = (uint32_t)(__builtin_amdgcn_s_memrealtime() - tl0);
 #endif
                     }
-                    blkNext += nGen;
+                    if (!(kOneExit && leanSkippedSky)) blkNext += nGen;
                 }
             }
         } else if (kCache) {
@@ -879,8 +1029,13 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
         if (__ballot(state != kIdle) == 0ull) {
             // queue empty and every lane drained -- but hits may still wait in the stash: a wave of 64 hits whose paths ALL
             // ended at that hit (a tile looking at an emissive sphere) leaves every lane idle with records behind it
-            if (kStash && stashCnt != 0u) continue;  // back to the top: the idle lanes pop them (at most 63: one more round)
-            break;
+            if (kOneExit) {
+                leanNoScan = true;
+                leanAgain = __builtin_amdgcn_readfirstlane((int)stashCnt) != 0 || leanSkippedSky;  // (a finished empty-list tile: back to the top for the paths behind it)
+            } else {
+                if (kStash && stashCnt != 0u) continue;  // back to the top: the idle lanes pop them (at most 63: one more round)
+                break;
+            }
         }
 #ifdef RT_TIMELINE
         ++tlIters;
@@ -924,6 +1079,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             }
         }
 
+        if (!(kOneExit && leanNoScan)) {
         RT_STAMP(ts1);
         // ------------------------------------------------ one list scan for every live lane
         float tmin = 0.f;
@@ -936,10 +1092,11 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
             if (kPrim && primTile != 0xffffffffu && (primTile & 0x80000000u) != 0u) {
                 // the tile's sphere list: every lane tests its own ray against the listed spheres (rt_scan.h scan_tile_spheres)
                 if (lane == 0) __hip_atomic_fetch_add(&ldsK->prim_direct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                scan_tile_spheres(scanTab, origTab, p.tile_spheres + (size_t)kTileSphereHalfs * (primTile & 0x7fffffffu), ro, rd, live, tmin, idx, lane);
+                const uint16_t* const tileSpheres = kLean ? lds_global<const uint16_t>(chunk(0) + kLeanPlaneTileSpheres) : p.tile_spheres;
+                scan_tile_spheres(scanTab, origTab, tileSpheres + (size_t)kTileSphereHalfs * (primTile & 0x7fffffffu), ro, rd, live, tmin, idx, lane);
             } else {
             if (kPrim && primTile != 0xffffffffu) {
-                tileMask = p.tile_masks + kTileMaskWords * primTile;
+                tileMask = (kLean ? lds_global<const uint32_t>(chunk(0) + kLeanPlaneTileMasks) : p.tile_masks) + kTileMaskWords * primTile;
                 // statistics (rt_unit_tile_masks): one LDS add per masked scan into the workgroup's constants block -- no register
                 // lives across the persistent loop for it (two wave-uniform counters cost the kernel two VGPR spills and 1.1 %)
                 if (lane == 0) __hip_atomic_fetch_add(&ldsK->prim_masked, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1011,6 +1168,8 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
 #ifdef RT_STAMPS
         cyIters += 1;
 #endif
+        }
+        if (kOneExit && !leanAgain) break;
     }
 
     if (kCarry) {
@@ -1050,18 +1209,21 @@ __device__ __forceinline__ void trace_body(const TraceParams& p) {
     }
 #endif
     if (lane == 0) {
-        atomicAdd(&p.counters[0], t);
-        atomicAdd(&p.counters[1], s);
-        if (kPrim && p.tile_masks != nullptr) {
+        // (behind the loop the kernel arguments would do, but reading them here keeps them alive in scalar registers across it)
+        unsigned long long* const counters = kLean ? lds_global<unsigned long long>(chunk(1) + kLeanQueueCounters, false) : p.counters;
+        const bool haveMasks = kLean ? (chunk(0)[kLeanPlaneTileMasks] | chunk(0)[kLeanPlaneTileMasks + 1]) != 0u : p.tile_masks != nullptr;
+        atomicAdd(&counters[0], t);
+        atomicAdd(&counters[1], s);
+        if (kPrim && haveMasks) {
             // the wave that leaves last adds the workgroup's count of masked scans (every other wave's adds precede its ticket)
             const uint32_t ticket = __hip_atomic_fetch_add(&ldsK->exit_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
             if (ticket == (uint32_t)(kThreads / kWaveSize) - 1u)
             {
                 // (a directly resolved scan took its tile's tables as well: [3] counts both kinds, [4] the direct ones)
                 const unsigned long long nDirect = __hip_atomic_load(&ldsK->prim_direct, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                atomicAdd(&p.counters[3], nDirect + (unsigned long long)__hip_atomic_load(&ldsK->prim_masked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-                atomicAdd(&p.counters[4], nDirect);
-                if (kSky) atomicAdd(&p.counters[5], (unsigned long long)__hip_atomic_load(&ldsK->prim_sky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                atomicAdd(&counters[3], nDirect + (unsigned long long)__hip_atomic_load(&ldsK->prim_masked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                atomicAdd(&counters[4], nDirect);
+                if (kSky) atomicAdd(&counters[5], (unsigned long long)__hip_atomic_load(&ldsK->prim_sky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
             }
         }
 #ifdef RT_STAMPS

@@ -265,6 +265,104 @@ RT_DEV void fill_consts(const TraceParams& p, SceneConsts& k) {
     k.exit_age_max = 0u; k.exit_ticket = 0u; k.dry_mask = 0u; k.prim_masked = 0u; k.prim_direct = 0u; k.prim_sky = 0u;
 }
 
+// ---- The LAUNCH constants of the kernels without far-hit state (rt_kernels.h trace_body, kFarState == false), in LDS for the same
+// reason as SceneConsts: whatever the persistent loop reads of the kernel arguments lives in SGPRs for the whole launch, and the loop
+// reads some forty dwords of them -- once per queue block, per fresh tile plane, per hit -- which is why those kernels spilled more
+// than a hundred SGPRs into VGPR lanes (a v_readlane and its wait states at every use).  Here thread 0 writes them once, before the
+// barrier the prologue has anyway, and every use reads them back as short-lived temporaries; what the scan reads at every iteration
+// (table bases, nTiles / nTop, bound_norm, single_mask, n_always, tree_box) stays in the kernel arguments.
+// Where they live: the words read per hit or per finished path (kLeanHot...) in the 40 bytes SceneConsts leaves of its 256, at a fixed
+// address; the rest in three chunks of at most 16 dwords (kLeanPlane..., kLeanQueue..., kLeanRare...) in the last stash_cap dwords of
+// the hit-stash regions of waves 0, 1 and 2 -- field 18 of the stash record (the per-path traversal count), which these kernels
+// neither read nor write.  A stash kernel has stash_cap >= 16 (host/rt_launch_plan.cpp) and 16 waves, so the room is there whatever
+// the cap; neither kConstBytes nor the launch plan changes.  Pointers are kept as two words and rebuilt as GLOBAL-address-space
+// pointers (lds_global below): a generic pointer out of LDS would make every access through it a FLAT one (gen_primary_ray says why
+// that matters).
+enum : uint32_t {
+    kLeanHotSamples = 0,  // [2] p.samples
+    kLeanHotMats16 = 2,   // [2] p.mats16
+    kLeanHotMaxDepth = 4,
+    kLeanHotStashCap = 5,
+    kLeanHotStashProcess = 6,
+    kLeanHotFlags = 7,    // mats16_mode | (sg_glob16 != 0) << 8
+    kLeanHotTail = 8,     // dword offset in the LDS image of chunk 0 ...
+    kLeanHotStride = 9,   // ... and from one chunk to the next (a wave's stash region)
+    kLeanHotWords = 10,
+    // chunk 0: what a fresh tile plane reads (K_GEN, K_GEN_TILE, path_coordinates)
+    kLeanPlaneTileOrder = 0, kLeanPlaneTileMasks = 2, kLeanPlaneTileSpheres = 4,  // [2] each
+    kLeanPlaneFdTile = 6,                                                          // m, sh
+    kLeanPlaneNpix = 8, kLeanPlaneSpp = 9, kLeanPlaneSampleBase = 10, kLeanPlaneSkySkip = 11,
+    kLeanPlaneSeed = 12,  // [2]
+    kLeanPlaneFdW = 14,   // m, sh
+    // chunk 1: what a queue block reads (nextBlock, claim_block), the counters, and the rest of path_coordinates
+    kLeanQueueTotal = 0, kLeanQueueDynBegin = 1, kLeanQueueDynBlocks = 2, kLeanQueueHeads = 3 /* [2] */, kLeanQueueStatic = 5, kLeanQueueBlock = 6,
+    kLeanQueueCounters = 7,  // [2]
+    kLeanQueueFdRows = 9,    // m, sh
+    kLeanQueueRsFirst = 11, kLeanQueueRsBlockRows = 12, kLeanQueueRsShard = 13, kLeanQueueRsNshards = 14,
+    // chunk 2: what only a far hit point or a list of lights reads
+    kLeanRareNPadded = 0, kLeanRareFarIndex = 1, kLeanRareNLights = 2, kLeanRareExtraLights = 3 /* [2] */,
+    kLeanChunkWords = 16, kLeanChunks = 3
+};
+constexpr uint32_t kLeanHotOffset = (uint32_t)((sizeof(SceneConsts) + 7u) & ~(size_t)7u);  // bytes, in the constants block
+static_assert(kLeanHotOffset + 4u * kLeanHotWords <= kSceneConstBytes, "the lean kernels' hot launch constants must fit behind SceneConsts");
+static_assert(kLeanPlaneFdW + 2u <= kLeanChunkWords && kLeanQueueRsNshards + 1u <= kLeanChunkWords && kLeanRareExtraLights + 2u <= kLeanChunkWords,
+              "a chunk of lean launch constants is at most 16 dwords: what the smallest hit stash (16 records) leaves per wave");
+
+RT_DEV void lean_store_ptr(uint32_t* w, const void* ptr) {
+    const unsigned long long a = (unsigned long long)(uintptr_t)ptr;
+    w[0] = (uint32_t)a;
+    w[1] = (uint32_t)(a >> 32);
+}
+// image: the start of the dynamic LDS image (one thread of the workgroup, before the prologue's barrier)
+RT_DEV void fill_lean_consts(const TraceParams& p, uint32_t* image) {
+    uint32_t* hot = image + kLeanHotOffset / 4u;
+    const uint32_t tail = p.ray_cache_off16 * 4u + (kStashDwords - 1u) * p.stash_cap, stride = p.ray_cache_stride16 * 4u;
+    lean_store_ptr(hot + kLeanHotSamples, p.samples);
+    lean_store_ptr(hot + kLeanHotMats16, p.mats16);
+    hot[kLeanHotMaxDepth] = p.max_depth; hot[kLeanHotStashCap] = p.stash_cap; hot[kLeanHotStashProcess] = p.stash_process;
+    hot[kLeanHotFlags] = p.mats16_mode | (p.sg_glob16 != 0u ? 256u : 0u);
+    hot[kLeanHotTail] = tail; hot[kLeanHotStride] = stride;
+    uint32_t* a = image + tail;
+    lean_store_ptr(a + kLeanPlaneTileOrder, p.tile_order);
+    lean_store_ptr(a + kLeanPlaneTileMasks, p.tile_masks);
+    lean_store_ptr(a + kLeanPlaneTileSpheres, p.tile_spheres);
+    a[kLeanPlaneFdTile] = p.fd_tile.m; a[kLeanPlaneFdTile + 1] = p.fd_tile.sh;
+    a[kLeanPlaneNpix] = p.npix_local; a[kLeanPlaneSpp] = p.spp_pass; a[kLeanPlaneSampleBase] = p.sample_base; a[kLeanPlaneSkySkip] = p.sky_skip;
+    a[kLeanPlaneSeed] = (uint32_t)p.seed; a[kLeanPlaneSeed + 1] = (uint32_t)(p.seed >> 32);
+    a[kLeanPlaneFdW] = p.fd_w.m; a[kLeanPlaneFdW + 1] = p.fd_w.sh;
+    uint32_t* b = a + stride;
+    b[kLeanQueueTotal] = p.total_paths; b[kLeanQueueDynBegin] = p.dyn_begin; b[kLeanQueueDynBlocks] = p.dyn_blocks;
+    lean_store_ptr(b + kLeanQueueHeads, p.shard_heads);
+    b[kLeanQueueStatic] = p.static_blocks; b[kLeanQueueBlock] = p.queue_block;
+    lean_store_ptr(b + kLeanQueueCounters, p.counters);
+    b[kLeanQueueFdRows] = p.fd_rows.m; b[kLeanQueueFdRows + 1] = p.fd_rows.sh;
+    b[kLeanQueueRsFirst] = p.rs.first_row; b[kLeanQueueRsBlockRows] = p.rs.block_rows; b[kLeanQueueRsShard] = p.rs.shard; b[kLeanQueueRsNshards] = p.rs.nshards;
+    uint32_t* c = b + stride;
+    c[kLeanRareNPadded] = p.n_padded; c[kLeanRareFarIndex] = p.far_index; c[kLeanRareNLights] = p.n_lights;
+    lean_store_ptr(c + kLeanRareExtraLights, p.extra_lights);
+}
+// A wave-uniform word out of LDS, as a scalar: every lane read the same address.
+RT_DEV uint32_t lds_uniform(const uint32_t* w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)*w);
+#else
+    return *w;
+#endif
+}
+// A pointer kept in LDS as two words, rebuilt in the GLOBAL address space (the generic pointer returned is derived from a global
+// one, which is what the compiler's address-space inference needs to keep global_load / global_store / global_atomic).
+template <class T>
+RT_DEV T* lds_global(const uint32_t* w, bool uniform = true) {
+    const unsigned long long a = uniform ? ((unsigned long long)lds_uniform(w) | (unsigned long long)lds_uniform(w + 1) << 32)
+                                         : ((unsigned long long)w[0] | (unsigned long long)w[1] << 32);
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef T __attribute__((address_space(1)))* G;
+    return (T*)(G)a;
+#else
+    return (T*)(uintptr_t)a;
+#endif
+}
+
 // --------------------------------------------------------------------------- row sets
 RT_DEV uint32_t rowset_global_row(const rt_rowset& rs, uint32_t lr, FastDiv byBlockRows) {
     const uint32_t lb = fastdiv(lr, byBlockRows);
@@ -306,13 +404,15 @@ RT_DEV void halton_disk_4_5(uint32_t k, float& lensx, float& lensy, uint32_t sam
     lensx = r * (float)cs;
     lensy = r * (float)sn;
 }
-template <class P>
+// kTabs: the launch provides both tables by construction (the kernels without far-hit state: rt_capi.hip LaunchTrace), so that the
+// radical-inverse fallback is not compiled into them
+template <bool kTabs = false, class P>
 RT_DEV void gen_primary_ray(const P& p, uint32_t i, uint32_t j, uint32_t s, V3& origin, V3& dir) {
     const float xsize = (float)p.W;
     const float ysize = (float)p.H;
     float jx, jy, lensx, lensy;
     const uint32_t li = s + i + j;
-    if (p.jitter_tab) {
+    if (kTabs || p.jitter_tab) {
         // the radical inverses depend on s (jitter) and s+i+j (lens) only: a per-pass device kernel
         // tabulates them so that a refilled lane does two 8-byte loads instead of four divide loops
         // the pointers may come out of LDS (SceneConsts): say that they point to global memory, or the loads become FLAT

@@ -464,6 +464,9 @@ int rt_unit_halton(rt_ctx* ctx, const uint32_t* index, uint32_t base, uint32_t n
  * 7: the path's square root (guarded fast form), 8: its fast form alone (x in [2^-80, inf)), 9: the compiler's sqrtf on the
  * device -- all three must equal the IEEE square root */
 int rt_unit_math(rt_ctx* ctx, uint32_t op, const float* x, const float* y, uint32_t n, float* out);
+/* ops 0 to 3 of rt_unit_math from the same source compiled for the host (csrc/rt_device_math.h).  y may be NULL except for op 2.
+ * Needs no GPU. */
+int rt_unit_math_host(uint32_t op, const float* x, const float* y, uint32_t n, float* out);
 /* GenerateRays for chosen pixels: (i,j,s) -> origin xyz, direction xyz (6 floats each) */
 int rt_unit_primary_rays(rt_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* ijs /*3 per ray*/,
                          uint32_t n, float* out_rays);

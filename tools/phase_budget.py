@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "cpuraytracer_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
 KERNELS = {  # the instantiation rt_render launches for the config (RT_VERBOSE prints the variant)
-    "c2": "_ZN3rtd15rt_trace_kernelILb1ELi1024ELi1ELb1ELb1ELb0ELb1ELb1ELb0ELb0EEEvNS_11TraceParamsE",
+    "c2": "_ZN3rtd20rt_trace_kernel_leanILb1ELi1024ELi1ELb1ELb1ELb0ELb1ELb1ELb0ELb0EEEvNS_11TraceParamsE",  # (picture launches: no far-hit state)
     "c5": "_ZN3rtd15rt_trace_kernelILb0ELi1024ELi3ELb1ELb1ELb0ELb1ELb0ELb0ELb0EEEvNS_11TraceParamsE",
 }
 WORKLOADS = {"c2": ("cover", 1200, 800, 128, -1.0), "c5": ("grid10k", 4096, 4096, 64, -1.0)}
