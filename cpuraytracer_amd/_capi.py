@@ -57,6 +57,11 @@ class RtShardParts(C.Structure):
                 ("rs", RtRowset), ("n", C.c_uint32), ("m", C.c_uint32)]
 
 
+class RtShardFrame(C.Structure):
+    """rt_shard_frame: the parts, the shards' ids in the same layout (a device pointer), the image's height and the shards' camera."""
+    _fields_ = [("parts", RtShardParts), ("ids", C.c_void_p), ("H", C.c_uint32), ("camera", RtCamera)]
+
+
 SPHERE_DTYPE = np.dtype([("cx", "<f4"), ("cy", "<f4"), ("cz", "<f4"), ("r", "<f4")])
 MATERIAL_DTYPE = np.dtype([("type", "<u4"), ("tex_type", "<u4"), ("smoothness", "<f4"), ("ior", "<f4"),
                            ("tiling", "<f4"), ("rgb0", "<f4", (3,)), ("rgb1", "<f4", (3,)), ("luminance", "<f4")])
@@ -85,6 +90,7 @@ EXPORTS = [
     "rt_copy_moments_to_device", "rt_rowset_locate", "rt_denoise_shards", "rt_unit_denoise_shards_host",
     "rt_temporal_default_params", "rt_denoise_temporal", "rt_temporal_reset", "rt_download_temporal", "rt_unit_temporal_host",
     "rt_temporal_default_params_fetch", "rt_denoise_temporal_fetch", "rt_unit_temporal_host_fetch",
+    "rt_denoise_shards_temporal", "rt_unit_temporal_shards_host",
 ]
 
 _lib = None
@@ -226,6 +232,12 @@ def load():
                                                   C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtCamera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "rt_denoise_shards_temporal"):
+        L.rt_denoise_shards_temporal.argtypes = [C.c_void_p, C.POINTER(RtShardFrame), C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32,
+                                                 C.POINTER(C.c_double)]
+        L.rt_unit_temporal_shards_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtShardFrame), C.POINTER(RtCamera), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -302,6 +314,45 @@ def shard_parts(W, H, world, rows_max, n, m, hdr=None, sq=None, feat=None, block
     """An rt_shard_parts for a W x H picture cut cyclically into `world` shards of block_rows rows (default BLOCK_ROWS)."""
     rs = RtRowset(first_row, H, BLOCK_ROWS if block_rows is None else block_rows, 0, world)
     return RtShardParts(hdr or None, sq or None, feat or None, W, rows_max, rs, n, m)
+
+
+def shard_frame(W, H, world, rows_max, n, m, camera, hdr=None, sq=None, feat=None, ids=None, block_rows=None, first_row=0, num_rows=None):
+    """An rt_shard_frame: rows [first_row, first_row + num_rows) (default: all) of the W x H image, rendered with `camera` (an
+    rt_camera record) and cut cyclically into `world` shards of block_rows rows (default BLOCK_ROWS)."""
+    parts = shard_parts(W, H - first_row if num_rows is None else num_rows, world, rows_max, n, m, hdr, sq, feat, block_rows=block_rows, first_row=first_row)
+    return RtShardFrame(parts, ids or None, H, RtCamera.from_buffer_copy(bytes(camera)))
+
+
+def unit_temporal_shards_host(hdr, sq, feat8, ids, frame, history=None, params=None, tparams=None, fetch=1):
+    """rt_unit_temporal_shards_host over numpy parts ([world, rows_max, W, c] each; ids uint32) shaped by `frame` (shard_frame(...), its
+    pointers unused).  history and the returned dict as unit_temporal_host's: everything in image order, num_rows x W."""
+    hdr = np.ascontiguousarray(hdr, dtype=np.float32)
+    sq = np.ascontiguousarray(sq, dtype=np.float32)
+    feat8 = np.ascontiguousarray(feat8, dtype=np.float32)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    W, rows, world, rows_max, block_rows = frame.parts.W, frame.parts.rs.num_rows, frame.parts.rs.nshards, frame.parts.rows_max, frame.parts.rs.block_rows
+    px = world * rows_max * W
+    assert hdr.size == px * 3 and sq.size == px * 3 and feat8.size == px * 8 and ids.size == px
+    out = {"rgb": np.zeros((rows, W, 3), np.float32), "var": np.zeros((rows, W), np.float32), "state": np.zeros((rows, W, 4), np.float32),
+           "guides": np.zeros((rows, W, 8), np.float32), "len": np.zeros((rows, W), np.uint32), "target": np.zeros((rows, W), np.uint32)}
+    if history is None:
+        hc, hs, hg, hi, hl = None, None, None, None, None
+    else:
+        hc = C.byref(RtCamera.from_buffer_copy(bytes(history["camera"])))
+        keep = [np.ascontiguousarray(history["state"], dtype=np.float32), np.ascontiguousarray(history["guides"], dtype=np.float32),
+                np.ascontiguousarray(history["ids"], dtype=np.uint32), np.ascontiguousarray(history["len"], dtype=np.uint32)]
+        assert keep[0].size == rows * W * 4 and keep[1].size == rows * W * 8 and keep[2].size == rows * W and keep[3].size == rows * W
+        hs, hg, hi, hl = (a.ctypes.data for a in keep)
+    check(load().rt_unit_temporal_shards_host(hdr.ctypes.data, sq.ctypes.data, feat8.ctypes.data, ids.ctypes.data, C.byref(frame), hc, hs, hg, hi, hl,
+                                              C.byref(params) if params is not None else None, C.byref(tparams) if tparams is not None else None,
+                                              int(fetch), out["rgb"].ctypes.data, out["var"].ctypes.data, out["state"].ctypes.data,
+                                              out["guides"].ctypes.data, out["len"].ctypes.data, out["target"].ctypes.data))
+    # the new history's ids: the parts' ids in image order (block b of the range is block b // world of part b % world)
+    j = np.arange(rows)
+    b = j // block_rows
+    out["ids"] = ids.reshape(world, rows_max, W)[b % world, (b // world) * block_rows + j % block_rows].copy()
+    out["camera"] = RtCamera.from_buffer_copy(bytes(frame.camera))
+    return out
 
 
 def whole_image(H):

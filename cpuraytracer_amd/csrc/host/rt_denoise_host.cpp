@@ -60,6 +60,8 @@ void RunLevelsHost(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseSt
     RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
 }
 
+// (CheckShardFrame, the same for an rt_shard_frame, ends with this one and lives in rt_temporal_host.cpp, beside the temporal parameters'
+// checks it calls: denoise_selftest links this file without that one)
 int CheckShardParts(const char* who_, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P) {
     const std::string who(who_);
     if (!parts || !P) return Fail(RT_ERR_INVALID_ARG, who + ": null argument");

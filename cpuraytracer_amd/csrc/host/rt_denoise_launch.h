@@ -73,12 +73,25 @@ struct Temporal {
 int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
                           uint32_t forms[rtd::kDenoiseMaxLevels]);
 
+// The temporal form over the parts (rt_denoise_shards_temporal): hdr, sq and feat of Strips and Temporal::ids are the gathered parts
+// (ids: [nshards] parts of rowsMax x W words), W x rows is the IMAGE's row range and t.geom.num_rows == rows.  The prepare pass reads
+// the current frame through the mapping; the history sets, target and everything the levels touch are in image order.
+int LaunchDenoiseShardsTemporal(void* stream, const Strips& s, const ShardLayout& parts, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
+                                uint32_t forms[rtd::kDenoiseMaxLevels]);
+
 }  // namespace rtdn
 
 // What rt_denoise_shards and rt_unit_denoise_shards_host refuse, checked once (rt_denoise_host.cpp): the shape, the sample counts and
 // the parameters (NULL: the defaults), which are returned in P.  The struct's own pointers are looked at only with devicePointers.
 struct rt_shard_parts;
 struct rt_denoise_params;
+// ... and what rt_denoise_shards_temporal and rt_unit_temporal_shards_host refuse: all of that for frame->parts, the frame's own
+// fields (ids only with devicePointers), the fetch and the temporal parameters (NULL: that fetch's defaults), returned in T.  On
+// RT_OK *G is the geometry of the parts' row range in the W x H image.
+struct rt_shard_frame;
+struct rt_temporal_params;
 namespace rtdn {
 int CheckShardParts(const char* who, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P);
+int CheckShardFrame(const char* who, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
+                    bool devicePointers, rtd::DenoiseParams* P, rtd::TemporalParams* T, rtd::TemporalGeom* G);
 }

@@ -1533,20 +1533,27 @@ int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise
 }
 
 // rt_denoise with the temporal step in its prepare pass (rt_temporal.h).  The history is the context's: set tmpCur is read, the other
-// set is written and becomes tmpCur once everything is enqueued.  Every refusal comes before the first change.
-// (who: the entry's name for the messages; fetch: which prepare kernel reads the history, and whose defaults tparams == NULL takes)
-static int DenoiseTemporal(rt_ctx* ctx, const char* who, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms) {
-    rtd::DenoiseParams P{};
-    int rc = DenoiseParamsReady(ctx, who, params, &P);
-    if (rc != RT_OK) return rc;
-    rtd::TemporalParams T{};
-    if ((rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &T)) != RT_OK) return rc;
-    if ((rc = DenoisePictureReady(ctx, who)) != RT_OK) return rc;
-    const rtseq::PictureKey& pic = ctx->seq.pic;
-    const uint32_t W = pic.W, rows = ctx->seq.rows;
-    const rtd::TemporalGeom G{W, pic.H, pic.rs.first_row, rows};
-    if (!rtd::temporal_geom_ok(G) || rows != pic.rs.num_rows)
-        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a picture wider or taller than 2^24, or a strip that is not its row range");
+// set is written and becomes tmpCur once everything is enqueued.  Every refusal comes before the first change: the entries make their
+// checks (DenoiseTemporal for the context's own picture, rt_denoise_shards_temporal for gathered parts) and TemporalStep does the rest.
+// What the checks leave of a call: the picture the history is keyed with, its row range, the current frame's inputs -- in image order
+// (parts == NULL) or as gathered parts -- and camera, and the parameters.
+struct TemporalCall {
+    rtseq::PictureKey pic;
+    rtd::TemporalGeom geom;
+    const float *hdr, *sq, *feat;
+    const uint32_t* ids;
+    uint32_t n, m;
+    const rtdn::ShardLayout* parts;
+    rtd::TemporalCam cam;
+    rtd::DenoiseParams P;
+    rtd::TemporalParams T;
+    uint32_t fetch;
+};
+static int TemporalStep(rt_ctx* ctx, const char* who, const TemporalCall& c, double* out_ms) {
+    int rc;
+    const rtseq::PictureKey& pic = c.pic;
+    const uint32_t W = c.geom.W, rows = c.geom.num_rows;
+    const uint32_t fetch = c.fetch;
     const size_t npix = (size_t)W * rows;
     const bool hasPrev = ctx->tmpValid && ctx->tmpPic == pic;
     if (!hasPrev) ctx->tmpValid = false;  // (a Reserve below may let the old sets go: they were of another picture)
@@ -1558,14 +1565,18 @@ static int DenoiseTemporal(rt_ctx* ctx, const char* who, const rt_denoise_params
     rtdn::Strips S{};
     int knob;
     if ((rc = DenoiseStrips(ctx, W, rows, false, &S, &knob)) != RT_OK) return rc;
-    DenoiseInputsOfPicture(ctx, &S);
-    const rtd::TraceParams& b = ctx->base;
+    S.hdr = c.hdr;
+    S.sq = c.sq;
+    S.feat = c.feat;
+    S.n = c.n;
+    S.m = c.m;
+    const rtd::DenoiseParams& P = c.P;
     rtdn::Temporal Q{};
-    Q.ids = ctx->featIds.ptr;
-    Q.geom = G;
-    rtd::temporal_cam(b.cam_o, b.cam_x, b.cam_y, b.cam_oip, Q.cam);
+    Q.ids = c.ids;
+    Q.geom = c.geom;
+    Q.cam = c.cam;
     Q.camPrev = hasPrev ? ctx->tmpCam : Q.cam;
-    Q.params = T;
+    Q.params = c.T;
     Q.fetch = fetch;
     Q.hasPrev = hasPrev;
     const uint32_t cur = ctx->tmpCur & 1u, nxt = cur ^ 1u;
@@ -1575,12 +1586,38 @@ static int DenoiseTemporal(rt_ctx* ctx, const char* who, const rt_denoise_params
     Q.target = ctx->tmpTarget.ptr;
     ctx->tmpValid = false;  // the history is being rewritten, until everything is enqueued
     if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
-    if ((rc = DenoiseFinish(ctx, who, S, rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms), out_ms)) != RT_OK) return rc;
+    const int launched = c.parts ? rtdn::LaunchDenoiseShardsTemporal(ctx->stream, S, *c.parts, Q, P, knob, ctx->denForms)
+                                 : rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms);
+    if ((rc = DenoiseFinish(ctx, who, S, launched, out_ms)) != RT_OK) return rc;
     ctx->tmpCur = nxt;
     ctx->tmpPic = pic;
     ctx->tmpCam = Q.cam;
     ctx->tmpValid = true;
     return RT_OK;
+}
+
+// (who: the entry's name for the messages; fetch: which prepare kernel reads the history, and whose defaults tparams == NULL takes)
+static int DenoiseTemporal(rt_ctx* ctx, const char* who, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms) {
+    TemporalCall c{};
+    int rc = DenoiseParamsReady(ctx, who, params, &c.P);
+    if (rc != RT_OK) return rc;
+    if ((rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &c.T)) != RT_OK) return rc;
+    if ((rc = DenoisePictureReady(ctx, who)) != RT_OK) return rc;
+    c.pic = ctx->seq.pic;
+    c.geom = rtd::TemporalGeom{c.pic.W, c.pic.H, c.pic.rs.first_row, ctx->seq.rows};
+    if (!rtd::temporal_geom_ok(c.geom) || ctx->seq.rows != c.pic.rs.num_rows)
+        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a picture wider or taller than 2^24, or a strip that is not its row range");
+    c.hdr = ctx->hdr.ptr;
+    c.sq = ctx->sq.ptr;
+    c.feat = ctx->feat.ptr;
+    c.ids = ctx->featIds.ptr;
+    c.n = ctx->seq.accumulated;
+    c.m = ctx->featCount;
+    c.parts = nullptr;
+    const rtd::TraceParams& b = ctx->base;
+    rtd::temporal_cam(b.cam_o, b.cam_x, b.cam_y, b.cam_oip, c.cam);
+    c.fetch = fetch;
+    return TemporalStep(ctx, who, c, out_ms);
 }
 
 int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, double* out_ms) {
@@ -1590,6 +1627,33 @@ int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_t
 // The same call with the way the history is fetched chosen: 1 runs the kernel above, 4 the bilinear one; the history is one state.
 int rt_denoise_temporal_fetch(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms) {
     return DenoiseTemporal(ctx, "rt_denoise_temporal_fetch", params, tparams, fetch, out_ms);
+}
+
+// The same step over the gathered parts of a row-sharded picture: the frame brings what DenoiseTemporal takes from the context (the
+// inputs, the ids, the image's height, the camera), and the history is keyed with the parts' row set, shard 0 -- a contiguous call's
+// key where nshards == 1.  Only the denoiser's strips and the history are touched.
+int rt_denoise_shards_temporal(rt_ctx* ctx, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
+                               double* out_ms) {
+    const char* who = "rt_denoise_shards_temporal";
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    TemporalCall c{};
+    const int rc = rtdn::CheckShardFrame(who, frame, params, tparams, fetch, true, &c.P, &c.T, &c.geom);
+    if (rc != RT_OK) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    const rt_shard_parts& parts = frame->parts;
+    c.pic = rtseq::PictureKey{parts.W, frame->H, parts.rs};
+    c.pic.rs.shard = 0;
+    c.hdr = static_cast<const float*>(parts.hdr);
+    c.sq = static_cast<const float*>(parts.sq);
+    c.feat = static_cast<const float*>(parts.feat);
+    c.ids = static_cast<const uint32_t*>(frame->ids);
+    c.n = parts.n;
+    c.m = parts.m;
+    const rtdn::ShardLayout layout{parts.rows_max, parts.rs.block_rows, parts.rs.nshards};
+    c.parts = &layout;
+    c.cam = rtdn::CamOf(frame->camera);
+    c.fetch = fetch;
+    return TemporalStep(ctx, who, c, out_ms);
 }
 
 int rt_temporal_reset(rt_ctx* ctx) {

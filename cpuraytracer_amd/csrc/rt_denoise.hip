@@ -85,10 +85,9 @@ struct TemporalArgs {
     uint32_t* __restrict__ target;
 };
 
-__global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const TemporalArgs A) {
-    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= A.npix) return;
-    const size_t p = pix;
+// The pass's body, shared with the sharded form below: pix is the pixel of the strip (IMAGE order: every history read and every write),
+// p where its current-frame inputs lie -- pix itself, or its place in the gathered parts.
+__device__ __forceinline__ void temporal_prepare_nearest(const TemporalArgs& A, const uint32_t pix, const size_t p) {
     const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
     const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
     const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
@@ -114,12 +113,19 @@ __global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const 
             if (ok) target = q;
         }
     }
-    A.oS[p] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
-    A.oG0[p] = make_float4(g[0], g[1], g[2], g[3]);
-    A.oG1[p] = make_float4(g[4], g[5], g[6], g[7]);
-    A.oId[p] = id;
-    A.oLen[p] = len;
-    A.target[p] = target;
+    const size_t o = pix;
+    A.oS[o] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
+    A.oG0[o] = make_float4(g[0], g[1], g[2], g[3]);
+    A.oG1[o] = make_float4(g[4], g[5], g[6], g[7]);
+    A.oId[o] = id;
+    A.oLen[o] = len;
+    A.target[o] = target;
+}
+
+__global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const TemporalArgs A) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    temporal_prepare_nearest(A, pix, pix);
 }
 
 // The bilinear fetch (rt_temporal.h): the same pass, but the history is read at the four pixels around the reprojected point.  The two
@@ -127,10 +133,7 @@ __global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const 
 // All four taps' loads are issued before the first is used: a tap outside the strip loads the pixel's own index instead (pix < npix, a
 // contiguous read) and what it loaded is dropped, so no load waits for a test and none leaves the arrays -- a tap inside has q < npix by
 // temporal_tap_index.  Only taps that take part are added (temporal_gather_tap).  Writes as in the nearest kernel.
-__global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_bilinear_kernel(const TemporalArgs A) {
-    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= A.npix) return;
-    const size_t p = pix;
+__device__ __forceinline__ void temporal_prepare_bilinear(const TemporalArgs& A, const uint32_t pix, const size_t p) {
     const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
     const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
     const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
@@ -181,12 +184,49 @@ __global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_bilinear_kern
             if (ok) target = S.target;
         }
     }
-    A.oS[p] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
-    A.oG0[p] = make_float4(g[0], g[1], g[2], g[3]);
-    A.oG1[p] = make_float4(g[4], g[5], g[6], g[7]);
-    A.oId[p] = id;
-    A.oLen[p] = len;
-    A.target[p] = target;
+    const size_t o = pix;
+    A.oS[o] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
+    A.oG0[o] = make_float4(g[0], g[1], g[2], g[3]);
+    A.oG1[o] = make_float4(g[4], g[5], g[6], g[7]);
+    A.oId[o] = id;
+    A.oLen[o] = len;
+    A.target[o] = target;
+}
+
+__global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_bilinear_kernel(const TemporalArgs A) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    temporal_prepare_bilinear(A, pix, pix);
+}
+
+// The two passes over the gathered parts of a row-sharded picture (rt_denoise_shards_temporal): a thread owns pixel pix of the IMAGE's
+// row range, finds the part and the local row that hold its row (rt_rowset_map.h, as rt_denoise_prepare_shards_kernel does) and reads
+// hdr, sq, feat and ids of the current frame there -- a row is contiguous inside its part, so the lanes of a wave still read contiguous
+// segments; padding rows belong to no image row and are never read.  Everything else is the body above at image-order indices: the
+// history sets are in image order, and so is the bilinear kernel's stand-in load for a tap outside the strip (the pixel's own index).
+// p < nshards * rowsMax * W by the mapping: lr < rowsMax for every row of the range (rowset_max_shard_rows, checked by the caller).
+struct TemporalShardArgs {
+    TemporalArgs A;
+    uint32_t rowsMax, blockRows, nshards;
+};
+
+__device__ __forceinline__ size_t temporal_shard_source(const TemporalShardArgs& S, const uint32_t pix) {
+    const uint32_t y = pix / S.A.G.W, x = pix - y * S.A.G.W;
+    uint32_t shard, lr;
+    rowset_locate(S.blockRows, S.nshards, y, shard, lr);
+    return ((size_t)shard * S.rowsMax + lr) * S.A.G.W + x;
+}
+
+__global__ void __launch_bounds__(256) rt_denoise_prepare_shards_temporal_kernel(const TemporalShardArgs S) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= S.A.npix) return;
+    temporal_prepare_nearest(S.A, pix, temporal_shard_source(S, pix));
+}
+
+__global__ void __launch_bounds__(256) rt_denoise_prepare_shards_temporal_bilinear_kernel(const TemporalShardArgs S) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= S.A.npix) return;
+    temporal_prepare_bilinear(S.A, pix, temporal_shard_source(S, pix));
 }
 
 // One level.  Thread (tx, ty) of the 32 x 8 workgroup owns pixel (32 bx + tx, 8 by + ty); its 25 taps lie (a - 2) step rows and
@@ -330,17 +370,13 @@ int LaunchDenoiseShards(void* stream, const Strips& s, const ShardLayout& parts,
                         forms);
 }
 
-int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
-                          uint32_t forms[rtd::kDenoiseMaxLevels]) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint32_t npix = s.W * s.rows;
-    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
+static rtd::TemporalArgs TemporalArgsOf(const Strips& s, const Temporal& t) {
     rtd::TemporalArgs A{};
     A.hdr = s.hdr;
     A.sq = s.sq;
     A.feat = reinterpret_cast<const float4*>(s.feat);
     A.ids = t.ids;
-    A.npix = npix;
+    A.npix = s.W * s.rows;
     A.n = s.n;
     A.m = s.m;
     A.hasPrev = t.hasPrev ? 1u : 0u;
@@ -359,6 +395,15 @@ int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, cons
     A.oId = t.next.ids;
     A.oLen = t.next.len;
     A.target = t.target;
+    return A;
+}
+
+int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
+                          uint32_t forms[rtd::kDenoiseMaxLevels]) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t npix = s.W * s.rows;
+    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
+    const rtd::TemporalArgs A = TemporalArgsOf(s, t);
     if (t.fetch == rtd::kTemporalFetchBilinear)
         hipLaunchKernelGGL(rtd::rt_denoise_prepare_temporal_bilinear_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, A);
     else
@@ -366,6 +411,21 @@ int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, cons
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     return LaunchLevels(st, s, A.oS, A.oG0, A.oG1, P, stageKnob, forms);
+}
+
+int LaunchDenoiseShardsTemporal(void* stream, const Strips& s, const ShardLayout& parts, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
+                                uint32_t forms[rtd::kDenoiseMaxLevels]) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t npix = s.W * s.rows;
+    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
+    const rtd::TemporalShardArgs S{TemporalArgsOf(s, t), parts.rowsMax, parts.blockRows, parts.nshards};
+    if (t.fetch == rtd::kTemporalFetchBilinear)
+        hipLaunchKernelGGL(rtd::rt_denoise_prepare_shards_temporal_bilinear_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, S);
+    else
+        hipLaunchKernelGGL(rtd::rt_denoise_prepare_shards_temporal_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, S);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return LaunchLevels(st, s, S.A.oS, S.A.oG0, S.A.oG1, P, stageKnob, forms);
 }
 
 }  // namespace rtdn

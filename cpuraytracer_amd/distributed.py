@@ -9,7 +9,9 @@ which de-interleaves them.  Each pixel depends only on (global pixel id, s, seed
 image is byte-identical to the single-GPU image.  No other collective exists on the path.
 
 Denoising the sharded picture (PostExchange, denoise_gathered) is again one gather: hdr, second moments and features of every rank's
-strip in one buffer, filtered on rank 0 by rt_denoise_shards, which reads the gathered parts through the row mapping.
+strip in one buffer, filtered on rank 0 by rt_denoise_shards, which reads the gathered parts through the row mapping.  With the
+feature ids in the same buffer (PostExchange(with_ids=True)) rank 0 also keeps the temporal history of the sharded picture
+(denoise_gathered_temporal, rt_denoise_shards_temporal).
 """
 import numpy as np
 
@@ -105,53 +107,67 @@ class PostExchange:
     largest shard: [rows_max * W * 3 | rows_max * W * 3 | rows_max * W * 8].  On rank 0 the gathered buffers are regrouped -- three
     strided copies on the device, no pass over the host -- into hdr_parts, sq_parts [world, rows_max, W, 3] and feat_parts
     [world, rows_max, W, 8], each contiguous and an allocation of its own: exactly the layout rt_shard_parts takes
-    (HipRenderer.denoise_shards, denoise_gathered below).  The padding rows are never read by the filter."""
+    (HipRenderer.denoise_shards, denoise_gathered below).  The padding rows are never read by the filter.
 
-    def __init__(self, H, W, rank, world, device, block_rows=BLOCK_ROWS):
+    with_ids=True (temporal accumulation, denoise_gathered_temporal below) adds a tail of rows_max * W words to the buffer: the rank's
+    feature ids.  They are uint32 and travel as the bytes they are -- the buffer's float32 is only its element size, nothing ever
+    converts them -- viewed as int32 at both ends, and rank 0 regroups them into ids_parts [world, rows_max, W] int32 (torch has no
+    arithmetic-free uint32 tensor everywhere; the bits are the ids').  Without it the buffer, cut and the results are what they were."""
+
+    def __init__(self, H, W, rank, world, device, block_rows=BLOCK_ROWS, with_ids=False):
         import torch
         self.H, self.W, self.rank, self.world, self.block_rows, self.device = H, W, rank, world, block_rows, device
+        self.with_ids = with_ids
         self.rows = local_rows(H, rank, world, block_rows)
         self.rows_max = max_local_rows(H, world, block_rows)
         px = self.rows_max * W
         self.cut = (3 * px, 6 * px, 14 * px)  # floats: end of hdr, of sq, of feat
-        self.buf = torch.zeros(self.cut[2], dtype=torch.float32, device=device)
+        self.words = self.cut[2] + (px if with_ids else 0)  # 4-byte elements of the buffer
+        self.buf = torch.zeros(self.words, dtype=torch.float32, device=device)
         self.hdr = self.buf[:self.cut[0]].view(self.rows_max, W, 3)
         self.sq = self.buf[self.cut[0]:self.cut[1]].view(self.rows_max, W, 3)
-        self.feat = self.buf[self.cut[1]:].view(self.rows_max, W, 8)
-        self.hdr_parts = self.sq_parts = self.feat_parts = None
+        self.feat = self.buf[self.cut[1]:self.cut[2]].view(self.rows_max, W, 8)
+        self.ids = self.buf[self.cut[2]:].view(torch.int32).view(self.rows_max, W) if with_ids else None
+        self.hdr_parts = self.sq_parts = self.feat_parts = self.ids_parts = None
         if rank == 0:
-            self.all = torch.empty((world, self.cut[2]), dtype=torch.float32, device=device) if world > 1 else self.buf.view(1, -1)
+            self.all = torch.empty((world, self.words), dtype=torch.float32, device=device) if world > 1 else self.buf.view(1, -1)
             self.hdr_parts = torch.empty((world, self.rows_max, W, 3), dtype=torch.float32, device=device)
             self.sq_parts = torch.empty_like(self.hdr_parts)
             self.feat_parts = torch.empty((world, self.rows_max, W, 8), dtype=torch.float32, device=device)
+            if with_ids:
+                self.ids_parts = torch.empty((world, self.rows_max, W), dtype=torch.int32, device=device)
 
     def fill(self, renderer):
-        """This rank's three strips, device to device into the buffer.  Asynchronous on the renderer's stream: where that is not the
-        stream the gather runs on (torch's current one), call renderer.synchronize() before gather()."""
+        """This rank's three strips (with_ids: and its ids), device to device into the buffer.  Asynchronous on the renderer's stream:
+        where that is not the stream the gather runs on (torch's current one), call renderer.synchronize() before gather()."""
         renderer.copy_to_device(self.hdr.data_ptr(), None)
         renderer.copy_moments_to_device(self.sq.data_ptr())
-        renderer.copy_features_to_device(self.feat.data_ptr(), None)
+        renderer.copy_features_to_device(self.feat.data_ptr(), self.ids.data_ptr() if self.with_ids else None)
 
     def gather(self, through_host=False):
-        """-> (hdr_parts, sq_parts, feat_parts) on rank 0, (None, None, None) elsewhere.  through_host: CPU tensors over gloo
-        (rehearsal: ranks that share a device); the parts still end on rank 0's device."""
+        """-> (hdr_parts, sq_parts, feat_parts) on rank 0, (None, None, None) elsewhere; with_ids: ids_parts as a fourth value (a fourth
+        None).  through_host: CPU tensors over gloo (rehearsal: ranks that share a device); the parts still end on rank 0's device."""
         import torch.distributed as dist
         if self.world > 1:
             if through_host:
                 import torch
                 src = self.buf.cpu()
-                got = torch.empty((self.world, self.cut[2]), dtype=torch.float32) if self.rank == 0 else None
+                got = torch.empty((self.world, self.words), dtype=torch.float32) if self.rank == 0 else None
                 dist.gather(src, [got[s] for s in range(self.world)] if self.rank == 0 else None, dst=0)
                 if self.rank == 0:
                     self.all.copy_(got)
             else:
                 dist.gather(self.buf, [self.all[s] for s in range(self.world)] if self.rank == 0 else None, dst=0)
         if self.rank != 0:
-            return None, None, None
+            return (None, None, None, None) if self.with_ids else (None, None, None)
         shape3, shape8 = (self.world, self.rows_max, self.W, 3), (self.world, self.rows_max, self.W, 8)
         self.hdr_parts.copy_(self.all[:, :self.cut[0]].reshape(shape3))
         self.sq_parts.copy_(self.all[:, self.cut[0]:self.cut[1]].reshape(shape3))
-        self.feat_parts.copy_(self.all[:, self.cut[1]:].reshape(shape8))
+        self.feat_parts.copy_(self.all[:, self.cut[1]:self.cut[2]].reshape(shape8))
+        if self.with_ids:
+            import torch
+            self.ids_parts.copy_(self.all[:, self.cut[2]:].view(torch.int32).reshape(self.world, self.rows_max, self.W))
+            return self.hdr_parts, self.sq_parts, self.feat_parts, self.ids_parts
         return self.hdr_parts, self.sq_parts, self.feat_parts
 
 
@@ -166,3 +182,19 @@ def denoise_gathered(renderer, xch, n, m, params=None, timed=False):
         torch.cuda.current_stream(xch.hdr_parts.device).synchronize()
     return renderer.denoise_shards(xch.hdr_parts.data_ptr(), xch.sq_parts.data_ptr(), xch.feat_parts.data_ptr(), xch.W, xch.H, xch.world,
                                    xch.rows_max, n, m, params=params, timed=timed, block_rows=xch.block_rows)
+
+
+def denoise_gathered_temporal(renderer, xch, n, m, camera, params=None, tparams=None, fetch=1, timed=False):
+    """Rank 0, after xch.gather() of a PostExchange(with_ids=True) on the renderer's device: rt_denoise_shards_temporal over the gathered
+    parts -- denoise_gathered with the renderer's history blended in (HipRenderer.denoise_shards_temporal).  camera: the rt_camera record
+    every rank rendered the frame with (scene.camera).  Call it frame after frame on the same renderer: the history is the renderer's."""
+    import torch
+    if xch.rank != 0 or xch.hdr_parts is None:
+        raise ValueError("denoise_gathered_temporal: rank 0 holds the gathered parts")
+    if xch.ids_parts is None:
+        raise ValueError("denoise_gathered_temporal: the exchange carries no ids (PostExchange(..., with_ids=True))")
+    if xch.hdr_parts.is_cuda:
+        torch.cuda.current_stream(xch.hdr_parts.device).synchronize()
+    return renderer.denoise_shards_temporal(xch.hdr_parts.data_ptr(), xch.sq_parts.data_ptr(), xch.feat_parts.data_ptr(), xch.ids_parts.data_ptr(), xch.W, xch.H,
+                                            xch.world, xch.rows_max, n, m, camera, params=params, tparams=tparams, fetch=fetch, timed=timed,
+                                            block_rows=xch.block_rows)

@@ -289,6 +289,24 @@ class HipRenderer:
         self.temporal_W, self.temporal_rows = self.W, self.rows
         return ms.value if timed else None
 
+    def denoise_shards_temporal(self, hdr_ptr, sq_ptr, feat_ptr, ids_ptr, W, H, world, rows_max, n, m, camera, params=None, tparams=None, fetch=1,
+                                timed=False, block_rows=_capi.BLOCK_ROWS, first_row=0, num_rows=None):
+        """rt_denoise_shards_temporal: denoise_temporal() over the gathered parts of denoise_shards() -- plus ids_ptr ([world][rows_max * W]
+        uint32, the shards' feature ids) and `camera`, the rt_camera record the shards were rendered with (scene.camera).  The parts hold
+        rows [first_row, first_row + num_rows) of the W x H image (default: all of it).  The history is this context's one history, kept
+        across calls and uploads and keyed with the image's size and the sharding: another sharding starts from an empty one, and world = 1
+        with the rows and block_rows of a denoise_temporal() picture continues that picture's history.  Needs no scene and no accumulation
+        in this context; download_denoised() and download_temporal() then return the num_rows x W results in image order.  params,
+        tparams, fetch and timed as in denoise_temporal()."""
+        frame = _capi.shard_frame(W, H, world, rows_max, n, m, camera, hdr_ptr, sq_ptr, feat_ptr, ids_ptr, block_rows=block_rows, first_row=first_row,
+                                  num_rows=num_rows)
+        ms = C.c_double(0.0)
+        check(self._L.rt_denoise_shards_temporal(self._h, C.byref(frame), C.byref(params) if params is not None else None,
+                                                 C.byref(tparams) if tparams is not None else None, int(fetch), C.byref(ms) if timed else None))
+        self.denoised_W, self.denoised_rows = W, frame.parts.rs.num_rows
+        self.temporal_W, self.temporal_rows = W, frame.parts.rs.num_rows
+        return ms.value if timed else None
+
     def temporal_reset(self):
         """rt_temporal_reset: drop the history; the next denoise_temporal() starts from an empty one."""
         check(self._L.rt_temporal_reset(self._h))

@@ -425,6 +425,33 @@ int rt_temporal_default_params_fetch(uint32_t fetch, rt_temporal_params* out);
 /* rt_denoise_temporal with the fetch chosen: its preconditions, refusals, snapshot and history lifetime, every refusal before the first
  * change.  tparams == NULL: that fetch's defaults.  fetch neither 1 nor 4: RT_ERR_INVALID_ARG.  Fetch 1 gives rt_denoise_temporal's bits. */
 int rt_denoise_temporal_fetch(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms);
+/* Temporal accumulation for a picture that was rendered in row shards and gathered onto this context's device (rt_denoise_shards
+ * above): the gathered parts, the shards' feature ids in the same layout, and what the reprojection needs of the picture they are rows
+ * of -- the image's height and the camera the shards were rendered with (every shard renders with the same one). */
+typedef struct rt_shard_frame {
+    rt_shard_parts parts;   /* as rt_denoise_shards reads it */
+    const void* ids;        /* device: [nshards][rows_max * W] uint32, the shards' feature ids, padded like the other parts */
+    uint32_t H;             /* height of the whole image; parts.rs.first_row + parts.rs.num_rows <= H */
+    rt_camera camera;       /* the camera the shards were rendered with */
+} rt_shard_frame;
+/* rt_denoise_temporal_fetch over the parts: den, den_var, the LDR, the new history (state, guides, ids, len) and target have the bits
+ * rt_denoise_temporal_fetch gives in one context that rendered rows [first_row, first_row + num_rows) of the W x H image contiguously
+ * with that camera; target counts in image order, (yi - first_row)*W + xi.  The prepare pass reads the current frame through the row
+ * mapping (rt_rowset_locate) and reads and writes the history in image order; the padding rows are never read, and no assembled copy
+ * of the inputs is made.  Like rt_denoise_shards the call needs no scene and no accumulation in ctx and reads and changes nothing of
+ * the context's render, noise or feature state.
+ * The history is the context's one history, with rt_denoise_temporal's lifetime (it survives rt_scene_upload; rt_temporal_reset and
+ * rt_destroy drop it); rt_download_temporal, rt_download_denoised, rt_copy_denoised_to_device and rt_unit_denoise_forms serve the call
+ * as they serve rt_denoise_temporal_fetch.  Its picture is W, H and parts.rs with shard = 0, compared field by field with the
+ * history's: a call with nshards = 1 whose W, H, first_row, num_rows and block_rows are a contiguous call's continues that call's
+ * history, and the reverse (the whole image is {0, H, H, 0, 1}); any other difference -- another sharding of the same rows too --
+ * starts from an empty history, on which the result has rt_denoise_shards' bits.  The fetches may alternate.
+ * Refused with RT_ERR_INVALID_ARG: everything rt_denoise_shards refuses so; ids null or not 4-byte aligned; H < first_row + num_rows;
+ * W or H above 2^24; fetch neither 1 nor 4; tparams outside their domain (NULL: that fetch's defaults); a camera whose origin, x, y,
+ * origin_image_plane (three components each), aperture or focal_length is not finite.  n < 2 or m == 0: RT_ERR_SEQUENCE.  Every refusal
+ * comes before the first change: a refused call keeps history and snapshot. */
+int rt_denoise_shards_temporal(rt_ctx* ctx, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams,
+                               uint32_t fetch, double* out_ms);
 
 /* Replaces the transform(par) tonemap (spheres-app.cpp:186-214): hdr / n_samples,
  * ACES fit, gamma 1/2.2, XMStoreColor.  n_samples == 0 uses the accumulated count. */
@@ -577,7 +604,17 @@ int rt_unit_temporal_host_fetch(const float* hdr, const float* sq, uint32_t n, c
                                 const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
                                 const rt_temporal_params* tparams, uint32_t fetch, float* out_rgb, float* out_var, float* out_state4, float* out_guides8,
                                 uint32_t* out_len, uint32_t* out_target);
-/* Which form each level of the last rt_denoise, rt_denoise_shards or rt_denoise_temporal took: out[l] = 0 the level did not run, 1 its taps were read from
+/* The twin of rt_denoise_shards_temporal, from the same sources compiled for the host (csrc/rt_rowset_map.h, csrc/rt_temporal.h,
+ * csrc/rt_denoise.h).  hdr, sq, feat8, ids: host memory in the layout of rt_shard_frame; of *shape the pointers are ignored, everything
+ * else -- the camera too -- is read as rt_denoise_shards_temporal reads it.  The history's strips and every output are as
+ * rt_unit_temporal_host_fetch's, in image order, W x rs.num_rows pixels (the new history's ids are the parts' ids in image order, its
+ * camera shape->camera).  The padding rows are never read.  Refusals as rt_denoise_shards_temporal's and rt_unit_temporal_host_fetch's.
+ * Needs no context and no GPU. */
+int rt_unit_temporal_shards_host(const float* hdr, const float* sq, const float* feat8, const uint32_t* ids, const rt_shard_frame* shape,
+                                 const rt_camera* hist_camera, const float* hist_state4, const float* hist_guides8, const uint32_t* hist_ids,
+                                 const uint32_t* hist_len, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
+                                 float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len, uint32_t* out_target);
+/* Which form each level of the last rt_denoise, rt_denoise_shards, rt_denoise_temporal or rt_denoise_shards_temporal took: out[l] = 0 the level did not run, 1 its taps were read from
  * global memory, 2 from a tile staged in LDS. */
 int rt_unit_denoise_forms(rt_ctx* ctx, uint32_t out[5]);
 /* The shadow index rt_scene_upload would build for light `light` of the list, under the environment of the moment.
