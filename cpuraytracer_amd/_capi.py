@@ -51,6 +51,11 @@ class RtTemporalParams(C.Structure):
                 ("coverage_tol", C.c_float)]
 
 
+class RtVarianceParams(C.Structure):
+    """rt_variance_params: where the filter's v0 comes from (source 0 the second moments, 1 the spatial estimate) and the window's radius."""
+    _fields_ = [("source", C.c_uint32), ("radius", C.c_uint32)]
+
+
 class RtShardParts(C.Structure):
     """rt_shard_parts: the gathered parts of a row-sharded picture (device pointers) and their shape."""
     _fields_ = [("hdr", C.c_void_p), ("sq", C.c_void_p), ("feat", C.c_void_p), ("W", C.c_uint32), ("rows_max", C.c_uint32),
@@ -71,6 +76,7 @@ RT_ERR_NO_DEVICE = 1
 RT_ERR_SEQUENCE = 6
 RT_SAMPLER_COSINE_HEMISPHERE, RT_SAMPLER_SQRT_DISK = 1, 2
 RT_TEMPORAL_FETCH_NEAREST, RT_TEMPORAL_FETCH_BILINEAR = 1, 4
+RT_VARIANCE_MOMENTS, RT_VARIANCE_SPATIAL = 0, 1
 
 # every symbol include/rt_api.h declares
 EXPORTS = [
@@ -91,6 +97,7 @@ EXPORTS = [
     "rt_temporal_default_params", "rt_denoise_temporal", "rt_temporal_reset", "rt_download_temporal", "rt_unit_temporal_host",
     "rt_temporal_default_params_fetch", "rt_denoise_temporal_fetch", "rt_unit_temporal_host_fetch",
     "rt_denoise_shards_temporal", "rt_unit_temporal_shards_host",
+    "rt_variance_default_params", "rt_denoise_variance", "rt_denoise_temporal_variance", "rt_unit_denoise_variance_host", "rt_unit_temporal_variance_host",
 ]
 
 _lib = None
@@ -238,6 +245,17 @@ def load():
         L.rt_unit_temporal_shards_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtShardFrame), C.POINTER(RtCamera), C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "rt_denoise_variance"):
+        L.rt_variance_default_params.argtypes = [C.POINTER(RtVarianceParams)]
+        L.rt_denoise_variance.argtypes = [C.c_void_p, C.POINTER(RtDenoiseParams), C.POINTER(RtVarianceParams), C.POINTER(C.c_double)]
+        L.rt_denoise_temporal_variance.argtypes = [C.c_void_p, C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32,
+                                                   C.POINTER(RtVarianceParams), C.POINTER(C.c_double)]
+        L.rt_unit_denoise_variance_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.POINTER(RtDenoiseParams), C.POINTER(RtVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_unit_temporal_variance_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtCamera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32, C.POINTER(RtVarianceParams),
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -280,16 +298,41 @@ def temporal_params_fetch(fetch, **fields):
     return p
 
 
-def unit_temporal_host(hdr, sq, n, feat8, m, ids, W, H, camera, history=None, params=None, tparams=None, first_row=0, fetch=1):
+def variance_params(**fields):
+    """rt_variance_default_params with the given fields replaced (source: RT_VARIANCE_MOMENTS 0 or RT_VARIANCE_SPATIAL 1; radius 1..3)."""
+    p = RtVarianceParams()
+    check(load().rt_variance_default_params(C.byref(p)))
+    for k, v in fields.items():
+        if k not in dict(RtVarianceParams._fields_):
+            raise TypeError("rt_variance_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def unit_denoise_variance_host(hdr, sq, n, feat8, m, params=None, variance=None):
+    """rt_unit_denoise_variance_host over numpy strips (hdr [rows, W, 3]; sq the same or None, which only the spatial source accepts;
+    feat8 [rows, W, 8]).  Returns rgb, var (den and den_var) and state, the prepared (c0, v0) [rows, W, 4]."""
+    hdr = np.ascontiguousarray(hdr, dtype=np.float32)
+    feat8 = np.ascontiguousarray(feat8, dtype=np.float32)
+    sq = None if sq is None else np.ascontiguousarray(sq, dtype=np.float32)
+    rows, W = hdr.shape[:2]
+    out = {"rgb": np.full((rows, W, 3), -1.0, np.float32), "var": np.full((rows, W), -1.0, np.float32), "state": np.full((rows, W, 4), -1.0, np.float32)}
+    check(load().rt_unit_denoise_variance_host(hdr.ctypes.data, sq.ctypes.data if sq is not None else None, n, feat8.ctypes.data, m, W, rows,
+                                               C.byref(params) if params is not None else None, C.byref(variance) if variance is not None else None,
+                                               out["rgb"].ctypes.data, out["var"].ctypes.data, out["state"].ctypes.data))
+    return out
+
+
+def unit_temporal_host(hdr, sq, n, feat8, m, ids, W, H, camera, history=None, params=None, tparams=None, first_row=0, fetch=1, variance=None):
     """rt_unit_temporal_host_fetch (fetch 1, nearest: rt_unit_temporal_host's bits; 4: bilinear; tparams None: that fetch's defaults) over numpy strips of rows [first_row, first_row + rows) of the W x H image.  history: None (empty) or a dict
     with camera, state (rows, W, 4), guides (rows, W, 8), ids and len (rows, W).  Returns a dict: rgb, var (den and den_var), target,
     and state, guides, len, ids, camera -- the last five are the next call's history."""
     hdr = np.ascontiguousarray(hdr, dtype=np.float32)
-    sq = np.ascontiguousarray(sq, dtype=np.float32)
+    sq = None if sq is None else np.ascontiguousarray(sq, dtype=np.float32)
     feat8 = np.ascontiguousarray(feat8, dtype=np.float32)
     ids = np.ascontiguousarray(ids, dtype=np.uint32)
     rows = hdr.size // (3 * W)
-    assert hdr.size == rows * W * 3 and sq.size == hdr.size and feat8.size == rows * W * 8 and ids.size == rows * W
+    assert hdr.size == rows * W * 3 and (sq is None or sq.size == hdr.size) and feat8.size == rows * W * 8 and ids.size == rows * W
     out = {"rgb": np.zeros((rows, W, 3), np.float32), "var": np.zeros((rows, W), np.float32), "state": np.zeros((rows, W, 4), np.float32),
            "guides": np.zeros((rows, W, 8), np.float32), "len": np.zeros((rows, W), np.uint32), "target": np.zeros((rows, W), np.uint32)}
     cam = RtCamera.from_buffer_copy(bytes(camera))
@@ -301,10 +344,14 @@ def unit_temporal_host(hdr, sq, n, feat8, m, ids, W, H, camera, history=None, pa
                 np.ascontiguousarray(history["ids"], dtype=np.uint32), np.ascontiguousarray(history["len"], dtype=np.uint32)]
         assert keep[0].size == rows * W * 4 and keep[1].size == rows * W * 8 and keep[2].size == rows * W and keep[3].size == rows * W
         hs, hg, hi, hl = (a.ctypes.data for a in keep)
-    check(load().rt_unit_temporal_host_fetch(hdr.ctypes.data, sq.ctypes.data, n, feat8.ctypes.data, m, ids.ctypes.data, W, H, first_row, rows, C.byref(cam),
-                                             hc, hs, hg, hi, hl, C.byref(params) if params is not None else None,
-                                             C.byref(tparams) if tparams is not None else None, int(fetch), out["rgb"].ctypes.data, out["var"].ctypes.data,
-                                             out["state"].ctypes.data, out["guides"].ctypes.data, out["len"].ctypes.data, out["target"].ctypes.data))
+    tail = (out["rgb"].ctypes.data, out["var"].ctypes.data, out["state"].ctypes.data, out["guides"].ctypes.data, out["len"].ctypes.data,
+            out["target"].ctypes.data)
+    head = (hdr.ctypes.data, sq.ctypes.data if sq is not None else None, n, feat8.ctypes.data, m, ids.ctypes.data, W, H, first_row, rows, C.byref(cam),
+            hc, hs, hg, hi, hl, C.byref(params) if params is not None else None, C.byref(tparams) if tparams is not None else None, int(fetch))
+    if variance is None:
+        check(load().rt_unit_temporal_host_fetch(*head, *tail))
+    else:  # (rt_unit_temporal_variance_host: sq None is accepted under the spatial source only)
+        check(load().rt_unit_temporal_variance_host(*head, C.byref(variance), *tail))
     out["ids"] = ids.reshape(rows, W).copy()
     out["camera"] = cam
     return out

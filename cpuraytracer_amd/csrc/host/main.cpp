@@ -20,6 +20,10 @@ static void Usage() {
               "                                PREFIX.normal.pfm (three channels), PREFIX.depth.pfm and PREFIX.coverage.pfm (one channel)\n"
               "               [--denoise-out file.ppm [--denoise-levels N]]   the picture after the feature-guided a-trous filter (rt_denoise, N = 1..5\n"
               "                                levels, default 3), written beside --out, which is unchanged; needs --spp >= 2\n"
+              "               [--denoise-variance moments|spatial [--denoise-radius R]]   with --denoise-out: where the filter's variance comes from\n"
+              "                                (rt_denoise_variance).  moments (default): the second moments, --spp >= 2.  spatial: the picture's own\n"
+              "                                (2R+1)^2 neighbourhoods (R = 1..3, default 1), so --spp 1 is enough -- with --orbit-frames too -- and the\n"
+              "                                noise estimate is not switched on for the filter's sake\n"
               "               [--orbit-frames K [--orbit-deg D] [--orbit-fetch nearest|bilinear]]   with --denoise-out: K pictures of --spp samples each (seed --seed + f) from a camera\n"
               "                                that turns D degrees (default 0.5) per picture about the scene's look-at point, each followed by the\n"
               "                                feature pass and rt_denoise_temporal; the last picture is written.  --orbit-fetch bilinear\n"
@@ -39,6 +43,9 @@ int main(int argc, char** argv) {
     double orbitDeg = 0.5;
     bool orbitSet = false;
     uint32_t orbitFetch = RT_TEMPORAL_FETCH_NEAREST;
+    rt_variance_params variance;
+    rt_variance_default_params(&variance);
+    bool varianceSet = false;
     float targetError = 0.f;
     double targetFraction = 0.0;
     uint32_t maxSpp = 0;
@@ -70,6 +77,13 @@ int main(int argc, char** argv) {
         else if (k == "--features-out") featuresOut = val();
         else if (k == "--denoise-out") denoiseOut = val();
         else if (k == "--denoise-levels") denoiseLevels = (uint32_t)std::atoi(val());
+        else if (k == "--denoise-variance") {
+            const std::string v = val();
+            if (v != "moments" && v != "spatial") { Usage(); return 2; }
+            variance.source = v == "spatial" ? RT_VARIANCE_SPATIAL : RT_VARIANCE_MOMENTS;
+            varianceSet = true;
+        }
+        else if (k == "--denoise-radius") { variance.radius = (uint32_t)std::atoi(val()); varianceSet = true; }
         else if (k == "--orbit-frames") { orbitFrames = (uint32_t)std::atoi(val()); orbitSet = true; }
         else if (k == "--orbit-deg") { orbitDeg = std::atof(val()); orbitSet = true; }
         else if (k == "--orbit-fetch") {
@@ -100,12 +114,18 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "spheres: --orbit-frames, --orbit-deg and --orbit-fetch need --denoise-out and are not available with --gpus or --target-error\n");
         return 2;
     }
-    if (orbitSet && (orbitFrames == 0 || spp < 2 || !(orbitDeg == orbitDeg))) { Usage(); return 2; }
+    if (varianceSet && denoiseOut.empty()) {
+        std::fprintf(stderr, "spheres: --denoise-variance and --denoise-radius need --denoise-out\n");
+        return 2;
+    }
+    const bool spatial = variance.source == RT_VARIANCE_SPATIAL;
+    if (spatial && (variance.radius < 1 || variance.radius > 3)) { Usage(); return 2; }
+    if (orbitSet && (orbitFrames == 0 || spp < (spatial ? 1u : 2u) || !(orbitDeg == orbitDeg))) { Usage(); return 2; }
     if (!denoiseOut.empty() && gpus > 0) {
         std::fprintf(stderr, "spheres: --denoise-out is not available with --gpus: the multi-GPU gather carries neither second moments nor feature strips\n");
         return 2;
     }
-    st.noiseEstimate = targetSet || !noiseOut.empty() || !denoiseOut.empty();
+    st.noiseEstimate = targetSet || !noiseOut.empty() || (!denoiseOut.empty() && !spatial);  // (the spatial source reads no second moments)
     if (st.noiseEstimate && gpus > 0) {
         std::fprintf(stderr, "spheres: --noise-out and --target-error are not available with --gpus: the multi-GPU gather carries no second moments\n");
         return 2;
@@ -146,7 +166,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "spheres: %s\n", e.what());
         return 1;
     }
-    const int rc = orbitSet ? app.RunOrbit(orbitFrames, orbitDeg, spp, denoiseLevels, orbitFetch)
+    const int rc = orbitSet ? app.RunOrbit(orbitFrames, orbitDeg, spp, denoiseLevels, orbitFetch, varianceSet ? &variance : nullptr)
                             : (targetSet ? app.RunUntil(targetError, targetFraction, maxSpp) : app.Run(spp / st.samplesPerFrame));
     if (rc != 0) return rc;
     if (!noiseOut.empty() && !app.WriteNoisePFM(noiseOut)) {
@@ -162,7 +182,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "spheres: cannot write the denoised picture %s: %s\n", denoiseOut.c_str(), rt_last_error());
             return 1;
         }
-    } else if (!denoiseOut.empty() && !app.WriteDenoisedPPM(denoiseOut, denoiseLevels)) {
+    } else if (!denoiseOut.empty() && !app.WriteDenoisedPPM(denoiseOut, denoiseLevels, varianceSet ? &variance : nullptr)) {
         std::fprintf(stderr, "spheres: cannot write the denoised picture %s: %s\n", denoiseOut.c_str(), rt_last_error());
         return 1;
     }

@@ -53,7 +53,47 @@ static void RunLevels(std::vector<rtd::DenoiseState>& a, std::vector<rtd::Denois
     }
 }
 
+static_assert(sizeof(rt_variance_params) == sizeof(rtd::VarianceParams) && offsetof(rt_variance_params, radius) == offsetof(rtd::VarianceParams, radius),
+              "rt_variance_params is laid out like rtd::VarianceParams");
+static_assert(RT_VARIANCE_MOMENTS == rtd::kVarianceMoments && RT_VARIANCE_SPATIAL == rtd::kVarianceSpatial, "the sources of rt_api.h are those of rt_denoise.h");
+
 namespace rtdn {
+
+int CheckVarianceParams(const char* who_, const rt_variance_params* vparams, rtd::VarianceParams* V) {
+    *V = vparams ? rtd::VarianceParams{vparams->source, vparams->radius} : rtd::VarianceParams{rtd::kVarianceMoments, rtd::kVarianceMaxRadius};
+    if (!rtd::variance_params_ok(*V))
+        return Fail(RT_ERR_INVALID_ARG, std::string(who_) + ": source must be RT_VARIANCE_MOMENTS (0) or RT_VARIANCE_SPATIAL (1), and under it radius 1..3");
+    return RT_OK;
+}
+
+// The spatial prepare pass as rt_denoise_prepare_spatial_kernel runs it: c0 and g of every pixel first, then the window's taps.
+void PrepareSpatialHost(const float* hdr, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows, const rtd::DenoiseParams& P, uint32_t radius,
+                        std::vector<rtd::DenoiseState>& a, std::vector<float>& g) {
+    const size_t npix = (size_t)W * rows;
+    for (size_t p = 0; p < npix; ++p) {
+        rtd::denoise_prepare_mean(hdr + 3 * p, n, feat8 + 8 * p, m, a[p].c, &g[8 * p]);
+        a[p].v = 0.0f;
+    }
+    const int64_t R = (int64_t)radius;
+    for (int64_t y = 0; y < (int64_t)rows; ++y) {
+        for (int64_t x = 0; x < (int64_t)W; ++x) {
+            const size_t p = (size_t)y * W + (size_t)x;
+            rtd::SpatialSums S;
+            rtd::spatial_begin(S);
+            for (int64_t ta = 0; ta <= 2 * R; ++ta) {
+                const int64_t qy = y + ta - R;
+                if (qy < 0 || qy >= (int64_t)rows) continue;
+                for (int64_t tb = 0; tb <= 2 * R; ++tb) {
+                    const int64_t qx = x + tb - R;
+                    if (qx < 0 || qx >= (int64_t)W) continue;
+                    const size_t q = (size_t)qy * W + (size_t)qx;
+                    rtd::spatial_tap(P, &g[8 * p], a[q].c, &g[8 * q], S);
+                }
+            }
+            a[p].v = rtd::spatial_finish(S);
+        }
+    }
+}
 
 void RunLevelsHost(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseState>& b, const std::vector<float>& g, uint32_t W, uint32_t rows,
                    const rtd::DenoiseParams& P, float* out_rgb, float* out_var) {
@@ -116,6 +156,48 @@ int rt_unit_denoise_host(const float* hdr, const float* sq, uint32_t n, const fl
     std::vector<rtd::DenoiseState> a(npix), b(npix);
     std::vector<float> g(npix * 8);
     for (size_t p = 0; p < npix; ++p) rtd::denoise_prepare(hdr + 3 * p, sq + 3 * p, n, feat8 + 8 * p, m, a[p], &g[8 * p]);
+    RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
+    return RT_OK;
+}
+
+int rt_variance_default_params(rt_variance_params* out) {
+    if (!out) return Fail(RT_ERR_INVALID_ARG, "rt_variance_default_params: null argument");
+    out->source = RT_VARIANCE_MOMENTS;
+    out->radius = 1;  // (docs/EXPERIMENTS.md, the spatial-variance grid: the 3 x 3 window beat the wider ones on both measures, and costs least)
+    return RT_OK;
+}
+
+// rt_unit_denoise_host with the variance source chosen; the moments source IS that entry.
+int rt_unit_denoise_variance_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
+                                  const rt_denoise_params* params, const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4) {
+    const char* who = "rt_unit_denoise_variance_host";
+    rtd::VarianceParams V{};
+    int rc = rtdn::CheckVarianceParams(who, vparams, &V);
+    if (rc != RT_OK) return rc;
+    const bool spatial = V.source == rtd::kVarianceSpatial;
+    if (!hdr || (!sq && !spatial) || !feat8 || !out_rgb || !out_var) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+    if (W == 0 || rows == 0 || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": empty or too large strip");
+    rt_denoise_params def;
+    rt_denoise_default_params(&def);
+    if (!params) params = &def;
+    rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
+    if (!rtd::denoise_params_ok(P))
+        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    if (spatial ? n == 0 : n < 2)
+        return Fail(RT_ERR_SEQUENCE, std::string(who) + (spatial ? ": the strips hold no sample" : ": the noise estimate needs at least 2 samples per pixel"));
+    if (m == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the feature strips hold no sample");
+    const size_t npix = (size_t)W * rows;
+    std::vector<rtd::DenoiseState> a(npix), b(npix);
+    std::vector<float> g(npix * 8);
+    if (spatial)
+        rtdn::PrepareSpatialHost(hdr, n, feat8, m, W, rows, P, V.radius, a, g);
+    else
+        for (size_t p = 0; p < npix; ++p) rtd::denoise_prepare(hdr + 3 * p, sq + 3 * p, n, feat8 + 8 * p, m, a[p], &g[8 * p]);
+    if (out_state4)
+        for (size_t p = 0; p < npix; ++p) {
+            for (int k = 0; k < 3; ++k) out_state4[4 * p + k] = a[p].c[k];
+            out_state4[4 * p + 3] = a[p].v;
+        }
     RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
     return RT_OK;
 }

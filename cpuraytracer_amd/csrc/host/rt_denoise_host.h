@@ -11,6 +11,7 @@
 
 struct rt_camera;
 struct rt_temporal_params;
+struct rt_variance_params;
 
 namespace rtdn {
 
@@ -18,6 +19,15 @@ namespace rtdn {
 // picture; the last level's state goes out as out_rgb (3 floats per pixel) and out_var.
 void RunLevelsHost(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseState>& b, const std::vector<float>& g, uint32_t W, uint32_t rows,
                    const rtd::DenoiseParams& P, float* out_rgb, float* out_var);
+
+// vparams (NULL: the moments source) into V; an unknown source, or a radius outside 1..3 under the spatial one: RT_ERR_INVALID_ARG with a
+// message that starts with who.
+int CheckVarianceParams(const char* who, const rt_variance_params* vparams, rtd::VarianceParams* V);
+
+// The spatial prepare pass (../rt_denoise.h "the spatial variance source") over a W x rows strip: a[p] = (c0, v0), g = the guides (8 floats
+// per pixel); a and g are sized by the caller.
+void PrepareSpatialHost(const float* hdr, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows, const rtd::DenoiseParams& P, uint32_t radius,
+                        std::vector<rtd::DenoiseState>& a, std::vector<float>& g);
 
 // tparams (NULL: the defaults) into T; outside their domain: RT_ERR_INVALID_ARG with a message that starts with who.
 int CheckTemporalParams(const char* who, const rt_temporal_params* tparams, rtd::TemporalParams* T);

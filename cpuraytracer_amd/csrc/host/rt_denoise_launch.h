@@ -73,6 +73,18 @@ struct Temporal {
 int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
                           uint32_t forms[rtd::kDenoiseMaxLevels]);
 
+// The spatial variance source (rt_denoise_variance, rt_denoise_temporal_variance under RT_VARIANCE_SPATIAL; ../rt_denoise.h): the
+// prepare pass is rt_denoise_prepare_spatial_kernel, which takes v0 from the (2 radius + 1)^2 window around the pixel; Strips::sq is not
+// read and may be NULL.  radius: 1..3.  committed: NULL, or a device word that holds the strip's sample count where only the device
+// knows it (frames in flight: rt_resolve's rule, 0 reads as 1); Strips::n is then not read.  LDS of the pass at a radius:
+inline uint32_t SpatialLdsBytes(uint32_t radius) { return (kTileW + 2u * radius) * (kTileH + 2u * radius) * 3u * 16u; }
+int LaunchDenoiseSpatial(void* stream, const Strips& s, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed, int stageKnob,
+                         uint32_t forms[rtd::kDenoiseMaxLevels]);
+// LaunchDenoiseTemporal with that source: the spatial pass writes Strips::state[0] and Strips::guide (which the temporal form leaves
+// idle, so they must be reserved here), then the chosen temporal pass reads its pixel's state and guides from them.
+int LaunchDenoiseTemporalSpatial(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed,
+                                 int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]);
+
 // The temporal form over the parts (rt_denoise_shards_temporal): hdr, sq and feat of Strips and Temporal::ids are the gathered parts
 // (ids: [nshards] parts of rowsMax x W words), W x rows is the IMAGE's row range and t.geom.num_rows == rows.  The prepare pass reads
 // the current frame through the mapping; the history sets, target and everything the levels touch are in image order.

@@ -105,13 +105,17 @@ int rt_temporal_default_params_fetch(uint32_t fetch, rt_temporal_params* out) {
 static void TemporalRun(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, const rtd::TemporalGeom& G,
                         const rtdn::ShardLayout* parts, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4, const float* hist_guides8,
                         const uint32_t* hist_ids, const uint32_t* hist_len, const rtd::DenoiseParams& P, const rtd::TemporalParams& T, uint32_t fetch,
-                        float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len, uint32_t* out_target) {
+                        float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len, uint32_t* out_target,
+                        const rtd::VarianceParams V = rtd::VarianceParams{rtd::kVarianceMoments, 0}) {
     const uint32_t W = G.W, first_row = G.first_row, num_rows = G.num_rows;
     const size_t npix = (size_t)W * num_rows;
     const rtd::TemporalCam C = rtdn::CamOf(*camera);
     const rtd::TemporalCam Cp = hist_len ? rtdn::CamOf(*hist_camera) : C;
     std::vector<rtd::DenoiseState> a(npix), b(npix);
     std::vector<float> g(npix * 8);
+    // (the spatial source, contiguous strips only: the whole strip's (c0, v0) and g first, as the device's extra pass leaves them)
+    const bool spatial = V.source == rtd::kVarianceSpatial;
+    if (spatial) rtdn::PrepareSpatialHost(hdr, n, feat8, m, W, num_rows, P, V.radius, a, g);
     for (uint32_t ly = 0; ly < num_rows; ++ly) {
         size_t row = (size_t)ly * W;  // where the row's current-frame pixels start
         if (parts) {
@@ -123,7 +127,10 @@ static void TemporalRun(const float* hdr, const float* sq, uint32_t n, const flo
             const size_t p = (size_t)ly * W + x, src = row + x;
             rtd::DenoiseState s;
             float* gp = &g[8 * p];
-            rtd::denoise_prepare(hdr + 3 * src, sq + 3 * src, n, feat8 + 8 * src, m, s, gp);
+            if (spatial)
+                s = a[p];
+            else
+                rtd::denoise_prepare(hdr + 3 * src, sq + 3 * src, n, feat8 + 8 * src, m, s, gp);
             const uint32_t id = ids[src];
             uint32_t len = 1u, target = rtd::kTemporalNoTarget;
             uint32_t xi = 0, yi = 0;
@@ -186,8 +193,11 @@ static int TemporalHost(const char* who, const float* hdr, const float* sq, uint
                         uint32_t H, uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
                         const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
                         const rt_temporal_params* tparams, uint32_t fetch, float* out_rgb, float* out_var, float* out_state4, float* out_guides8,
-                        uint32_t* out_len, uint32_t* out_target) {
-    if (!hdr || !sq || !feat8 || !ids || !camera) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+                        uint32_t* out_len, uint32_t* out_target, const rt_variance_params* vparams = nullptr) {
+    rtd::VarianceParams V{};
+    if (const int rcv = rtdn::CheckVarianceParams(who, vparams, &V)) return rcv;
+    const bool spatial = V.source == rtd::kVarianceSpatial;
+    if (!hdr || (!sq && !spatial) || !feat8 || !ids || !camera) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null buffer");
     if (hist_len && (!hist_camera || !hist_state4 || !hist_guides8 || !hist_ids))
         return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a history (hist_len != NULL) needs its camera, state, guides and ids");
     const rtd::TemporalGeom G{W, H, first_row, num_rows};
@@ -202,10 +212,11 @@ static int TemporalHost(const char* who, const float* hdr, const float* sq, uint
     rtd::TemporalParams T{};
     const int rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &T);
     if (rc != RT_OK) return rc;
-    if (n < 2) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the noise estimate needs at least 2 samples per pixel");
+    if (spatial && n == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the strips hold no sample");
+    if (!spatial && n < 2) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the noise estimate needs at least 2 samples per pixel");
     if (m == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the feature strips hold no sample");
     TemporalRun(hdr, sq, n, feat8, m, ids, G, nullptr, camera, hist_camera, hist_state4, hist_guides8, hist_ids, hist_len, P, T, fetch, out_rgb, out_var,
-                out_state4, out_guides8, out_len, out_target);
+                out_state4, out_guides8, out_len, out_target, V);
     return RT_OK;
 }
 
@@ -227,6 +238,16 @@ int rt_unit_temporal_host_fetch(const float* hdr, const float* sq, uint32_t n, c
                                 uint32_t* out_len, uint32_t* out_target) {
     return TemporalHost("rt_unit_temporal_host_fetch", hdr, sq, n, feat8, m, ids, W, H, first_row, num_rows, camera, hist_camera, hist_state4, hist_guides8,
                         hist_ids, hist_len, params, tparams, fetch, out_rgb, out_var, out_state4, out_guides8, out_len, out_target);
+}
+
+// rt_unit_temporal_host_fetch with the variance source chosen (the twin of rt_denoise_temporal_variance); sq may be NULL under the spatial one.
+int rt_unit_temporal_variance_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W, uint32_t H,
+                                   uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
+                                   const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
+                                   const rt_temporal_params* tparams, uint32_t fetch, const rt_variance_params* vparams, float* out_rgb, float* out_var,
+                                   float* out_state4, float* out_guides8, uint32_t* out_len, uint32_t* out_target) {
+    return TemporalHost("rt_unit_temporal_variance_host", hdr, sq, n, feat8, m, ids, W, H, first_row, num_rows, camera, hist_camera, hist_state4, hist_guides8,
+                        hist_ids, hist_len, params, tparams, fetch, out_rgb, out_var, out_state4, out_guides8, out_len, out_target, vparams);
 }
 
 // The sharded form: the same step, the current frame read through the mapping (TemporalRun).

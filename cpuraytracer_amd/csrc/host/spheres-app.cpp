@@ -248,7 +248,7 @@ bool SpheresApp::WriteFeaturePFMs(const std::string& prefix) const {
     return true;
 }
 
-bool SpheresApp::WriteDenoisedPPM(const std::string& path, uint32_t levels) const {
+bool SpheresApp::WriteDenoisedPPM(const std::string& path, uint32_t levels, const rt_variance_params* variance) const {
     const uint32_t W = (uint32_t)GetBackBufferWidth(), H = (uint32_t)GetBackBufferHeight();
     const uint32_t rows = m_lastStats.local_rows;
     if (m_sampleCount == 0) return false;
@@ -257,7 +257,7 @@ bool SpheresApp::WriteDenoisedPPM(const std::string& path, uint32_t levels) cons
     rt_denoise_params params;
     if (rt_denoise_default_params(&params) != RT_OK) return false;
     if (levels != 0) params.levels = levels;
-    if (rt_denoise(m_device, &params, nullptr) != RT_OK) return false;
+    if ((variance ? rt_denoise_variance(m_device, &params, variance, nullptr) : rt_denoise(m_device, &params, nullptr)) != RT_OK) return false;
     std::vector<uint8_t> rgb((size_t)W * rows * 3);
     if (rt_download_denoised(m_device, nullptr, nullptr, rgb.data()) != RT_OK) return false;
     FILE* f = std::fopen(path.c_str(), "wb");
@@ -284,8 +284,9 @@ rt_camera OrbitCamera(const rt_camera& camera, double degrees, const float pivot
     return out;
 }
 
-int SpheresApp::RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels, uint32_t fetch) noexcept {
+int SpheresApp::RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels, uint32_t fetch, const rt_variance_params* variance) noexcept {
     try {
+        const bool spatial = variance && variance->source == RT_VARIANCE_SPATIAL;
         const uint32_t W = (uint32_t)GetBackBufferWidth(), H = (uint32_t)GetBackBufferHeight();
         const rt_rowset rs = m_hasRowset ? m_rowset : rt_rowset{0, H, H, 0, 1};
         std::vector<rt_sphere> spheres;
@@ -304,7 +305,7 @@ int SpheresApp::RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint
             RT_CALL(rt_scene_upload(m_device, spheres.data(), materials.data(), (uint32_t)spheres.size(), &turned, lights.data(), (uint32_t)lights.size(), &sky,
                                     exposureAdjustment));
             RT_CALL(rt_set_sampler(m_device, AppSettings.samplerFlags));
-            RT_CALL(rt_set_noise_estimate(m_device, 1));
+            RT_CALL(rt_set_noise_estimate(m_device, spatial ? (AppSettings.noiseEstimate ? 1 : 0) : 1));
             RT_CALL(rt_set_frame_pipelining(m_device, 0));
             RT_CALL(rt_set_frame_batch(m_device, 1u));
             m_uploaded = true;
@@ -313,7 +314,9 @@ int SpheresApp::RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint
             RT_CALL(rt_resolve(m_device, spp));
             m_lastStats.ms_resolve = rt_last_resolve_ms(m_device);
             RT_CALL(rt_render_features(m_device, W, H, rs, 1u, 1u + spp, nullptr));
-            if (fetch == RT_TEMPORAL_FETCH_NEAREST)
+            if (variance)
+                RT_CALL(rt_denoise_temporal_variance(m_device, &params, nullptr, fetch, variance, nullptr));
+            else if (fetch == RT_TEMPORAL_FETCH_NEAREST)
                 RT_CALL(rt_denoise_temporal(m_device, &params, nullptr, nullptr));
             else
                 RT_CALL(rt_denoise_temporal_fetch(m_device, &params, nullptr, fetch, nullptr));

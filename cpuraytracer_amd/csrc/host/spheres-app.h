@@ -73,7 +73,8 @@ public:
     bool WriteFeaturePFMs(const std::string& prefix) const;
     // Runs the feature pass over the samples rendered so far, then rt_denoise (the defaults; levels != 0 replaces the number of levels),
     // and writes the filtered picture's tonemap as a PPM like WritePPM's.  Needs AppSettings.noiseEstimate and at least 2 samples.
-    bool WriteDenoisedPPM(const std::string& path, uint32_t levels) const;
+    // variance != NULL: rt_denoise_variance with that source; the spatial one needs neither the noise estimate nor a second sample.
+    bool WriteDenoisedPPM(const std::string& path, uint32_t levels, const rt_variance_params* variance = nullptr) const;
     // Frames of samplesPerFrame samples until at most `fraction` of the pixels have a relative error above relError, or the next
     // frame would pass maxSpp (every frame waits for its summary, so every frame is resolved).  SampleCount() is the spp reached.
     int RunUntil(float relError, double fraction, uint32_t maxSpp) noexcept;
@@ -82,7 +83,9 @@ public:
     // pass and rt_denoise_temporal (the defaults; levels != 0 replaces the number of levels), so the history follows the camera.
     // WritePPM then writes the last frame, WriteTemporalPPM its temporally accumulated and filtered picture.  fetch: RT_TEMPORAL_FETCH_NEAREST
     // is that call; RT_TEMPORAL_FETCH_BILINEAR goes through rt_denoise_temporal_fetch with that fetch's defaults.
-    int RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels, uint32_t fetch = RT_TEMPORAL_FETCH_NEAREST) noexcept;
+    // variance != NULL: rt_denoise_temporal_variance with that source; under the spatial one the noise estimate stays as AppSettings has it.
+    int RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint32_t levels, uint32_t fetch = RT_TEMPORAL_FETCH_NEAREST,
+                 const rt_variance_params* variance = nullptr) noexcept;
     bool WriteTemporalPPM(const std::string& path) const;
     const std::vector<XMVECTOR>& Hdr() const { return m_backbufferHdr; }
     const std::vector<XMCOLOR>& Ldr() const { return m_backbufferLdr; }

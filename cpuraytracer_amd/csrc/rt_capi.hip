@@ -1299,6 +1299,17 @@ static int NoiseReady(rt_ctx* ctx, const char* who, uint32_t minSamples) {
     return RT_OK;
 }
 
+// The same without the switch, for readers of hdr alone (the spatial variance source): a picture with samples in the strip, as
+// rt_resolve(ctx, 0) sees it.  With frames in flight the count is the device's (CommittedWord); nothing in flight is settled.
+static int PictureReady(rt_ctx* ctx, const char* who) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    if (const int rcb = RenderPendingForReader(ctx)) return rcb;
+    if (ctx->seq.accumulated == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": nothing accumulated");
+    RT_HIP(hipSetDevice(ctx->device));
+    return RT_OK;
+}
+static const uint32_t* CommittedWord(const rt_ctx* ctx) { return ctx->pipeOpen ? &ctx->ctl.ptr->committed_samples[ctx->pipeCommits & 1u] : nullptr; }
+
 static int ReadMoments(rt_ctx* ctx, const char* who, bool toDevice, void* sq_rgb) {
     const int rc = NoiseReady(ctx, who, 1);
     if (rc != RT_OK) return rc;
@@ -1432,8 +1443,9 @@ int rt_clear_features(rt_ctx* ctx) {
 // Readers of hdr, sq and feat that write strips of their own: no sequencing state of rt_render or rt_render_features changes.  The
 // three entries share what follows and differ in where their inputs come from and in the rtdn::Launch* they call; their messages
 // carry their own name in front, and every refusal comes before the first change of state.
-static int DenoiseParamsReady(rt_ctx* ctx, const char* who, const rt_denoise_params* params, rtd::DenoiseParams* P) {
-    const int rc = NoiseReady(ctx, who, 2);
+// (moments: the variance comes from the strip of second moments -- the switch on, n >= 2; else from the picture itself, n >= 1)
+static int DenoiseParamsReady(rt_ctx* ctx, const char* who, const rt_denoise_params* params, rtd::DenoiseParams* P, bool moments = true) {
+    const int rc = moments ? NoiseReady(ctx, who, 2) : PictureReady(ctx, who);
     if (rc != RT_OK) return rc;
     rt_denoise_params def;
     rt_denoise_default_params(&def);
@@ -1512,6 +1524,26 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms) {
     return DenoiseFinish(ctx, "rt_denoise", S, rtdn::LaunchDenoise(ctx->stream, S, P, knob, ctx->denForms), out_ms);
 }
 
+// rt_denoise with the variance source chosen: the moments source is rt_denoise; the spatial one differs in what it asks of the picture
+// and in its prepare pass, which does not read sq.
+int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_params* params, const rt_variance_params* vparams, double* out_ms) {
+    const char* who = "rt_denoise_variance";
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    rtd::VarianceParams V{};
+    int rc = rtdn::CheckVarianceParams(who, vparams, &V);
+    if (rc != RT_OK) return rc;
+    if (V.source == rtd::kVarianceMoments) return rt_denoise(ctx, params, out_ms);
+    rtd::DenoiseParams P{};
+    if ((rc = DenoiseParamsReady(ctx, who, params, &P, false)) != RT_OK || (rc = DenoisePictureReady(ctx, who)) != RT_OK) return rc;
+    rtdn::Strips S{};
+    int knob;
+    if ((rc = DenoiseStrips(ctx, ctx->seq.pic.W, ctx->seq.rows, true, &S, &knob)) != RT_OK) return rc;
+    DenoiseInputsOfPicture(ctx, &S);
+    S.sq = nullptr;
+    if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
+    return DenoiseFinish(ctx, who, S, rtdn::LaunchDenoiseSpatial(ctx->stream, S, P, V.radius, CommittedWord(ctx), knob, ctx->denForms), out_ms);
+}
+
 // The same filter over the gathered parts of a row-sharded picture: only the denoiser's own strips of the context are touched.
 int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise_params* params, double* out_ms) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_denoise_shards: null ctx");
@@ -1548,6 +1580,8 @@ struct TemporalCall {
     rtd::DenoiseParams P;
     rtd::TemporalParams T;
     uint32_t fetch;
+    uint32_t spatialRadius;     // 0: v0 from the moments; else the spatial source's radius (contiguous calls only)
+    const uint32_t* committed;  // the spatial pass's device-side sample count, or NULL (CommittedWord)
 };
 static int TemporalStep(rt_ctx* ctx, const char* who, const TemporalCall& c, double* out_ms) {
     int rc;
@@ -1564,7 +1598,7 @@ static int TemporalStep(rt_ctx* ctx, const char* who, const TemporalCall& c, dou
     if ((rc = ctx->tmpTarget.Reserve(npix)) != RT_OK) return rc;
     rtdn::Strips S{};
     int knob;
-    if ((rc = DenoiseStrips(ctx, W, rows, false, &S, &knob)) != RT_OK) return rc;
+    if ((rc = DenoiseStrips(ctx, W, rows, c.spatialRadius != 0, &S, &knob)) != RT_OK) return rc;  // (the spatial pass writes the guide strips)
     S.hdr = c.hdr;
     S.sq = c.sq;
     S.feat = c.feat;
@@ -1586,8 +1620,9 @@ static int TemporalStep(rt_ctx* ctx, const char* who, const TemporalCall& c, dou
     Q.target = ctx->tmpTarget.ptr;
     ctx->tmpValid = false;  // the history is being rewritten, until everything is enqueued
     if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
-    const int launched = c.parts ? rtdn::LaunchDenoiseShardsTemporal(ctx->stream, S, *c.parts, Q, P, knob, ctx->denForms)
-                                 : rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms);
+    const int launched = c.parts           ? rtdn::LaunchDenoiseShardsTemporal(ctx->stream, S, *c.parts, Q, P, knob, ctx->denForms)
+                         : c.spatialRadius ? rtdn::LaunchDenoiseTemporalSpatial(ctx->stream, S, Q, P, c.spatialRadius, c.committed, knob, ctx->denForms)
+                                           : rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms);
     if ((rc = DenoiseFinish(ctx, who, S, launched, out_ms)) != RT_OK) return rc;
     ctx->tmpCur = nxt;
     ctx->tmpPic = pic;
@@ -1597,9 +1632,11 @@ static int TemporalStep(rt_ctx* ctx, const char* who, const TemporalCall& c, dou
 }
 
 // (who: the entry's name for the messages; fetch: which prepare kernel reads the history, and whose defaults tparams == NULL takes)
-static int DenoiseTemporal(rt_ctx* ctx, const char* who, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms) {
+// (spatialRadius: 0, or the radius of the spatial variance source, under which the noise switch and a second sample are not asked for)
+static int DenoiseTemporal(rt_ctx* ctx, const char* who, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms,
+                           uint32_t spatialRadius = 0) {
     TemporalCall c{};
-    int rc = DenoiseParamsReady(ctx, who, params, &c.P);
+    int rc = DenoiseParamsReady(ctx, who, params, &c.P, spatialRadius == 0);
     if (rc != RT_OK) return rc;
     if ((rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &c.T)) != RT_OK) return rc;
     if ((rc = DenoisePictureReady(ctx, who)) != RT_OK) return rc;
@@ -1608,7 +1645,9 @@ static int DenoiseTemporal(rt_ctx* ctx, const char* who, const rt_denoise_params
     if (!rtd::temporal_geom_ok(c.geom) || ctx->seq.rows != c.pic.rs.num_rows)
         return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a picture wider or taller than 2^24, or a strip that is not its row range");
     c.hdr = ctx->hdr.ptr;
-    c.sq = ctx->sq.ptr;
+    c.sq = spatialRadius ? nullptr : ctx->sq.ptr;
+    c.spatialRadius = spatialRadius;
+    c.committed = spatialRadius ? CommittedWord(ctx) : nullptr;
     c.feat = ctx->feat.ptr;
     c.ids = ctx->featIds.ptr;
     c.n = ctx->seq.accumulated;
@@ -1627,6 +1666,18 @@ int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_t
 // The same call with the way the history is fetched chosen: 1 runs the kernel above, 4 the bilinear one; the history is one state.
 int rt_denoise_temporal_fetch(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms) {
     return DenoiseTemporal(ctx, "rt_denoise_temporal_fetch", params, tparams, fetch, out_ms);
+}
+
+// ... and with the variance source chosen: the moments source is the entry above.
+int rt_denoise_temporal_variance(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
+                                 const rt_variance_params* vparams, double* out_ms) {
+    const char* who = "rt_denoise_temporal_variance";
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    rtd::VarianceParams V{};
+    const int rc = rtdn::CheckVarianceParams(who, vparams, &V);
+    if (rc != RT_OK) return rc;
+    if (V.source == rtd::kVarianceMoments) return rt_denoise_temporal_fetch(ctx, params, tparams, fetch, out_ms);
+    return DenoiseTemporal(ctx, who, params, tparams, fetch, out_ms, V.radius);
 }
 
 // The same step over the gathered parts of a row-sharded picture: the frame brings what DenoiseTemporal takes from the context (the

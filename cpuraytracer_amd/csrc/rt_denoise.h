@@ -5,7 +5,8 @@
 // + - * / and comparisons in the order and association below, the one square root inside noise_estimate.  It is compiled with
 // -ffp-contract=off for the device (rt_denoise.hip) and for the host (host/rt_denoise_host.cpp, rt_unit_denoise_host), so the
 // kernels, the host twin and a numpy restatement give the same bits.  Pixels whose inputs are all finite are covered; a NaN's
-// sign and payload are not.
+// sign and payload are not.  Where the picture has no usable second moments -- one sample per pixel, the noise estimate off -- v0 comes
+// from the picture's own neighbourhoods instead ("the spatial variance source" below); everything after v0 is the same.
 #pragma once
 
 #include <stdint.h>
@@ -77,6 +78,69 @@ RT_DEV void denoise_tap(const DenoiseParams& P, float hab, const DenoiseState& s
 RT_DEV void denoise_finish(const DenoiseSums& S, DenoiseState& out) {
     for (int k = 0; k < 3; ++k) out.c[k] = S.sc[k] / S.sw;
     out.v = S.sv / (S.sw * S.sw);
+}
+
+// ---- the spatial variance source: where a pixel has too few samples for a variance of its own (n = 1 has none), v0 is
+// the guide-weighted variance of c0 over the (2R+1)^2 window around it.  sq is not read; c0 and g are denoise_prepare's.
+constexpr uint32_t kVarianceMoments = 0, kVarianceSpatial = 1;  // rt_variance_params::source
+constexpr uint32_t kVarianceMaxRadius = 3;
+
+// rt_variance_params of include/rt_api.h, field for field
+struct VarianceParams {
+    uint32_t source, radius;
+};
+
+RT_DEV bool variance_params_ok(const VarianceParams& V) {
+    if (V.source == kVarianceMoments) return true;  // (the radius is read only under the spatial source)
+    return V.source == kVarianceSpatial && V.radius >= 1u && V.radius <= kVarianceMaxRadius;
+}
+
+// c0 and g alone: denoise_prepare's two quotients without its noise estimate
+RT_DEV void denoise_prepare_mean(const float hdr[3], uint32_t n, const float feat[8], uint32_t m, float c[3], float g[8]) {
+    const float fn = (float)n, fm = (float)m;
+    for (int k = 0; k < 3; ++k) c[k] = hdr[k] / fn;
+    for (int k = 0; k < 8; ++k) g[k] = feat[k] / fm;
+}
+
+struct SpatialSums {
+    float s1[3], s2[3];
+    float sw;
+};
+
+RT_DEV void spatial_begin(SpatialSums& S) {
+    for (int k = 0; k < 3; ++k) S.s1[k] = S.s2[k] = 0.0f;
+    S.sw = 0.0f;
+}
+
+// One tap q of pixel p: the four guide terms are denoise_tap's, expression for expression; there is no colour term and no h.
+RT_DEV void spatial_tap(const DenoiseParams& P, const float gp[8], const float cq[3], const float gq[8], SpatialSums& S) {
+    const float dn0 = gp[3] - gq[3], dn1 = gp[4] - gq[4], dn2 = gp[5] - gq[5];
+    const float xn = P.k_normal * ((dn0 * dn0 + dn1 * dn1) + dn2 * dn2);
+    const float da0 = gp[0] - gq[0], da1 = gp[1] - gq[1], da2 = gp[2] - gq[2];
+    const float xa = P.k_albedo * ((da0 * da0 + da1 * da1) + da2 * da2);
+    const float dz = gp[6] - gq[6];
+    const float zm = gp[6] > gq[6] ? gp[6] : gq[6];
+    const float xz = P.k_depth * ((dz * dz) / (zm * zm + 1e-12f));
+    const float dc = gp[7] - gq[7];
+    const float xc = P.k_coverage * (dc * dc);
+    const float x = ((xn + xz) + xa) + xc;
+    const float w = 1.0f / (1.0f + x);
+    for (int k = 0; k < 3; ++k) {
+        S.s1[k] = S.s1[k] + w * cq[k];
+        S.s2[k] = S.s2[k] + w * (cq[k] * cq[k]);
+    }
+    S.sw = S.sw + w;
+}
+
+// After the taps (the centre tap has w == 1, so sw >= 1): the weighted variance per channel, floor 0, channels summed
+RT_DEV float spatial_finish(const SpatialSums& S) {
+    float d[3];
+    for (int k = 0; k < 3; ++k) {
+        const float mu = S.s1[k] / S.sw, e = S.s2[k] / S.sw;
+        d[k] = e - mu * mu;
+        if (!(d[k] > 0.0f)) d[k] = 0.0f;
+    }
+    return (d[0] + d[1]) + d[2];
 }
 
 // levels 1..5; every k and var_floor finite and >= 0, var_floor > 0

@@ -85,17 +85,32 @@ struct TemporalArgs {
     uint32_t* __restrict__ target;
 };
 
+// The planes a spatial prepare pass (rt_denoise_prepare_spatial_kernel below) wrote, in image order: the prepared forms of the two
+// passes read (c0, v0) and g there instead of forming them from hdr, sq and feat.
+struct PreparedPlanes {
+    const float4* __restrict__ s;
+    const float4* __restrict__ g0;
+    const float4* __restrict__ g1;
+};
+
 // The pass's body, shared with the sharded form below: pix is the pixel of the strip (IMAGE order: every history read and every write),
 // p where its current-frame inputs lie -- pix itself, or its place in the gathered parts.
-__device__ __forceinline__ void temporal_prepare_nearest(const TemporalArgs& A, const uint32_t pix, const size_t p) {
-    const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
-    const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
-    const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
-    const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
-    const uint32_t id = A.ids[p];
+template <bool kPrepared>
+__device__ __forceinline__ void temporal_prepare_nearest(const TemporalArgs& A, const PreparedPlanes& Q, const uint32_t pix, const size_t p) {
     DenoiseState s;
     float g[8];
-    denoise_prepare(h, q3, A.n, f, A.m, s, g);
+    uint32_t id;
+    if (kPrepared) {  // the pixel's state and guides as the spatial pass left them
+        id = A.ids[p];
+        unpack(Q.s[pix], Q.g0[pix], Q.g1[pix], s, g);
+    } else {
+        const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
+        const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
+        const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
+        const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+        id = A.ids[p];
+        denoise_prepare(h, q3, A.n, f, A.m, s, g);
+    }
     uint32_t len = 1u, target = kTemporalNoTarget;
     if (A.hasPrev) {
         const uint32_t ly = pix / A.G.W, x = pix - ly * A.G.W;
@@ -125,7 +140,7 @@ __device__ __forceinline__ void temporal_prepare_nearest(const TemporalArgs& A, 
 __global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const TemporalArgs A) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= A.npix) return;
-    temporal_prepare_nearest(A, pix, pix);
+    temporal_prepare_nearest<false>(A, PreparedPlanes{}, pix, pix);
 }
 
 // The bilinear fetch (rt_temporal.h): the same pass, but the history is read at the four pixels around the reprojected point.  The two
@@ -133,15 +148,22 @@ __global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const 
 // All four taps' loads are issued before the first is used: a tap outside the strip loads the pixel's own index instead (pix < npix, a
 // contiguous read) and what it loaded is dropped, so no load waits for a test and none leaves the arrays -- a tap inside has q < npix by
 // temporal_tap_index.  Only taps that take part are added (temporal_gather_tap).  Writes as in the nearest kernel.
-__device__ __forceinline__ void temporal_prepare_bilinear(const TemporalArgs& A, const uint32_t pix, const size_t p) {
-    const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
-    const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
-    const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
-    const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
-    const uint32_t id = A.ids[p];
+template <bool kPrepared>
+__device__ __forceinline__ void temporal_prepare_bilinear(const TemporalArgs& A, const PreparedPlanes& Q, const uint32_t pix, const size_t p) {
     DenoiseState s;
     float g[8];
-    denoise_prepare(h, q3, A.n, f, A.m, s, g);
+    uint32_t id;
+    if (kPrepared) {  // the pixel's state and guides as the spatial pass left them
+        id = A.ids[p];
+        unpack(Q.s[pix], Q.g0[pix], Q.g1[pix], s, g);
+    } else {
+        const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
+        const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
+        const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
+        const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+        id = A.ids[p];
+        denoise_prepare(h, q3, A.n, f, A.m, s, g);
+    }
     uint32_t len = 1u, target = kTemporalNoTarget;
     if (A.hasPrev) {
         const uint32_t ly = pix / A.G.W, x = pix - ly * A.G.W;
@@ -196,7 +218,26 @@ __device__ __forceinline__ void temporal_prepare_bilinear(const TemporalArgs& A,
 __global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_bilinear_kernel(const TemporalArgs A) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= A.npix) return;
-    temporal_prepare_bilinear(A, pix, pix);
+    temporal_prepare_bilinear<false>(A, PreparedPlanes{}, pix, pix);
+}
+
+// The two passes over a state the spatial prepare pass wrote (rt_denoise_temporal_variance under RT_VARIANCE_SPATIAL): the same bodies,
+// hdr, sq and feat not read.
+struct TemporalPreparedArgs {
+    TemporalArgs A;
+    PreparedPlanes Q;
+};
+
+__global__ void __launch_bounds__(256) rt_denoise_prepared_temporal_kernel(const TemporalPreparedArgs S) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= S.A.npix) return;
+    temporal_prepare_nearest<true>(S.A, S.Q, pix, pix);
+}
+
+__global__ void __launch_bounds__(256) rt_denoise_prepared_temporal_bilinear_kernel(const TemporalPreparedArgs S) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= S.A.npix) return;
+    temporal_prepare_bilinear<true>(S.A, S.Q, pix, pix);
 }
 
 // The two passes over the gathered parts of a row-sharded picture (rt_denoise_shards_temporal): a thread owns pixel pix of the IMAGE's
@@ -220,13 +261,13 @@ __device__ __forceinline__ size_t temporal_shard_source(const TemporalShardArgs&
 __global__ void __launch_bounds__(256) rt_denoise_prepare_shards_temporal_kernel(const TemporalShardArgs S) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= S.A.npix) return;
-    temporal_prepare_nearest(S.A, pix, temporal_shard_source(S, pix));
+    temporal_prepare_nearest<false>(S.A, PreparedPlanes{}, pix, temporal_shard_source(S, pix));
 }
 
 __global__ void __launch_bounds__(256) rt_denoise_prepare_shards_temporal_bilinear_kernel(const TemporalShardArgs S) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= S.A.npix) return;
-    temporal_prepare_bilinear(S.A, pix, temporal_shard_source(S, pix));
+    temporal_prepare_bilinear<false>(S.A, PreparedPlanes{}, pix, temporal_shard_source(S, pix));
 }
 
 // One level.  Thread (tx, ty) of the 32 x 8 workgroup owns pixel (32 bx + tx, 8 by + ty); its 25 taps lie (a - 2) step rows and
@@ -312,9 +353,94 @@ __global__ void __launch_bounds__(256) rt_atrous_kernel(const float4* __restrict
     }
 }
 
+// The prepare pass of the spatial variance source (rt_denoise.h).  The a-trous kernel's geometry: thread (tx, ty) of the
+// 32 x 8 workgroup owns pixel (32 bx + tx, 8 by + ty).  The workgroup forms c0 = hdr / n and g = feat / m of its tile and a halo of kR
+// pixels ONCE while staging them into LDS -- three planes of float4 with contiguous rows, (c0, unused), (g 0..3), (g 4..7): 48 bytes per
+// pixel, (32 + 2 kR) x (8 + 2 kR) pixels, 25,536 bytes at kR = 3 -- and after one barrier every thread runs its (2 kR + 1)^2 taps from
+// there, a outer, b inner.  A tap outside the strip is skipped, never clamped; slots of pixels outside the strip are never written and
+// never read.  sq is not read.  committed (rt_resolve's rule): with frames in flight the strip's sample count is a word only the device
+// knows.  Writes state (c0, v0), g0, g1 in image order, as rt_denoise_prepare_kernel does.
+template <int kR>
+__global__ void __launch_bounds__(256) rt_denoise_prepare_spatial_kernel(const float* __restrict__ hdr, const float4* __restrict__ feat, uint32_t W,
+                                                                         uint32_t rows, uint32_t n, uint32_t m, const uint32_t* __restrict__ committed,
+                                                                         const DenoiseParams P, float4* __restrict__ state, float4* __restrict__ g0,
+                                                                         float4* __restrict__ g1) {
+    constexpr uint32_t tw = rtdn::kTileW + 2u * kR, th = rtdn::kTileH + 2u * kR;
+    __shared__ float4 ldsC[tw * th];
+    __shared__ float4 ldsA[tw * th];
+    __shared__ float4 ldsB[tw * th];
+    const uint32_t tx = threadIdx.x & (rtdn::kTileW - 1u), ty = threadIdx.x / rtdn::kTileW;
+    const int x0 = (int)(blockIdx.x * rtdn::kTileW), y0 = (int)(blockIdx.y * rtdn::kTileH);
+    const int x = x0 + (int)tx, y = y0 + (int)ty;
+    if (committed) n = *committed > 0u ? *committed : 1u;
+    for (uint32_t ly = ty; ly < th; ly += rtdn::kTileH) {
+        const int gy = y0 - kR + (int)ly;
+        if (gy < 0 || gy >= (int)rows) continue;
+        for (uint32_t lx = tx; lx < tw; lx += rtdn::kTileW) {
+            const int gx = x0 - kR + (int)lx;
+            if (gx < 0 || gx >= (int)W) continue;
+            const size_t q = (size_t)gy * W + (size_t)gx;
+            const float h[3] = {hdr[3 * q], hdr[3 * q + 1], hdr[3 * q + 2]};
+            const float4 fa = feat[2 * q], fb = feat[2 * q + 1];
+            const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+            float c[3], g[8];
+            denoise_prepare_mean(h, n, f, m, c, g);
+            const uint32_t slot = ly * tw + lx;
+            ldsC[slot] = make_float4(c[0], c[1], c[2], 0.0f);
+            ldsA[slot] = make_float4(g[0], g[1], g[2], g[3]);
+            ldsB[slot] = make_float4(g[4], g[5], g[6], g[7]);
+        }
+    }
+    __syncthreads();
+    if (x >= (int)W || y >= (int)rows) return;
+    const uint32_t centre = (ty + (uint32_t)kR) * tw + tx + (uint32_t)kR;
+    DenoiseState sp;
+    float gp[8];
+    unpack(ldsC[centre], ldsA[centre], ldsB[centre], sp, gp);
+    SpatialSums S;
+    spatial_begin(S);
+#pragma unroll
+    for (int a = 0; a <= 2 * kR; ++a) {
+        const int dy = a - kR;
+        const int qy = y + dy;
+        if (qy < 0 || qy >= (int)rows) continue;
+#pragma unroll
+        for (int b = 0; b <= 2 * kR; ++b) {
+            const int dx = b - kR;
+            const int qx = x + dx;
+            if (qx < 0 || qx >= (int)W) continue;
+            const uint32_t slot = (uint32_t)((int)ty + kR + dy) * tw + (uint32_t)((int)tx + kR + dx);
+            DenoiseState sq;
+            float gq[8];
+            unpack(ldsC[slot], ldsA[slot], ldsB[slot], sq, gq);
+            spatial_tap(P, gp, sq.c, gq, S);
+        }
+    }
+    const size_t p = (size_t)y * W + (size_t)x;
+    state[p] = make_float4(sp.c[0], sp.c[1], sp.c[2], spatial_finish(S));
+    g0[p] = make_float4(gp[0], gp[1], gp[2], gp[3]);
+    g1[p] = make_float4(gp[4], gp[5], gp[6], gp[7]);
+}
+
 }  // namespace rtd
 
 namespace rtdn {
+
+// The spatial prepare pass into the three planes (radius 1..3: the caller's check).
+static int LaunchPrepareSpatial(hipStream_t st, const Strips& s, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed, float4* state,
+                                float4* g0, float4* g1) {
+    const dim3 grid((s.W + kTileW - 1u) / kTileW, (s.rows + kTileH - 1u) / kTileH);
+    const float4* feat = reinterpret_cast<const float4*>(s.feat);
+    if (radius == 1u)
+        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<1>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, state, g0, g1);
+    else if (radius == 2u)
+        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<2>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, state, g0, g1);
+    else if (radius == 3u)
+        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<3>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, state, g0, g1);
+    else
+        return (int)hipErrorInvalidValue;
+    return (int)hipGetLastError();
+}
 
 // The levels over the prepared state and guides of a W x rows picture in image order.
 // (first: level 0's input -- state[0] itself, or the temporal form's new history, which no level may overwrite)
@@ -411,6 +537,38 @@ int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, cons
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     return LaunchLevels(st, s, A.oS, A.oG0, A.oG1, P, stageKnob, forms);
+}
+
+int LaunchDenoiseSpatial(void* stream, const Strips& s, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed, int stageKnob,
+                         uint32_t forms[rtd::kDenoiseMaxLevels]) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
+    const int e = LaunchPrepareSpatial(st, s, P, radius, committed, static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]),
+                                       static_cast<float4*>(s.guide[1]));
+    if (e != 0) return e;
+    return LaunchLevels(st, s, static_cast<const float4*>(s.state[0]), static_cast<const float4*>(s.guide[0]), static_cast<const float4*>(s.guide[1]), P, stageKnob,
+                        forms);
+}
+
+// The spatial pass writes Strips::state[0] and Strips::guide -- idle in the temporal form until level 1 writes state[0] -- and the
+// prepared form of the chosen pass reads them.
+int LaunchDenoiseTemporalSpatial(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed,
+                                 int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t npix = s.W * s.rows;
+    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
+    int e = LaunchPrepareSpatial(st, s, P, radius, committed, static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]),
+                                 static_cast<float4*>(s.guide[1]));
+    if (e != 0) return e;
+    const rtd::TemporalPreparedArgs S{TemporalArgsOf(s, t),
+                                      {static_cast<const float4*>(s.state[0]), static_cast<const float4*>(s.guide[0]), static_cast<const float4*>(s.guide[1])}};
+    if (t.fetch == rtd::kTemporalFetchBilinear)
+        hipLaunchKernelGGL(rtd::rt_denoise_prepared_temporal_bilinear_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, S);
+    else
+        hipLaunchKernelGGL(rtd::rt_denoise_prepared_temporal_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, S);
+    e = (int)hipGetLastError();
+    if (e != 0) return e;
+    return LaunchLevels(st, s, S.A.oS, S.A.oG0, S.A.oG1, P, stageKnob, forms);
 }
 
 int LaunchDenoiseShardsTemporal(void* stream, const Strips& s, const ShardLayout& parts, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,

@@ -252,13 +252,19 @@ class HipRenderer:
         check(self._L.rt_clear_features(self._h))
 
     # ---- denoise (rt_api.h "denoise")
-    def denoise(self, params=None, timed=False):
+    def denoise(self, params=None, timed=False, variance=None):
         """rt_denoise: the feature-guided a-trous filter over the picture, its noise estimate and the feature strips as they are now
         (noise estimate on, at least 2 samples; feature strips of the same image and row set).  params: an RtDenoiseParams
         (_capi.denoise_params(levels=..., ...)) or None for the defaults.  timed=True waits and returns the HIP-event time in ms; else
-        the call only enqueues work and returns None."""
+        the call only enqueues work and returns None.  variance (rt_denoise_variance): an RtVarianceParams
+        (_capi.variance_params(source=..., radius=...)) or None for this call as it always was; with source RT_VARIANCE_SPATIAL the
+        variance comes from the picture's own neighbourhoods, so one sample suffices, the noise estimate may be off and pipelined
+        frames stay in flight."""
         ms = C.c_double(0.0)
-        check(self._L.rt_denoise(self._h, C.byref(params) if params is not None else None, C.byref(ms) if timed else None))
+        if variance is None:
+            check(self._L.rt_denoise(self._h, C.byref(params) if params is not None else None, C.byref(ms) if timed else None))
+        else:
+            check(self._L.rt_denoise_variance(self._h, C.byref(params) if params is not None else None, C.byref(variance), C.byref(ms) if timed else None))
         self.denoised_W, self.denoised_rows = self.W, self.rows
         return ms.value if timed else None
 
@@ -274,17 +280,22 @@ class HipRenderer:
         return ms.value if timed else None
 
     # ---- temporal accumulation (rt_api.h "temporal accumulation")
-    def denoise_temporal(self, params=None, tparams=None, timed=False, fetch=1):
+    def denoise_temporal(self, params=None, tparams=None, timed=False, fetch=1, variance=None):
         """rt_denoise_temporal: denoise() with the previous call's pre-filter state reprojected into the uploaded scene's camera,
         validated against the guides and blended in before the levels.  The history survives upload() -- a camera move is an upload
         -- and starts empty after temporal_reset() or when the picture's size or row set changes; on an empty history the result is
         denoise()'s.  tparams: an RtTemporalParams (_capi.temporal_params(max_history=..., ...)) or None for the defaults; params and
         timed as in denoise().  download_denoised() serves the result.  fetch (rt_denoise_temporal_fetch): 1, nearest, is
         rt_denoise_temporal's bits; 4, bilinear, interpolates the history from the four pixels around the reprojected point.  tparams
-        None means that fetch's defaults (_capi.temporal_params_fetch)."""
+        None means that fetch's defaults (_capi.temporal_params_fetch).  variance (rt_denoise_temporal_variance): as in denoise()."""
         ms = C.c_double(0.0)
-        check(self._L.rt_denoise_temporal_fetch(self._h, C.byref(params) if params is not None else None,
-                                                C.byref(tparams) if tparams is not None else None, int(fetch), C.byref(ms) if timed else None))
+        if variance is None:
+            check(self._L.rt_denoise_temporal_fetch(self._h, C.byref(params) if params is not None else None,
+                                                    C.byref(tparams) if tparams is not None else None, int(fetch), C.byref(ms) if timed else None))
+        else:
+            check(self._L.rt_denoise_temporal_variance(self._h, C.byref(params) if params is not None else None,
+                                                       C.byref(tparams) if tparams is not None else None, int(fetch), C.byref(variance),
+                                                       C.byref(ms) if timed else None))
         self.denoised_W, self.denoised_rows = self.W, self.rows
         self.temporal_W, self.temporal_rows = self.W, self.rows
         return ms.value if timed else None

@@ -453,6 +453,40 @@ typedef struct rt_shard_frame {
 int rt_denoise_shards_temporal(rt_ctx* ctx, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams,
                                uint32_t fetch, double* out_ms);
 
+/* ----------------------------------------------------------------- spatial variance estimate
+ * Where the filter's v0 comes from, chosen per call (csrc/rt_denoise.h).  RT_VARIANCE_MOMENTS is everything above: the
+ * strip of second moments, which needs rt_set_noise_estimate(1) and n >= 2.  RT_VARIANCE_SPATIAL takes v0 from the picture itself -- the
+ * guide-weighted variance of c0 over the (2R+1)^2 window around the pixel -- and so runs at ONE sample per pixel, with the noise switch
+ * off and with frames in flight.  The arithmetic rules are the denoiser's (binary32; only + - * / and comparisons in this order and
+ * association; never fused; correctly rounded division).  c0[k] = hdr[k] / (float)n and g = feat / (float)m as above; sq is not read.
+ * For pixel p, R = radius: taps a = 0..2R outer (dy = a - R), b = 0..2R inner (dx = b - R), the centre included; a tap outside the strip
+ * is skipped (adds nothing, never clamped); the sums start at +0; for tap q
+ *     xn, xa, xz, xc   the four guide terms of the filter's tap above (same expressions, the call's k_normal, k_albedo, k_depth, k_coverage)
+ *     x  = ((xn + xz) + xa) + xc;            w = 1.0f / (1.0f + x)
+ *     s1[k] = s1[k] + w*cq[k];   s2[k] = s2[k] + w*(cq[k]*cq[k]);   sw = sw + w        k = r, g, b
+ * and after the taps mu[k] = s1[k]/sw; e[k] = s2[k]/sw; d[k] = e[k] - mu[k]*mu[k]; if !(d[k] > 0) d[k] = 0;  v0 = (d[0] + d[1]) + d[2]
+ * (the centre has w = 1, so sw >= 1).  The pixel's state is (c0, v0); from there everything is unchanged: the temporal validation and
+ * blend, the levels and den_var, the tonemap, the snapshot and its readers, RT_DENOISE_STAGE, rt_unit_denoise_forms, and the history's
+ * layout, key and lifetime.  Calls may alternate sources and fetches over one history.  Pixels whose inputs are all finite are covered; a
+ * NaN's sign and payload are not. */
+enum { RT_VARIANCE_MOMENTS = 0, RT_VARIANCE_SPATIAL = 1 };
+typedef struct rt_variance_params {
+    uint32_t source;   /* default RT_VARIANCE_MOMENTS */
+    uint32_t radius;   /* 1..3, window (2R+1)^2, default 1 (docs/EXPERIMENTS.md: the grid); read only under RT_VARIANCE_SPATIAL */
+} rt_variance_params;
+int rt_variance_default_params(rt_variance_params* out);   /* needs no GPU */
+/* rt_denoise and rt_denoise_temporal_fetch with the variance source chosen.  vparams == NULL or source == RT_VARIANCE_MOMENTS: exactly
+ * those two entries -- preconditions, refusals, bits and history.  Under RT_VARIANCE_SPATIAL: a picture accumulated with n >= 1 samples
+ * in the strip, n being the count rt_resolve(ctx, 0) and rt_download see (pending batches are settled as they settle them; planes traced
+ * ahead are not in the strip; with frames in flight it is rt_committed_samples, read on the device); nothing accumulated is
+ * RT_ERR_SEQUENCE.  The noise switch may be off, and the call settles nothing that rt_resolve would not: pipelined frames stay in flight.
+ * Feature strips, the nshards rule and the row limits are rt_denoise's.  radius outside 1..3 under SPATIAL, or an unknown source:
+ * RT_ERR_INVALID_ARG.  Every refusal comes before the first change: history and snapshot stay.  The sharded entries (rt_denoise_shards,
+ * rt_denoise_shards_temporal) are unchanged and have no spatial form. */
+int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_params* params, const rt_variance_params* vparams, double* out_ms);
+int rt_denoise_temporal_variance(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
+                                 const rt_variance_params* vparams, double* out_ms);
+
 /* Replaces the transform(par) tonemap (spheres-app.cpp:186-214): hdr / n_samples,
  * ACES fit, gamma 1/2.2, XMStoreColor.  n_samples == 0 uses the accumulated count. */
 int rt_resolve(rt_ctx* ctx, uint32_t n_samples);
@@ -614,6 +648,18 @@ int rt_unit_temporal_shards_host(const float* hdr, const float* sq, const float*
                                  const rt_camera* hist_camera, const float* hist_state4, const float* hist_guides8, const uint32_t* hist_ids,
                                  const uint32_t* hist_len, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
                                  float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len, uint32_t* out_target);
+/* rt_unit_denoise_host with the variance source chosen: the twin of rt_denoise_variance.  vparams == NULL or RT_VARIANCE_MOMENTS:
+ * rt_unit_denoise_host's refusals and bits.  Under RT_VARIANCE_SPATIAL sq may be NULL (it is not read) and n >= 1 suffices (n == 0:
+ * RT_ERR_SEQUENCE); a radius outside 1..3 or an unknown source: RT_ERR_INVALID_ARG.  out_state4 (may be NULL): the prepared (c0, v0), 4
+ * floats per pixel, as the levels read it.  Needs no GPU. */
+int rt_unit_denoise_variance_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
+                                  const rt_denoise_params* params, const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4);
+/* rt_unit_temporal_host_fetch with the variance source chosen: the twin of rt_denoise_temporal_variance, sq and n as above. */
+int rt_unit_temporal_variance_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W, uint32_t H,
+                                   uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
+                                   const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
+                                   const rt_temporal_params* tparams, uint32_t fetch, const rt_variance_params* vparams, float* out_rgb, float* out_var,
+                                   float* out_state4, float* out_guides8, uint32_t* out_len, uint32_t* out_target);
 /* Which form each level of the last rt_denoise, rt_denoise_shards, rt_denoise_temporal or rt_denoise_shards_temporal took: out[l] = 0 the level did not run, 1 its taps were read from
  * global memory, 2 from a tile staged in LDS. */
 int rt_unit_denoise_forms(rt_ctx* ctx, uint32_t out[5]);
