@@ -19,8 +19,8 @@ static_assert(sizeof(rt_denoise_params) == sizeof(rtd::DenoiseParams) && offseto
               "rt_denoise_params is laid out like rtd::DenoiseParams");
 
 // The levels over the prepared state a (b: the other buffer) and guides g of a W x rows picture; the last level's state goes out.
-static void RunLevels(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseState>& b, const std::vector<float>& g, uint32_t W, uint32_t rows,
-                      const rtd::DenoiseParams& P, float* out_rgb, float* out_var) {
+void rtdn::RunLevelsHost(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseState>& b, const std::vector<float>& g, uint32_t W, uint32_t rows,
+                         const rtd::DenoiseParams& P, float* out_rgb, float* out_var) {
     const size_t npix = (size_t)W * rows;
     const rtd::DenoiseState* in = a.data();
     rtd::DenoiseState* out = b.data();
@@ -59,6 +59,23 @@ static_assert(RT_VARIANCE_MOMENTS == rtd::kVarianceMoments && RT_VARIANCE_SPATIA
 
 namespace rtdn {
 
+int CheckDenoiseParams(const char* who_, const rt_denoise_params* params, rtd::DenoiseParams* P) {
+    rt_denoise_params def;
+    rt_denoise_default_params(&def);
+    if (!params) params = &def;
+    *P = rtd::DenoiseParams{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
+    if (!rtd::denoise_params_ok(*P))
+        return Fail(RT_ERR_INVALID_ARG, std::string(who_) + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    return RT_OK;
+}
+
+// Where row y of the image's row range starts in the gathered parts (../rt_rowset_map.h).
+size_t PartsRowStart(const ShardLayout& parts, uint32_t W, uint32_t y) {
+    uint32_t shard, lr;
+    rtd::rowset_locate(parts.blockRows, parts.nshards, y, shard, lr);
+    return ((size_t)shard * parts.rowsMax + lr) * W;
+}
+
 int CheckVarianceParams(const char* who_, const rt_variance_params* vparams, rtd::VarianceParams* V) {
     *V = vparams ? rtd::VarianceParams{vparams->source, vparams->radius} : rtd::VarianceParams{rtd::kVarianceMoments, rtd::kVarianceMaxRadius};
     if (!rtd::variance_params_ok(*V))
@@ -95,11 +112,6 @@ void PrepareSpatialHost(const float* hdr, uint32_t n, const float* feat8, uint32
     }
 }
 
-void RunLevelsHost(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseState>& b, const std::vector<float>& g, uint32_t W, uint32_t rows,
-                   const rtd::DenoiseParams& P, float* out_rgb, float* out_var) {
-    RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
-}
-
 // (CheckShardFrame, the same for an rt_shard_frame, ends with this one and lives in rt_temporal_host.cpp, beside the temporal parameters'
 // checks it calls: denoise_selftest links this file without that one)
 int CheckShardParts(const char* who_, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P) {
@@ -114,11 +126,7 @@ int CheckShardParts(const char* who_, const rt_shard_parts* parts, const rt_deno
     if (parts->rows_max < rtd::rowset_max_shard_rows(rs.num_rows, rs.block_rows, rs.nshards))
         return Fail(RT_ERR_INVALID_ARG, who + ": rows_max is below the rows of the largest shard");
     if (devicePointers && (reinterpret_cast<uintptr_t>(parts->feat) & 15u) != 0) return Fail(RT_ERR_INVALID_ARG, who + ": feat is not 16-byte aligned");
-    rt_denoise_params def;
-    rt_denoise_default_params(&def);
-    if (!params) params = &def;
-    *P = rtd::DenoiseParams{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
-    if (!rtd::denoise_params_ok(*P)) return Fail(RT_ERR_INVALID_ARG, who + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    if (const int rc = CheckDenoiseParams(who_, params, P)) return rc;
     if (parts->n < 2) return Fail(RT_ERR_SEQUENCE, who + ": the noise estimate needs at least 2 samples per pixel");
     if (parts->m == 0) return Fail(RT_ERR_SEQUENCE, who + ": the feature parts hold no sample");
     return RT_OK;
@@ -140,52 +148,20 @@ int rt_denoise_default_params(rt_denoise_params* out) {
     return RT_OK;
 }
 
-int rt_unit_denoise_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
-                         const rt_denoise_params* params, float* out_rgb, float* out_var) {
-    if (!hdr || !sq || !feat8 || !out_rgb || !out_var) return Fail(RT_ERR_INVALID_ARG, "rt_unit_denoise_host: null buffer");
-    if (W == 0 || rows == 0 || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, "rt_unit_denoise_host: empty or too large strip");
-    rt_denoise_params def;
-    rt_denoise_default_params(&def);
-    if (!params) params = &def;
-    rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
-    if (!rtd::denoise_params_ok(P))
-        return Fail(RT_ERR_INVALID_ARG, "rt_unit_denoise_host: levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
-    if (n < 2) return Fail(RT_ERR_SEQUENCE, "rt_unit_denoise_host: the noise estimate needs at least 2 samples per pixel");
-    if (m == 0) return Fail(RT_ERR_SEQUENCE, "rt_unit_denoise_host: the feature strips hold no sample");
-    const size_t npix = (size_t)W * rows;
-    std::vector<rtd::DenoiseState> a(npix), b(npix);
-    std::vector<float> g(npix * 8);
-    for (size_t p = 0; p < npix; ++p) rtd::denoise_prepare(hdr + 3 * p, sq + 3 * p, n, feat8 + 8 * p, m, a[p], &g[8 * p]);
-    RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
-    return RT_OK;
-}
-
-int rt_variance_default_params(rt_variance_params* out) {
-    if (!out) return Fail(RT_ERR_INVALID_ARG, "rt_variance_default_params: null argument");
-    out->source = RT_VARIANCE_MOMENTS;
-    out->radius = 1;  // (docs/EXPERIMENTS.md, the spatial-variance grid: the 3 x 3 window beat the wider ones on both measures, and costs least)
-    return RT_OK;
-}
-
-// rt_unit_denoise_host with the variance source chosen; the moments source IS that entry.
-int rt_unit_denoise_variance_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
-                                  const rt_denoise_params* params, const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4) {
-    const char* who = "rt_unit_denoise_variance_host";
+// The twin of either entry (who: its name for the messages; vparams == NULL: the moments source).
+static int DenoiseHost(const char* who_, const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
+                       const rt_denoise_params* params, const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4) {
+    const std::string who(who_);
     rtd::VarianceParams V{};
-    int rc = rtdn::CheckVarianceParams(who, vparams, &V);
+    int rc = rtdn::CheckVarianceParams(who_, vparams, &V);
     if (rc != RT_OK) return rc;
     const bool spatial = V.source == rtd::kVarianceSpatial;
-    if (!hdr || (!sq && !spatial) || !feat8 || !out_rgb || !out_var) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null buffer");
-    if (W == 0 || rows == 0 || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": empty or too large strip");
-    rt_denoise_params def;
-    rt_denoise_default_params(&def);
-    if (!params) params = &def;
-    rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
-    if (!rtd::denoise_params_ok(P))
-        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
-    if (spatial ? n == 0 : n < 2)
-        return Fail(RT_ERR_SEQUENCE, std::string(who) + (spatial ? ": the strips hold no sample" : ": the noise estimate needs at least 2 samples per pixel"));
-    if (m == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the feature strips hold no sample");
+    if (!hdr || (!sq && !spatial) || !feat8 || !out_rgb || !out_var) return Fail(RT_ERR_INVALID_ARG, who + ": null buffer");
+    if (W == 0 || rows == 0 || (uint64_t)W * rows > (1ull << 31)) return Fail(RT_ERR_INVALID_ARG, who + ": empty or too large strip");
+    rtd::DenoiseParams P{};
+    if ((rc = rtdn::CheckDenoiseParams(who_, params, &P)) != RT_OK) return rc;
+    if (spatial ? n == 0 : n < 2) return Fail(RT_ERR_SEQUENCE, who + (spatial ? ": the strips hold no sample" : ": the noise estimate needs at least 2 samples per pixel"));
+    if (m == 0) return Fail(RT_ERR_SEQUENCE, who + ": the feature strips hold no sample");
     const size_t npix = (size_t)W * rows;
     std::vector<rtd::DenoiseState> a(npix), b(npix);
     std::vector<float> g(npix * 8);
@@ -198,7 +174,25 @@ int rt_unit_denoise_variance_host(const float* hdr, const float* sq, uint32_t n,
             for (int k = 0; k < 3; ++k) out_state4[4 * p + k] = a[p].c[k];
             out_state4[4 * p + 3] = a[p].v;
         }
-    RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
+    rtdn::RunLevelsHost(a, b, g, W, rows, P, out_rgb, out_var);
+    return RT_OK;
+}
+
+int rt_unit_denoise_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
+                         const rt_denoise_params* params, float* out_rgb, float* out_var) {
+    return DenoiseHost("rt_unit_denoise_host", hdr, sq, n, feat8, m, W, rows, params, nullptr, out_rgb, out_var, nullptr);
+}
+
+// rt_unit_denoise_host with the variance source chosen.
+int rt_unit_denoise_variance_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
+                                  const rt_denoise_params* params, const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4) {
+    return DenoiseHost("rt_unit_denoise_variance_host", hdr, sq, n, feat8, m, W, rows, params, vparams, out_rgb, out_var, out_state4);
+}
+
+int rt_variance_default_params(rt_variance_params* out) {
+    if (!out) return Fail(RT_ERR_INVALID_ARG, "rt_variance_default_params: null argument");
+    out->source = RT_VARIANCE_MOMENTS;
+    out->radius = 1;  // (docs/EXPERIMENTS.md, the spatial-variance grid: the 3 x 3 window beat the wider ones on both measures, and costs least)
     return RT_OK;
 }
 
@@ -221,14 +215,13 @@ int rt_unit_denoise_shards_host(const float* hdr, const float* sq, const float* 
     const size_t npix = (size_t)W * rows;
     std::vector<rtd::DenoiseState> a(npix), b(npix);
     std::vector<float> g(npix * 8);
+    const rtdn::ShardLayout layout{shape->rows_max, shape->rs.block_rows, shape->rs.nshards};
     for (uint32_t y = 0; y < rows; ++y) {
-        uint32_t s, lr;
-        rtd::rowset_locate(shape->rs.block_rows, shape->rs.nshards, y, s, lr);
-        const size_t src = ((size_t)s * shape->rows_max + lr) * W, dst = (size_t)y * W;
+        const size_t src = rtdn::PartsRowStart(layout, W, y), dst = (size_t)y * W;
         for (size_t x = 0; x < W; ++x)
             rtd::denoise_prepare(hdr + 3 * (src + x), sq + 3 * (src + x), shape->n, feat8 + 8 * (src + x), shape->m, a[dst + x], &g[8 * (dst + x)]);
     }
-    RunLevels(a, b, g, W, rows, P, out_rgb, out_var);
+    rtdn::RunLevelsHost(a, b, g, W, rows, P, out_rgb, out_var);
     return RT_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "../rt_temporal.h"
 
 struct rt_camera;
+struct rt_denoise_params;
 struct rt_temporal_params;
 struct rt_variance_params;
 
@@ -19,6 +20,9 @@ namespace rtdn {
 // picture; the last level's state goes out as out_rgb (3 floats per pixel) and out_var.
 void RunLevelsHost(std::vector<rtd::DenoiseState>& a, std::vector<rtd::DenoiseState>& b, const std::vector<float>& g, uint32_t W, uint32_t rows,
                    const rtd::DenoiseParams& P, float* out_rgb, float* out_var);
+
+// params (NULL: the defaults) into P; outside their domain: RT_ERR_INVALID_ARG with a message that starts with who.
+int CheckDenoiseParams(const char* who, const rt_denoise_params* params, rtd::DenoiseParams* P);
 
 // vparams (NULL: the moments source) into V; an unknown source, or a radius outside 1..3 under the spatial one: RT_ERR_INVALID_ARG with a
 // message that starts with who.

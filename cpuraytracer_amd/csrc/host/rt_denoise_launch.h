@@ -3,6 +3,7 @@
 // register allocation -- stays what it was (DESIGN.md "Denoise").
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../rt_denoise.h"
@@ -37,23 +38,27 @@ struct Strips {
     float* denVar;      // [npix] out
 };
 
-// Enqueues the prepare pass and one a-trous launch per level on the stream (a hipStream_t).  forms[l] = the form level l took.
-// Returns a hipError_t as int (0 = success); nothing is waited for.
-int LaunchDenoise(void* stream, const Strips& s, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]);
-
-// The parts form (rt_denoise_shards): hdr, sq and feat of Strips are the gathered parts of a row-sharded picture, [nshards] parts of
-// rowsMax x W pixels each, and W x rows is the IMAGE; row j of it is the row of the part that ../rt_rowset_map.h names.
+// A call of the denoiser is a point on three independent axes, each described once here (Job below puts them together).
+//
+// 1. Where a pixel's current-frame inputs lie.  In image order (parts == NULL), or -- the parts form, rt_denoise_shards* -- hdr, sq
+//    and feat of Strips and Temporal::ids are the gathered parts of a row-sharded picture, [nshards] parts of rowsMax x W pixels each,
+//    and W x rows is the IMAGE's row range; row j of it is the row of the part that ../rt_rowset_map.h names.  The prepare pass reads
+//    through the mapping; everything it writes, the history and everything the levels touch are in image order.
 struct ShardLayout {
     uint32_t rowsMax, blockRows, nshards;
 };
-// The same launches, the prepare pass reading through the mapping; everything it writes is in image order.
-int LaunchDenoiseShards(void* stream, const Strips& s, const ShardLayout& parts, const rtd::DenoiseParams& P, int stageKnob,
-                        uint32_t forms[rtd::kDenoiseMaxLevels]);
 
-// The temporal form (rt_denoise_temporal; ../rt_temporal.h): the prepare pass also reprojects every pixel into the history's camera,
-// gathers the history there, validates and blends, and writes the new history -- one pass.  Level 0 then reads the new history's
-// state and guides where they lie (Strips::state[0] and Strips::guide are not used: state[0] and state[1] are the later levels' ping
-// and pong).  The history is never updated in place: prev and next are different sets of buffers.
+// 2. Where v0 comes from.  The second moments (spatialRadius == 0), or -- the spatial source, ../rt_denoise.h -- the (2 radius + 1)^2
+//    window around the pixel, radius 1..3: rt_denoise_prepare_spatial_kernel runs first and writes Strips::state[0] and Strips::guide;
+//    Strips::sq is not read and may be NULL.  committed: NULL, or a device word that holds the strip's sample count where only the
+//    device knows it (frames in flight: rt_resolve's rule, 0 reads as 1); Strips::n is then not read.  LDS of that pass at a radius:
+inline uint32_t SpatialLdsBytes(uint32_t radius) { return (kTileW + 2u * radius) * (kTileH + 2u * radius) * 3u * 16u; }
+
+// 3. What the history does.  Nothing (temporal == NULL), or -- the temporal form, ../rt_temporal.h -- the prepare pass also reprojects
+//    every pixel into the history's camera, gathers the history there (fetch: nearest or bilinear), validates and blends, and writes
+//    the new history -- one pass.  Level 0 then reads the new history's state and guides where they lie: Strips::state[0] and
+//    Strips::guide are idle until level 1 writes state[0], so only a spatial pass, which writes them for the temporal pass to read,
+//    needs the guide strips reserved.  The history is never updated in place: prev and next are different sets of buffers.
 struct TemporalSet {
     void* state;     // [npix] float4 (c.rgb, v) before the levels
     void* guide[2];  // [npix] float4 each, as Strips::guide
@@ -62,7 +67,7 @@ struct TemporalSet {
 };
 struct Temporal {
     const uint32_t* ids;   // [npix] the feature strips' ids of this frame
-    rtd::TemporalGeom geom;
+    rtd::TemporalGeom geom;  // geom.num_rows == Strips::rows
     rtd::TemporalCam cam, camPrev;
     rtd::TemporalParams params;
     uint32_t fetch;        // rtd::kTemporalFetchNearest or kTemporalFetchBilinear: which prepare kernel reads the history
@@ -70,26 +75,18 @@ struct Temporal {
     TemporalSet prev, next;
     uint32_t* target;      // [npix] out
 };
-int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
-                          uint32_t forms[rtd::kDenoiseMaxLevels]);
 
-// The spatial variance source (rt_denoise_variance, rt_denoise_temporal_variance under RT_VARIANCE_SPATIAL; ../rt_denoise.h): the
-// prepare pass is rt_denoise_prepare_spatial_kernel, which takes v0 from the (2 radius + 1)^2 window around the pixel; Strips::sq is not
-// read and may be NULL.  radius: 1..3.  committed: NULL, or a device word that holds the strip's sample count where only the device
-// knows it (frames in flight: rt_resolve's rule, 0 reads as 1); Strips::n is then not read.  LDS of the pass at a radius:
-inline uint32_t SpatialLdsBytes(uint32_t radius) { return (kTileW + 2u * radius) * (kTileH + 2u * radius) * 3u * 16u; }
-int LaunchDenoiseSpatial(void* stream, const Strips& s, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed, int stageKnob,
-                         uint32_t forms[rtd::kDenoiseMaxLevels]);
-// LaunchDenoiseTemporal with that source: the spatial pass writes Strips::state[0] and Strips::guide (which the temporal form leaves
-// idle, so they must be reserved here), then the chosen temporal pass reads its pixel's state and guides from them.
-int LaunchDenoiseTemporalSpatial(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed,
-                                 int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]);
-
-// The temporal form over the parts (rt_denoise_shards_temporal): hdr, sq and feat of Strips and Temporal::ids are the gathered parts
-// (ids: [nshards] parts of rowsMax x W words), W x rows is the IMAGE's row range and t.geom.num_rows == rows.  The prepare pass reads
-// the current frame through the mapping; the history sets, target and everything the levels touch are in image order.
-int LaunchDenoiseShardsTemporal(void* stream, const Strips& s, const ShardLayout& parts, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
-                                uint32_t forms[rtd::kDenoiseMaxLevels]);
+struct Job {
+    Strips strips;
+    const ShardLayout* parts;   // axis 1
+    uint32_t spatialRadius;     // axis 2
+    const uint32_t* committed;
+    const Temporal* temporal;   // axis 3
+};
+// Enqueues the spatial pass if asked for, the one prepare kernel the axes select and one a-trous launch per level on the stream (a
+// hipStream_t).  forms[l] = the form level l took.  Returns a hipError_t as int (0 = success); nothing is waited for.  Every product of
+// the axes runs but parts with a spatial radius, which is hipErrorInvalidValue before anything is enqueued.
+int Launch(void* stream, const Job& j, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]);
 
 }  // namespace rtdn
 
@@ -103,6 +100,8 @@ struct rt_denoise_params;
 struct rt_shard_frame;
 struct rt_temporal_params;
 namespace rtdn {
+// Where row y of the image's row range starts in the gathered parts, in pixels: the host twins' reading of the mapping.
+size_t PartsRowStart(const ShardLayout& parts, uint32_t W, uint32_t y);
 int CheckShardParts(const char* who, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P);
 int CheckShardFrame(const char* who, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
                     bool devicePointers, rtd::DenoiseParams* P, rtd::TemporalParams* T, rtd::TemporalGeom* G);

@@ -117,12 +117,7 @@ static void TemporalRun(const float* hdr, const float* sq, uint32_t n, const flo
     const bool spatial = V.source == rtd::kVarianceSpatial;
     if (spatial) rtdn::PrepareSpatialHost(hdr, n, feat8, m, W, num_rows, P, V.radius, a, g);
     for (uint32_t ly = 0; ly < num_rows; ++ly) {
-        size_t row = (size_t)ly * W;  // where the row's current-frame pixels start
-        if (parts) {
-            uint32_t shard, lr;
-            rtd::rowset_locate(parts->blockRows, parts->nshards, ly, shard, lr);
-            row = ((size_t)shard * parts->rowsMax + lr) * W;
-        }
+        const size_t row = parts ? rtdn::PartsRowStart(*parts, W, ly) : (size_t)ly * W;  // where the row's current-frame pixels start
         for (uint32_t x = 0; x < W; ++x) {
             const size_t p = (size_t)ly * W + x, src = row + x;
             rtd::DenoiseState s;
@@ -203,15 +198,10 @@ static int TemporalHost(const char* who, const float* hdr, const float* sq, uint
     const rtd::TemporalGeom G{W, H, first_row, num_rows};
     if (!rtd::temporal_geom_ok(G) || (uint64_t)first_row + num_rows > H || (uint64_t)W * num_rows > (1ull << 31))
         return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": empty or too large strip, or rows beyond the image");
-    rt_denoise_params def;
-    rt_denoise_default_params(&def);
-    if (!params) params = &def;
-    const rtd::DenoiseParams P{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
-    if (!rtd::denoise_params_ok(P))
-        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
+    rtd::DenoiseParams P{};
     rtd::TemporalParams T{};
-    const int rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &T);
-    if (rc != RT_OK) return rc;
+    int rc = rtdn::CheckDenoiseParams(who, params, &P);
+    if (rc != RT_OK || (rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &T)) != RT_OK) return rc;
     if (spatial && n == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the strips hold no sample");
     if (!spatial && n < 2) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the noise estimate needs at least 2 samples per pixel");
     if (m == 0) return Fail(RT_ERR_SEQUENCE, std::string(who) + ": the feature strips hold no sample");

@@ -1440,21 +1440,10 @@ int rt_clear_features(rt_ctx* ctx) {
 }
 
 // ---------------------------------------------------------------- denoise (rt_denoise.h; kernels and launcher: rt_denoise.hip)
-// Readers of hdr, sq and feat that write strips of their own: no sequencing state of rt_render or rt_render_features changes.  The
-// three entries share what follows and differ in where their inputs come from and in the rtdn::Launch* they call; their messages
-// carry their own name in front, and every refusal comes before the first change of state.
-// (moments: the variance comes from the strip of second moments -- the switch on, n >= 2; else from the picture itself, n >= 1)
-static int DenoiseParamsReady(rt_ctx* ctx, const char* who, const rt_denoise_params* params, rtd::DenoiseParams* P, bool moments = true) {
-    const int rc = moments ? NoiseReady(ctx, who, 2) : PictureReady(ctx, who);
-    if (rc != RT_OK) return rc;
-    rt_denoise_params def;
-    rt_denoise_default_params(&def);
-    if (!params) params = &def;
-    *P = rtd::DenoiseParams{params->levels, params->k_normal, params->k_depth, params->k_albedo, params->k_coverage, params->k_colour, params->var_floor};
-    if (!rtd::denoise_params_ok(*P))
-        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": levels must be 1..5, every k and var_floor finite and >= 0, var_floor > 0");
-    return RT_OK;
-}
+// Readers of hdr, sq and feat that write strips of their own: no sequencing state of rt_render or rt_render_features changes.  An
+// entry makes its checks and describes what they leave as a DenoiseCall -- DescribePicture for the context's own picture,
+// DescribeParts for gathered parts -- and DenoiseRun does the rest; the messages carry the entry's own name in front, and every refusal
+// comes before the first change of state.
 // "The picture is ready for the filter": the context's accumulation is a row range with feature strips of the same picture.
 static int DenoisePictureReady(const rt_ctx* ctx, const char* who) {
     if (ctx->seq.pic.rs.nshards != 1)
@@ -1485,13 +1474,6 @@ static int DenoiseStrips(rt_ctx* ctx, uint32_t W, uint32_t rows, bool guides, rt
     S->denVar = ctx->denVar.ptr;
     return RT_OK;
 }
-static void DenoiseInputsOfPicture(const rt_ctx* ctx, rtdn::Strips* S) {
-    S->hdr = ctx->hdr.ptr;
-    S->sq = ctx->sq.ptr;
-    S->feat = ctx->feat.ptr;
-    S->n = ctx->seq.accumulated;
-    S->m = ctx->featCount;
-}
 // "Time, launch the resolve, publish", on either side of the entry's own launch (launched: what it returned, a hipError_t as int).
 static int DenoiseBegin(rt_ctx* ctx, double* out_ms) {
     ctx->denValid = false;  // the strips are being rewritten
@@ -1512,160 +1494,177 @@ static int DenoiseFinish(rt_ctx* ctx, const char* who, const rtdn::Strips& S, in
     return RT_OK;
 }
 
-int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms) {
-    rtd::DenoiseParams P{};
-    int rc = DenoiseParamsReady(ctx, "rt_denoise", params, &P);
-    if (rc != RT_OK || (rc = DenoisePictureReady(ctx, "rt_denoise")) != RT_OK) return rc;
-    rtdn::Strips S{};
-    int knob;
-    if ((rc = DenoiseStrips(ctx, ctx->seq.pic.W, ctx->seq.rows, true, &S, &knob)) != RT_OK) return rc;
-    DenoiseInputsOfPicture(ctx, &S);
-    if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
-    return DenoiseFinish(ctx, "rt_denoise", S, rtdn::LaunchDenoise(ctx->stream, S, P, knob, ctx->denForms), out_ms);
-}
-
-// rt_denoise with the variance source chosen: the moments source is rt_denoise; the spatial one differs in what it asks of the picture
-// and in its prepare pass, which does not read sq.
-int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_params* params, const rt_variance_params* vparams, double* out_ms) {
-    const char* who = "rt_denoise_variance";
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
-    rtd::VarianceParams V{};
-    int rc = rtdn::CheckVarianceParams(who, vparams, &V);
-    if (rc != RT_OK) return rc;
-    if (V.source == rtd::kVarianceMoments) return rt_denoise(ctx, params, out_ms);
-    rtd::DenoiseParams P{};
-    if ((rc = DenoiseParamsReady(ctx, who, params, &P, false)) != RT_OK || (rc = DenoisePictureReady(ctx, who)) != RT_OK) return rc;
-    rtdn::Strips S{};
-    int knob;
-    if ((rc = DenoiseStrips(ctx, ctx->seq.pic.W, ctx->seq.rows, true, &S, &knob)) != RT_OK) return rc;
-    DenoiseInputsOfPicture(ctx, &S);
-    S.sq = nullptr;
-    if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
-    return DenoiseFinish(ctx, who, S, rtdn::LaunchDenoiseSpatial(ctx->stream, S, P, V.radius, CommittedWord(ctx), knob, ctx->denForms), out_ms);
-}
-
-// The same filter over the gathered parts of a row-sharded picture: only the denoiser's own strips of the context are touched.
-int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise_params* params, double* out_ms) {
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_denoise_shards: null ctx");
-    rtd::DenoiseParams P{};
-    int rc = rtdn::CheckShardParts("rt_denoise_shards", parts, params, true, &P);
-    if (rc != RT_OK) return rc;
-    RT_HIP(hipSetDevice(ctx->device));
-    rtdn::Strips S{};
-    int knob;
-    if ((rc = DenoiseStrips(ctx, parts->W, parts->rs.num_rows, true, &S, &knob)) != RT_OK) return rc;
-    S.hdr = static_cast<const float*>(parts->hdr);
-    S.sq = static_cast<const float*>(parts->sq);
-    S.feat = static_cast<const float*>(parts->feat);
-    S.n = parts->n;
-    S.m = parts->m;
-    const rtdn::ShardLayout layout{parts->rows_max, parts->rs.block_rows, parts->rs.nshards};
-    if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
-    return DenoiseFinish(ctx, "rt_denoise_shards", S, rtdn::LaunchDenoiseShards(ctx->stream, S, layout, P, knob, ctx->denForms), out_ms);
-}
-
-// rt_denoise with the temporal step in its prepare pass (rt_temporal.h).  The history is the context's: set tmpCur is read, the other
-// set is written and becomes tmpCur once everything is enqueued.  Every refusal comes before the first change: the entries make their
-// checks (DenoiseTemporal for the context's own picture, rt_denoise_shards_temporal for gathered parts) and TemporalStep does the rest.
-// What the checks leave of a call: the picture the history is keyed with, its row range, the current frame's inputs -- in image order
-// (parts == NULL) or as gathered parts -- and camera, and the parameters.
-struct TemporalCall {
+// What the checks leave of a call, along the launcher's three axes (host/rt_denoise_launch.h): the current frame's inputs of a W x rows
+// picture -- in image order, or as gathered parts (parts) --, the variance source, and the temporal step's part, filled only where
+// temporal: the picture the history is keyed with, its row range, the ids, the camera and the fetch.
+struct DenoiseCall {
+    uint32_t W, rows;
+    const float *hdr, *sq, *feat;
+    uint32_t n, m;
+    rtdn::ShardLayout layout;   // gathered parts where nshards != 0 (the checks refuse 0 there), else image order
+    rtd::DenoiseParams P;
+    uint32_t spatialRadius;     // 0: v0 from the moments; else the spatial source's radius
+    const uint32_t* committed;  // the spatial pass's device-side sample count, or NULL (CommittedWord)
+    bool temporal;
     rtseq::PictureKey pic;
     rtd::TemporalGeom geom;
-    const float *hdr, *sq, *feat;
     const uint32_t* ids;
-    uint32_t n, m;
-    const rtdn::ShardLayout* parts;
     rtd::TemporalCam cam;
-    rtd::DenoiseParams P;
     rtd::TemporalParams T;
     uint32_t fetch;
-    uint32_t spatialRadius;     // 0: v0 from the moments; else the spatial source's radius (contiguous calls only)
-    const uint32_t* committed;  // the spatial pass's device-side sample count, or NULL (CommittedWord)
 };
-static int TemporalStep(rt_ctx* ctx, const char* who, const TemporalCall& c, double* out_ms) {
+// The history is the context's: set tmpCur is read, the other set is written and becomes tmpCur once everything is enqueued.
+static int DenoiseRun(rt_ctx* ctx, const char* who, const DenoiseCall& c, double* out_ms) {
     int rc;
-    const rtseq::PictureKey& pic = c.pic;
-    const uint32_t W = c.geom.W, rows = c.geom.num_rows;
-    const uint32_t fetch = c.fetch;
-    const size_t npix = (size_t)W * rows;
-    const bool hasPrev = ctx->tmpValid && ctx->tmpPic == pic;
-    if (!hasPrev) ctx->tmpValid = false;  // (a Reserve below may let the old sets go: they were of another picture)
-    for (auto& t : ctx->tmpSet)
-        if ((rc = t.state.Reserve(npix * 4)) != RT_OK || (rc = t.guide[0].Reserve(npix * 4)) != RT_OK || (rc = t.guide[1].Reserve(npix * 4)) != RT_OK ||
-            (rc = t.ids.Reserve(npix)) != RT_OK || (rc = t.len.Reserve(npix)) != RT_OK)
-            return rc;
-    if ((rc = ctx->tmpTarget.Reserve(npix)) != RT_OK) return rc;
-    rtdn::Strips S{};
+    const size_t npix = (size_t)c.W * c.rows;
+    const bool hasPrev = c.temporal && ctx->tmpValid && ctx->tmpPic == c.pic;
+    if (c.temporal) {
+        if (!hasPrev) ctx->tmpValid = false;  // (a Reserve below may let the old sets go: they were of another picture)
+        for (auto& t : ctx->tmpSet)
+            if ((rc = t.state.Reserve(npix * 4)) != RT_OK || (rc = t.guide[0].Reserve(npix * 4)) != RT_OK || (rc = t.guide[1].Reserve(npix * 4)) != RT_OK ||
+                (rc = t.ids.Reserve(npix)) != RT_OK || (rc = t.len.Reserve(npix)) != RT_OK)
+                return rc;
+        if ((rc = ctx->tmpTarget.Reserve(npix)) != RT_OK) return rc;
+    }
+    rtdn::Job J{};
+    rtdn::Strips& S = J.strips;
     int knob;
-    if ((rc = DenoiseStrips(ctx, W, rows, c.spatialRadius != 0, &S, &knob)) != RT_OK) return rc;  // (the spatial pass writes the guide strips)
+    // (the guide strips: the temporal pass writes its history's instead, unless a spatial pass writes them for it to read)
+    if ((rc = DenoiseStrips(ctx, c.W, c.rows, !c.temporal || c.spatialRadius != 0, &S, &knob)) != RT_OK) return rc;
     S.hdr = c.hdr;
     S.sq = c.sq;
     S.feat = c.feat;
     S.n = c.n;
     S.m = c.m;
-    const rtd::DenoiseParams& P = c.P;
+    J.parts = c.layout.nshards != 0 ? &c.layout : nullptr;
+    J.spatialRadius = c.spatialRadius;
+    J.committed = c.committed;
     rtdn::Temporal Q{};
-    Q.ids = c.ids;
-    Q.geom = c.geom;
-    Q.cam = c.cam;
-    Q.camPrev = hasPrev ? ctx->tmpCam : Q.cam;
-    Q.params = c.T;
-    Q.fetch = fetch;
-    Q.hasPrev = hasPrev;
-    const uint32_t cur = ctx->tmpCur & 1u, nxt = cur ^ 1u;
-    const auto setOf = [](rt_ctx::TemporalSet& t) { return rtdn::TemporalSet{t.state.ptr, {t.guide[0].ptr, t.guide[1].ptr}, t.ids.ptr, t.len.ptr}; };
-    Q.prev = setOf(ctx->tmpSet[cur]);
-    Q.next = setOf(ctx->tmpSet[nxt]);
-    Q.target = ctx->tmpTarget.ptr;
-    ctx->tmpValid = false;  // the history is being rewritten, until everything is enqueued
+    const uint32_t nxt = (ctx->tmpCur & 1u) ^ 1u;
+    if (c.temporal) {
+        Q.ids = c.ids;
+        Q.geom = c.geom;
+        Q.cam = c.cam;
+        Q.camPrev = hasPrev ? ctx->tmpCam : Q.cam;
+        Q.params = c.T;
+        Q.fetch = c.fetch;
+        Q.hasPrev = hasPrev;
+        const auto setOf = [](rt_ctx::TemporalSet& t) { return rtdn::TemporalSet{t.state.ptr, {t.guide[0].ptr, t.guide[1].ptr}, t.ids.ptr, t.len.ptr}; };
+        Q.prev = setOf(ctx->tmpSet[nxt ^ 1u]);
+        Q.next = setOf(ctx->tmpSet[nxt]);
+        Q.target = ctx->tmpTarget.ptr;
+        J.temporal = &Q;
+        ctx->tmpValid = false;  // the history is being rewritten, until everything is enqueued
+    }
     if ((rc = DenoiseBegin(ctx, out_ms)) != RT_OK) return rc;
-    const int launched = c.parts           ? rtdn::LaunchDenoiseShardsTemporal(ctx->stream, S, *c.parts, Q, P, knob, ctx->denForms)
-                         : c.spatialRadius ? rtdn::LaunchDenoiseTemporalSpatial(ctx->stream, S, Q, P, c.spatialRadius, c.committed, knob, ctx->denForms)
-                                           : rtdn::LaunchDenoiseTemporal(ctx->stream, S, Q, P, knob, ctx->denForms);
-    if ((rc = DenoiseFinish(ctx, who, S, launched, out_ms)) != RT_OK) return rc;
+    if ((rc = DenoiseFinish(ctx, who, S, rtdn::Launch(ctx->stream, J, c.P, knob, ctx->denForms), out_ms)) != RT_OK || !c.temporal) return rc;
     ctx->tmpCur = nxt;
-    ctx->tmpPic = pic;
-    ctx->tmpCam = Q.cam;
+    ctx->tmpPic = c.pic;
+    ctx->tmpCam = c.cam;
     ctx->tmpValid = true;
     return RT_OK;
 }
 
-// (who: the entry's name for the messages; fetch: which prepare kernel reads the history, and whose defaults tparams == NULL takes)
-// (spatialRadius: 0, or the radius of the spatial variance source, under which the noise switch and a second sample are not asked for)
-static int DenoiseTemporal(rt_ctx* ctx, const char* who, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms,
-                           uint32_t spatialRadius = 0) {
-    TemporalCall c{};
-    int rc = DenoiseParamsReady(ctx, who, params, &c.P, spatialRadius == 0);
-    if (rc != RT_OK) return rc;
-    if ((rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &c.T)) != RT_OK) return rc;
+// The context's own picture.  (spatialRadius: 0 -- the variance comes from the strip of second moments: the switch on, n >= 2 -- or the
+// radius of the spatial source, which reads the picture itself: n >= 1, sq not read)
+// (temporal: with the temporal step; fetch: which prepare kernel reads the history, and whose defaults tparams == NULL takes)
+static int DescribePicture(rt_ctx* ctx, const char* who, const rt_denoise_params* params, uint32_t spatialRadius, bool temporal,
+                           const rt_temporal_params* tparams, uint32_t fetch, DenoiseCall* c) {
+    *c = DenoiseCall{};
+    int rc = spatialRadius != 0 ? PictureReady(ctx, who) : NoiseReady(ctx, who, 2);
+    if (rc != RT_OK || (rc = rtdn::CheckDenoiseParams(who, params, &c->P)) != RT_OK) return rc;
+    if (temporal && (rc = rtdn::CheckTemporalParamsFetch(who, tparams, fetch, &c->T)) != RT_OK) return rc;
     if ((rc = DenoisePictureReady(ctx, who)) != RT_OK) return rc;
-    c.pic = ctx->seq.pic;
-    c.geom = rtd::TemporalGeom{c.pic.W, c.pic.H, c.pic.rs.first_row, ctx->seq.rows};
-    if (!rtd::temporal_geom_ok(c.geom) || ctx->seq.rows != c.pic.rs.num_rows)
-        return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a picture wider or taller than 2^24, or a strip that is not its row range");
-    c.hdr = ctx->hdr.ptr;
-    c.sq = spatialRadius ? nullptr : ctx->sq.ptr;
-    c.spatialRadius = spatialRadius;
-    c.committed = spatialRadius ? CommittedWord(ctx) : nullptr;
-    c.feat = ctx->feat.ptr;
-    c.ids = ctx->featIds.ptr;
-    c.n = ctx->seq.accumulated;
-    c.m = ctx->featCount;
-    c.parts = nullptr;
-    const rtd::TraceParams& b = ctx->base;
-    rtd::temporal_cam(b.cam_o, b.cam_x, b.cam_y, b.cam_oip, c.cam);
-    c.fetch = fetch;
-    return TemporalStep(ctx, who, c, out_ms);
+    c->W = ctx->seq.pic.W;
+    c->rows = ctx->seq.rows;
+    if (temporal) {
+        c->temporal = true;
+        c->pic = ctx->seq.pic;
+        c->geom = rtd::TemporalGeom{c->pic.W, c->pic.H, c->pic.rs.first_row, ctx->seq.rows};
+        if (!rtd::temporal_geom_ok(c->geom) || ctx->seq.rows != c->pic.rs.num_rows)
+            return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a picture wider or taller than 2^24, or a strip that is not its row range");
+        c->ids = ctx->featIds.ptr;
+        const rtd::TraceParams& b = ctx->base;
+        rtd::temporal_cam(b.cam_o, b.cam_x, b.cam_y, b.cam_oip, c->cam);
+        c->fetch = fetch;
+    }
+    c->hdr = ctx->hdr.ptr;
+    c->sq = spatialRadius != 0 ? nullptr : ctx->sq.ptr;
+    c->feat = ctx->feat.ptr;
+    c->n = ctx->seq.accumulated;
+    c->m = ctx->featCount;
+    c->spatialRadius = spatialRadius;
+    c->committed = spatialRadius != 0 ? CommittedWord(ctx) : nullptr;
+    return RT_OK;
 }
 
+// The gathered parts of a row-sharded picture; only the denoiser's own strips of the context (and the history) are touched.  With the
+// temporal step the caller passes its frame and no parts: the frame's parts are then the parts, and it brings what DescribePicture takes
+// from the context -- the ids, the image's height, the camera; the history is keyed with the parts' row set, shard 0: a contiguous call's
+// key where nshards == 1.  (Neither: "null argument", the refusal of both checks for a missing record.)
+static int DescribeParts(rt_ctx* ctx, const char* who, const rt_shard_parts* parts, const rt_shard_frame* frame, const rt_denoise_params* params,
+                         const rt_temporal_params* tparams, uint32_t fetch, DenoiseCall* c) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    *c = DenoiseCall{};
+    const int rc = frame ? rtdn::CheckShardFrame(who, frame, params, tparams, fetch, true, &c->P, &c->T, &c->geom)
+                         : rtdn::CheckShardParts(who, parts, params, true, &c->P);
+    if (rc != RT_OK) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    if (frame) {
+        parts = &frame->parts;
+        c->temporal = true;
+        c->pic = rtseq::PictureKey{parts->W, frame->H, parts->rs};
+        c->pic.rs.shard = 0;
+        c->ids = static_cast<const uint32_t*>(frame->ids);
+        c->cam = rtdn::CamOf(frame->camera);
+        c->fetch = fetch;
+    }
+    c->W = parts->W;
+    c->rows = parts->rs.num_rows;
+    c->hdr = static_cast<const float*>(parts->hdr);
+    c->sq = static_cast<const float*>(parts->sq);
+    c->feat = static_cast<const float*>(parts->feat);
+    c->n = parts->n;
+    c->m = parts->m;
+    c->layout = rtdn::ShardLayout{parts->rows_max, parts->rs.block_rows, parts->rs.nshards};
+    return RT_OK;
+}
+
+// The entry behind the five of the context's own picture.
+static int DenoisePicture(rt_ctx* ctx, const char* who, const rt_denoise_params* params, uint32_t spatialRadius, bool temporal,
+                          const rt_temporal_params* tparams, uint32_t fetch, double* out_ms) {
+    DenoiseCall c;
+    const int rc = DescribePicture(ctx, who, params, spatialRadius, temporal, tparams, fetch, &c);
+    return rc != RT_OK ? rc : DenoiseRun(ctx, who, c, out_ms);
+}
+
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, double* out_ms) { return DenoisePicture(ctx, "rt_denoise", params, 0, false, nullptr, 0, out_ms); }
+
+// rt_denoise with the variance source chosen: the moments source is rt_denoise.
+int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_params* params, const rt_variance_params* vparams, double* out_ms) {
+    const char* who = "rt_denoise_variance";
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    rtd::VarianceParams V{};
+    const int rc = rtdn::CheckVarianceParams(who, vparams, &V);
+    if (rc != RT_OK) return rc;
+    if (V.source == rtd::kVarianceMoments) return rt_denoise(ctx, params, out_ms);
+    return DenoisePicture(ctx, who, params, V.radius, false, nullptr, 0, out_ms);
+}
+
+int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise_params* params, double* out_ms) {
+    DenoiseCall c;
+    const int rc = DescribeParts(ctx, "rt_denoise_shards", parts, nullptr, params, nullptr, 0, &c);
+    return rc != RT_OK ? rc : DenoiseRun(ctx, "rt_denoise_shards", c, out_ms);
+}
+
+// rt_denoise with the temporal step in its prepare pass (rt_temporal.h) ...
 int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, double* out_ms) {
-    return DenoiseTemporal(ctx, "rt_denoise_temporal", params, tparams, RT_TEMPORAL_FETCH_NEAREST, out_ms);
+    return DenoisePicture(ctx, "rt_denoise_temporal", params, 0, true, tparams, RT_TEMPORAL_FETCH_NEAREST, out_ms);
 }
 
-// The same call with the way the history is fetched chosen: 1 runs the kernel above, 4 the bilinear one; the history is one state.
+// ... with the way the history is fetched chosen: 1 runs the nearest kernel, 4 the bilinear one; the history is one state ...
 int rt_denoise_temporal_fetch(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch, double* out_ms) {
-    return DenoiseTemporal(ctx, "rt_denoise_temporal_fetch", params, tparams, fetch, out_ms);
+    return DenoisePicture(ctx, "rt_denoise_temporal_fetch", params, 0, true, tparams, fetch, out_ms);
 }
 
 // ... and with the variance source chosen: the moments source is the entry above.
@@ -1677,34 +1676,14 @@ int rt_denoise_temporal_variance(rt_ctx* ctx, const rt_denoise_params* params, c
     const int rc = rtdn::CheckVarianceParams(who, vparams, &V);
     if (rc != RT_OK) return rc;
     if (V.source == rtd::kVarianceMoments) return rt_denoise_temporal_fetch(ctx, params, tparams, fetch, out_ms);
-    return DenoiseTemporal(ctx, who, params, tparams, fetch, out_ms, V.radius);
+    return DenoisePicture(ctx, who, params, V.radius, true, tparams, fetch, out_ms);
 }
 
-// The same step over the gathered parts of a row-sharded picture: the frame brings what DenoiseTemporal takes from the context (the
-// inputs, the ids, the image's height, the camera), and the history is keyed with the parts' row set, shard 0 -- a contiguous call's
-// key where nshards == 1.  Only the denoiser's strips and the history are touched.
 int rt_denoise_shards_temporal(rt_ctx* ctx, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
                                double* out_ms) {
-    const char* who = "rt_denoise_shards_temporal";
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
-    TemporalCall c{};
-    const int rc = rtdn::CheckShardFrame(who, frame, params, tparams, fetch, true, &c.P, &c.T, &c.geom);
-    if (rc != RT_OK) return rc;
-    RT_HIP(hipSetDevice(ctx->device));
-    const rt_shard_parts& parts = frame->parts;
-    c.pic = rtseq::PictureKey{parts.W, frame->H, parts.rs};
-    c.pic.rs.shard = 0;
-    c.hdr = static_cast<const float*>(parts.hdr);
-    c.sq = static_cast<const float*>(parts.sq);
-    c.feat = static_cast<const float*>(parts.feat);
-    c.ids = static_cast<const uint32_t*>(frame->ids);
-    c.n = parts.n;
-    c.m = parts.m;
-    const rtdn::ShardLayout layout{parts.rows_max, parts.rs.block_rows, parts.rs.nshards};
-    c.parts = &layout;
-    c.cam = rtdn::CamOf(frame->camera);
-    c.fetch = fetch;
-    return TemporalStep(ctx, who, c, out_ms);
+    DenoiseCall c;
+    const int rc = DescribeParts(ctx, "rt_denoise_shards_temporal", nullptr, frame, params, tparams, fetch, &c);
+    return rc != RT_OK ? rc : DenoiseRun(ctx, "rt_denoise_shards_temporal", c, out_ms);
 }
 
 int rt_temporal_reset(rt_ctx* ctx) {

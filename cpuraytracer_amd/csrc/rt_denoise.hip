@@ -1,54 +1,65 @@
 // rt_denoise.hip -- the denoiser's kernels and their launcher (DESIGN.md "Denoise"; arithmetic: rt_denoise.h).  A translation unit
-// of its own: rt_capi.hip calls LaunchDenoise (host/rt_denoise_launch.h) and holds none of this device code.
+// of its own: rt_capi.hip calls rtdn::Launch (host/rt_denoise_launch.h) and holds none of this device code.
 #include <hip/hip_runtime.h>
 
 #include "host/rt_denoise_launch.h"
 
 namespace rtd {
 
-// One pass over the strip: the state (c.rgb, v) as one float4, the guides as two float4 planes.
+// The three pieces every prepare pass is made of.  The inputs of a pixel of the current frame, read where they lie (p): hdr and sq as
+// three floats each, feat as two float4 -- what denoise_prepare forms the state (c.rgb, v) and the guides from ...
+__device__ __forceinline__ void load_pixel(const float* __restrict__ hdr, const float* __restrict__ sq, const float4* __restrict__ feat, const size_t p,
+                                           float h[3], float q[3], float f[8]) {
+    h[0] = hdr[3 * p], h[1] = hdr[3 * p + 1], h[2] = hdr[3 * p + 2];
+    q[0] = sq[3 * p], q[1] = sq[3 * p + 1], q[2] = sq[3 * p + 2];
+    const float4 fa = feat[2 * p], fb = feat[2 * p + 1];
+    f[0] = fa.x, f[1] = fa.y, f[2] = fa.z, f[3] = fa.w, f[4] = fb.x, f[5] = fb.y, f[6] = fb.z, f[7] = fb.w;
+}
+// ... a prepared pixel written in image order (o): the state as one float4, the guides as two float4 planes ...
+__device__ __forceinline__ void store_pixel(float4* __restrict__ state, float4* __restrict__ g0, float4* __restrict__ g1, const size_t o,
+                                            const DenoiseState& s, const float g[8]) {
+    state[o] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
+    g0[o] = make_float4(g[0], g[1], g[2], g[3]);
+    g1[o] = make_float4(g[4], g[5], g[6], g[7]);
+}
+// ... and where the current-frame inputs of IMAGE pixel pix lie in the gathered parts of a row-sharded picture: in the part and the
+// local row that hold its row (rt_rowset_map.h).  A row is contiguous inside its part, so the lanes of a wave still read contiguous
+// segments.  Rows of a part beyond its shard's own (the gather's padding) belong to no image row and are never read.  The result is
+// < nshards * rowsMax * W: lr < rowsMax for every row of the range (rowset_max_shard_rows, checked by the caller).
+__device__ __forceinline__ size_t parts_source(const rtdn::ShardLayout& L, const uint32_t W, const uint32_t pix) {
+    const uint32_t y = pix / W, x = pix - y * W;
+    uint32_t shard, lr;
+    rowset_locate(L.blockRows, L.nshards, y, shard, lr);
+    return ((size_t)shard * L.rowsMax + lr) * W + x;
+}
+
+// One pass, a thread per pixel of the strip (kParts: of the IMAGE, its inputs read through the mapping): state, g0, g1 in image order,
+// so the levels run on them unchanged.
+template <bool kParts>
+__device__ __forceinline__ void prepare_pass(const float* __restrict__ hdr, const float* __restrict__ sq, const float4* __restrict__ feat, uint32_t W,
+                                             uint32_t npix, const rtdn::ShardLayout& L, uint32_t n, uint32_t m, float4* __restrict__ state,
+                                             float4* __restrict__ g0, float4* __restrict__ g1) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= npix) return;
+    DenoiseState s;
+    float g[8];
+    float h[3], q[3], f[8];
+    load_pixel(hdr, sq, feat, kParts ? parts_source(L, W, pix) : (size_t)pix, h, q, f);
+    denoise_prepare(h, q, n, f, m, s, g);
+    store_pixel(state, g0, g1, pix, s, g);
+}
+
 __global__ void __launch_bounds__(256) rt_denoise_prepare_kernel(const float* __restrict__ hdr, const float* __restrict__ sq,
                                                                  const float4* __restrict__ feat, uint32_t npix, uint32_t n, uint32_t m,
                                                                  float4* __restrict__ state, float4* __restrict__ g0, float4* __restrict__ g1) {
-    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= npix) return;
-    const size_t p = pix;
-    const float h[3] = {hdr[3 * p], hdr[3 * p + 1], hdr[3 * p + 2]};
-    const float q[3] = {sq[3 * p], sq[3 * p + 1], sq[3 * p + 2]};
-    const float4 fa = feat[2 * p], fb = feat[2 * p + 1];
-    const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
-    DenoiseState s;
-    float g[8];
-    denoise_prepare(h, q, n, f, m, s, g);
-    state[p] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
-    g0[p] = make_float4(g[0], g[1], g[2], g[3]);
-    g1[p] = make_float4(g[4], g[5], g[6], g[7]);
+    prepare_pass<false>(hdr, sq, feat, 0u, npix, rtdn::ShardLayout{}, n, m, state, g0, g1);
 }
 
-// The same pass over the gathered parts of a row-sharded picture (rt_denoise_shards): a thread owns pixel pix of the IMAGE, finds
-// the part and the local row that hold its row (rt_rowset_map.h) and writes state, g0, g1 in image order, so the levels run on them
-// unchanged.  A row is contiguous inside its part: the lanes of a wave still read contiguous segments.  Rows of a part beyond its
-// shard's own (the gather's padding) belong to no image row and are never read.
 __global__ void __launch_bounds__(256) rt_denoise_prepare_shards_kernel(const float* __restrict__ hdr, const float* __restrict__ sq,
                                                                         const float4* __restrict__ feat, uint32_t W, uint32_t npix, uint32_t rowsMax,
                                                                         uint32_t blockRows, uint32_t nshards, uint32_t n, uint32_t m,
                                                                         float4* __restrict__ state, float4* __restrict__ g0, float4* __restrict__ g1) {
-    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= npix) return;
-    const uint32_t y = pix / W, x = pix - y * W;
-    uint32_t shard, lr;
-    rowset_locate(blockRows, nshards, y, shard, lr);
-    const size_t p = ((size_t)shard * rowsMax + lr) * W + x;
-    const float h[3] = {hdr[3 * p], hdr[3 * p + 1], hdr[3 * p + 2]};
-    const float q[3] = {sq[3 * p], sq[3 * p + 1], sq[3 * p + 2]};
-    const float4 fa = feat[2 * p], fb = feat[2 * p + 1];
-    const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
-    DenoiseState s;
-    float g[8];
-    denoise_prepare(h, q, n, f, m, s, g);
-    state[pix] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
-    g0[pix] = make_float4(g[0], g[1], g[2], g[3]);
-    g1[pix] = make_float4(g[4], g[5], g[6], g[7]);
+    prepare_pass<true>(hdr, sq, feat, W, npix, rtdn::ShardLayout{rowsMax, blockRows, nshards}, n, m, state, g0, g1);
 }
 
 __device__ __forceinline__ void unpack(const float4 s, const float4 a, const float4 b, DenoiseState& st, float g[8]) {
@@ -57,12 +68,10 @@ __device__ __forceinline__ void unpack(const float4 s, const float4 a, const flo
     g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
 }
 
-// The temporal form of the prepare pass (rt_temporal.h): a thread owns pixel pix of the strip, prepares it through the unchanged
-// denoise_prepare, reprojects it into the history's camera, reads the history's pixel there -- one gathered read of a float4 state, two
-// float4 guide planes, an id and a length; neighbouring lanes are neighbouring pixels, so under small motion the gather is a row
-// segment shifted by a few pixels -- validates, blends and writes the blended state, the guides, the id, the length and the target
-// into the NEXT history set.  The current-frame reads and every write are contiguous row segments.  Nothing of the set that is read
-// is written: a pixel reads other pixels' history.  q < npix by temporal_reproject's bounds (xi < W, yi - first_row < num_rows).
+// The temporal form of the prepare pass (rt_temporal.h): a thread owns pixel pix of the strip, forms its state and guides, reprojects
+// it into the history's camera, reads the history there, validates, blends and writes the blended state, the guides, the id, the
+// length and the target into the NEXT history set.  The history sets, target and every write are in image order; the current-frame
+// reads and every write are contiguous row segments.  Nothing of the set that is read is written: a pixel reads other pixels' history.
 struct TemporalArgs {
     const float* __restrict__ hdr;
     const float* __restrict__ sq;
@@ -84,17 +93,42 @@ struct TemporalArgs {
     uint32_t* __restrict__ oLen;
     uint32_t* __restrict__ target;
 };
-
-// The planes a spatial prepare pass (rt_denoise_prepare_spatial_kernel below) wrote, in image order: the prepared forms of the two
-// passes read (c0, v0) and g there instead of forming them from hdr, sq and feat.
+// What the two other kinds of input add to the arguments.  Prepared: the planes a spatial prepare pass (rt_denoise_prepare_spatial_kernel
+// below) wrote, in image order -- (c0, v0) and g are read there, hdr, sq and feat are not read.  Parts: the layout of the gathered
+// parts, where hdr, sq, feat and ids of the current frame are read through parts_source.
 struct PreparedPlanes {
     const float4* __restrict__ s;
     const float4* __restrict__ g0;
     const float4* __restrict__ g1;
 };
+struct TemporalPreparedArgs {
+    TemporalArgs A;
+    PreparedPlanes Q;
+};
+struct TemporalShardArgs {
+    TemporalArgs A;
+    rtdn::ShardLayout L;
+};
 
-// The pass's body, shared with the sharded form below: pix is the pixel of the strip (IMAGE order: every history read and every write),
-// p where its current-frame inputs lie -- pix itself, or its place in the gathered parts.
+// The pass has one body per fetch, called by the six kernels with pix, the pixel of the strip they guard (pix < npix), and p, where
+// its current-frame inputs lie: pix itself, or parts_source(pix) -- strips and parts differ in nothing else.  kPrepared: the pixel's
+// state and guides are read from the spatial pass's planes instead of formed from hdr, sq and feat.  A body begins with the pixel's id,
+// state and guides, ends with the writes into the next history set (temporal_end) and holds the history's answer in between.  The
+// two bodies, their beginnings and the kernels' guards are written out, not shared further: with them in shared functions four of the
+// six kernels were compiled to other instruction streams than the separately written kernels they replace
+// (profiles/denoise_refactor_codegen.txt); as they stand all six have those streams.
+
+__device__ __forceinline__ void temporal_end(const TemporalArgs& A, const uint32_t pix, const DenoiseState& s, const float g[8], const uint32_t id,
+                                             const uint32_t len, const uint32_t target) {
+    store_pixel(A.oS, A.oG0, A.oG1, pix, s, g);
+    A.oId[pix] = id;
+    A.oLen[pix] = len;
+    A.target[pix] = target;
+}
+
+// The nearest fetch: one gathered read of a float4 state, two float4 guide planes, an id and a length; neighbouring lanes are neighbouring pixels,
+// so under small motion the gather is a row segment shifted by a few pixels.  q < npix by temporal_reproject's bounds (xi < W,
+// yi - first_row < num_rows).
 template <bool kPrepared>
 __device__ __forceinline__ void temporal_prepare_nearest(const TemporalArgs& A, const PreparedPlanes& Q, const uint32_t pix, const size_t p) {
     DenoiseState s;
@@ -104,10 +138,8 @@ __device__ __forceinline__ void temporal_prepare_nearest(const TemporalArgs& A, 
         id = A.ids[p];
         unpack(Q.s[pix], Q.g0[pix], Q.g1[pix], s, g);
     } else {
-        const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
-        const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
-        const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
-        const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+        float h[3], q3[3], f[8];
+        load_pixel(A.hdr, A.sq, A.feat, p, h, q3, f);
         id = A.ids[p];
         denoise_prepare(h, q3, A.n, f, A.m, s, g);
     }
@@ -128,26 +160,14 @@ __device__ __forceinline__ void temporal_prepare_nearest(const TemporalArgs& A, 
             if (ok) target = q;
         }
     }
-    const size_t o = pix;
-    A.oS[o] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
-    A.oG0[o] = make_float4(g[0], g[1], g[2], g[3]);
-    A.oG1[o] = make_float4(g[4], g[5], g[6], g[7]);
-    A.oId[o] = id;
-    A.oLen[o] = len;
-    A.target[o] = target;
+    temporal_end(A, pix, s, g, id, len, target);
 }
 
-__global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const TemporalArgs A) {
-    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= A.npix) return;
-    temporal_prepare_nearest<false>(A, PreparedPlanes{}, pix, pix);
-}
-
-// The bilinear fetch (rt_temporal.h): the same pass, but the history is read at the four pixels around the reprojected point.  The two
-// taps of a row are adjacent (32 bytes per float4 plane) and under small motion a wave's taps are two row segments its lanes share.
-// All four taps' loads are issued before the first is used: a tap outside the strip loads the pixel's own index instead (pix < npix, a
-// contiguous read) and what it loaded is dropped, so no load waits for a test and none leaves the arrays -- a tap inside has q < npix by
-// temporal_tap_index.  Only taps that take part are added (temporal_gather_tap).  Writes as in the nearest kernel.
+// The bilinear fetch (rt_temporal.h): the history is read at the four pixels around the reprojected point.  The two taps of a row are adjacent
+// (32 bytes per float4 plane) and under small motion a wave's taps are two row segments its lanes share.  All four taps' loads are
+// issued before the first is used: a tap outside the strip loads the pixel's own index instead (pix < npix, a contiguous read) and what
+// it loaded is dropped, so no load waits for a test and none leaves the arrays -- a tap inside has its index < npix by
+// temporal_tap_index.  Only taps that take part are added (temporal_gather_tap).
 template <bool kPrepared>
 __device__ __forceinline__ void temporal_prepare_bilinear(const TemporalArgs& A, const PreparedPlanes& Q, const uint32_t pix, const size_t p) {
     DenoiseState s;
@@ -157,10 +177,8 @@ __device__ __forceinline__ void temporal_prepare_bilinear(const TemporalArgs& A,
         id = A.ids[p];
         unpack(Q.s[pix], Q.g0[pix], Q.g1[pix], s, g);
     } else {
-        const float h[3] = {A.hdr[3 * p], A.hdr[3 * p + 1], A.hdr[3 * p + 2]};
-        const float q3[3] = {A.sq[3 * p], A.sq[3 * p + 1], A.sq[3 * p + 2]};
-        const float4 fa = A.feat[2 * p], fb = A.feat[2 * p + 1];
-        const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+        float h[3], q3[3], f[8];
+        load_pixel(A.hdr, A.sq, A.feat, p, h, q3, f);
         id = A.ids[p];
         denoise_prepare(h, q3, A.n, f, A.m, s, g);
     }
@@ -206,68 +224,38 @@ __device__ __forceinline__ void temporal_prepare_bilinear(const TemporalArgs& A,
             if (ok) target = S.target;
         }
     }
-    const size_t o = pix;
-    A.oS[o] = make_float4(s.c[0], s.c[1], s.c[2], s.v);
-    A.oG0[o] = make_float4(g[0], g[1], g[2], g[3]);
-    A.oG1[o] = make_float4(g[4], g[5], g[6], g[7]);
-    A.oId[o] = id;
-    A.oLen[o] = len;
-    A.target[o] = target;
+    temporal_end(A, pix, s, g, id, len, target);
 }
 
+__global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_kernel(const TemporalArgs A) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    temporal_prepare_nearest<false>(A, PreparedPlanes{}, pix, pix);
+}
 __global__ void __launch_bounds__(256) rt_denoise_prepare_temporal_bilinear_kernel(const TemporalArgs A) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= A.npix) return;
     temporal_prepare_bilinear<false>(A, PreparedPlanes{}, pix, pix);
 }
-
-// The two passes over a state the spatial prepare pass wrote (rt_denoise_temporal_variance under RT_VARIANCE_SPATIAL): the same bodies,
-// hdr, sq and feat not read.
-struct TemporalPreparedArgs {
-    TemporalArgs A;
-    PreparedPlanes Q;
-};
-
 __global__ void __launch_bounds__(256) rt_denoise_prepared_temporal_kernel(const TemporalPreparedArgs S) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= S.A.npix) return;
     temporal_prepare_nearest<true>(S.A, S.Q, pix, pix);
 }
-
 __global__ void __launch_bounds__(256) rt_denoise_prepared_temporal_bilinear_kernel(const TemporalPreparedArgs S) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= S.A.npix) return;
     temporal_prepare_bilinear<true>(S.A, S.Q, pix, pix);
 }
-
-// The two passes over the gathered parts of a row-sharded picture (rt_denoise_shards_temporal): a thread owns pixel pix of the IMAGE's
-// row range, finds the part and the local row that hold its row (rt_rowset_map.h, as rt_denoise_prepare_shards_kernel does) and reads
-// hdr, sq, feat and ids of the current frame there -- a row is contiguous inside its part, so the lanes of a wave still read contiguous
-// segments; padding rows belong to no image row and are never read.  Everything else is the body above at image-order indices: the
-// history sets are in image order, and so is the bilinear kernel's stand-in load for a tap outside the strip (the pixel's own index).
-// p < nshards * rowsMax * W by the mapping: lr < rowsMax for every row of the range (rowset_max_shard_rows, checked by the caller).
-struct TemporalShardArgs {
-    TemporalArgs A;
-    uint32_t rowsMax, blockRows, nshards;
-};
-
-__device__ __forceinline__ size_t temporal_shard_source(const TemporalShardArgs& S, const uint32_t pix) {
-    const uint32_t y = pix / S.A.G.W, x = pix - y * S.A.G.W;
-    uint32_t shard, lr;
-    rowset_locate(S.blockRows, S.nshards, y, shard, lr);
-    return ((size_t)shard * S.rowsMax + lr) * S.A.G.W + x;
-}
-
 __global__ void __launch_bounds__(256) rt_denoise_prepare_shards_temporal_kernel(const TemporalShardArgs S) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= S.A.npix) return;
-    temporal_prepare_nearest<false>(S.A, PreparedPlanes{}, pix, temporal_shard_source(S, pix));
+    temporal_prepare_nearest<false>(S.A, PreparedPlanes{}, pix, parts_source(S.L, S.A.G.W, pix));
 }
-
 __global__ void __launch_bounds__(256) rt_denoise_prepare_shards_temporal_bilinear_kernel(const TemporalShardArgs S) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= S.A.npix) return;
-    temporal_prepare_bilinear<false>(S.A, PreparedPlanes{}, pix, temporal_shard_source(S, pix));
+    temporal_prepare_bilinear<false>(S.A, PreparedPlanes{}, pix, parts_source(S.L, S.A.G.W, pix));
 }
 
 // One level.  Thread (tx, ty) of the 32 x 8 workgroup owns pixel (32 bx + tx, 8 by + ty); its 25 taps lie (a - 2) step rows and
@@ -426,34 +414,39 @@ __global__ void __launch_bounds__(256) rt_denoise_prepare_spatial_kernel(const f
 
 namespace rtdn {
 
+// A state and its two guide planes as the kernels take them.
+struct Planes {
+    float4 *s, *g0, *g1;
+};
+static Planes PlanesOf(void* state, void* const guide[2]) { return Planes{static_cast<float4*>(state), static_cast<float4*>(guide[0]), static_cast<float4*>(guide[1])}; }
+
 // The spatial prepare pass into the three planes (radius 1..3: the caller's check).
-static int LaunchPrepareSpatial(hipStream_t st, const Strips& s, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed, float4* state,
-                                float4* g0, float4* g1) {
+static int LaunchPrepareSpatial(hipStream_t st, const Strips& s, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed, const Planes& o) {
     const dim3 grid((s.W + kTileW - 1u) / kTileW, (s.rows + kTileH - 1u) / kTileH);
     const float4* feat = reinterpret_cast<const float4*>(s.feat);
     if (radius == 1u)
-        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<1>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, state, g0, g1);
+        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<1>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, o.s, o.g0, o.g1);
     else if (radius == 2u)
-        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<2>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, state, g0, g1);
+        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<2>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, o.s, o.g0, o.g1);
     else if (radius == 3u)
-        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<3>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, state, g0, g1);
+        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<3>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, o.s, o.g0, o.g1);
     else
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
 // The levels over the prepared state and guides of a W x rows picture in image order.
-// (first: level 0's input -- state[0] itself, or the temporal form's new history, which no level may overwrite)
-static int LaunchLevels(hipStream_t st, const Strips& s, const float4* first, const float4* g0, const float4* g1, const rtd::DenoiseParams& P, int stageKnob,
-                        uint32_t forms[rtd::kDenoiseMaxLevels]) {
+// (first: level 0's input -- the strips' own state[0] and guides, or the temporal form's new history, which no level may overwrite)
+static int LaunchLevels(hipStream_t st, const Strips& s, const Planes& first, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
     float4* state[2] = {static_cast<float4*>(s.state[0]), static_cast<float4*>(s.state[1])};
+    const float4 *g0 = first.g0, *g1 = first.g1;
     hipError_t e = hipSuccess;
     const dim3 grid((s.W + kTileW - 1u) / kTileW, (s.rows + kTileH - 1u) / kTileH);
     for (uint32_t l = 0; l < P.levels; ++l) {
         const uint32_t step = 1u << l;
         const bool staged = Staged(step, stageKnob), last = l + 1u == P.levels;
         const size_t lds = staged ? StageBytes(step) : 0;
-        const float4* in = l == 0 ? first : state[l & 1u];
+        const float4* in = l == 0 ? first.s : state[l & 1u];
         float4* out = state[(l + 1u) & 1u];
         if (staged && last)
             hipLaunchKernelGGL((rtd::rt_atrous_kernel<true, true>), grid, dim3(256), lds, st, in, g0, g1, s.W, s.rows, step, P, out, s.den, s.denVar);
@@ -470,32 +463,6 @@ static int LaunchLevels(hipStream_t st, const Strips& s, const float4* first, co
     return 0;
 }
 
-int LaunchDenoise(void* stream, const Strips& s, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint32_t npix = s.W * s.rows;
-    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
-    hipLaunchKernelGGL(rtd::rt_denoise_prepare_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, s.hdr, s.sq, reinterpret_cast<const float4*>(s.feat),
-                       npix, s.n, s.m, static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]), static_cast<float4*>(s.guide[1]));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    return LaunchLevels(st, s, static_cast<const float4*>(s.state[0]), static_cast<const float4*>(s.guide[0]), static_cast<const float4*>(s.guide[1]), P, stageKnob,
-                        forms);
-}
-
-int LaunchDenoiseShards(void* stream, const Strips& s, const ShardLayout& parts, const rtd::DenoiseParams& P, int stageKnob,
-                        uint32_t forms[rtd::kDenoiseMaxLevels]) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint32_t npix = s.W * s.rows;
-    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
-    hipLaunchKernelGGL(rtd::rt_denoise_prepare_shards_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, s.hdr, s.sq,
-                       reinterpret_cast<const float4*>(s.feat), s.W, npix, parts.rowsMax, parts.blockRows, parts.nshards, s.n, s.m,
-                       static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]), static_cast<float4*>(s.guide[1]));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    return LaunchLevels(st, s, static_cast<const float4*>(s.state[0]), static_cast<const float4*>(s.guide[0]), static_cast<const float4*>(s.guide[1]), P, stageKnob,
-                        forms);
-}
-
 static rtd::TemporalArgs TemporalArgsOf(const Strips& s, const Temporal& t) {
     rtd::TemporalArgs A{};
     A.hdr = s.hdr;
@@ -510,80 +477,54 @@ static rtd::TemporalArgs TemporalArgsOf(const Strips& s, const Temporal& t) {
     A.C = t.cam;
     A.Cp = t.camPrev;
     A.T = t.params;
-    A.hS = static_cast<const float4*>(t.prev.state);
-    A.hG0 = static_cast<const float4*>(t.prev.guide[0]);
-    A.hG1 = static_cast<const float4*>(t.prev.guide[1]);
+    const Planes h = PlanesOf(t.prev.state, t.prev.guide), o = PlanesOf(t.next.state, t.next.guide);
+    A.hS = h.s;
+    A.hG0 = h.g0;
+    A.hG1 = h.g1;
     A.hId = t.prev.ids;
     A.hLen = t.prev.len;
-    A.oS = static_cast<float4*>(t.next.state);
-    A.oG0 = static_cast<float4*>(t.next.guide[0]);
-    A.oG1 = static_cast<float4*>(t.next.guide[1]);
+    A.oS = o.s;
+    A.oG0 = o.g0;
+    A.oG1 = o.g1;
     A.oId = t.next.ids;
     A.oLen = t.next.len;
     A.target = t.target;
     return A;
 }
 
-int LaunchDenoiseTemporal(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
-                          uint32_t forms[rtd::kDenoiseMaxLevels]) {
+int Launch(void* stream, const Job& j, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
+    if (j.parts && j.spatialRadius != 0) return (int)hipErrorInvalidValue;  // (no spatial pass reads through the mapping)
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const Strips& s = j.strips;
     const uint32_t npix = s.W * s.rows;
+    const dim3 grid((npix + 255u) / 256u), block(256);
     for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
-    const rtd::TemporalArgs A = TemporalArgsOf(s, t);
-    if (t.fetch == rtd::kTemporalFetchBilinear)
-        hipLaunchKernelGGL(rtd::rt_denoise_prepare_temporal_bilinear_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, A);
-    else
-        hipLaunchKernelGGL(rtd::rt_denoise_prepare_temporal_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, A);
+    const Planes own = PlanesOf(s.state[0], s.guide);
+    Planes first = own;  // what the levels start from: the pass's outputs
+    if (j.spatialRadius != 0)
+        if (const int e = LaunchPrepareSpatial(st, s, P, j.spatialRadius, j.committed, own)) return e;
+    if (j.temporal) {
+        const rtd::TemporalArgs A = TemporalArgsOf(s, *j.temporal);
+        const bool bilinear = j.temporal->fetch == rtd::kTemporalFetchBilinear;
+        if (j.parts)
+            hipLaunchKernelGGL((bilinear ? rtd::rt_denoise_prepare_shards_temporal_bilinear_kernel : rtd::rt_denoise_prepare_shards_temporal_kernel), grid, block, 0, st,
+                               rtd::TemporalShardArgs{A, *j.parts});
+        else if (j.spatialRadius != 0)
+            hipLaunchKernelGGL((bilinear ? rtd::rt_denoise_prepared_temporal_bilinear_kernel : rtd::rt_denoise_prepared_temporal_kernel), grid, block, 0, st,
+                               rtd::TemporalPreparedArgs{A, {own.s, own.g0, own.g1}});
+        else
+            hipLaunchKernelGGL((bilinear ? rtd::rt_denoise_prepare_temporal_bilinear_kernel : rtd::rt_denoise_prepare_temporal_kernel), grid, block, 0, st, A);
+        first = Planes{A.oS, A.oG0, A.oG1};
+    } else if (j.parts) {
+        hipLaunchKernelGGL(rtd::rt_denoise_prepare_shards_kernel, grid, block, 0, st, s.hdr, s.sq, reinterpret_cast<const float4*>(s.feat), s.W, npix,
+                           j.parts->rowsMax, j.parts->blockRows, j.parts->nshards, s.n, s.m, own.s, own.g0, own.g1);
+    } else if (j.spatialRadius == 0) {
+        hipLaunchKernelGGL(rtd::rt_denoise_prepare_kernel, grid, block, 0, st, s.hdr, s.sq, reinterpret_cast<const float4*>(s.feat), npix, s.n, s.m, own.s, own.g0,
+                           own.g1);
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    return LaunchLevels(st, s, A.oS, A.oG0, A.oG1, P, stageKnob, forms);
-}
-
-int LaunchDenoiseSpatial(void* stream, const Strips& s, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed, int stageKnob,
-                         uint32_t forms[rtd::kDenoiseMaxLevels]) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
-    const int e = LaunchPrepareSpatial(st, s, P, radius, committed, static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]),
-                                       static_cast<float4*>(s.guide[1]));
-    if (e != 0) return e;
-    return LaunchLevels(st, s, static_cast<const float4*>(s.state[0]), static_cast<const float4*>(s.guide[0]), static_cast<const float4*>(s.guide[1]), P, stageKnob,
-                        forms);
-}
-
-// The spatial pass writes Strips::state[0] and Strips::guide -- idle in the temporal form until level 1 writes state[0] -- and the
-// prepared form of the chosen pass reads them.
-int LaunchDenoiseTemporalSpatial(void* stream, const Strips& s, const Temporal& t, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed,
-                                 int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint32_t npix = s.W * s.rows;
-    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
-    int e = LaunchPrepareSpatial(st, s, P, radius, committed, static_cast<float4*>(s.state[0]), static_cast<float4*>(s.guide[0]),
-                                 static_cast<float4*>(s.guide[1]));
-    if (e != 0) return e;
-    const rtd::TemporalPreparedArgs S{TemporalArgsOf(s, t),
-                                      {static_cast<const float4*>(s.state[0]), static_cast<const float4*>(s.guide[0]), static_cast<const float4*>(s.guide[1])}};
-    if (t.fetch == rtd::kTemporalFetchBilinear)
-        hipLaunchKernelGGL(rtd::rt_denoise_prepared_temporal_bilinear_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, S);
-    else
-        hipLaunchKernelGGL(rtd::rt_denoise_prepared_temporal_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, S);
-    e = (int)hipGetLastError();
-    if (e != 0) return e;
-    return LaunchLevels(st, s, S.A.oS, S.A.oG0, S.A.oG1, P, stageKnob, forms);
-}
-
-int LaunchDenoiseShardsTemporal(void* stream, const Strips& s, const ShardLayout& parts, const Temporal& t, const rtd::DenoiseParams& P, int stageKnob,
-                                uint32_t forms[rtd::kDenoiseMaxLevels]) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint32_t npix = s.W * s.rows;
-    for (uint32_t l = 0; l < rtd::kDenoiseMaxLevels; ++l) forms[l] = kFormNone;
-    const rtd::TemporalShardArgs S{TemporalArgsOf(s, t), parts.rowsMax, parts.blockRows, parts.nshards};
-    if (t.fetch == rtd::kTemporalFetchBilinear)
-        hipLaunchKernelGGL(rtd::rt_denoise_prepare_shards_temporal_bilinear_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, S);
-    else
-        hipLaunchKernelGGL(rtd::rt_denoise_prepare_shards_temporal_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, st, S);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    return LaunchLevels(st, s, S.A.oS, S.A.oG0, S.A.oG1, P, stageKnob, forms);
+    return LaunchLevels(st, s, first, P, stageKnob, forms);
 }
 
 }  // namespace rtdn
