@@ -98,6 +98,7 @@ EXPORTS = [
     "rt_temporal_default_params_fetch", "rt_denoise_temporal_fetch", "rt_unit_temporal_host_fetch",
     "rt_denoise_shards_temporal", "rt_unit_temporal_shards_host",
     "rt_variance_default_params", "rt_denoise_variance", "rt_denoise_temporal_variance", "rt_unit_denoise_variance_host", "rt_unit_temporal_variance_host",
+    "rt_denoise_shards_variance", "rt_denoise_shards_temporal_variance", "rt_unit_denoise_shards_variance_host", "rt_unit_temporal_shards_variance_host",
 ]
 
 _lib = None
@@ -256,6 +257,15 @@ def load():
                                                      C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtCamera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32, C.POINTER(RtVarianceParams),
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "rt_denoise_shards_variance"):
+        L.rt_denoise_shards_variance.argtypes = [C.c_void_p, C.POINTER(RtShardParts), C.POINTER(RtDenoiseParams), C.POINTER(RtVarianceParams), C.POINTER(C.c_double)]
+        L.rt_denoise_shards_temporal_variance.argtypes = [C.c_void_p, C.POINTER(RtShardFrame), C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32,
+                                                          C.POINTER(RtVarianceParams), C.POINTER(C.c_double)]
+        L.rt_unit_denoise_shards_variance_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtShardParts), C.POINTER(RtDenoiseParams),
+                                                           C.POINTER(RtVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_unit_temporal_shards_variance_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtShardFrame), C.POINTER(RtCamera), C.c_void_p,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtDenoiseParams), C.POINTER(RtTemporalParams), C.c_uint32,
+                                                            C.POINTER(RtVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -370,16 +380,37 @@ def shard_frame(W, H, world, rows_max, n, m, camera, hdr=None, sq=None, feat=Non
     return RtShardFrame(parts, ids or None, H, RtCamera.from_buffer_copy(bytes(camera)))
 
 
-def unit_temporal_shards_host(hdr, sq, feat8, ids, frame, history=None, params=None, tparams=None, fetch=1):
+def unit_denoise_shards_variance_host(hdr, sq, feat8, parts, params=None, variance=None):
+    """rt_unit_denoise_shards_variance_host over numpy parts ([world, rows_max, W, c] each; sq None is accepted under the spatial source
+    only) shaped by `parts` (shard_parts(...), its pointers unused).  Returns rgb, var and state, the prepared (c0, v0), in image order."""
+    hdr = np.ascontiguousarray(hdr, dtype=np.float32)
+    sq = None if sq is None else np.ascontiguousarray(sq, dtype=np.float32)
+    feat8 = np.ascontiguousarray(feat8, dtype=np.float32)
+    W, rows, px = parts.W, parts.rs.num_rows, parts.rs.nshards * parts.rows_max * parts.W
+    assert hdr.size == px * 3 and (sq is None or sq.size == px * 3) and feat8.size == px * 8
+    out = {"rgb": np.full((rows, W, 3), -1.0, np.float32), "var": np.full((rows, W), -1.0, np.float32), "state": np.full((rows, W, 4), -1.0, np.float32)}
+    check(load().rt_unit_denoise_shards_variance_host(hdr.ctypes.data, sq.ctypes.data if sq is not None else None, feat8.ctypes.data, C.byref(parts),
+                                                      C.byref(params) if params is not None else None, C.byref(variance) if variance is not None else None,
+                                                      out["rgb"].ctypes.data, out["var"].ctypes.data, out["state"].ctypes.data))
+    return out
+
+
+def unit_temporal_shards_variance_host(hdr, sq, feat8, ids, frame, history=None, params=None, tparams=None, fetch=1, variance=None):
+    """rt_unit_temporal_shards_variance_host: unit_temporal_shards_host with the variance source chosen; sq None is accepted under the
+    spatial source only."""
+    return unit_temporal_shards_host(hdr, sq, feat8, ids, frame, history, params, tparams, fetch, variance, _entry="rt_unit_temporal_shards_variance_host")
+
+
+def unit_temporal_shards_host(hdr, sq, feat8, ids, frame, history=None, params=None, tparams=None, fetch=1, variance=None, _entry=None):
     """rt_unit_temporal_shards_host over numpy parts ([world, rows_max, W, c] each; ids uint32) shaped by `frame` (shard_frame(...), its
     pointers unused).  history and the returned dict as unit_temporal_host's: everything in image order, num_rows x W."""
     hdr = np.ascontiguousarray(hdr, dtype=np.float32)
-    sq = np.ascontiguousarray(sq, dtype=np.float32)
+    sq = None if sq is None else np.ascontiguousarray(sq, dtype=np.float32)
     feat8 = np.ascontiguousarray(feat8, dtype=np.float32)
     ids = np.ascontiguousarray(ids, dtype=np.uint32)
     W, rows, world, rows_max, block_rows = frame.parts.W, frame.parts.rs.num_rows, frame.parts.rs.nshards, frame.parts.rows_max, frame.parts.rs.block_rows
     px = world * rows_max * W
-    assert hdr.size == px * 3 and sq.size == px * 3 and feat8.size == px * 8 and ids.size == px
+    assert hdr.size == px * 3 and (sq is None or sq.size == px * 3) and feat8.size == px * 8 and ids.size == px
     out = {"rgb": np.zeros((rows, W, 3), np.float32), "var": np.zeros((rows, W), np.float32), "state": np.zeros((rows, W, 4), np.float32),
            "guides": np.zeros((rows, W, 8), np.float32), "len": np.zeros((rows, W), np.uint32), "target": np.zeros((rows, W), np.uint32)}
     if history is None:
@@ -390,10 +421,14 @@ def unit_temporal_shards_host(hdr, sq, feat8, ids, frame, history=None, params=N
                 np.ascontiguousarray(history["ids"], dtype=np.uint32), np.ascontiguousarray(history["len"], dtype=np.uint32)]
         assert keep[0].size == rows * W * 4 and keep[1].size == rows * W * 8 and keep[2].size == rows * W and keep[3].size == rows * W
         hs, hg, hi, hl = (a.ctypes.data for a in keep)
-    check(load().rt_unit_temporal_shards_host(hdr.ctypes.data, sq.ctypes.data, feat8.ctypes.data, ids.ctypes.data, C.byref(frame), hc, hs, hg, hi, hl,
-                                              C.byref(params) if params is not None else None, C.byref(tparams) if tparams is not None else None,
-                                              int(fetch), out["rgb"].ctypes.data, out["var"].ctypes.data, out["state"].ctypes.data,
-                                              out["guides"].ctypes.data, out["len"].ctypes.data, out["target"].ctypes.data))
+    head = (hdr.ctypes.data, sq.ctypes.data if sq is not None else None, feat8.ctypes.data, ids.ctypes.data, C.byref(frame), hc, hs, hg, hi, hl,
+            C.byref(params) if params is not None else None, C.byref(tparams) if tparams is not None else None, int(fetch))
+    tail = (out["rgb"].ctypes.data, out["var"].ctypes.data, out["state"].ctypes.data, out["guides"].ctypes.data, out["len"].ctypes.data,
+            out["target"].ctypes.data)
+    if _entry is None:
+        check(load().rt_unit_temporal_shards_host(*head, *tail))
+    else:
+        check(load().rt_unit_temporal_shards_variance_host(*head, C.byref(variance) if variance is not None else None, *tail))
     # the new history's ids: the parts' ids in image order (block b of the range is block b // world of part b % world)
     j = np.arange(rows)
     b = j // block_rows

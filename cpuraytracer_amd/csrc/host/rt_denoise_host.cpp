@@ -83,13 +83,17 @@ int CheckVarianceParams(const char* who_, const rt_variance_params* vparams, rtd
     return RT_OK;
 }
 
-// The spatial prepare pass as rt_denoise_prepare_spatial_kernel runs it: c0 and g of every pixel first, then the window's taps.
-void PrepareSpatialHost(const float* hdr, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows, const rtd::DenoiseParams& P, uint32_t radius,
-                        std::vector<rtd::DenoiseState>& a, std::vector<float>& g) {
-    const size_t npix = (size_t)W * rows;
-    for (size_t p = 0; p < npix; ++p) {
-        rtd::denoise_prepare_mean(hdr + 3 * p, n, feat8 + 8 * p, m, a[p].c, &g[8 * p]);
-        a[p].v = 0.0f;
+// The spatial prepare pass as rt_denoise_prepare_spatial_kernel runs it: c0 and g of every pixel first, then the window's taps.  parts:
+// hdr and feat8 are gathered parts and a row of the range is read where the mapping puts it (rt_denoise_prepare_spatial_shards_kernel);
+// a and g are in image order either way, so the taps do not see the difference.
+void PrepareSpatialHost(const float* hdr, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows, const ShardLayout* parts,
+                        const rtd::DenoiseParams& P, uint32_t radius, std::vector<rtd::DenoiseState>& a, std::vector<float>& g) {
+    for (uint32_t y = 0; y < rows; ++y) {
+        const size_t src = parts ? PartsRowStart(*parts, W, y) : (size_t)y * W, dst = (size_t)y * W;
+        for (size_t x = 0; x < W; ++x) {
+            rtd::denoise_prepare_mean(hdr + 3 * (src + x), n, feat8 + 8 * (src + x), m, a[dst + x].c, &g[8 * (dst + x)]);
+            a[dst + x].v = 0.0f;
+        }
     }
     const int64_t R = (int64_t)radius;
     for (int64_t y = 0; y < (int64_t)rows; ++y) {
@@ -114,10 +118,11 @@ void PrepareSpatialHost(const float* hdr, uint32_t n, const float* feat8, uint32
 
 // (CheckShardFrame, the same for an rt_shard_frame, ends with this one and lives in rt_temporal_host.cpp, beside the temporal parameters'
 // checks it calls: denoise_selftest links this file without that one)
-int CheckShardParts(const char* who_, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P) {
+// (spatial: the spatial variance source -- sq is not looked at, and one sample is enough)
+int CheckShardParts(const char* who_, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P, bool spatial) {
     const std::string who(who_);
     if (!parts || !P) return Fail(RT_ERR_INVALID_ARG, who + ": null argument");
-    if (devicePointers && (!parts->hdr || !parts->sq || !parts->feat)) return Fail(RT_ERR_INVALID_ARG, who + ": null parts");
+    if (devicePointers && (!parts->hdr || (!parts->sq && !spatial) || !parts->feat)) return Fail(RT_ERR_INVALID_ARG, who + ": null parts");
     const rt_rowset rs = parts->rs;
     if (parts->W == 0 || rs.num_rows == 0 || rs.nshards == 0 || rs.block_rows == 0)
         return Fail(RT_ERR_INVALID_ARG, who + ": W, rs.num_rows, rs.nshards and rs.block_rows must not be 0");
@@ -127,7 +132,8 @@ int CheckShardParts(const char* who_, const rt_shard_parts* parts, const rt_deno
         return Fail(RT_ERR_INVALID_ARG, who + ": rows_max is below the rows of the largest shard");
     if (devicePointers && (reinterpret_cast<uintptr_t>(parts->feat) & 15u) != 0) return Fail(RT_ERR_INVALID_ARG, who + ": feat is not 16-byte aligned");
     if (const int rc = CheckDenoiseParams(who_, params, P)) return rc;
-    if (parts->n < 2) return Fail(RT_ERR_SEQUENCE, who + ": the noise estimate needs at least 2 samples per pixel");
+    if (spatial ? parts->n == 0 : parts->n < 2)
+        return Fail(RT_ERR_SEQUENCE, who + (spatial ? ": the parts hold no sample" : ": the noise estimate needs at least 2 samples per pixel"));
     if (parts->m == 0) return Fail(RT_ERR_SEQUENCE, who + ": the feature parts hold no sample");
     return RT_OK;
 }
@@ -166,7 +172,7 @@ static int DenoiseHost(const char* who_, const float* hdr, const float* sq, uint
     std::vector<rtd::DenoiseState> a(npix), b(npix);
     std::vector<float> g(npix * 8);
     if (spatial)
-        rtdn::PrepareSpatialHost(hdr, n, feat8, m, W, rows, P, V.radius, a, g);
+        rtdn::PrepareSpatialHost(hdr, n, feat8, m, W, rows, nullptr, P, V.radius, a, g);
     else
         for (size_t p = 0; p < npix; ++p) rtd::denoise_prepare(hdr + 3 * p, sq + 3 * p, n, feat8 + 8 * p, m, a[p], &g[8 * p]);
     if (out_state4)
@@ -204,25 +210,48 @@ int rt_rowset_locate(rt_rowset rs, uint32_t image_row, uint32_t* shard, uint32_t
     return RT_OK;
 }
 
-// The prepare pass reads every pixel through the mapping, as rt_denoise_prepare_shards_kernel does; the levels are the same code.
-int rt_unit_denoise_shards_host(const float* hdr, const float* sq, const float* feat8, const rt_shard_parts* shape, const rt_denoise_params* params,
-                                float* out_rgb, float* out_var) {
-    if (!hdr || !sq || !feat8 || !out_rgb || !out_var) return Fail(RT_ERR_INVALID_ARG, "rt_unit_denoise_shards_host: null buffer");
-    rtd::DenoiseParams P{};
-    const int rc = rtdn::CheckShardParts("rt_unit_denoise_shards_host", shape, params, false, &P);
+// The prepare pass reads every pixel through the mapping, as rt_denoise_prepare_shards_kernel (spatial source:
+// rt_denoise_prepare_spatial_shards_kernel) does; the levels are the same code.  (vparams == NULL: the moments source.)
+static int DenoiseShardsHost(const char* who_, const float* hdr, const float* sq, const float* feat8, const rt_shard_parts* shape, const rt_denoise_params* params,
+                             const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4) {
+    rtd::VarianceParams V{};
+    int rc = rtdn::CheckVarianceParams(who_, vparams, &V);
     if (rc != RT_OK) return rc;
+    const bool spatial = V.source == rtd::kVarianceSpatial;
+    if (!hdr || (!sq && !spatial) || !feat8 || !out_rgb || !out_var) return Fail(RT_ERR_INVALID_ARG, std::string(who_) + ": null buffer");
+    rtd::DenoiseParams P{};
+    if ((rc = rtdn::CheckShardParts(who_, shape, params, false, &P, spatial)) != RT_OK) return rc;
     const uint32_t W = shape->W, rows = shape->rs.num_rows;
     const size_t npix = (size_t)W * rows;
     std::vector<rtd::DenoiseState> a(npix), b(npix);
     std::vector<float> g(npix * 8);
     const rtdn::ShardLayout layout{shape->rows_max, shape->rs.block_rows, shape->rs.nshards};
-    for (uint32_t y = 0; y < rows; ++y) {
-        const size_t src = rtdn::PartsRowStart(layout, W, y), dst = (size_t)y * W;
-        for (size_t x = 0; x < W; ++x)
-            rtd::denoise_prepare(hdr + 3 * (src + x), sq + 3 * (src + x), shape->n, feat8 + 8 * (src + x), shape->m, a[dst + x], &g[8 * (dst + x)]);
-    }
+    if (spatial)
+        rtdn::PrepareSpatialHost(hdr, shape->n, feat8, shape->m, W, rows, &layout, P, V.radius, a, g);
+    else
+        for (uint32_t y = 0; y < rows; ++y) {
+            const size_t src = rtdn::PartsRowStart(layout, W, y), dst = (size_t)y * W;
+            for (size_t x = 0; x < W; ++x)
+                rtd::denoise_prepare(hdr + 3 * (src + x), sq + 3 * (src + x), shape->n, feat8 + 8 * (src + x), shape->m, a[dst + x], &g[8 * (dst + x)]);
+        }
+    if (out_state4)
+        for (size_t p = 0; p < npix; ++p) {
+            for (int k = 0; k < 3; ++k) out_state4[4 * p + k] = a[p].c[k];
+            out_state4[4 * p + 3] = a[p].v;
+        }
     rtdn::RunLevelsHost(a, b, g, W, rows, P, out_rgb, out_var);
     return RT_OK;
+}
+
+int rt_unit_denoise_shards_host(const float* hdr, const float* sq, const float* feat8, const rt_shard_parts* shape, const rt_denoise_params* params,
+                                float* out_rgb, float* out_var) {
+    return DenoiseShardsHost("rt_unit_denoise_shards_host", hdr, sq, feat8, shape, params, nullptr, out_rgb, out_var, nullptr);
+}
+
+// rt_unit_denoise_shards_host with the variance source chosen (the twin of rt_denoise_shards_variance); sq may be NULL under the spatial one.
+int rt_unit_denoise_shards_variance_host(const float* hdr, const float* sq, const float* feat8, const rt_shard_parts* shape, const rt_denoise_params* params,
+                                         const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4) {
+    return DenoiseShardsHost("rt_unit_denoise_shards_variance_host", hdr, sq, feat8, shape, params, vparams, out_rgb, out_var, out_state4);
 }
 
 }  // extern "C"

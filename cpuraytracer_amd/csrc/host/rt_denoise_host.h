@@ -29,9 +29,11 @@ int CheckDenoiseParams(const char* who, const rt_denoise_params* params, rtd::De
 int CheckVarianceParams(const char* who, const rt_variance_params* vparams, rtd::VarianceParams* V);
 
 // The spatial prepare pass (../rt_denoise.h "the spatial variance source") over a W x rows strip: a[p] = (c0, v0), g = the guides (8 floats
-// per pixel); a and g are sized by the caller.
-void PrepareSpatialHost(const float* hdr, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows, const rtd::DenoiseParams& P, uint32_t radius,
-                        std::vector<rtd::DenoiseState>& a, std::vector<float>& g);
+// per pixel), both in image order; a and g are sized by the caller.  parts: NULL -- hdr and feat8 are the strip in image order -- or the
+// layout of the gathered parts they are, read through the mapping (rt_denoise_launch.h).
+struct ShardLayout;
+void PrepareSpatialHost(const float* hdr, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows, const ShardLayout* parts,
+                        const rtd::DenoiseParams& P, uint32_t radius, std::vector<rtd::DenoiseState>& a, std::vector<float>& g);
 
 // tparams (NULL: the defaults) into T; outside their domain: RT_ERR_INVALID_ARG with a message that starts with who.
 int CheckTemporalParams(const char* who, const rt_temporal_params* tparams, rtd::TemporalParams* T);

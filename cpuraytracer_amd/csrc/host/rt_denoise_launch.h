@@ -49,7 +49,7 @@ struct ShardLayout {
 };
 
 // 2. Where v0 comes from.  The second moments (spatialRadius == 0), or -- the spatial source, ../rt_denoise.h -- the (2 radius + 1)^2
-//    window around the pixel, radius 1..3: rt_denoise_prepare_spatial_kernel runs first and writes Strips::state[0] and Strips::guide;
+//    window around the pixel, radius 1..3: rt_denoise_prepare_spatial_kernel (over parts: _spatial_shards_kernel) runs first and writes Strips::state[0] and Strips::guide;
 //    Strips::sq is not read and may be NULL.  committed: NULL, or a device word that holds the strip's sample count where only the
 //    device knows it (frames in flight: rt_resolve's rule, 0 reads as 1); Strips::n is then not read.  LDS of that pass at a radius:
 inline uint32_t SpatialLdsBytes(uint32_t radius) { return (kTileW + 2u * radius) * (kTileH + 2u * radius) * 3u * 16u; }
@@ -85,13 +85,16 @@ struct Job {
 };
 // Enqueues the spatial pass if asked for, the one prepare kernel the axes select and one a-trous launch per level on the stream (a
 // hipStream_t).  forms[l] = the form level l took.  Returns a hipError_t as int (0 = success); nothing is waited for.  Every product of
-// the axes runs but parts with a spatial radius, which is hipErrorInvalidValue before anything is enqueued.
+// the axes runs.  Parts with a spatial radius: the spatial pass reads hdr and feat through the mapping (committed is not read: the parts
+// are a snapshot, n is Strips::n), and a temporal pass after it reads only Temporal::ids there -- the planes it takes lie in image order.
 int Launch(void* stream, const Job& j, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]);
 
 }  // namespace rtdn
 
 // What rt_denoise_shards and rt_unit_denoise_shards_host refuse, checked once (rt_denoise_host.cpp): the shape, the sample counts and
 // the parameters (NULL: the defaults), which are returned in P.  The struct's own pointers are looked at only with devicePointers.
+// spatial (rt_denoise_shards_variance and its twins under the spatial source): sq is not looked at and may be NULL, and the parts need
+// n >= 1 instead of n >= 2; nothing else differs.
 struct rt_shard_parts;
 struct rt_denoise_params;
 // ... and what rt_denoise_shards_temporal and rt_unit_temporal_shards_host refuse: all of that for frame->parts, the frame's own
@@ -102,7 +105,8 @@ struct rt_temporal_params;
 namespace rtdn {
 // Where row y of the image's row range starts in the gathered parts, in pixels: the host twins' reading of the mapping.
 size_t PartsRowStart(const ShardLayout& parts, uint32_t W, uint32_t y);
-int CheckShardParts(const char* who, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P);
+int CheckShardParts(const char* who, const rt_shard_parts* parts, const rt_denoise_params* params, bool devicePointers, rtd::DenoiseParams* P,
+                    bool spatial = false);
 int CheckShardFrame(const char* who, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
-                    bool devicePointers, rtd::DenoiseParams* P, rtd::TemporalParams* T, rtd::TemporalGeom* G);
+                    bool devicePointers, rtd::DenoiseParams* P, rtd::TemporalParams* T, rtd::TemporalGeom* G, bool spatial = false);
 }

@@ -51,7 +51,7 @@ rtd::TemporalCam CamOf(const rt_camera& c) {
 // Beside CheckShardParts (rt_denoise_host.cpp), which it ends with: the frame's own fields first, so that every RT_ERR_INVALID_ARG
 // comes before the sample counts' RT_ERR_SEQUENCE.
 int CheckShardFrame(const char* who_, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
-                    bool devicePointers, rtd::DenoiseParams* P, rtd::TemporalParams* T, rtd::TemporalGeom* G) {
+                    bool devicePointers, rtd::DenoiseParams* P, rtd::TemporalParams* T, rtd::TemporalGeom* G, bool spatial) {
     const std::string who(who_);
     if (!frame || !P || !T || !G) return Fail(RT_ERR_INVALID_ARG, who + ": null argument");
     if (devicePointers && !frame->ids) return Fail(RT_ERR_INVALID_ARG, who + ": null ids");
@@ -69,7 +69,7 @@ int CheckShardFrame(const char* who_, const rt_shard_frame* frame, const rt_deno
     for (int k = 0; k < 3; ++k)
         finite = finite && std::isfinite(c.origin[k]) && std::isfinite(c.x[k]) && std::isfinite(c.y[k]) && std::isfinite(c.origin_image_plane[k]);
     if (!finite) return Fail(RT_ERR_INVALID_ARG, who + ": a field of the camera is not finite");
-    return CheckShardParts(who_, &frame->parts, params, devicePointers, P);
+    return CheckShardParts(who_, &frame->parts, params, devicePointers, P, spatial);
 }
 
 }  // namespace rtdn
@@ -113,9 +113,9 @@ static void TemporalRun(const float* hdr, const float* sq, uint32_t n, const flo
     const rtd::TemporalCam Cp = hist_len ? rtdn::CamOf(*hist_camera) : C;
     std::vector<rtd::DenoiseState> a(npix), b(npix);
     std::vector<float> g(npix * 8);
-    // (the spatial source, contiguous strips only: the whole strip's (c0, v0) and g first, as the device's extra pass leaves them)
+    // (the spatial source: the whole picture's (c0, v0) and g first, in image order, as the device's extra pass leaves them)
     const bool spatial = V.source == rtd::kVarianceSpatial;
-    if (spatial) rtdn::PrepareSpatialHost(hdr, n, feat8, m, W, num_rows, P, V.radius, a, g);
+    if (spatial) rtdn::PrepareSpatialHost(hdr, n, feat8, m, W, num_rows, parts, P, V.radius, a, g);
     for (uint32_t ly = 0; ly < num_rows; ++ly) {
         const size_t row = parts ? rtdn::PartsRowStart(*parts, W, ly) : (size_t)ly * W;  // where the row's current-frame pixels start
         for (uint32_t x = 0; x < W; ++x) {
@@ -240,24 +240,50 @@ int rt_unit_temporal_variance_host(const float* hdr, const float* sq, uint32_t n
                         hist_ids, hist_len, params, tparams, fetch, out_rgb, out_var, out_state4, out_guides8, out_len, out_target, vparams);
 }
 
-// The sharded form: the same step, the current frame read through the mapping (TemporalRun).
-int rt_unit_temporal_shards_host(const float* hdr, const float* sq, const float* feat8, const uint32_t* ids, const rt_shard_frame* shape,
-                                 const rt_camera* hist_camera, const float* hist_state4, const float* hist_guides8, const uint32_t* hist_ids,
-                                 const uint32_t* hist_len, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
-                                 float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len, uint32_t* out_target) {
-    const char* who = "rt_unit_temporal_shards_host";
-    if (!hdr || !sq || !feat8 || !ids) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+}  // extern "C"
+
+// The sharded form: the same step, the current frame read through the mapping (TemporalRun).  (vparams == NULL: the moments source.)
+static int TemporalShardsHost(const char* who, const float* hdr, const float* sq, const float* feat8, const uint32_t* ids, const rt_shard_frame* shape,
+                              const rt_camera* hist_camera, const float* hist_state4, const float* hist_guides8, const uint32_t* hist_ids,
+                              const uint32_t* hist_len, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
+                              const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len,
+                              uint32_t* out_target) {
+    rtd::VarianceParams V{};
+    if (const int rcv = rtdn::CheckVarianceParams(who, vparams, &V)) return rcv;
+    const bool spatial = V.source == rtd::kVarianceSpatial;
+    if (!hdr || (!sq && !spatial) || !feat8 || !ids) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null buffer");
     if (hist_len && (!hist_camera || !hist_state4 || !hist_guides8 || !hist_ids))
         return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": a history (hist_len != NULL) needs its camera, state, guides and ids");
     rtd::DenoiseParams P{};
     rtd::TemporalParams T{};
     rtd::TemporalGeom G{};
-    const int rc = rtdn::CheckShardFrame(who, shape, params, tparams, fetch, false, &P, &T, &G);
+    const int rc = rtdn::CheckShardFrame(who, shape, params, tparams, fetch, false, &P, &T, &G, spatial);
     if (rc != RT_OK) return rc;
     const rtdn::ShardLayout layout{shape->parts.rows_max, shape->parts.rs.block_rows, shape->parts.rs.nshards};
     TemporalRun(hdr, sq, shape->parts.n, feat8, shape->parts.m, ids, G, &layout, &shape->camera, hist_camera, hist_state4, hist_guides8, hist_ids, hist_len, P,
-                T, fetch, out_rgb, out_var, out_state4, out_guides8, out_len, out_target);
+                T, fetch, out_rgb, out_var, out_state4, out_guides8, out_len, out_target, V);
     return RT_OK;
+}
+
+extern "C" {
+
+int rt_unit_temporal_shards_host(const float* hdr, const float* sq, const float* feat8, const uint32_t* ids, const rt_shard_frame* shape,
+                                 const rt_camera* hist_camera, const float* hist_state4, const float* hist_guides8, const uint32_t* hist_ids,
+                                 const uint32_t* hist_len, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
+                                 float* out_rgb, float* out_var, float* out_state4, float* out_guides8, uint32_t* out_len, uint32_t* out_target) {
+    return TemporalShardsHost("rt_unit_temporal_shards_host", hdr, sq, feat8, ids, shape, hist_camera, hist_state4, hist_guides8, hist_ids, hist_len, params,
+                              tparams, fetch, nullptr, out_rgb, out_var, out_state4, out_guides8, out_len, out_target);
+}
+
+// rt_unit_temporal_shards_host with the variance source chosen (the twin of rt_denoise_shards_temporal_variance); sq may be NULL under the
+// spatial one.
+int rt_unit_temporal_shards_variance_host(const float* hdr, const float* sq, const float* feat8, const uint32_t* ids, const rt_shard_frame* shape,
+                                          const rt_camera* hist_camera, const float* hist_state4, const float* hist_guides8, const uint32_t* hist_ids,
+                                          const uint32_t* hist_len, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
+                                          const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4, float* out_guides8,
+                                          uint32_t* out_len, uint32_t* out_target) {
+    return TemporalShardsHost("rt_unit_temporal_shards_variance_host", hdr, sq, feat8, ids, shape, hist_camera, hist_state4, hist_guides8, hist_ids, hist_len,
+                              params, tparams, fetch, vparams, out_rgb, out_var, out_state4, out_guides8, out_len, out_target);
 }
 
 }  // extern "C"

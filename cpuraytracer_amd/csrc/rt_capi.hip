@@ -1602,12 +1602,15 @@ static int DescribePicture(rt_ctx* ctx, const char* who, const rt_denoise_params
 // temporal step the caller passes its frame and no parts: the frame's parts are then the parts, and it brings what DescribePicture takes
 // from the context -- the ids, the image's height, the camera; the history is keyed with the parts' row set, shard 0: a contiguous call's
 // key where nshards == 1.  (Neither: "null argument", the refusal of both checks for a missing record.)
+// (spatialRadius: 0, or the radius of the spatial source, under which parts->sq is not looked at and n >= 1 is enough; the parts are a
+// snapshot with their own n, so there is no committed word)
 static int DescribeParts(rt_ctx* ctx, const char* who, const rt_shard_parts* parts, const rt_shard_frame* frame, const rt_denoise_params* params,
-                         const rt_temporal_params* tparams, uint32_t fetch, DenoiseCall* c) {
+                         uint32_t spatialRadius, const rt_temporal_params* tparams, uint32_t fetch, DenoiseCall* c) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
     *c = DenoiseCall{};
-    const int rc = frame ? rtdn::CheckShardFrame(who, frame, params, tparams, fetch, true, &c->P, &c->T, &c->geom)
-                         : rtdn::CheckShardParts(who, parts, params, true, &c->P);
+    const bool spatial = spatialRadius != 0;
+    const int rc = frame ? rtdn::CheckShardFrame(who, frame, params, tparams, fetch, true, &c->P, &c->T, &c->geom, spatial)
+                         : rtdn::CheckShardParts(who, parts, params, true, &c->P, spatial);
     if (rc != RT_OK) return rc;
     RT_HIP(hipSetDevice(ctx->device));
     if (frame) {
@@ -1622,10 +1625,11 @@ static int DescribeParts(rt_ctx* ctx, const char* who, const rt_shard_parts* par
     c->W = parts->W;
     c->rows = parts->rs.num_rows;
     c->hdr = static_cast<const float*>(parts->hdr);
-    c->sq = static_cast<const float*>(parts->sq);
+    c->sq = spatial ? nullptr : static_cast<const float*>(parts->sq);
     c->feat = static_cast<const float*>(parts->feat);
     c->n = parts->n;
     c->m = parts->m;
+    c->spatialRadius = spatialRadius;
     c->layout = rtdn::ShardLayout{parts->rows_max, parts->rs.block_rows, parts->rs.nshards};
     return RT_OK;
 }
@@ -1653,8 +1657,21 @@ int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_params* params, const rt_v
 
 int rt_denoise_shards(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise_params* params, double* out_ms) {
     DenoiseCall c;
-    const int rc = DescribeParts(ctx, "rt_denoise_shards", parts, nullptr, params, nullptr, 0, &c);
+    const int rc = DescribeParts(ctx, "rt_denoise_shards", parts, nullptr, params, 0, nullptr, 0, &c);
     return rc != RT_OK ? rc : DenoiseRun(ctx, "rt_denoise_shards", c, out_ms);
+}
+
+// rt_denoise_shards with the variance source chosen: the moments source is rt_denoise_shards.
+int rt_denoise_shards_variance(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise_params* params, const rt_variance_params* vparams, double* out_ms) {
+    const char* who = "rt_denoise_shards_variance";
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    rtd::VarianceParams V{};
+    int rc = rtdn::CheckVarianceParams(who, vparams, &V);
+    if (rc != RT_OK) return rc;
+    if (V.source == rtd::kVarianceMoments) return rt_denoise_shards(ctx, parts, params, out_ms);
+    DenoiseCall c;
+    rc = DescribeParts(ctx, who, parts, nullptr, params, V.radius, nullptr, 0, &c);
+    return rc != RT_OK ? rc : DenoiseRun(ctx, who, c, out_ms);
 }
 
 // rt_denoise with the temporal step in its prepare pass (rt_temporal.h) ...
@@ -1682,8 +1699,22 @@ int rt_denoise_temporal_variance(rt_ctx* ctx, const rt_denoise_params* params, c
 int rt_denoise_shards_temporal(rt_ctx* ctx, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
                                double* out_ms) {
     DenoiseCall c;
-    const int rc = DescribeParts(ctx, "rt_denoise_shards_temporal", nullptr, frame, params, tparams, fetch, &c);
+    const int rc = DescribeParts(ctx, "rt_denoise_shards_temporal", nullptr, frame, params, 0, tparams, fetch, &c);
     return rc != RT_OK ? rc : DenoiseRun(ctx, "rt_denoise_shards_temporal", c, out_ms);
+}
+
+// ... and with the variance source chosen: the moments source is the entry above.
+int rt_denoise_shards_temporal_variance(rt_ctx* ctx, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams,
+                                        uint32_t fetch, const rt_variance_params* vparams, double* out_ms) {
+    const char* who = "rt_denoise_shards_temporal_variance";
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, std::string(who) + ": null ctx");
+    rtd::VarianceParams V{};
+    int rc = rtdn::CheckVarianceParams(who, vparams, &V);
+    if (rc != RT_OK) return rc;
+    if (V.source == rtd::kVarianceMoments) return rt_denoise_shards_temporal(ctx, frame, params, tparams, fetch, out_ms);
+    DenoiseCall c;
+    rc = DescribeParts(ctx, who, nullptr, frame, params, V.radius, tparams, fetch, &c);
+    return rc != RT_OK ? rc : DenoiseRun(ctx, who, c, out_ms);
 }
 
 int rt_temporal_reset(rt_ctx* ctx) {

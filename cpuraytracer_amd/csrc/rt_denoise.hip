@@ -109,14 +109,20 @@ struct TemporalShardArgs {
     TemporalArgs A;
     rtdn::ShardLayout L;
 };
+struct TemporalPreparedShardArgs {  // both: the planes lie in image order, only the frame's ids are read through the mapping
+    TemporalArgs A;
+    PreparedPlanes Q;
+    rtdn::ShardLayout L;
+};
 
-// The pass has one body per fetch, called by the six kernels with pix, the pixel of the strip they guard (pix < npix), and p, where
+// The pass has one body per fetch, called by the eight kernels with pix, the pixel of the strip they guard (pix < npix), and p, where
 // its current-frame inputs lie: pix itself, or parts_source(pix) -- strips and parts differ in nothing else.  kPrepared: the pixel's
 // state and guides are read from the spatial pass's planes instead of formed from hdr, sq and feat.  A body begins with the pixel's id,
 // state and guides, ends with the writes into the next history set (temporal_end) and holds the history's answer in between.  The
 // two bodies, their beginnings and the kernels' guards are written out, not shared further: with them in shared functions four of the
 // six kernels were compiled to other instruction streams than the separately written kernels they replace
-// (profiles/denoise_refactor_codegen.txt); as they stand all six have those streams.
+// (profiles/denoise_refactor_codegen.txt); as they stand those six have those streams, and the two that are both prepared and parts
+// (profiles/denoise_shards_spatial_codegen.txt) left them alone.
 
 __device__ __forceinline__ void temporal_end(const TemporalArgs& A, const uint32_t pix, const DenoiseState& s, const float g[8], const uint32_t id,
                                              const uint32_t len, const uint32_t target) {
@@ -256,6 +262,16 @@ __global__ void __launch_bounds__(256) rt_denoise_prepare_shards_temporal_biline
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= S.A.npix) return;
     temporal_prepare_bilinear<false>(S.A, PreparedPlanes{}, pix, parts_source(S.L, S.A.G.W, pix));
+}
+__global__ void __launch_bounds__(256) rt_denoise_prepared_shards_temporal_kernel(const TemporalPreparedShardArgs S) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= S.A.npix) return;
+    temporal_prepare_nearest<true>(S.A, S.Q, pix, parts_source(S.L, S.A.G.W, pix));
+}
+__global__ void __launch_bounds__(256) rt_denoise_prepared_shards_temporal_bilinear_kernel(const TemporalPreparedShardArgs S) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= S.A.npix) return;
+    temporal_prepare_bilinear<true>(S.A, S.Q, pix, parts_source(S.L, S.A.G.W, pix));
 }
 
 // One level.  Thread (tx, ty) of the 32 x 8 workgroup owns pixel (32 bx + tx, 8 by + ty); its 25 taps lie (a - 2) step rows and
@@ -410,6 +426,77 @@ __global__ void __launch_bounds__(256) rt_denoise_prepare_spatial_kernel(const f
     g1[p] = make_float4(gp[4], gp[5], gp[6], gp[7]);
 }
 
+// The same pass over the gathered parts of a row-sharded picture: W x rows is the IMAGE's row range, and while staging, image row gy is
+// read where the mapping puts it (rt_rowset_map.h) -- a wave stages two rows, which may come from two parts, each a contiguous segment
+// of its part.  A row or column outside the range is skipped BEFORE it is located: a part's padding rows (lr >= its shard's rows)
+// belong to no image row and are never read; row + gx < nshards * rowsMax * W as in parts_source.  n is the call's: the parts are a
+// snapshot, there is no committed word.  Everything after the barrier -- tile, halo, LDS planes, tap order, writes in image order -- is
+// the kernel above, written out a second time: as one shared body the three kernels above were compiled to other register numbers and
+// instruction orders than the parent's (profiles/denoise_shards_spatial_codegen.txt).
+template <int kR>
+__global__ void __launch_bounds__(256) rt_denoise_prepare_spatial_shards_kernel(const float* __restrict__ hdr, const float4* __restrict__ feat, uint32_t W,
+                                                                                uint32_t rows, uint32_t n, uint32_t m, const rtdn::ShardLayout L,
+                                                                                const DenoiseParams P, float4* __restrict__ state, float4* __restrict__ g0,
+                                                                                float4* __restrict__ g1) {
+    constexpr uint32_t tw = rtdn::kTileW + 2u * kR, th = rtdn::kTileH + 2u * kR;
+    __shared__ float4 ldsC[tw * th];
+    __shared__ float4 ldsA[tw * th];
+    __shared__ float4 ldsB[tw * th];
+    const uint32_t tx = threadIdx.x & (rtdn::kTileW - 1u), ty = threadIdx.x / rtdn::kTileW;
+    const int x0 = (int)(blockIdx.x * rtdn::kTileW), y0 = (int)(blockIdx.y * rtdn::kTileH);
+    const int x = x0 + (int)tx, y = y0 + (int)ty;
+    for (uint32_t ly = ty; ly < th; ly += rtdn::kTileH) {
+        const int gy = y0 - kR + (int)ly;
+        if (gy < 0 || gy >= (int)rows) continue;
+        uint32_t shard, lr;  // located once per staged row: one division chain per row, not one per lane
+        rowset_locate(L.blockRows, L.nshards, (uint32_t)gy, shard, lr);
+        const size_t row = ((size_t)shard * L.rowsMax + lr) * W;
+        for (uint32_t lx = tx; lx < tw; lx += rtdn::kTileW) {
+            const int gx = x0 - kR + (int)lx;
+            if (gx < 0 || gx >= (int)W) continue;
+            const size_t q = row + (size_t)gx;
+            const float h[3] = {hdr[3 * q], hdr[3 * q + 1], hdr[3 * q + 2]};
+            const float4 fa = feat[2 * q], fb = feat[2 * q + 1];
+            const float f[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
+            float c[3], g[8];
+            denoise_prepare_mean(h, n, f, m, c, g);
+            const uint32_t slot = ly * tw + lx;
+            ldsC[slot] = make_float4(c[0], c[1], c[2], 0.0f);
+            ldsA[slot] = make_float4(g[0], g[1], g[2], g[3]);
+            ldsB[slot] = make_float4(g[4], g[5], g[6], g[7]);
+        }
+    }
+    __syncthreads();
+    if (x >= (int)W || y >= (int)rows) return;
+    const uint32_t centre = (ty + (uint32_t)kR) * tw + tx + (uint32_t)kR;
+    DenoiseState sp;
+    float gp[8];
+    unpack(ldsC[centre], ldsA[centre], ldsB[centre], sp, gp);
+    SpatialSums S;
+    spatial_begin(S);
+#pragma unroll
+    for (int a = 0; a <= 2 * kR; ++a) {
+        const int dy = a - kR;
+        const int qy = y + dy;
+        if (qy < 0 || qy >= (int)rows) continue;
+#pragma unroll
+        for (int b = 0; b <= 2 * kR; ++b) {
+            const int dx = b - kR;
+            const int qx = x + dx;
+            if (qx < 0 || qx >= (int)W) continue;
+            const uint32_t slot = (uint32_t)((int)ty + kR + dy) * tw + (uint32_t)((int)tx + kR + dx);
+            DenoiseState sq;
+            float gq[8];
+            unpack(ldsC[slot], ldsA[slot], ldsB[slot], sq, gq);
+            spatial_tap(P, gp, sq.c, gq, S);
+        }
+    }
+    const size_t p = (size_t)y * W + (size_t)x;
+    state[p] = make_float4(sp.c[0], sp.c[1], sp.c[2], spatial_finish(S));
+    g0[p] = make_float4(gp[0], gp[1], gp[2], gp[3]);
+    g1[p] = make_float4(gp[4], gp[5], gp[6], gp[7]);
+}
+
 }  // namespace rtd
 
 namespace rtdn {
@@ -420,11 +507,20 @@ struct Planes {
 };
 static Planes PlanesOf(void* state, void* const guide[2]) { return Planes{static_cast<float4*>(state), static_cast<float4*>(guide[0]), static_cast<float4*>(guide[1])}; }
 
-// The spatial prepare pass into the three planes (radius 1..3: the caller's check).
-static int LaunchPrepareSpatial(hipStream_t st, const Strips& s, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed, const Planes& o) {
+// The spatial prepare pass into the three planes (radius 1..3: the caller's check).  parts: NULL, or the layout the inputs are read
+// through (the parts form takes n from the strips: committed is not read).
+static int LaunchPrepareSpatial(hipStream_t st, const Strips& s, const ShardLayout* parts, const rtd::DenoiseParams& P, uint32_t radius, const uint32_t* committed,
+                                const Planes& o) {
     const dim3 grid((s.W + kTileW - 1u) / kTileW, (s.rows + kTileH - 1u) / kTileH);
     const float4* feat = reinterpret_cast<const float4*>(s.feat);
-    if (radius == 1u)
+    if (radius < 1u || radius > 3u) return (int)hipErrorInvalidValue;
+    if (parts && radius == 1u)
+        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_shards_kernel<1>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, *parts, P, o.s, o.g0, o.g1);
+    else if (parts && radius == 2u)
+        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_shards_kernel<2>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, *parts, P, o.s, o.g0, o.g1);
+    else if (parts)
+        hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_shards_kernel<3>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, *parts, P, o.s, o.g0, o.g1);
+    else if (radius == 1u)
         hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<1>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, o.s, o.g0, o.g1);
     else if (radius == 2u)
         hipLaunchKernelGGL((rtd::rt_denoise_prepare_spatial_kernel<2>), grid, dim3(256), 0, st, s.hdr, feat, s.W, s.rows, s.n, s.m, committed, P, o.s, o.g0, o.g1);
@@ -493,7 +589,6 @@ static rtd::TemporalArgs TemporalArgsOf(const Strips& s, const Temporal& t) {
 }
 
 int Launch(void* stream, const Job& j, const rtd::DenoiseParams& P, int stageKnob, uint32_t forms[rtd::kDenoiseMaxLevels]) {
-    if (j.parts && j.spatialRadius != 0) return (int)hipErrorInvalidValue;  // (no spatial pass reads through the mapping)
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Strips& s = j.strips;
     const uint32_t npix = s.W * s.rows;
@@ -502,11 +597,14 @@ int Launch(void* stream, const Job& j, const rtd::DenoiseParams& P, int stageKno
     const Planes own = PlanesOf(s.state[0], s.guide);
     Planes first = own;  // what the levels start from: the pass's outputs
     if (j.spatialRadius != 0)
-        if (const int e = LaunchPrepareSpatial(st, s, P, j.spatialRadius, j.committed, own)) return e;
+        if (const int e = LaunchPrepareSpatial(st, s, j.parts, P, j.spatialRadius, j.committed, own)) return e;
     if (j.temporal) {
         const rtd::TemporalArgs A = TemporalArgsOf(s, *j.temporal);
         const bool bilinear = j.temporal->fetch == rtd::kTemporalFetchBilinear;
-        if (j.parts)
+        if (j.parts && j.spatialRadius != 0)
+            hipLaunchKernelGGL((bilinear ? rtd::rt_denoise_prepared_shards_temporal_bilinear_kernel : rtd::rt_denoise_prepared_shards_temporal_kernel), grid, block, 0,
+                               st, rtd::TemporalPreparedShardArgs{A, {own.s, own.g0, own.g1}, *j.parts});
+        else if (j.parts)
             hipLaunchKernelGGL((bilinear ? rtd::rt_denoise_prepare_shards_temporal_bilinear_kernel : rtd::rt_denoise_prepare_shards_temporal_kernel), grid, block, 0, st,
                                rtd::TemporalShardArgs{A, *j.parts});
         else if (j.spatialRadius != 0)
@@ -515,7 +613,7 @@ int Launch(void* stream, const Job& j, const rtd::DenoiseParams& P, int stageKno
         else
             hipLaunchKernelGGL((bilinear ? rtd::rt_denoise_prepare_temporal_bilinear_kernel : rtd::rt_denoise_prepare_temporal_kernel), grid, block, 0, st, A);
         first = Planes{A.oS, A.oG0, A.oG1};
-    } else if (j.parts) {
+    } else if (j.parts && j.spatialRadius == 0) {
         hipLaunchKernelGGL(rtd::rt_denoise_prepare_shards_kernel, grid, block, 0, st, s.hdr, s.sq, reinterpret_cast<const float4*>(s.feat), s.W, npix,
                            j.parts->rowsMax, j.parts->blockRows, j.parts->nshards, s.n, s.m, own.s, own.g0, own.g1);
     } else if (j.spatialRadius == 0) {

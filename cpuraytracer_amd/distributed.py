@@ -15,7 +15,7 @@ feature ids in the same buffer (PostExchange(with_ids=True)) rank 0 also keeps t
 """
 import numpy as np
 
-from ._capi import BLOCK_ROWS, RtRowset
+from ._capi import BLOCK_ROWS, RT_VARIANCE_SPATIAL, RtRowset
 
 
 def shard_rowset(H, rank, world, block_rows=BLOCK_ROWS):
@@ -112,27 +112,32 @@ class PostExchange:
     with_ids=True (temporal accumulation, denoise_gathered_temporal below) adds a tail of rows_max * W words to the buffer: the rank's
     feature ids.  They are uint32 and travel as the bytes they are -- the buffer's float32 is only its element size, nothing ever
     converts them -- viewed as int32 at both ends, and rank 0 regroups them into ids_parts [world, rows_max, W] int32 (torch has no
-    arithmetic-free uint32 tensor everywhere; the bits are the ids').  Without it the buffer, cut and the results are what they were."""
+    arithmetic-free uint32 tensor everywhere; the bits are the ids').  Without it the buffer, cut and the results are what they were.
 
-    def __init__(self, H, W, rank, world, device, block_rows=BLOCK_ROWS, with_ids=False):
+    with_moments=False (the spatial variance source, denoise_gathered(..., variance=...) below) leaves the strip of second moments out:
+    the buffer is [hdr 3 | feat 8 | ids 1 if with_ids] words per pixel, 11 or 12 instead of 14 or 15; fill() copies no moments, so the
+    ranks may render ONE sample with the noise estimate off; sq and sq_parts are None and gather() returns None in their place.  With the
+    default the buffer, cut and the results are what they were."""
+
+    def __init__(self, H, W, rank, world, device, block_rows=BLOCK_ROWS, with_ids=False, with_moments=True):
         import torch
         self.H, self.W, self.rank, self.world, self.block_rows, self.device = H, W, rank, world, block_rows, device
-        self.with_ids = with_ids
+        self.with_ids, self.with_moments = with_ids, with_moments
         self.rows = local_rows(H, rank, world, block_rows)
         self.rows_max = max_local_rows(H, world, block_rows)
         px = self.rows_max * W
-        self.cut = (3 * px, 6 * px, 14 * px)  # floats: end of hdr, of sq, of feat
+        self.cut = (3 * px, 6 * px, 14 * px) if with_moments else (3 * px, 3 * px, 11 * px)  # floats: end of hdr, of sq, of feat
         self.words = self.cut[2] + (px if with_ids else 0)  # 4-byte elements of the buffer
         self.buf = torch.zeros(self.words, dtype=torch.float32, device=device)
         self.hdr = self.buf[:self.cut[0]].view(self.rows_max, W, 3)
-        self.sq = self.buf[self.cut[0]:self.cut[1]].view(self.rows_max, W, 3)
+        self.sq = self.buf[self.cut[0]:self.cut[1]].view(self.rows_max, W, 3) if with_moments else None
         self.feat = self.buf[self.cut[1]:self.cut[2]].view(self.rows_max, W, 8)
         self.ids = self.buf[self.cut[2]:].view(torch.int32).view(self.rows_max, W) if with_ids else None
         self.hdr_parts = self.sq_parts = self.feat_parts = self.ids_parts = None
         if rank == 0:
             self.all = torch.empty((world, self.words), dtype=torch.float32, device=device) if world > 1 else self.buf.view(1, -1)
             self.hdr_parts = torch.empty((world, self.rows_max, W, 3), dtype=torch.float32, device=device)
-            self.sq_parts = torch.empty_like(self.hdr_parts)
+            self.sq_parts = torch.empty_like(self.hdr_parts) if with_moments else None
             self.feat_parts = torch.empty((world, self.rows_max, W, 8), dtype=torch.float32, device=device)
             if with_ids:
                 self.ids_parts = torch.empty((world, self.rows_max, W), dtype=torch.int32, device=device)
@@ -141,12 +146,13 @@ class PostExchange:
         """This rank's three strips (with_ids: and its ids), device to device into the buffer.  Asynchronous on the renderer's stream:
         where that is not the stream the gather runs on (torch's current one), call renderer.synchronize() before gather()."""
         renderer.copy_to_device(self.hdr.data_ptr(), None)
-        renderer.copy_moments_to_device(self.sq.data_ptr())
+        if self.with_moments:
+            renderer.copy_moments_to_device(self.sq.data_ptr())
         renderer.copy_features_to_device(self.feat.data_ptr(), self.ids.data_ptr() if self.with_ids else None)
 
     def gather(self, through_host=False):
         """-> (hdr_parts, sq_parts, feat_parts) on rank 0, (None, None, None) elsewhere; with_ids: ids_parts as a fourth value (a fourth
-        None).  through_host: CPU tensors over gloo (rehearsal: ranks that share a device); the parts still end on rank 0's device."""
+        None); with_moments=False: sq_parts is None.  through_host: CPU tensors over gloo (rehearsal: ranks that share a device); the parts still end on rank 0's device."""
         import torch.distributed as dist
         if self.world > 1:
             if through_host:
@@ -162,7 +168,8 @@ class PostExchange:
             return (None, None, None, None) if self.with_ids else (None, None, None)
         shape3, shape8 = (self.world, self.rows_max, self.W, 3), (self.world, self.rows_max, self.W, 8)
         self.hdr_parts.copy_(self.all[:, :self.cut[0]].reshape(shape3))
-        self.sq_parts.copy_(self.all[:, self.cut[0]:self.cut[1]].reshape(shape3))
+        if self.with_moments:
+            self.sq_parts.copy_(self.all[:, self.cut[0]:self.cut[1]].reshape(shape3))
         self.feat_parts.copy_(self.all[:, self.cut[1]:self.cut[2]].reshape(shape8))
         if self.with_ids:
             import torch
@@ -171,30 +178,49 @@ class PostExchange:
         return self.hdr_parts, self.sq_parts, self.feat_parts
 
 
-def denoise_gathered(renderer, xch, n, m, params=None, timed=False):
+def _sq_ptr(who, xch, variance):
+    """The gathered second moments' address, or None where the exchange carries none -- which only the spatial source accepts."""
+    if xch.sq_parts is not None:
+        return xch.sq_parts.data_ptr()
+    if variance is None or variance.source != RT_VARIANCE_SPATIAL:
+        raise ValueError(who + ": the moments source needs the second moments, and the exchange carries none (PostExchange(..., with_moments=True))")
+    return None
+
+
+def denoise_gathered(renderer, xch, n, m, params=None, timed=False, variance=None):
     """Rank 0, after xch.gather() of a PostExchange on the renderer's device: rt_denoise_shards over the gathered parts (n samples in
     hdr and sq, m in feat).  The H x W result is the renderer's download_denoised() / copy_denoised_to_device().  The regrouping copies
-    of gather() ran on torch's current stream: they are waited for here."""
+    of gather() ran on torch's current stream: they are waited for here.  variance (HipRenderer.denoise_shards): None, or an
+    RtVarianceParams; the spatial source runs on one-sample frames and over an exchange without moments (with_moments=False)."""
     import torch
     if xch.rank != 0 or xch.hdr_parts is None:
         raise ValueError("denoise_gathered: rank 0 holds the gathered parts")
+    sq = _sq_ptr("denoise_gathered", xch, variance)
     if xch.hdr_parts.is_cuda:
         torch.cuda.current_stream(xch.hdr_parts.device).synchronize()
-    return renderer.denoise_shards(xch.hdr_parts.data_ptr(), xch.sq_parts.data_ptr(), xch.feat_parts.data_ptr(), xch.W, xch.H, xch.world,
-                                   xch.rows_max, n, m, params=params, timed=timed, block_rows=xch.block_rows)
+    return renderer.denoise_shards(xch.hdr_parts.data_ptr(), sq, xch.feat_parts.data_ptr(), xch.W, xch.H, xch.world, xch.rows_max, n, m, params=params,
+                                   timed=timed, block_rows=xch.block_rows, variance=variance)
 
 
 def denoise_gathered_temporal(renderer, xch, n, m, camera, params=None, tparams=None, fetch=1, timed=False):
     """Rank 0, after xch.gather() of a PostExchange(with_ids=True) on the renderer's device: rt_denoise_shards_temporal over the gathered
     parts -- denoise_gathered with the renderer's history blended in (HipRenderer.denoise_shards_temporal).  camera: the rt_camera record
     every rank rendered the frame with (scene.camera).  Call it frame after frame on the same renderer: the history is the renderer's."""
+    return denoise_gathered_temporal_variance(renderer, xch, n, m, camera, params, tparams, fetch, timed)
+
+
+def denoise_gathered_temporal_variance(renderer, xch, n, m, camera, params=None, tparams=None, fetch=1, timed=False, variance=None):
+    """denoise_gathered_temporal with the variance source chosen (HipRenderer.denoise_shards_temporal_variance), over the same history:
+    variance None is denoise_gathered_temporal; the spatial source runs on one-sample frames and over an exchange without moments."""
     import torch
+    who = "denoise_gathered_temporal" if variance is None else "denoise_gathered_temporal_variance"
     if xch.rank != 0 or xch.hdr_parts is None:
-        raise ValueError("denoise_gathered_temporal: rank 0 holds the gathered parts")
+        raise ValueError(who + ": rank 0 holds the gathered parts")
     if xch.ids_parts is None:
-        raise ValueError("denoise_gathered_temporal: the exchange carries no ids (PostExchange(..., with_ids=True))")
+        raise ValueError(who + ": the exchange carries no ids (PostExchange(..., with_ids=True))")
+    sq = _sq_ptr(who, xch, variance)
     if xch.hdr_parts.is_cuda:
         torch.cuda.current_stream(xch.hdr_parts.device).synchronize()
-    return renderer.denoise_shards_temporal(xch.hdr_parts.data_ptr(), xch.sq_parts.data_ptr(), xch.feat_parts.data_ptr(), xch.ids_parts.data_ptr(), xch.W, xch.H,
-                                            xch.world, xch.rows_max, n, m, camera, params=params, tparams=tparams, fetch=fetch, timed=timed,
-                                            block_rows=xch.block_rows)
+    return renderer.denoise_shards_temporal_variance(xch.hdr_parts.data_ptr(), sq, xch.feat_parts.data_ptr(), xch.ids_parts.data_ptr(), xch.W, xch.H, xch.world,
+                                                     xch.rows_max, n, m, camera, params=params, tparams=tparams, fetch=fetch, timed=timed,
+                                                     block_rows=xch.block_rows, variance=variance)

@@ -268,14 +268,20 @@ class HipRenderer:
         self.denoised_W, self.denoised_rows = self.W, self.rows
         return ms.value if timed else None
 
-    def denoise_shards(self, hdr_ptr, sq_ptr, feat_ptr, W, H, world, rows_max, n, m, params=None, timed=False, block_rows=_capi.BLOCK_ROWS):
+    def denoise_shards(self, hdr_ptr, sq_ptr, feat_ptr, W, H, world, rows_max, n, m, params=None, timed=False, block_rows=_capi.BLOCK_ROWS, variance=None):
         """rt_denoise_shards: the same filter over a W x H picture that `world` shards rendered (cyclic blocks of block_rows rows) and a
         gather brought to this device: hdr_ptr, sq_ptr ([world][rows_max * W * 3] float32) and feat_ptr ([world][rows_max * W * 8] float32,
         16-byte aligned) are device memory holding the shards' sums after n and m samples.  Needs no scene and no accumulation in this
-        context; download_denoised() then returns the H x W result.  params and timed as in denoise()."""
+        context; download_denoised() then returns the H x W result.  params and timed as in denoise().  variance
+        (rt_denoise_shards_variance): as in denoise(); with source RT_VARIANCE_SPATIAL the shards may have rendered ONE sample with the
+        noise estimate off, and sq_ptr may be None: the second moments are not read."""
         parts = _capi.shard_parts(W, H, world, rows_max, n, m, hdr_ptr, sq_ptr, feat_ptr, block_rows=block_rows)
         ms = C.c_double(0.0)
-        check(self._L.rt_denoise_shards(self._h, C.byref(parts), C.byref(params) if params is not None else None, C.byref(ms) if timed else None))
+        if variance is None:
+            check(self._L.rt_denoise_shards(self._h, C.byref(parts), C.byref(params) if params is not None else None, C.byref(ms) if timed else None))
+        else:
+            check(self._L.rt_denoise_shards_variance(self._h, C.byref(parts), C.byref(params) if params is not None else None, C.byref(variance),
+                                                     C.byref(ms) if timed else None))
         self.denoised_W, self.denoised_rows = W, H
         return ms.value if timed else None
 
@@ -309,11 +315,24 @@ class HipRenderer:
         with the rows and block_rows of a denoise_temporal() picture continues that picture's history.  Needs no scene and no accumulation
         in this context; download_denoised() and download_temporal() then return the num_rows x W results in image order.  params,
         tparams, fetch and timed as in denoise_temporal()."""
+        return self.denoise_shards_temporal_variance(hdr_ptr, sq_ptr, feat_ptr, ids_ptr, W, H, world, rows_max, n, m, camera, params, tparams, fetch, timed,
+                                                     block_rows, first_row, num_rows)
+
+    def denoise_shards_temporal_variance(self, hdr_ptr, sq_ptr, feat_ptr, ids_ptr, W, H, world, rows_max, n, m, camera, params=None, tparams=None, fetch=1,
+                                         timed=False, block_rows=_capi.BLOCK_ROWS, first_row=0, num_rows=None, variance=None):
+        """rt_denoise_shards_temporal_variance: denoise_shards_temporal() with the variance source chosen, over the same one history.
+        variance as in denoise_shards(): None is denoise_shards_temporal() as it always was; under RT_VARIANCE_SPATIAL n = 1 suffices and
+        sq_ptr may be None."""
         frame = _capi.shard_frame(W, H, world, rows_max, n, m, camera, hdr_ptr, sq_ptr, feat_ptr, ids_ptr, block_rows=block_rows, first_row=first_row,
                                   num_rows=num_rows)
         ms = C.c_double(0.0)
-        check(self._L.rt_denoise_shards_temporal(self._h, C.byref(frame), C.byref(params) if params is not None else None,
-                                                 C.byref(tparams) if tparams is not None else None, int(fetch), C.byref(ms) if timed else None))
+        if variance is None:
+            check(self._L.rt_denoise_shards_temporal(self._h, C.byref(frame), C.byref(params) if params is not None else None,
+                                                     C.byref(tparams) if tparams is not None else None, int(fetch), C.byref(ms) if timed else None))
+        else:
+            check(self._L.rt_denoise_shards_temporal_variance(self._h, C.byref(frame), C.byref(params) if params is not None else None,
+                                                              C.byref(tparams) if tparams is not None else None, int(fetch), C.byref(variance),
+                                                              C.byref(ms) if timed else None))
         self.denoised_W, self.denoised_rows = W, frame.parts.rs.num_rows
         self.temporal_W, self.temporal_rows = W, frame.parts.rs.num_rows
         return ms.value if timed else None

@@ -482,10 +482,28 @@ int rt_variance_default_params(rt_variance_params* out);   /* needs no GPU */
  * RT_ERR_SEQUENCE.  The noise switch may be off, and the call settles nothing that rt_resolve would not: pipelined frames stay in flight.
  * Feature strips, the nshards rule and the row limits are rt_denoise's.  radius outside 1..3 under SPATIAL, or an unknown source:
  * RT_ERR_INVALID_ARG.  Every refusal comes before the first change: history and snapshot stay.  The sharded entries (rt_denoise_shards,
- * rt_denoise_shards_temporal) are unchanged and have no spatial form. */
+ * rt_denoise_shards_temporal) are unchanged; their forms with the source chosen follow. */
 int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_params* params, const rt_variance_params* vparams, double* out_ms);
 int rt_denoise_temporal_variance(rt_ctx* ctx, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
                                  const rt_variance_params* vparams, double* out_ms);
+/* rt_denoise_shards and rt_denoise_shards_temporal with the variance source chosen: a picture rendered in row shards at ONE sample per
+ * pixel, gathered, filtered and accumulated on one device.  vparams is checked first.  vparams == NULL or source == RT_VARIANCE_MOMENTS:
+ * exactly those two entries -- preconditions, refusals, messages, bits and history.  Under RT_VARIANCE_SPATIAL parts->sq is not
+ * inspected and may be NULL (the gather need not carry the second moments: 11 words per pixel, 12 with ids, instead of 14 or 15), and
+ * parts->n >= 1 suffices (n == 0: RT_ERR_SEQUENCE); m, the shape, alignment, row limits, camera, fetch and tparams rules are those of the
+ * two entries; a radius outside 1..3 or an unknown source is RT_ERR_INVALID_ARG.  Every refusal comes before the first change: history
+ * and snapshot stay.  The spatial pass reads hdr and feat of image pixel (x, y) through the row mapping; its window is the IMAGE's, so it
+ * crosses shard and block boundaries as if there were none, and a part's padding rows are never read.  Bits: those of
+ * rt_denoise_variance / rt_denoise_temporal_variance in one context that rendered rows [first_row, first_row + num_rows) of the W x H
+ * image contiguously with that camera -- den, den_var, LDR, the new history (state, guides, ids, len) and target.  The history is the
+ * context's one history with rt_denoise_shards_temporal's key and lifetime: nshards == 1 with a contiguous call's rows continues that
+ * call's history and the reverse, and sources and fetches may alternate over it.  The snapshot's readers, RT_DENOISE_STAGE,
+ * rt_unit_denoise_forms and out_ms are unchanged.  Like the entries above the calls need no scene and no accumulation in ctx, and touch
+ * nothing of its render, noise or feature state. */
+int rt_denoise_shards_variance(rt_ctx* ctx, const rt_shard_parts* parts, const rt_denoise_params* params, const rt_variance_params* vparams,
+                               double* out_ms);
+int rt_denoise_shards_temporal_variance(rt_ctx* ctx, const rt_shard_frame* frame, const rt_denoise_params* params, const rt_temporal_params* tparams,
+                                        uint32_t fetch, const rt_variance_params* vparams, double* out_ms);
 
 /* Replaces the transform(par) tonemap (spheres-app.cpp:186-214): hdr / n_samples,
  * ACES fit, gamma 1/2.2, XMStoreColor.  n_samples == 0 uses the accumulated count. */
@@ -660,6 +678,17 @@ int rt_unit_temporal_variance_host(const float* hdr, const float* sq, uint32_t n
                                    const float* hist_guides8, const uint32_t* hist_ids, const uint32_t* hist_len, const rt_denoise_params* params,
                                    const rt_temporal_params* tparams, uint32_t fetch, const rt_variance_params* vparams, float* out_rgb, float* out_var,
                                    float* out_state4, float* out_guides8, uint32_t* out_len, uint32_t* out_target);
+/* rt_unit_denoise_shards_host and rt_unit_temporal_shards_host with the variance source chosen: the twins of rt_denoise_shards_variance
+ * and rt_denoise_shards_temporal_variance.  vparams == NULL or RT_VARIANCE_MOMENTS: those twins' refusals and bits.  Under
+ * RT_VARIANCE_SPATIAL sq may be NULL and shape's n >= 1 suffices, as above.  out_state4 (may be NULL) of the first: the prepared (c0, v0)
+ * in image order.  Need no GPU. */
+int rt_unit_denoise_shards_variance_host(const float* hdr, const float* sq, const float* feat8, const rt_shard_parts* shape, const rt_denoise_params* params,
+                                         const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4);
+int rt_unit_temporal_shards_variance_host(const float* hdr, const float* sq, const float* feat8, const uint32_t* ids, const rt_shard_frame* shape,
+                                          const rt_camera* hist_camera, const float* hist_state4, const float* hist_guides8, const uint32_t* hist_ids,
+                                          const uint32_t* hist_len, const rt_denoise_params* params, const rt_temporal_params* tparams, uint32_t fetch,
+                                          const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4, float* out_guides8,
+                                          uint32_t* out_len, uint32_t* out_target);
 /* Which form each level of the last rt_denoise, rt_denoise_shards, rt_denoise_temporal or rt_denoise_shards_temporal took: out[l] = 0 the level did not run, 1 its taps were read from
  * global memory, 2 from a tile staged in LDS. */
 int rt_unit_denoise_forms(rt_ctx* ctx, uint32_t out[5]);
