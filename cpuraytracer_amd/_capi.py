@@ -99,6 +99,7 @@ EXPORTS = [
     "rt_denoise_shards_temporal", "rt_unit_temporal_shards_host",
     "rt_variance_default_params", "rt_denoise_variance", "rt_denoise_temporal_variance", "rt_unit_denoise_variance_host", "rt_unit_temporal_variance_host",
     "rt_denoise_shards_variance", "rt_denoise_shards_temporal_variance", "rt_unit_denoise_shards_variance_host", "rt_unit_temporal_shards_variance_host",
+    "rt_set_camera", "rt_get_camera",
 ]
 
 _lib = None
@@ -133,6 +134,8 @@ def load():
     L.rt_set_frame_lookahead.argtypes = [C.c_void_p, C.c_uint32]
     L.rt_scene_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtLight), C.c_uint32,
                                   C.POINTER(RtMaterial), C.c_float]
+    L.rt_set_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera)]
+    L.rt_get_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera)]
     L.rt_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                             C.POINTER(RtStats)]
     L.rt_clear.argtypes = [C.c_void_p]

@@ -28,6 +28,13 @@ uint32_t SceneReplaced(State& st) {
     return kAhead | kAccumulation | kInFlight | kFeatures | kDenoised;  // the feature strips and the denoised picture belonged to the scene that was replaced
 }
 
+uint32_t CameraChanged(State& st) {
+    // (the batch was settled under the old camera, kSettleBeforeCamera; hasScene is the caller's precondition and stays as it is)
+    st.ahead.valid = false;  // planes traced ahead were traced through the old camera
+    st.accumulated = 0;      // samples of two cameras do not mix: the next rt_render starts over
+    return kAhead | kAccumulation | kInFlight | kFeatures | kDenoised;  // frames in flight, feature strips and snapshot were the old camera's too
+}
+
 uint32_t StreamReplaced(State& st) {
     st.ahead.valid = false;  // planes traced ahead were produced on the old stream
     return kAhead | kTileOrder;  // ... and so were the order, the flags and the copy of their count

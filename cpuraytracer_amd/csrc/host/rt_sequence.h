@@ -75,6 +75,7 @@ enum : uint32_t {
 // Rendered (kPending) or flushed (kInFlight) BEFORE the event takes effect, in this order.  An error there refuses a new scene or
 // stream; the two settings are stored all the same (nothing is pending or in flight any more), as they always were.
 constexpr uint32_t kSettleBeforeScene = kPending;               // pending frames were asked of the scene that is being replaced
+constexpr uint32_t kSettleBeforeCamera = kPending;              // ... or of the camera that is being replaced
 constexpr uint32_t kSettleBeforeStream = kPending | kInFlight;  // pending frames and frames in flight belong to the old stream
 constexpr uint32_t kSettleBeforeBatchSetting = kPending;
 // (rt_set_frame_pipelining settles kPending, then kInFlight, and stores the depth unless the BATCH failed; rt_set_frame_lookahead
@@ -83,6 +84,8 @@ constexpr uint32_t kSettleAtSynchronize = kPending | kInFlight;  // pending fram
 
 // One function per outside event.  Each applies the event to the state and returns everything it voided.
 uint32_t SceneReplaced(State& st);              // rt_scene_upload, once the new tables are in place
+uint32_t CameraChanged(State& st);              // rt_set_camera with another record than before (the caller requires hasScene): what
+                                                // SceneReplaced voids -- every picture is a function of the camera -- with no scene set
 uint32_t StreamReplaced(State& st);             // rt_set_stream
 uint32_t SamplerChanged(State& st);             // rt_set_sampler with other flags than before
 uint32_t NoiseToggled(State& st, bool on);      // rt_set_noise_estimate; voids only where `on` differs from the state

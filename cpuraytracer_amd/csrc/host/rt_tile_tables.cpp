@@ -9,6 +9,15 @@ void SceneReplaced(State& st) {
     st.masks.valid = false;
 }
 
+void CameraChanged(State& st) {
+    // No host wait separates the old camera's tables from the new one's: a copy of the old count may still be on its way.  It can
+    // never be taken for the new picture's -- pending is false until the rebuild's own copy is recorded behind it on the same
+    // stream, and the one event is recorded again after that copy, so it completes only once the newer word has landed
+    // (DESIGN.md 4.3).
+    Dropped(st);
+    st.masks.valid = false;
+}
+
 void Dropped(State& st) {
     st.order.keyValid = st.order.orderValid = st.order.flagsValid = false;
     st.count.pending = st.count.known = false;  // (a copy on its way lands in the pinned word unread; a newer one follows it on the stream)

@@ -53,6 +53,7 @@ struct State {
 // ---- events.  Each applies itself to the state; dropping order or flags also voids the planes traced ahead, which the caller
 // reports to the sequencer (rtseq::TileTablesDropped) -- after Dropped, and after a PlanOrder that answers Rebuild.
 void SceneReplaced(State& st);                           // rt_scene_upload, as soon as the old tables' inputs are overwritten: nothing is valid
+void CameraChanged(State& st);                           // rt_set_camera with another record: every table is a function of the camera, nothing is valid
 void Dropped(State& st);                                 // rtseq::kTileOrder: order, flags and count (the masks stay)
 void AccumulationStarts(State& st, const Knobs& knobs);  // before the two plans of the call that starts it
 void CountArrived(State& st, uint32_t n);                // the event behind the copy was found complete: n is the pinned word

@@ -302,13 +302,17 @@ int SpheresApp::RunOrbit(uint32_t frames, double degPerFrame, uint32_t spp, uint
         RT_CALL(rt_temporal_reset(m_device));
         for (uint32_t f = 0; f < frames; ++f) {
             const rt_camera turned = OrbitCamera(camera, (double)f * degPerFrame, m_lookAt);
-            RT_CALL(rt_scene_upload(m_device, spheres.data(), materials.data(), (uint32_t)spheres.size(), &turned, lights.data(), (uint32_t)lights.size(), &sky,
-                                    exposureAdjustment));
-            RT_CALL(rt_set_sampler(m_device, AppSettings.samplerFlags));
-            RT_CALL(rt_set_noise_estimate(m_device, spatial ? (AppSettings.noiseEstimate ? 1 : 0) : 1));
-            RT_CALL(rt_set_frame_pipelining(m_device, 0));
-            RT_CALL(rt_set_frame_batch(m_device, 1u));
-            m_uploaded = true;
+            if (f == 0) {  // one upload; every later frame only moves the camera (rt_set_camera keeps the scene tables and the settings)
+                RT_CALL(rt_scene_upload(m_device, spheres.data(), materials.data(), (uint32_t)spheres.size(), &turned, lights.data(), (uint32_t)lights.size(),
+                                        &sky, exposureAdjustment));
+                RT_CALL(rt_set_sampler(m_device, AppSettings.samplerFlags));
+                RT_CALL(rt_set_noise_estimate(m_device, spatial ? (AppSettings.noiseEstimate ? 1 : 0) : 1));
+                RT_CALL(rt_set_frame_pipelining(m_device, 0));
+                RT_CALL(rt_set_frame_batch(m_device, 1u));
+                m_uploaded = true;
+            } else {
+                RT_CALL(rt_set_camera(m_device, &turned));
+            }
             RT_CALL(rt_render(m_device, W, H, rs, 1u, 1u + spp, (uint32_t)AppSettings.k_recursionDepth, AppSettings.renderSeed + f, &m_lastStats));
             m_sampleCount = spp;
             RT_CALL(rt_resolve(m_device, spp));

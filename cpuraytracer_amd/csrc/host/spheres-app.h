@@ -79,7 +79,7 @@ public:
     // frame would pass maxSpp (every frame waits for its summary, so every frame is resolved).  SampleCount() is the spp reached.
     int RunUntil(float relError, double fraction, uint32_t maxSpp) noexcept;
     // `frames` pictures of `spp` samples each (samples 1 .. spp, render seed renderSeed + f) from a camera that has turned f * degPerFrame
-    // degrees about the vertical axis through the scene's look-at point (OrbitCamera); every frame is an upload, a render, the feature
+    // degrees about the vertical axis through the scene's look-at point (OrbitCamera); one upload, then every frame is an rt_set_camera, a render, the feature
     // pass and rt_denoise_temporal (the defaults; levels != 0 replaces the number of levels), so the history follows the camera.
     // WritePPM then writes the last frame, WriteTemporalPPM its temporally accumulated and filtered picture.  fetch: RT_TEMPORAL_FETCH_NEAREST
     // is that call; RT_TEMPORAL_FETCH_BILINEAR goes through rt_denoise_temporal_fetch with that fetch's defaults.

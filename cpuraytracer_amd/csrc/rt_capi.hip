@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/rt_api.h"
+#include "host/rt_camera_launch.h"
 #include "host/rt_denoise_host.h"
 #include "host/rt_denoise_launch.h"
 #include "host/rt_launch_plan.h"
@@ -148,7 +149,8 @@ struct rt_ctx {
     DevBuf<rt_material> mats;
     DevBuf<uint4> mats16;     // the same table packed into 16 bytes per entry (rt_shade.h load_material16), when the scene allows it
     bool mats16Ok = false;
-    rtd::TraceParams base{};  // scene part filled at upload
+    rtd::TraceParams base{};  // scene part filled at upload; its camera fields again by rt_set_camera
+    rt_camera camera{};       // the record of the last upload or rt_set_camera (rt_get_camera; the same-record test)
 
     // accumulation: the strips of seq's running accumulation
     uint32_t sampler = 0;      // RT_SAMPLER_* flags of the next / running accumulation (rt_set_sampler)
@@ -983,7 +985,62 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     b.exposure = exposure_scale;
     ctx->n = n;
     ctx->sky = *sky;
+    ctx->camera = *camera;
     DropVoided(ctx, rtseq::SceneReplaced(ctx->seq));
+    return RT_OK;
+}
+
+// The 14 floats of a camera record that the renderer reads (SetCamera above), with their names; the fourth components are padding.
+struct CameraField {
+    const char* name;
+    size_t offset;
+    uint32_t count;
+};
+static const CameraField kCameraFields[] = {{"origin", offsetof(rt_camera, origin), 3},
+                                            {"x", offsetof(rt_camera, x), 3},
+                                            {"y", offsetof(rt_camera, y), 3},
+                                            {"origin_image_plane", offsetof(rt_camera, origin_image_plane), 3},
+                                            {"aperture", offsetof(rt_camera, aperture), 1},
+                                            {"focal_length", offsetof(rt_camera, focal_length), 1}};
+static const char* CameraFieldNotFinite(const rt_camera& c) {
+    for (const CameraField& f : kCameraFields)
+        for (uint32_t k = 0; k < f.count; ++k) {
+            float v;
+            std::memcpy(&v, reinterpret_cast<const char*>(&c) + f.offset + k * sizeof(float), sizeof(float));
+            if (!std::isfinite(v)) return f.name;
+        }
+    return nullptr;
+}
+static bool SameCameraBits(const rt_camera& a, const rt_camera& b) {
+    for (const CameraField& f : kCameraFields)
+        if (std::memcmp(reinterpret_cast<const char*>(&a) + f.offset, reinterpret_cast<const char*>(&b) + f.offset, f.count * sizeof(float)) != 0) return false;
+    return true;
+}
+
+int rt_set_camera(rt_ctx* ctx, const rt_camera* camera) {
+    if (!ctx || !camera) return Fail(RT_ERR_INVALID_ARG, "rt_set_camera: null argument");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_set_camera: no scene uploaded");
+    if (const char* field = CameraFieldNotFinite(*camera)) return Fail(RT_ERR_INVALID_ARG, std::string("rt_set_camera: ") + field + " is not finite");
+    if (SameCameraBits(*camera, ctx->camera)) return RT_OK;  // the same record: not an event (rt_set_sampler's precedent)
+    RT_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old camera
+    // The one piece of device memory that holds the camera: cam_o of lights 1 .. (the far-tier record behind them carries none).  On
+    // the stream, behind every launch of the old camera, the origin by value: no host wait, nothing read later.
+    const uint32_t extra = ctx->base.n_lights > 1u ? ctx->base.n_lights - 1u : 0u;
+    RT_HIP((hipError_t)rtcam::LaunchLightCamera(ctx->stream, ctx->lightRecs.ptr, extra, camera->origin));
+    SetCamera(ctx->base, *camera);
+    ctx->camera = *camera;
+    rttile::CameraChanged(ctx->tiles);  // (every per-tile table is a function of the camera)
+    (void)rtseq::TileTablesDropped(ctx->seq);
+    DropVoided(ctx, rtseq::CameraChanged(ctx->seq));
+    return RT_OK;
+}
+
+int rt_get_camera(rt_ctx* ctx, rt_camera* out) {
+    if (!ctx || !out) return Fail(RT_ERR_INVALID_ARG, "rt_get_camera: null argument");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_get_camera: no scene uploaded");
+    *out = ctx->camera;
     return RT_OK;
 }
 

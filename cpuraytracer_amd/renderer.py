@@ -130,6 +130,21 @@ class HipRenderer:
         check(self._L.rt_scene_upload(self._h, sph.ctypes.data, mat.ctypes.data, sph.shape[0], C.byref(cam), lights, len(ls),
                                       C.byref(sky), float(scene.exposure_scale)))
 
+    def set_camera(self, camera):
+        """rt_set_camera: move the camera of the uploaded scene without an upload -- no scene preparation, no table copied, no host
+        wait.  camera: an rt_camera record (scene.camera, scenes.orbit_camera(...)).  Everything computed afterwards equals, bit
+        for bit, what an upload() of the same scene with this camera computes; the accumulation, the feature strips and the denoise
+        snapshot are void as after an upload, the sampler, the noise switch, the progressive settings and the temporal history
+        stay.  The same record again changes nothing and voids nothing.  A NaN or an infinity in the record is refused."""
+        cam = _capi.RtCamera.from_buffer_copy(bytes(camera))
+        check(self._L.rt_set_camera(self._h, C.byref(cam)))
+
+    def get_camera(self):
+        """rt_get_camera: the RtCamera record of the last upload() or set_camera()."""
+        cam = _capi.RtCamera()
+        check(self._L.rt_get_camera(self._h, C.byref(cam)))
+        return cam
+
     def render(self, W, H, s0, s1, max_depth, seed, rowset=None, stats=True):
         """rt_render; stats=False passes out_stats = NULL: the call only enqueues work on the context's stream (no host
         wait; progressive 1-spp frames are launch bound) and returns None."""
@@ -287,9 +302,9 @@ class HipRenderer:
 
     # ---- temporal accumulation (rt_api.h "temporal accumulation")
     def denoise_temporal(self, params=None, tparams=None, timed=False, fetch=1, variance=None):
-        """rt_denoise_temporal: denoise() with the previous call's pre-filter state reprojected into the uploaded scene's camera,
-        validated against the guides and blended in before the levels.  The history survives upload() -- a camera move is an upload
-        -- and starts empty after temporal_reset() or when the picture's size or row set changes; on an empty history the result is
+        """rt_denoise_temporal: denoise() with the previous call's pre-filter state reprojected into the current camera,
+        validated against the guides and blended in before the levels.  The history survives set_camera() -- a camera move -- and
+        upload(), and starts empty after temporal_reset() or when the picture's size or row set changes; on an empty history the result is
         denoise()'s.  tparams: an RtTemporalParams (_capi.temporal_params(max_history=..., ...)) or None for the defaults; params and
         timed as in denoise().  download_denoised() serves the result.  fetch (rt_denoise_temporal_fetch): 1, nearest, is
         rt_denoise_temporal's bits; 4, bilinear, interpolates the history from the four pixels around the reprojected point.  tparams

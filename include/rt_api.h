@@ -172,6 +172,29 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
                     const rt_camera* camera, const rt_light* lights, uint32_t n_lights, const rt_material* sky,
                     float exposure_scale);
 
+/* Moves the camera of the uploaded scene without an upload: no scene preparation, no table copied, no host wait of its own (the
+ * only waits are those that rendering a pending batch implies).  Everything else on the device -- scene tables, lights, sky,
+ * exposure -- stays.
+ * Equivalence: after a successful rt_set_camera(ctx, C) everything the context computes is, bit for bit, what it computes after an
+ * rt_scene_upload of the same spheres, materials, lights, sky and exposure with camera C: rt_render under every progressive mode
+ * (HDR, LDR, moments, rt_stats' counters, the kernel variant of rt_unit_last_trace_launch), the per-tile masks and lists of the unit
+ * entries, rt_render_features, the denoise family (picture, history, target) and the unit entries.
+ * Voids exactly what the upload voids: the accumulation (the next rt_render must start at s0 == 1; one that continues is
+ * RT_ERR_SEQUENCE), planes traced ahead, frames in flight under pipelining, every per-tile table (masks, sphere lists, work order,
+ * empty-list flags and their count: all functions of the camera), the feature strips and the denoise snapshot.  A pending batch was
+ * asked of the old camera and is rendered first; its errors surface here.
+ * Keeps the sampler flags, the noise switch, the three progressive settings, the stream and the temporal history: the next temporal
+ * call reprojects from the history's camera into C, as it does after an upload.
+ * Same record: a record whose 14 floats that the renderer reads -- three components each of origin, x, y and origin_image_plane,
+ * aperture, focal_length -- equal the current ones as bit patterns changes nothing and voids nothing (rt_set_sampler's precedent): a
+ * running accumulation continues, a pending batch stays pending.  The fourth components are neither read nor compared.
+ * Refused before any side effect: a null argument (RT_ERR_INVALID_ARG); no scene uploaded (RT_ERR_NO_SCENE); any of the 14 floats
+ * not finite (RT_ERR_INVALID_ARG, the message names the field).  This is the one place where the two differ: rt_scene_upload keeps
+ * accepting every camera record it accepted before, finite or not.  A refused call changes nothing. */
+int rt_set_camera(rt_ctx* ctx, const rt_camera* camera);
+/* The record of the last rt_scene_upload or (changing) rt_set_camera, all 72 bytes.  RT_ERR_NO_SCENE before any upload. */
+int rt_get_camera(rt_ctx* ctx, rt_camera* out);
+
 /* ----------------------------------------------------------------- render */
 
 /* Replaces GenerateRays + the for_each(par) trace loop for sample indices s in
@@ -396,9 +419,9 @@ typedef struct rt_temporal_params {
 int rt_temporal_default_params(rt_temporal_params* out);  /* needs no GPU */
 /* rt_denoise with the temporal step in its prepare pass.  Preconditions, refusals, params, out_ms, RT_DENOISE_STAGE and the snapshot
  * (rt_download_denoised, rt_copy_denoised_to_device, rt_unit_denoise_forms) are rt_denoise's; tparams == NULL: the defaults, outside
- * their domain: RT_ERR_INVALID_ARG; so is a picture wider or taller than 2^24.  The current camera is the uploaded scene's.  Changes
- * none of hdr, sq, feat, the ids or ldr, nor any sequencing state.  The history is state of its own: it survives rt_scene_upload (a
- * camera move is an upload; keeping object ids stable across uploads is the caller's business, use_id = 0 otherwise), is dropped by
+ * their domain: RT_ERR_INVALID_ARG; so is a picture wider or taller than 2^24.  The current camera is rt_get_camera's.  Changes
+ * none of hdr, sq, feat, the ids or ldr, nor any sequencing state.  The history is state of its own: it survives rt_set_camera (a
+ * camera move) and rt_scene_upload (keeping object ids stable across uploads is the caller's business, use_id = 0 otherwise), is dropped by
  * rt_temporal_reset and rt_destroy, and a call whose W, H or row set differ from the history's starts from an empty one -- on an
  * empty history the call gives rt_denoise's bits.  A refused call keeps history and snapshot.  rt_denoise and rt_denoise_shards
  * neither read nor change the history. */
