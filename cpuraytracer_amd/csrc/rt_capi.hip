@@ -118,6 +118,7 @@ struct rt_ctx {
     hipStream_t ownStream = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t streamEv = nullptr;  // rt_set_stream: the end of the old stream's work, which the new stream waits for (never the host)
     std::vector<hipEvent_t> passEv;  // three timing events per sample-range pass of rt_render, grown on demand
     int cuCount = 0;
     size_t ldsPerBlockMax = 0;
@@ -813,6 +814,7 @@ void rt_destroy(rt_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->skyCountHost) (void)hipHostFree(ctx->skyCountHost);
     if (ctx->skyEv) (void)hipEventDestroy(ctx->skyEv);
+    if (ctx->streamEv) (void)hipEventDestroy(ctx->streamEv);
     for (auto& ev : ctx->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->passEv)
@@ -848,7 +850,15 @@ int rt_set_stream(rt_ctx* ctx, void* hip_stream) {
     // when a picture's tables were built and never rendered from again)
     if (rttile::CountToAwait(ctx->tiles)) RT_HIP(hipEventSynchronize(ctx->skyEv));
     DropVoided(ctx, voids);
-    ctx->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx->ownStream;
+    const hipStream_t next = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx->ownStream;
+    if (next != ctx->stream) {
+        // Everything the context has enqueued so far -- the settle above included -- runs before anything it enqueues from here on:
+        // an accumulation, the feature strips and the history continue across the switch.  The device waits, the host does not.
+        if (!ctx->streamEv) RT_HIP(hipEventCreateWithFlags(&ctx->streamEv, hipEventDisableTiming));
+        RT_HIP(hipEventRecord(ctx->streamEv, ctx->stream));
+        RT_HIP(hipStreamWaitEvent(next, ctx->streamEv, 0));
+    }
+    ctx->stream = next;
     return RT_OK;
 }
 

@@ -143,8 +143,11 @@ class PostExchange:
                 self.ids_parts = torch.empty((world, self.rows_max, W), dtype=torch.int32, device=device)
 
     def fill(self, renderer):
-        """This rank's three strips (with_ids: and its ids), device to device into the buffer.  Asynchronous on the renderer's stream:
-        where that is not the stream the gather runs on (torch's current one), call renderer.synchronize() before gather()."""
+        """This rank's three strips (with_ids: and its ids), device to device into the buffer.  Asynchronous on the renderer's stream.
+        Where that is the stream the gather runs on -- a torch.cuda.Stream() made current and handed to renderer.set_stream(), as in
+        bench.py -- the gather is ordered behind the copies and nothing has to wait.  Where it is not, call renderer.synchronize()
+        before gather(): that is also the case after set_stream(torch.cuda.current_stream().cuda_stream) under torch's DEFAULT
+        stream, whose handle is 0 and therefore selects the renderer's own stream (rt_api.h at rt_set_stream)."""
         renderer.copy_to_device(self.hdr.data_ptr(), None)
         if self.with_moments:
             renderer.copy_moments_to_device(self.sq.data_ptr())

@@ -87,6 +87,8 @@ class HipRenderer:
             pass
 
     def set_stream(self, hip_stream_ptr):
+        """rt_set_stream: enqueue on the caller's hipStream_t (torch.cuda.Stream().cuda_stream) from here on, ordered behind what was
+        queued on the previous stream.  0 -- also the handle of torch's default stream -- selects the context's own stream."""
         check(self._L.rt_set_stream(self._h, C.c_void_p(hip_stream_ptr)))
 
     def set_workspace_limit(self, nbytes):

@@ -137,8 +137,16 @@ int rt_api_version(void);
 int rt_create(int device_ordinal, rt_ctx** out);
 void rt_destroy(rt_ctx* ctx);
 
-/* Launch on a caller-provided hipStream_t (e.g. torch's current stream); NULL restores
- * the context's own stream. */
+/* Launch on a caller-provided hipStream_t (e.g. a torch stream); NULL restores the context's own stream.
+ * Everything the context enqueues from here on goes to that stream, and the entries that hand data to the host wait for it.
+ * Order: work queued on the previous stream -- a pending batch and frames in flight are settled there first -- is ordered before
+ * work queued on the new one: the new stream waits on the device for an event recorded at the end of the old one; the host does
+ * not wait for it.  So an accumulation, the feature strips and the temporal history continue across the call (planes traced ahead and the
+ * tiles' work order are dropped, as documented at rt_set_frame_lookahead).  The handle already in force changes no result.
+ * The previous stream must still exist at the call: set another stream (or NULL) before destroying one the context was given.
+ * A handle of 0 selects the context's own stream, which is created hipStreamNonBlocking: the legacy default stream -- the handle
+ * of torch's default stream -- cannot be chosen, and work on it is not ordered with the context's.  Hand over a stream that was
+ * created (torch.cuda.Stream()). */
 int rt_set_stream(rt_ctx* ctx, void* hip_stream);
 
 /* Upper bound for the per-sample workspace in bytes (default: min(64 GiB, half of the
