@@ -100,6 +100,7 @@ EXPORTS = [
     "rt_variance_default_params", "rt_denoise_variance", "rt_denoise_temporal_variance", "rt_unit_denoise_variance_host", "rt_unit_temporal_variance_host",
     "rt_denoise_shards_variance", "rt_denoise_shards_temporal_variance", "rt_unit_denoise_shards_variance_host", "rt_unit_temporal_shards_variance_host",
     "rt_set_camera", "rt_get_camera",
+    "rt_set_materials", "rt_set_lights", "rt_set_exposure", "rt_temporal_forget", "rt_unit_temporal_forget_host",
 ]
 
 _lib = None
@@ -136,6 +137,12 @@ def load():
                                   C.POINTER(RtMaterial), C.c_float]
     L.rt_set_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera)]
     L.rt_get_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera)]
+    if hasattr(L, "rt_set_materials"):
+        L.rt_set_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtMaterial)]
+        L.rt_set_lights.argtypes = [C.c_void_p, C.POINTER(RtLight), C.c_uint32]
+        L.rt_set_exposure.argtypes = [C.c_void_p, C.c_float]
+        L.rt_temporal_forget.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.rt_unit_temporal_forget_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
     L.rt_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                             C.POINTER(RtStats)]
     L.rt_clear.argtypes = [C.c_void_p]
@@ -333,6 +340,21 @@ def unit_denoise_variance_host(hdr, sq, n, feat8, m, params=None, variance=None)
     check(load().rt_unit_denoise_variance_host(hdr.ctypes.data, sq.ctypes.data if sq is not None else None, n, feat8.ctypes.data, m, W, rows,
                                                C.byref(params) if params is not None else None, C.byref(variance) if variance is not None else None,
                                                out["rgb"].ctypes.data, out["var"].ctypes.data, out["state"].ctypes.data))
+    return out
+
+
+FORGET_SKY = 0xffffffff  # the id rt_temporal_forget and its twin take for the sky
+
+
+def unit_temporal_forget_host(length, ids, n_spheres, forget_ids):
+    """rt_unit_temporal_forget_host over numpy arrays: a copy of `length` (any shape, uint32) with 0 wherever the pixel's id (ids, the
+    same shape) is one of forget_ids; FORGET_SKY names the sky, ids at or above n_spheres match nothing."""
+    out = np.array(length, dtype=np.uint32, copy=True, order="C")
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    assert ids.size == out.size
+    f = np.ascontiguousarray(forget_ids, dtype=np.uint32).reshape(-1)
+    check(load().rt_unit_temporal_forget_host(out.ctypes.data if out.size else None, ids.ctypes.data if ids.size else None, out.size, int(n_spheres),
+                                              f.ctypes.data if f.size else None, f.size))
     return out
 
 

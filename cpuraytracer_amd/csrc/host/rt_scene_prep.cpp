@@ -752,6 +752,18 @@ static bool PackMaterials(const std::vector<rt_material>& matc, std::vector<U4>&
     return true;
 }
 
+PreparedMaterials PrepareMaterials(const rt_material* materials, uint32_t n, const uint32_t* orig, size_t nEntries) {
+    PreparedMaterials M;
+    M.mats.resize(nEntries);
+    std::memset(M.mats.data(), 0, nEntries * sizeof(rt_material));
+    for (size_t e = 0; e < nEntries; ++e)
+        if (orig[e] != 0xffffffffu) M.mats[e] = materials[orig[e]];
+    M.mats16Ok = PackMaterials(M.mats, M.mats16);
+    M.matType.resize(n);
+    for (uint32_t k = 0; k < n; ++k) M.matType[k] = materials[k].type;
+    return M;
+}
+
 PreparedScene PrepareScene(const rt_sphere* spheres, const rt_material* materials, uint32_t n, const rt_light* lights, uint32_t n_lights,
                            const PrepOptions& opt) {
     PreparedScene P;
@@ -760,16 +772,13 @@ PreparedScene PrepareScene(const rt_sphere* spheres, const rt_material* material
     if (L.scan.size() >= 65536) return P;
     const size_t nPad = L.scan.size();
     P.radius.assign(nPad, 0.f);
-    P.mats.resize(nPad);
-    std::memset(P.mats.data(), 0, nPad * sizeof(rt_material));
-    for (size_t e = 0; e < nPad; ++e) {
-        if (L.orig[e] == 0xffffffffu) continue;
-        P.radius[e] = spheres[L.orig[e]].r;
-        P.mats[e] = materials[L.orig[e]];
-    }
-    P.mats16Ok = PackMaterials(P.mats, P.mats16);
-    P.matType.resize(n);
-    for (uint32_t k = 0; k < n; ++k) P.matType[k] = materials[k].type;
+    for (size_t e = 0; e < nPad; ++e)
+        if (L.orig[e] != 0xffffffffu) P.radius[e] = spheres[L.orig[e]].r;
+    PreparedMaterials M = PrepareMaterials(materials, n, L.orig.data(), nPad);
+    P.mats = std::move(M.mats);
+    P.mats16 = std::move(M.mats16);
+    P.mats16Ok = M.mats16Ok;
+    P.matType = std::move(M.matType);
     // the first light's index is staged into LDS where the scan's tables are; the others', one each, stay in global memory
     if (opt.shadowGrid && n_lights != 0)
         BuildShadowGrid(spheres, L, lights[0].direction, L.InGlobalMemory() ? opt.shadowCellsGlobal : opt.shadowCellsLds, P.shadow);

@@ -110,6 +110,18 @@ void BuildShadowGrid(const rt_sphere* spheres, const SceneLayout& L, const float
 // tier 1: the same; tier 2: the index for the hit points beyond tier 1's radius (rt_scene_prep.cpp states its radius and why)
 void BuildShadowGridTier(const rt_sphere* spheres, const SceneLayout& L, const float lightDir[3], uint32_t maxCells, uint32_t tier, ShadowGrid& G);
 
+// The three tables that hold the materials, and nothing else of a scene: the 48-byte records in scan-entry order (padding entries
+// zero), the same packed into 16 bytes where every record fits, and the type by ORIGINAL sphere index.  orig: the layout's table of
+// nEntries scan entries (0xffffffff: padding).  The one writer of these tables: PrepareScene calls it with its own layout, and
+// rt_set_materials with the layout kept from the upload, so an edit's tables are the upload's by construction.
+struct PreparedMaterials {
+    std::vector<rt_material> mats;
+    std::vector<U4> mats16;  // nEntries records either way; past the first record that does not fit they are zero
+    bool mats16Ok = false;
+    std::vector<uint32_t> matType;
+};
+PreparedMaterials PrepareMaterials(const rt_material* materials, uint32_t n, const uint32_t* orig, size_t nEntries);
+
 // spheres: n > 0, all finite (AllFinite).  A layout of 65,536 scan entries or more cannot be indexed by the 16-bit ids of the
 // tables behind it: then only `layout` is filled, and the caller refuses the scene.
 PreparedScene PrepareScene(const rt_sphere* spheres, const rt_material* materials, uint32_t n, const rt_light* lights, uint32_t n_lights,

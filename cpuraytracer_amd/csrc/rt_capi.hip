@@ -22,6 +22,7 @@
 #include "../../include/rt_api.h"
 #include "host/rt_camera_launch.h"
 #include "host/rt_denoise_host.h"
+#include "host/rt_edit_launch.h"
 #include "host/rt_denoise_launch.h"
 #include "host/rt_launch_plan.h"
 #include "host/rt_scene_prep.h"
@@ -152,6 +153,24 @@ struct rt_ctx {
     bool mats16Ok = false;
     rtd::TraceParams base{};  // scene part filled at upload; its camera fields again by rt_set_camera
     rt_camera camera{};       // the record of the last upload or rt_set_camera (rt_get_camera; the same-record test)
+
+    // shading edits (rt_set_materials, rt_set_lights, rt_set_exposure): the records of the last upload or edit, for the
+    // same-record test, and the layout's orig table, over which an edit rebuilds the three material tables (rtprep::PrepareMaterials)
+    std::vector<rt_material> materials;  // by ORIGINAL sphere index (the sky's record is `sky` below)
+    std::vector<uint32_t> origHost;      // rtprep::SceneLayout::orig of the upload
+    rt_light lights[RT_MAX_LIGHTS] = {};
+    uint32_t nLights = 0;                // as the caller counted them (0: light 0's slots hold the dark light)
+    // Pinned staging for the copies an edit or rt_temporal_forget orders on the stream: two slots used in turn, each with an event
+    // recorded behind its copies.  A slot is written again only once that event has completed -- the one host wait an edit may take,
+    // and it takes it only when two newer edits are still queued.  Sized at the upload (never under running kernels).
+    struct Stage {
+        void* host = nullptr;  // pinned
+        size_t bytes = 0;
+        hipEvent_t ev = nullptr;
+        bool queued = false;   // copies out of `host` were ordered and ev recorded behind them
+    } stage[2];
+    uint32_t stageNext = 0;
+    DevBuf<uint32_t> forgetBits;  // rt_temporal_forget's table form: kForgetTableWords words, reserved at rt_create
 
     // accumulation: the strips of seq's running accumulation
     uint32_t sampler = 0;      // RT_SAMPLER_* flags of the next / running accumulation (rt_set_sampler)
@@ -746,6 +765,43 @@ extern "C" {
 const char* rt_last_error(void) { return rtprep::LastError(); }
 int rt_api_version(void) { return RT_API_VERSION; }
 
+// ---- pinned staging of the shading edits (rt_ctx::Stage).  The largest table rt_temporal_forget copies: one bit per id a scene can hold.
+constexpr uint32_t kForgetMaxIds = 65536;
+constexpr uint32_t kForgetTableWords = kForgetMaxIds / 32u;
+static size_t MaterialStageBytes(size_t nPad, size_t n) { return nPad * (sizeof(rt_material) + sizeof(uint4)) + n * sizeof(uint32_t); }
+// Both slots hold at least `bytes`.  Called where the stream has run dry or nothing was ever queued (rt_create, rt_scene_upload
+// behind its hipStreamSynchronize): a slot that grows is not being read.
+static int StageReserve(rt_ctx* ctx, size_t bytes) {
+    for (auto& st : ctx->stage) {
+        if (!st.ev) RT_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+        if (st.bytes >= bytes) continue;
+        if (st.queued) RT_HIP(hipEventSynchronize(st.ev));
+        st.queued = false;
+        if (st.host) RT_HIP(hipHostFree(st.host));
+        st.host = nullptr, st.bytes = 0;
+        RT_HIP(hipHostMalloc(&st.host, bytes, hipHostMallocDefault));
+        st.bytes = bytes;
+    }
+    return RT_OK;
+}
+// The slot whose turn it is, free to be written: waits -- the host, for the slot's event -- only while copies out of it are still
+// queued, i.e. while two newer edits have not run yet.
+static int StageAcquire(rt_ctx* ctx, size_t bytes, rt_ctx::Stage** out) {
+    rt_ctx::Stage& st = ctx->stage[ctx->stageNext & 1u];
+    if (st.bytes < bytes) return Fail(RT_ERR_HIP, "shading edit: the staging is smaller than the tables (no upload sized it)");
+    if (st.queued) RT_HIP(hipEventSynchronize(st.ev));
+    st.queued = false;
+    *out = &st;
+    return RT_OK;
+}
+// ... and once its copies are ordered on the stream
+static int StageQueued(rt_ctx* ctx, rt_ctx::Stage* st) {
+    RT_HIP(hipEventRecord(st->ev, ctx->stream));
+    st->queued = true;
+    ctx->stageNext ^= 1u;
+    return RT_OK;
+}
+
 int rt_create(int device_ordinal, rt_ctx** out) {
     if (!out) return Fail(RT_ERR_INVALID_ARG, "rt_create: null out");
     *out = nullptr;
@@ -791,6 +847,8 @@ int rt_create(int device_ordinal, rt_ctx** out) {
     if (ctx->blockThreads != 256 && ctx->blockThreads != 512 && ctx->blockThreads != 1024) ctx->blockThreads = 256;
     int rc = ctx->queue.Reserve(rtd::kQueueShards * rtd::kShardStrideWords);  // eight queue cursors, 128 bytes apart
     if (rc == RT_OK) rc = ctx->counters.Reserve(6);
+    if (rc == RT_OK) rc = ctx->forgetBits.Reserve(kForgetTableWords);
+    if (rc == RT_OK) rc = StageReserve(ctx, kForgetTableWords * sizeof(uint32_t));
     if (rc != RT_OK) return rc;
     {
         // sample-buffer workspace: sized for this GPU's HBM (288 GB on MI355X), so that BASELINE configs 3 (on one GPU:
@@ -814,6 +872,10 @@ void rt_destroy(rt_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->skyCountHost) (void)hipHostFree(ctx->skyCountHost);
     if (ctx->skyEv) (void)hipEventDestroy(ctx->skyEv);
+    for (auto& st : ctx->stage) {
+        if (st.host) (void)hipHostFree(st.host);
+        if (st.ev) (void)hipEventDestroy(st.ev);
+    }
     if (ctx->streamEv) (void)hipEventDestroy(ctx->streamEv);
     for (auto& ev : ctx->ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -905,7 +967,9 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     if ((rc = ctx->radius.Upload(P.radius)) != RT_OK) return rc;
     if ((rc = ctx->mats.Upload(P.mats)) != RT_OK) return rc;
     ctx->mats16Ok = P.mats16Ok;
-    if (P.mats16Ok && (rc = ctx->mats16.Upload(P.mats16)) != RT_OK) return rc;
+    // (the packed table has its full size whether or not this scene packs: a later rt_set_materials that flips mats16Ok only copies)
+    if ((rc = P.mats16Ok ? ctx->mats16.Upload(P.mats16) : ctx->mats16.Reserve(P.mats16.size())) != RT_OK) return rc;
+    if ((rc = StageReserve(ctx, MaterialStageBytes(nPad, n))) != RT_OK) return rc;
     if ((rc = ctx->matType.Upload(P.matType)) != RT_OK) return rc;
     rttile::SceneReplaced(ctx->tiles);  // (their inputs are overwritten: nothing of the tiles' tables is valid)
     (void)rtseq::TileTablesDropped(ctx->seq);
@@ -996,6 +1060,10 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     ctx->n = n;
     ctx->sky = *sky;
     ctx->camera = *camera;
+    ctx->materials.assign(materials, materials + n);
+    ctx->origHost = L.orig;
+    ctx->nLights = n_lights;
+    for (uint32_t k = 0; k < n_lights; ++k) ctx->lights[k] = lights[k];
     DropVoided(ctx, rtseq::SceneReplaced(ctx->seq));
     return RT_OK;
 }
@@ -1027,6 +1095,16 @@ static bool SameCameraBits(const rt_camera& a, const rt_camera& b) {
     return true;
 }
 
+// What a change of the camera voids, and a change of materials, sky, light radiance or exposure with it -- every picture and every
+// per-tile table is a function of each of them (the work order reads matType, the empty-list tiles' constant sample reads sky and
+// exposure): decided by the camera's two events, written here once for the four entries.  The caller has settled
+// rtseq::kSettleBeforeCamera and put the new values in place.
+static void PictureInputChanged(rt_ctx* ctx) {
+    rttile::CameraChanged(ctx->tiles);
+    (void)rtseq::TileTablesDropped(ctx->seq);
+    DropVoided(ctx, rtseq::CameraChanged(ctx->seq));
+}
+
 int rt_set_camera(rt_ctx* ctx, const rt_camera* camera) {
     if (!ctx || !camera) return Fail(RT_ERR_INVALID_ARG, "rt_set_camera: null argument");
     if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_set_camera: no scene uploaded");
@@ -1041,9 +1119,7 @@ int rt_set_camera(rt_ctx* ctx, const rt_camera* camera) {
     RT_HIP((hipError_t)rtcam::LaunchLightCamera(ctx->stream, ctx->lightRecs.ptr, extra, camera->origin));
     SetCamera(ctx->base, *camera);
     ctx->camera = *camera;
-    rttile::CameraChanged(ctx->tiles);  // (every per-tile table is a function of the camera)
-    (void)rtseq::TileTablesDropped(ctx->seq);
-    DropVoided(ctx, rtseq::CameraChanged(ctx->seq));
+    PictureInputChanged(ctx);
     return RT_OK;
 }
 
@@ -1051,6 +1127,98 @@ int rt_get_camera(rt_ctx* ctx, rt_camera* out) {
     if (!ctx || !out) return Fail(RT_ERR_INVALID_ARG, "rt_get_camera: null argument");
     if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_get_camera: no scene uploaded");
     *out = ctx->camera;
+    return RT_OK;
+}
+
+// ---- shading edits: materials, sky, light radiance and exposure without an upload (rt_api.h).  Each computes what an
+// upload with the new values computes, voids what rt_set_camera voids, runs no scene preparation and takes no host wait but the
+// staging's (StageAcquire).
+int rt_set_materials(rt_ctx* ctx, const rt_material* materials, uint32_t n, const rt_material* sky) {
+    if (!ctx || !materials || !sky) return Fail(RT_ERR_INVALID_ARG, "rt_set_materials: null argument");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_set_materials: no scene uploaded");
+    if (n != ctx->n) return Fail(RT_ERR_INVALID_ARG, "rt_set_materials: " + std::to_string(n) + " records for a scene of " + std::to_string(ctx->n) + " spheres");
+    uint32_t bad = 0;
+    const char* field = nullptr;
+    if (!rtprep::MaterialsInDomain(materials, n, &bad, &field))
+        return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_set_materials", "sphere " + std::to_string(bad), materials[bad], field));
+    if ((field = rtprep::MaterialFault(*sky)) != nullptr) return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_set_materials", "the sky", *sky, field));
+    // the same records, all 48 bytes of each (the device tables hold them whole): not an event
+    const bool sameTable = std::memcmp(materials, ctx->materials.data(), (size_t)n * sizeof(rt_material)) == 0;
+    const bool sameSky = std::memcmp(sky, &ctx->sky, sizeof(rt_material)) == 0;
+    if (sameTable && sameSky) return RT_OK;
+    RT_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old materials
+    if (!sameTable) {
+        // The three tables, by their one writer over the upload's layout, through pinned staging and copies ordered on the stream behind
+        // every launch of the old materials.  No allocation: each buffer has had its full size since the upload.
+        const size_t nPad = ctx->origHost.size();
+        const rtprep::PreparedMaterials M = rtprep::PrepareMaterials(materials, n, ctx->origHost.data(), nPad);
+        rt_ctx::Stage* st = nullptr;
+        if ((rc = StageAcquire(ctx, MaterialStageBytes(nPad, n), &st)) != RT_OK) return rc;
+        char* h = static_cast<char*>(st->host);
+        const size_t b0 = nPad * sizeof(rt_material), b1 = nPad * sizeof(uint4), b2 = (size_t)n * sizeof(uint32_t);
+        std::memcpy(h, M.mats.data(), b0);
+        std::memcpy(h + b0, M.mats16.data(), b1);
+        std::memcpy(h + b0 + b1, M.matType.data(), b2);
+        RT_HIP(hipMemcpyAsync(ctx->mats.ptr, h, b0, hipMemcpyHostToDevice, ctx->stream));
+        if (M.mats16Ok) RT_HIP(hipMemcpyAsync(ctx->mats16.ptr, h + b0, b1, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(hipMemcpyAsync(ctx->matType.ptr, h + b0 + b1, b2, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = StageQueued(ctx, st)) != RT_OK) return rc;
+        ctx->mats16Ok = M.mats16Ok;  // (either way round: the launch plan reads the pointer)
+        ctx->base.mats16 = M.mats16Ok ? ctx->mats16.ptr : nullptr;
+        ctx->materials.assign(materials, materials + n);
+    }
+    for (int k = 0; k < 3; ++k) ctx->base.sky_emit[k] = sky->luminance * sky->rgb0[k];  // as the upload
+    ctx->sky = *sky;
+    PictureInputChanged(ctx);
+    return RT_OK;
+}
+
+int rt_set_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights) {
+    if (!ctx || (!lights && n_lights != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_set_lights: null argument");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_set_lights: no scene uploaded");
+    if (n_lights != ctx->nLights)
+        return Fail(RT_ERR_INVALID_ARG, "rt_set_lights: " + std::to_string(n_lights) + " lights for a scene uploaded with " + std::to_string(ctx->nLights));
+    bool same = true;
+    for (uint32_t k = 0; k < n_lights; ++k) {
+        if (std::memcmp(lights[k].direction, ctx->lights[k].direction, sizeof lights[k].direction) != 0)
+            return Fail(RT_ERR_INVALID_ARG, "rt_set_lights: light " + std::to_string(k) +
+                                                " has another direction than the uploaded one: a direction change needs an rt_scene_upload (the light's shadow index is built for its direction)");
+        if (!std::isfinite(lights[k].luminance) || !std::isfinite(lights[k].color[0]) || !std::isfinite(lights[k].color[1]) || !std::isfinite(lights[k].color[2]))
+            return Fail(RT_ERR_INVALID_ARG, "rt_set_lights: light " + std::to_string(k) + " has a colour or a luminance that is not finite");
+        same = same && std::memcmp(lights[k].color, ctx->lights[k].color, sizeof lights[k].color) == 0 &&
+               std::memcmp(&lights[k].luminance, &ctx->lights[k].luminance, sizeof(float)) == 0;
+    }
+    if (same) return RT_OK;  // (n_lights == 0 included)
+    RT_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old lights
+    // Light 0's radiance is a launch parameter.  Lights 1 .. keep theirs in device memory: patched on the stream, by value, behind
+    // every launch of the old radiance (the far-tier record behind them holds an index and no light).
+    rtd::LightRec tmp{};
+    rtedit::LightRadiance R{};
+    for (uint32_t k = 1; k < n_lights; ++k) {
+        SetLight(tmp, lights[k]);
+        for (int c = 0; c < 3; ++c) R.rad[k - 1][c] = tmp.sun_rad[c];
+    }
+    RT_HIP((hipError_t)rtedit::LaunchLightRadiance(ctx->stream, ctx->lightRecs.ptr, n_lights - 1u, R));
+    SetLight(ctx->base, lights[0]);
+    for (uint32_t k = 0; k < n_lights; ++k) ctx->lights[k] = lights[k];
+    PictureInputChanged(ctx);
+    return RT_OK;
+}
+
+int rt_set_exposure(rt_ctx* ctx, float exposure_scale) {
+    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_set_exposure: null ctx");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_set_exposure: no scene uploaded");
+    if (!std::isfinite(exposure_scale)) return Fail(RT_ERR_INVALID_ARG, "rt_set_exposure: the exposure is not finite");
+    if (std::memcmp(&exposure_scale, &ctx->base.exposure, sizeof(float)) == 0) return RT_OK;
+    RT_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old exposure
+    ctx->base.exposure = exposure_scale;
+    PictureInputChanged(ctx);
     return RT_OK;
 }
 
@@ -1787,6 +1955,32 @@ int rt_denoise_shards_temporal_variance(rt_ctx* ctx, const rt_shard_frame* frame
 int rt_temporal_reset(rt_ctx* ctx) {
     if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_temporal_reset: null ctx");
     ctx->tmpValid = false;
+    return RT_OK;
+}
+
+// Empties the history of the pixels that hold one of the ids (rt_edit.hip, ../rt_forget.h): stream-ordered, no host wait but the
+// staging's, and that only for more than kForgetInlineIds ids.  Needs no scene: ids are then bounded by what a scene can hold.
+int rt_temporal_forget(rt_ctx* ctx, const uint32_t* ids, uint32_t n_ids) {
+    if (!ctx || (!ids && n_ids != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_temporal_forget: null argument");
+    if (n_ids == 0 || !ctx->tmpValid) return RT_OK;
+    const uint32_t nSpheres = ctx->seq.hasScene ? ctx->n : kForgetMaxIds;
+    rtedit::ForgetPlan P = rtedit::PlanForget(ids, n_ids, nSpheres < kForgetMaxIds ? nSpheres : kForgetMaxIds);
+    if (P.nothing) return RT_OK;
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->tmpPic.W * ctx->tmpPic.rs.num_rows;
+    if (npix > 0x7fffffffull) return Fail(RT_ERR_INVALID_ARG, "rt_temporal_forget: a history of more than 2^31 pixels");
+    if (!P.table.empty()) {
+        int rc;
+        rt_ctx::Stage* st = nullptr;
+        const size_t bytes = P.table.size() * sizeof(uint32_t);
+        if ((rc = StageAcquire(ctx, bytes, &st)) != RT_OK) return rc;
+        std::memcpy(st->host, P.table.data(), bytes);
+        RT_HIP(hipMemcpyAsync(ctx->forgetBits.ptr, st->host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = StageQueued(ctx, st)) != RT_OK) return rc;
+        P.set.bits = ctx->forgetBits.ptr;
+    }
+    const rt_ctx::TemporalSet& t = ctx->tmpSet[ctx->tmpCur & 1u];
+    RT_HIP((hipError_t)rtedit::LaunchTemporalForget(ctx->stream, t.len.ptr, t.ids.ptr, (uint32_t)npix, P.set));
     return RT_OK;
 }
 

@@ -131,6 +131,8 @@ class HipRenderer:
         sky = _capi.RtMaterial.from_buffer_copy(bytes(scene.sky))
         check(self._L.rt_scene_upload(self._h, sph.ctypes.data, mat.ctypes.data, sph.shape[0], C.byref(cam), lights, len(ls),
                                       C.byref(sky), float(scene.exposure_scale)))
+        self._materials = mat.copy()  # (set_materials compares against them: which spheres to forget)
+        self._sky = bytes(sky)
 
     def set_camera(self, camera):
         """rt_set_camera: move the camera of the uploaded scene without an upload -- no scene preparation, no table copied, no host
@@ -146,6 +148,54 @@ class HipRenderer:
         cam = _capi.RtCamera()
         check(self._L.rt_get_camera(self._h, C.byref(cam)))
         return cam
+
+    def set_materials(self, materials, sky=None, forget=True):
+        """rt_set_materials: new material records (the structured array of scene.materials, one per sphere) and sky (an rt_material
+        record; None keeps the current one) for the uploaded scene without an upload -- no scene preparation, no host wait of its
+        own.  Everything computed afterwards equals, bit for bit, what an upload() of the same spheres, camera and lights with these
+        records computes; voids and keeps what set_camera() does.  The same records again change nothing.
+        forget=True: the temporal history's validation never looks at colour, so the spheres whose 48-byte record changed -- and the
+        sky, 0xffffffff, when its record did -- are handed to temporal_forget(): their pixels start over.  Returns the ids forgotten.
+        forget=False is the bare C call and returns []."""
+        mat = np.ascontiguousarray(materials)
+        assert mat.dtype.itemsize == 48 and mat.ndim == 1
+        sky_bytes = self._sky if sky is None else bytes(sky)
+        sky_rec = _capi.RtMaterial.from_buffer_copy(sky_bytes)
+        check(self._L.rt_set_materials(self._h, mat.ctypes.data, mat.shape[0], C.byref(sky_rec)))
+        old = self._materials
+        changed = []
+        if forget:
+            a = mat.view(np.uint8).reshape(mat.shape[0], 48)
+            b = old.view(np.uint8).reshape(old.shape[0], 48)
+            changed = [int(k) for k in np.nonzero(np.any(a != b, axis=1))[0]]
+            if sky_bytes != self._sky:
+                changed.append(_capi.FORGET_SKY)
+        self._materials = mat.copy()
+        self._sky = sky_bytes
+        if changed:
+            self.temporal_forget(changed)
+        return changed
+
+    def set_lights(self, lights):
+        """rt_set_lights: new colours and luminances for the uploaded lights (a list of rt_light records, as many as uploaded, each
+        with the uploaded direction bit for bit: a direction change needs an upload()).  Equivalence, voids and keeps as
+        set_materials(); never waits."""
+        ls = list(lights)
+        arr = (_capi.RtLight * max(1, len(ls)))()
+        for k, l in enumerate(ls):
+            arr[k] = _capi.RtLight.from_buffer_copy(bytes(l))
+        check(self._L.rt_set_lights(self._h, arr, len(ls)))
+
+    def set_exposure(self, exposure_scale):
+        """rt_set_exposure: a new exposure for the uploaded scene.  Equivalence, voids and keeps as set_materials(); never waits."""
+        check(self._L.rt_set_exposure(self._h, float(exposure_scale)))
+
+    def temporal_forget(self, ids):
+        """rt_temporal_forget: every pixel of the current history whose id is in ids (sphere indices; 0xffffffff, _capi.FORGET_SKY, is
+        the sky) gets len = 0, so the next temporal call treats it as a pixel with no history.  Stream-ordered, no host wait; an empty
+        list or an empty history does nothing."""
+        f = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        check(self._L.rt_temporal_forget(self._h, f.ctypes.data if f.size else None, f.size))
 
     def render(self, W, H, s0, s1, max_depth, seed, rowset=None, stats=True):
         """rt_render; stats=False passes out_stats = NULL: the call only enqueues work on the context's stream (no host

@@ -203,6 +203,38 @@ int rt_set_camera(rt_ctx* ctx, const rt_camera* camera);
 /* The record of the last rt_scene_upload or (changing) rt_set_camera, all 72 bytes.  RT_ERR_NO_SCENE before any upload. */
 int rt_get_camera(rt_ctx* ctx, rt_camera* out);
 
+/* Shading edits: new materials and sky, new light colours and luminances, a new exposure for the uploaded scene, without an upload.
+ * No scene preparation, no host wait of their own, no device memory allocated or freed.  Clustering, bounds, hierarchy, cell grid and
+ * every shadow index are functions of the spheres and the light directions alone and stay as they are.
+ * Equivalence: after a successful call everything the context computes is, bit for bit, what it computes after an rt_scene_upload of
+ * the same spheres, camera and light directions with the new materials and sky, light colours and luminances, or exposure: rt_render
+ * under every progressive mode (HDR, LDR, moments, rt_stats' counters, the kernel variant of rt_unit_last_trace_launch -- an edit after
+ * which the materials pack into 16 bytes, or no longer do, takes the variant the upload takes), the per-tile unit entries,
+ * rt_render_features and the denoise family (picture, history, target).
+ * Void and keep: exactly what rt_set_camera voids and keeps -- the accumulation (a continuing rt_render is RT_ERR_SEQUENCE), planes
+ * traced ahead, frames in flight, every per-tile table (the work order reads the material types, the constant sample of the empty-list
+ * tiles reads sky and exposure), the feature strips and the denoise snapshot are void; a pending batch is rendered first, under the
+ * old values, and its errors surface here; scene tables, camera, sampler flags, noise switch, progressive settings, stream and the
+ * temporal history stay.  The history's validation never looks at colour: see rt_temporal_forget.
+ * Same values: records equal to the current ones as bit patterns change nothing and void nothing (rt_set_camera's precedent).
+ * Compared are all 48 bytes of every material record and of the sky's (the device tables hold the records whole), colour and
+ * luminance of every light, the exposure.
+ * Waits: the new tables travel through pinned memory the context owns, two sets used in turn; a call waits for the host only where
+ * the copies of the edit before the previous one have not run yet.  rt_set_lights and rt_set_exposure never wait.
+ * Refused before any side effect, a refused call changes nothing:
+ *   - a null argument: RT_ERR_INVALID_ARG (lights may be NULL where n_lights == 0); no scene uploaded: RT_ERR_NO_SCENE;
+ *   - rt_set_materials: n other than the uploaded sphere count; a record or the sky outside the material domain (rt_material above;
+ *     the message names the sphere, or "the sky", and the field): RT_ERR_INVALID_ARG;
+ *   - rt_set_lights: n_lights other than the uploaded count; a direction that differs as a bit pattern from the uploaded one -- the
+ *     light's shadow index is built for its direction, a direction change needs an upload; a colour or luminance that is not finite:
+ *     RT_ERR_INVALID_ARG;
+ *   - rt_set_exposure: an exposure that is not finite: RT_ERR_INVALID_ARG.
+ * Like rt_set_camera they are stricter than the upload in one place: rt_scene_upload keeps accepting light colours, luminances and
+ * exposures that are not finite. */
+int rt_set_materials(rt_ctx* ctx, const rt_material* materials, uint32_t n, const rt_material* sky);
+int rt_set_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights);
+int rt_set_exposure(rt_ctx* ctx, float exposure_scale);
+
 /* ----------------------------------------------------------------- render */
 
 /* Replaces GenerateRays + the for_each(par) trace loop for sample indices s in
@@ -438,6 +470,15 @@ int rt_temporal_reset(rt_ctx* ctx);
 /* The history as the last rt_denoise_temporal left it: state4 = W*rows*4 floats (c'.rgb, v'), len and target = W*rows words each.  Any
  * pointer may be NULL.  RT_ERR_SEQUENCE while the history is empty. */
 int rt_download_temporal(rt_ctx* ctx, float* state4, uint32_t* len, uint32_t* target);
+/* Forget what the history knows about some objects: every pixel of the current history whose stored id is one of ids[0 .. n_ids) gets
+ * len = 0, so that the next temporal call of either fetch, contiguous or sharded, treats it exactly as a pixel with no history (the
+ * nearest fetch's length test fails, a bilinear tap does not take part): len' = 1, target 0xffffffff, the state the frame's own.  What a
+ * caller does after recolouring a sphere (rt_set_materials), since the history's validation tests id, depth, normal and coverage,
+ * never colour.  0xffffffff names the sky; ids at or above the sphere count (without a scene: at or above 65536) are accepted and
+ * match nothing.  Everything else of the history -- state, guides, ids, other pixels' len, its camera -- is untouched.
+ * Stream-ordered, no host wait (more than 16 ids travel as a table through the edits' pinned memory, with its rule).  n_ids == 0 or an
+ * empty history: RT_OK, nothing happens.  A null context, or null ids with n_ids > 0: RT_ERR_INVALID_ARG.  Needs no scene. */
+int rt_temporal_forget(rt_ctx* ctx, const uint32_t* ids, uint32_t n_ids);
 /* The way the history is fetched, chosen per call.  RT_TEMPORAL_FETCH_NEAREST is everything above.  RT_TEMPORAL_FETCH_BILINEAR reads
  * the four pixels whose centres surround the reprojected point, so that a sample k calls old is not up to k/2 pixels off.  For a point
  * the reprojection accepts (fx, fy, xi, yi, dist as above), in the same arithmetic:
@@ -703,6 +744,10 @@ int rt_unit_temporal_shards_host(const float* hdr, const float* sq, const float*
  * floats per pixel, as the levels read it.  Needs no GPU. */
 int rt_unit_denoise_variance_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, uint32_t W, uint32_t rows,
                                   const rt_denoise_params* params, const rt_variance_params* vparams, float* out_rgb, float* out_var, float* out_state4);
+/* rt_temporal_forget on the host, from the same membership rule (csrc/rt_forget.h), in place: len[p] = 0 for every p < npix whose
+ * ids[p] is one of forget_ids[0 .. n_ids); 0xffffffff names the sky, ids at or above n_spheres match nothing.  npix > 0 with len or
+ * ids NULL, or n_ids > 0 with forget_ids NULL: RT_ERR_INVALID_ARG.  Needs no GPU. */
+int rt_unit_temporal_forget_host(uint32_t* len, const uint32_t* ids, uint32_t npix, uint32_t n_spheres, const uint32_t* forget_ids, uint32_t n_ids);
 /* rt_unit_temporal_host_fetch with the variance source chosen: the twin of rt_denoise_temporal_variance, sq and n as above. */
 int rt_unit_temporal_variance_host(const float* hdr, const float* sq, uint32_t n, const float* feat8, uint32_t m, const uint32_t* ids, uint32_t W, uint32_t H,
                                    uint32_t first_row, uint32_t num_rows, const rt_camera* camera, const rt_camera* hist_camera, const float* hist_state4,
