@@ -101,6 +101,7 @@ EXPORTS = [
     "rt_denoise_shards_variance", "rt_denoise_shards_temporal_variance", "rt_unit_denoise_shards_variance_host", "rt_unit_temporal_shards_variance_host",
     "rt_set_camera", "rt_get_camera",
     "rt_set_materials", "rt_set_lights", "rt_set_exposure", "rt_temporal_forget", "rt_unit_temporal_forget_host",
+    "rt_unit_tile_order", "rt_unit_tile_order_sort",
 ]
 
 _lib = None
@@ -187,6 +188,10 @@ def load():
         L.rt_unit_tile_spheres.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
         L.rt_unit_tile_spheres_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtCamera), C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.c_uint32,
                                                 C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
+    if hasattr(L, "rt_unit_tile_order"):
+        L.rt_unit_tile_order.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_unit_tile_order_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     if hasattr(L, "rt_set_noise_estimate"):
         L.rt_set_noise_estimate.argtypes = [C.c_void_p, C.c_int]
         L.rt_download_moments.argtypes = [C.c_void_p, C.c_void_p]

@@ -595,6 +595,44 @@ static void SkyCountPoll(rt_ctx* ctx) {
         rttile::CountFailed(ctx->tiles);  // a real error: the count stays unknown, and the error is left for the call that follows to report
     }
 }
+// The launches of a work order for nFull full tiles of a picture, into the buffers given: the one place they are written down, for
+// BuildTileOrder (the context's kept buffers) and rt_unit_tile_order (buffers of the entry's own).  flags: lists (kTileSphereHalfs per
+// tile) are read and dst.flags / dst.info written first; order: pilot rays, the production closest-hit scan, classes, the sort.
+// Every buffer has room for nFull tiles (rays 6, hits 10 floats per pilot; info 4 words).  On the stream, no host wait.
+struct TileOrderDest {
+    float* pilotRays = nullptr;
+    float* pilotHits = nullptr;
+    uint8_t* cls = nullptr;
+    uint32_t* order = nullptr;
+    uint8_t* flags = nullptr;
+    uint32_t* info = nullptr;
+};
+static int LaunchTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t nFull, bool flags, bool order, const uint16_t* lists,
+                           const TileOrderDest& dst) {
+    int rc;
+    if (flags) {
+        RT_HIP(hipMemsetAsync(dst.info, 0, 4 * sizeof(uint32_t), ctx->stream));
+        hipLaunchKernelGGL(rtd::rt_sky_tiles_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->base, lists, nFull, dst.flags, dst.info);
+        RT_HIP(hipGetLastError());
+    }
+    if (order) {
+        const uint32_t nPilot = nFull * rtd::kPilotsPerTile;
+        rtd::TraceParams tp = ctx->base;
+        SetPicture(tp, pic);
+        tp.s0 = 1;
+        tp.sampler = ctx->sampler;
+        tp.jitter_tab = nullptr;
+        tp.lens_tab = nullptr;
+        hipLaunchKernelGGL(rtd::rt_pilot_rays_kernel, dim3((nPilot + 255) / 256), dim3(256), 0, ctx->stream, tp, nFull, dst.pilotRays);
+        RT_HIP(hipGetLastError());
+        if ((rc = LaunchClosest(ctx, dst.pilotRays, nPilot, dst.pilotHits)) != RT_OK) return rc;
+        hipLaunchKernelGGL(rtd::rt_tile_class_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, dst.pilotHits, nFull, pic.W,
+                           ctx->matType.ptr, dst.cls, flags ? dst.flags : (const uint8_t*)nullptr);
+        hipLaunchKernelGGL(rtd::rt_tile_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, dst.cls, nFull, dst.order);
+        RT_HIP(hipGetLastError());
+    }
+    return RT_OK;
+}
 static int BuildTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t npix) {
     const rttile::OrderPlan plan = rttile::PlanOrder(ctx->tiles, pic, npix, (uint32_t)ctx->cuCount);
     if (!plan.rebuild) return RT_OK;
@@ -606,10 +644,6 @@ static int BuildTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t np
         if (!ctx->skyCountHost) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->skyCountHost), sizeof(uint32_t), hipHostMallocDefault));
         if ((rc = ctx->skyFlags.Reserve(nFull)) != RT_OK) return rc;
         if ((rc = ctx->skyInfo.Reserve(4)) != RT_OK) return rc;
-        RT_HIP(hipMemsetAsync(ctx->skyInfo.ptr, 0, 4 * sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(rtd::rt_sky_tiles_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->base, ctx->tileSpheres.ptr, nFull,
-                           ctx->skyFlags.ptr, ctx->skyInfo.ptr);
-        RT_HIP(hipGetLastError());
     }
     if (plan.order) {
         const uint32_t nPilot = nFull * rtd::kPilotsPerTile;
@@ -617,20 +651,11 @@ static int BuildTileOrder(rt_ctx* ctx, const rtseq::PictureKey& pic, uint32_t np
         if ((rc = ctx->pilotHits.Reserve((size_t)nPilot * 10)) != RT_OK) return rc;
         if ((rc = ctx->tileClass.Reserve(nFull)) != RT_OK) return rc;
         if ((rc = ctx->tileOrder.Reserve(nFull)) != RT_OK) return rc;
-        rtd::TraceParams tp = ctx->base;
-        SetPicture(tp, pic);
-        tp.s0 = 1;
-        tp.sampler = ctx->sampler;
-        tp.jitter_tab = nullptr;
-        tp.lens_tab = nullptr;
-        hipLaunchKernelGGL(rtd::rt_pilot_rays_kernel, dim3((nPilot + 255) / 256), dim3(256), 0, ctx->stream, tp, nFull, ctx->pilotRays.ptr);
-        RT_HIP(hipGetLastError());
-        if ((rc = LaunchClosest(ctx, ctx->pilotRays.ptr, nPilot, ctx->pilotHits.ptr)) != RT_OK) return rc;
-        hipLaunchKernelGGL(rtd::rt_tile_class_kernel, dim3((nFull + 255) / 256), dim3(256), 0, ctx->stream, ctx->pilotHits.ptr, nFull, pic.W,
-                           ctx->matType.ptr, ctx->tileClass.ptr, plan.flags ? ctx->skyFlags.ptr : (const uint8_t*)nullptr);
-        hipLaunchKernelGGL(rtd::rt_tile_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->tileClass.ptr, nFull, ctx->tileOrder.ptr);
-        RT_HIP(hipGetLastError());
     }
+    TileOrderDest dst;
+    dst.pilotRays = ctx->pilotRays.ptr, dst.pilotHits = ctx->pilotHits.ptr, dst.cls = ctx->tileClass.ptr, dst.order = ctx->tileOrder.ptr;
+    dst.flags = ctx->skyFlags.ptr, dst.info = ctx->skyInfo.ptr;
+    if ((rc = LaunchTileOrder(ctx, pic, nFull, plan.flags, plan.order, ctx->tileSpheres.ptr, dst)) != RT_OK) return rc;
     if (plan.count) {
         RT_HIP(hipMemcpyAsync(ctx->skyCountHost, ctx->skyInfo.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(hipEventRecord(ctx->skyEv, ctx->stream));
@@ -2411,6 +2436,88 @@ int rt_unit_tile_spheres(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint
         scans[1] = c[3];
         scans[2] = c[4];
     }
+    return RT_OK;
+}
+
+int rt_unit_tile_order_sort(rt_ctx* ctx, const uint8_t* classes, uint32_t n_tiles, uint32_t* order_out) {
+    if (!ctx || !classes || !order_out || n_tiles == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_order_sort: invalid argument");
+    for (uint32_t t = 0; t < n_tiles; ++t)
+        if (classes[t] >= rtd::kTileClasses) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_order_sort: tile " + std::to_string(t) + " has a class above 4");
+    RT_HIP(hipSetDevice(ctx->device));
+    constexpr size_t kGuard = 64;
+    DevBuf<uint8_t> dCls;
+    DevBuf<uint32_t> dOrder;
+    int rc;
+    if ((rc = dCls.UploadFrom(classes, n_tiles)) != RT_OK || (rc = dOrder.Reserve((size_t)n_tiles + kGuard)) != RT_OK) return rc;
+    RT_HIP(hipMemsetAsync(dOrder.ptr, 0xff, ((size_t)n_tiles + kGuard) * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(rtd::rt_tile_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, dCls.ptr, n_tiles, dOrder.ptr);  // as LaunchTileOrder
+    RT_HIP(hipGetLastError());
+    return dOrder.DownloadTo(order_out, (size_t)n_tiles + kGuard, ctx->stream);
+}
+
+int rt_unit_tile_order(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t source, uint32_t cap_tiles, uint32_t* n_tiles, float* pilot_rays,
+                       uint8_t* classes, uint8_t* flags, uint32_t* order, uint32_t info[4]) {
+    if (!ctx || !n_tiles || W == 0 || H == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_order: invalid argument");
+    if (source > 1u) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_order: source is 0 (build afresh) or 1 (the running accumulation's)");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_unit_tile_order: no scene uploaded");
+    const uint32_t rows = rtprep::UnitStripRows(rs, W, H);
+    if (rows == 0) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_order: bad row set");
+    const rtseq::PictureKey pic{W, H, rs};
+    const uint32_t nFull = (W * rows) >> 6, nPilot = nFull * rtd::kPilotsPerTile;
+    const bool wanted = pilot_rays || classes || flags || order;
+    RT_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if (source == 1u) {
+        const rttile::State::Order& o = ctx->tiles.order;
+        const bool held = o.keyValid && o.orderValid && o.pic == pic && nFull != 0u;
+        *n_tiles = held ? nFull : 0u;
+        RT_HIP(hipStreamSynchronize(ctx->stream));
+        if (!held) return RT_OK;
+        if (wanted && cap_tiles < nFull) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_order: capacity too small");
+        if (pilot_rays) RT_HIP(hipMemcpy(pilot_rays, ctx->pilotRays.ptr, (size_t)nPilot * 6 * sizeof(float), hipMemcpyDeviceToHost));
+        if (classes) RT_HIP(hipMemcpy(classes, ctx->tileClass.ptr, nFull, hipMemcpyDeviceToHost));
+        if (order) RT_HIP(hipMemcpy(order, ctx->tileOrder.ptr, (size_t)nFull * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (flags) {
+            if (o.flagsValid) RT_HIP(hipMemcpy(flags, ctx->skyFlags.ptr, nFull, hipMemcpyDeviceToHost));
+            else std::memset(flags, 0, nFull);
+        }
+        if (info) {
+            if (o.flagsValid) RT_HIP(hipMemcpy(info, ctx->skyInfo.ptr, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            else std::memset(info, 0, 4 * sizeof(uint32_t));
+        }
+        return RT_OK;
+    }
+    // source 0: masks and lists as rt_unit_tile_spheres obtains them (the mask tables may be rebuilt for this picture), everything
+    // else in buffers of this call's own: the kept order, flags and count, and rttile's account of them, are not touched.
+    const rttile::Knobs knobs = TileKnobsFromEnv();
+    if ((rc = BuildTileMasks(ctx, pic, W * rows, knobs)) != RT_OK) return rc;
+    *n_tiles = nFull;
+    if (nFull == 0u) {
+        RT_HIP(hipStreamSynchronize(ctx->stream));
+        return RT_OK;
+    }
+    if (wanted && cap_tiles < nFull) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_order: capacity too small");
+    const bool withFlags = rttile::ListTiles(ctx->tiles) != 0u && knobs.skipSky && knobs.excludeSky;
+    DevBuf<float> dRays, dHits;
+    DevBuf<uint8_t> dCls, dFlags;
+    DevBuf<uint32_t> dOrder, dInfo;
+    if ((rc = dRays.Reserve((size_t)nPilot * 6)) != RT_OK || (rc = dHits.Reserve((size_t)nPilot * 10)) != RT_OK || (rc = dCls.Reserve(nFull)) != RT_OK ||
+        (rc = dOrder.Reserve(nFull)) != RT_OK || (rc = dFlags.Reserve(nFull)) != RT_OK || (rc = dInfo.Reserve(4)) != RT_OK)
+        return rc;
+    if (!withFlags) {  // no flags: the outputs read 0
+        RT_HIP(hipMemsetAsync(dFlags.ptr, 0, nFull, ctx->stream));
+        RT_HIP(hipMemsetAsync(dInfo.ptr, 0, 4 * sizeof(uint32_t), ctx->stream));
+    }
+    TileOrderDest dst;
+    dst.pilotRays = dRays.ptr, dst.pilotHits = dHits.ptr, dst.cls = dCls.ptr, dst.order = dOrder.ptr, dst.flags = dFlags.ptr, dst.info = dInfo.ptr;
+    rc = LaunchTileOrder(ctx, pic, nFull, withFlags, true, ctx->tileSpheres.ptr, dst);
+    RT_HIP(hipStreamSynchronize(ctx->stream));  // (also after a failed launch: the buffers are freed at the return)
+    if (rc != RT_OK) return rc;
+    if (pilot_rays) RT_HIP(hipMemcpy(pilot_rays, dRays.ptr, (size_t)nPilot * 6 * sizeof(float), hipMemcpyDeviceToHost));
+    if (classes) RT_HIP(hipMemcpy(classes, dCls.ptr, nFull, hipMemcpyDeviceToHost));
+    if (flags) RT_HIP(hipMemcpy(flags, dFlags.ptr, nFull, hipMemcpyDeviceToHost));
+    if (order) RT_HIP(hipMemcpy(order, dOrder.ptr, (size_t)nFull * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (info) RT_HIP(hipMemcpy(info, dInfo.ptr, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

@@ -473,6 +473,32 @@ class HipRenderer:
             check(rc)
         return n.value
 
+    def unit_tile_order(self, W, H, rowset=None, source=0):
+        """rt_unit_tile_order: the work order of the strip's full tiles -- source 0 built afresh into buffers of the call's own (any tile
+        count), source 1 what the context keeps for its running accumulation of this picture.  Returns None where there is none
+        (*n_tiles = 0), else a dict: pilot_rays (n, 3, 6) float32, classes and flags (n,) uint8, order (n,) uint32, info (4,) uint32
+        ([0] flagged tiles, [1..3] the bits of their constant sample)."""
+        rs = rowset if rowset is not None else whole_image(H)
+        rs = RtRowset.from_buffer_copy(bytes(rs))
+        cap = max((W * self._L.rt_rowset_local_rows(rs)) >> 6, 1)
+        out = {"pilot_rays": np.zeros((cap, 3, 6), dtype=np.float32), "classes": np.full(cap, 0xEE, dtype=np.uint8),
+               "flags": np.full(cap, 0xEE, dtype=np.uint8), "order": np.full(cap, 0xEEEEEEEE, dtype=np.uint32),
+               "info": np.full(4, 0xEEEEEEEE, dtype=np.uint32)}
+        n = C.c_uint32(0)
+        check(self._L.rt_unit_tile_order(self._h, W, H, rs, int(source), cap, C.byref(n), out["pilot_rays"].ctypes.data, out["classes"].ctypes.data,
+                                         out["flags"].ctypes.data, out["order"].ctypes.data, out["info"].ctypes.data))
+        if n.value == 0:
+            return None
+        return {k: (v if k == "info" else v[:n.value]) for k, v in out.items()}
+
+    def unit_tile_order_sort(self, classes):
+        """rt_unit_tile_order_sort: the production sort kernel over the given stored classes (uint8, each below 5).  Returns (order,
+        guards): the n words of the order and the 64 guard words behind them (0xffffffff when intact)."""
+        cls = np.ascontiguousarray(classes, dtype=np.uint8).reshape(-1)
+        out = np.zeros(cls.shape[0] + 64, dtype=np.uint32)
+        check(self._L.rt_unit_tile_order_sort(self._h, cls.ctypes.data if cls.size else None, cls.shape[0], out.ctypes.data))
+        return out[:cls.shape[0]], out[cls.shape[0]:]
+
     def unit_halton(self, index, base):
         index = np.ascontiguousarray(index, dtype=np.uint32)
         out = np.zeros(index.shape[0], dtype=np.float32)

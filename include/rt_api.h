@@ -682,6 +682,44 @@ int rt_unit_sky_planes(rt_ctx* ctx, uint64_t* planes);
  * asynchronously where the tables are built and never waited for, so the first rt_render of a picture reports 0), RT_SKY_EXCLUDE=0,
  * RT_SKY_SKIP=0, RT_TILE_ORDER=0, too few tiles for a work order, a partial last tile, frame pipelining. */
 int rt_unit_sky_excluded(rt_ctx* ctx, uint32_t* tiles);
+/* The work order of the full tiles (csrc/rt_kernels.h, "work order of the tiles"), which rt_render builds where an accumulation of a
+ * picture with at least 2 x compute-units full tiles starts (RT_TILE_ORDER=0: never) and whose trace launches take their tiles through.
+ * The contract of the order, for a strip of npix = W x local rows pixels, tile t = local pixels [64 t, 64 t + 64) in row-major order of
+ * the strip (a tile may straddle two rows), nFull = npix / 64 full tiles:
+ *   - pilots: three primary rays per full tile, those of its local pixels 64 t, 64 t + 32 and 64 t + 63 (first, middle, last), each at
+ *     sample 1: pixel (i, j) = (p mod W, rt_rowset_global_row(rs, p / W)), the ray rt_unit_primary_rays gives for (i, j, 1) under the
+ *     context's sampler flags (jitter and lens sample included).  Their first hits are rt_unit_closest_hit's.
+ *   - pilot class of a tile: the largest over its three pilots of 0 nothing hit, 3 RT_MAT_DIELECTRIC_TRANSPARENT, 2 RT_MAT_METAL, 1 any
+ *     other material (the type of the sphere hit first).
+ *   - neighbour rule: a tile whose pilot class is below 3 gets 3 if one of six pixels lies in a FULL tile of pilot class 3 -- with
+ *     f = 64 t the local pixels f - 64, f + 64 (the tiles before and after), f - W, f - W + 63 (above its first and its last pixel),
+ *     f + W, f + W + 63 (below them); a pixel before the strip, or in the partial last tile or beyond, counts for nothing.  The rule
+ *     reads pilot classes only: it does not propagate.
+ *   - stored class: 0 for a flagged tile, else 1 + the class after the rule (1 nothing hit, 2 other, 3 metal, 4 glass).  A tile is
+ *     flagged iff its sphere list (rt_unit_tile_spheres) is EMPTY, where the picture has lists and RT_SKY_SKIP and RT_SKY_EXCLUDE are
+ *     on; the flag is applied AFTER the rule, so a flagged tile next to glass stays 0 -- and is never a source of the rule itself.
+ *   - order: the stable sort of 0 .. nFull - 1 by DESCENDING stored class -- a permutation that ends with exactly the flagged tiles.
+ *
+ * rt_unit_tile_order, source 0: builds all of that afresh for the strip rs of a W x H image -- pilot rays, the production closest-hit
+ * scan, the flags, classes, the sort: the very launches rt_render makes, into buffers of the call's own -- for ANY nFull >= 1 (the
+ * 2 x compute-units threshold is a scheduling decision, not part of what the kernels compute) and whatever RT_TILE_ORDER says.  Masks
+ * and lists are obtained as rt_unit_tile_spheres obtains them, under the knobs of the moment, and like it the call may rebuild the mask
+ * tables for this picture; the order, flags and count the context keeps for its running accumulation are not touched.  source 1: copies
+ * out what the context keeps for its running accumulation of exactly this picture; *n_tiles = 0 where it keeps no order (too few tiles,
+ * RT_TILE_ORDER=0, another picture, nothing rendered since an upload, a camera move or a shading edit).
+ * Out, each where the pointer is not null and for *n_tiles = nFull tiles: pilot_rays 18 floats per tile (origin xyz, direction xyz of
+ * the three pilots), classes and flags one byte per tile (flags 0 / 1), order one word per tile, info[0] = the number of flagged tiles,
+ * info[1..3] = the bits of the flagged tiles' constant sample (sky x exposure); without flags, flags and info read 0.  nFull == 0:
+ * RT_OK with *n_tiles = 0.  Refused: a null context or n_tiles, W or H of 0, source > 1, a bad row set (RT_ERR_INVALID_ARG); no scene
+ * (RT_ERR_NO_SCENE); cap_tiles below *n_tiles with any of the four arrays asked for (RT_ERR_INVALID_ARG, *n_tiles is written).  The
+ * context's stream has run dry when the call returns. */
+int rt_unit_tile_order(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32_t source, uint32_t cap_tiles, uint32_t* n_tiles, float* pilot_rays,
+                       uint8_t* classes, uint8_t* flags, uint32_t* order, uint32_t info[4]);
+/* The sort alone: the production rt_tile_order_kernel, launched as rt_render launches it (one workgroup of 1024 threads), over n_tiles
+ * stored classes given by the caller.  order_out: n_tiles + 64 words -- the order, then 64 guard words the entry set to 0xffffffff behind
+ * the kernel's destination and copied back with it (a test checks that they are intact).  Needs no scene; touches nothing the context
+ * keeps.  A null pointer, n_tiles == 0 or a class of 5 or more: RT_ERR_INVALID_ARG. */
+int rt_unit_tile_order_sort(rt_ctx* ctx, const uint8_t* classes, uint32_t n_tiles, uint32_t* order_out);
 /* ... the same lists evaluated on the host from the same source (both limits given).  entry_of_sphere (by original sphere index, may be
  * null): the scan entry of each sphere.  Needs no GPU. */
 int rt_unit_tile_spheres_host(const rt_sphere* spheres, uint32_t n, const rt_camera* camera, uint32_t W, uint32_t H, rt_rowset rs, uint32_t mask_limit,
