@@ -102,6 +102,7 @@ EXPORTS = [
     "rt_set_camera", "rt_get_camera",
     "rt_set_materials", "rt_set_lights", "rt_set_exposure", "rt_temporal_forget", "rt_unit_temporal_forget_host",
     "rt_unit_tile_order", "rt_unit_tile_order_sort",
+    "rt_turn_lights", "rt_get_lights",
 ]
 
 _lib = None
@@ -144,6 +145,9 @@ def load():
         L.rt_set_exposure.argtypes = [C.c_void_p, C.c_float]
         L.rt_temporal_forget.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.rt_unit_temporal_forget_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
+    if hasattr(L, "rt_turn_lights"):
+        L.rt_turn_lights.argtypes = [C.c_void_p, C.POINTER(RtLight), C.c_uint32]
+        L.rt_get_lights.argtypes = [C.c_void_p, C.POINTER(RtLight), C.c_uint32, C.POINTER(C.c_uint32)]
     L.rt_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, RtRowset, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                             C.POINTER(RtStats)]
     L.rt_clear.argtypes = [C.c_void_p]

@@ -1,4 +1,4 @@
-// rt_edit_launch.h -- what rt_capi.hip sees of the shading edits' translation unit (rt_edit.hip): two launchers over plain pointers,
+// rt_edit_launch.h -- what rt_capi.hip sees of the edits' translation unit (rt_edit.hip): three launchers over plain pointers,
 // and the host's way from a caller's list of ids to the set the forget kernel and its host twin test (../rt_forget.h).  The kernels
 // live in a unit of their own for the denoiser's reason: one more kernel in rt_capi.hip changes the register allocation of the trace
 // variants.
@@ -27,6 +27,11 @@ struct LightRadiance {
 // The floats travel by value, so nothing the caller may overwrite is read later, and launches queued before it on the stream still
 // read the old radiance.  n == 0: nothing is launched.  Returns the hipError_t of the launch as an int (0: launched).
 int LaunchLightRadiance(void* stream, rtd::LightRec* recs, uint32_t n, const LightRadiance& R);
+
+// Writes every field of recs[k] but cam_o from values[k] for k < n <= RT_MAX_LIGHTS on the stream (rt_turn_lights: direction, radiance,
+// the shadow index's constants and its three table pointers, of lights 1 .. and of the far-tier record behind them).  values is host
+// memory, read before the call returns: the records travel by value.  n == 0: nothing is launched.  Returns the hipError_t of the launch.
+int LaunchLightIndex(void* stream, rtd::LightRec* recs, uint32_t n, const rtd::LightRec* values);
 
 // Stores len[p] = 0 for every p < npix with forget_member(F, ids[p]) on the stream; every other word of len stays.  F.bits, where
 // not null, is device memory that holds forget_table_words(F.n_bits) words by the time the kernel runs.  npix == 0: nothing is

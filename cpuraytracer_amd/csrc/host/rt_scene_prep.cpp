@@ -597,7 +597,9 @@ void BuildShadowGrid(const rt_sphere* signedSp, const SceneLayout& L, const floa
 // |p| <= |c| + |r| up to the rounding of t d + o and of the root, for which one per cent is ample; nothing RELIES on that bound --
 // a point beyond P2 is answered by the any-hit over every entry (rt_kernels.h processHit), which is always right and merely slow.
 // Not enabled where P2 <= P0 (no sphere reaches beyond the first index) or where the first index's own reasons apply.
-void BuildShadowGridTier(const rt_sphere* signedSp, const SceneLayout& L, const float sunDir[3], uint32_t maxCells, uint32_t tier, ShadowGrid& G) {
+namespace {
+void BuildShadowGridAt(const rt_sphere* signedSp, const SceneLayout& L, const float sunDir[3], uint32_t maxCells, uint32_t tier, ShadowGrid& G,
+                       ShadowBuildCounts& n) {
     G = ShadowGrid{};
     uint32_t nSp = 0;
     for (uint32_t o : L.orig)
@@ -606,10 +608,16 @@ void BuildShadowGridTier(const rt_sphere* signedSp, const SceneLayout& L, const 
     const rt_sphere* sp = absSp.data();  // footprints and the reach are those of |r|
     const double Lx = sunDir[0], Ly = sunDir[1], Lz = sunDir[2];
     const double ln = std::sqrt(Lx * Lx + Ly * Ly + Lz * Lz);
-    if (!(ln > 0.5 && ln < 2.0)) return;  // not a direction: keep the scan
+    if (!(ln > 0.5 && ln < 2.0)) {  // not a direction: keep the scan
+        ++n.notADirection;
+        return;
+    }
     // orthonormal basis of the plane perpendicular to L
     double ax[3] = {1, 0, 0};
-    if (std::fabs(Lx) > std::fabs(Ly) && std::fabs(Lx) > std::fabs(Lz)) { ax[0] = 0; ax[1] = 1; }
+    if (std::fabs(Lx) > std::fabs(Ly) && std::fabs(Lx) > std::fabs(Lz)) {
+        ax[0] = 0; ax[1] = 1;
+        ++n.basisSwitch;
+    }
     double e1[3] = {Ly * ax[2] - Lz * ax[1], Lz * ax[0] - Lx * ax[2], Lx * ax[1] - Ly * ax[0]};
     const double n1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
     for (double& v : e1) v /= n1;
@@ -642,7 +650,10 @@ void BuildShadowGridTier(const rt_sphere* signedSp, const SceneLayout& L, const 
             far = std::max(far, std::sqrt((double)q.cx * q.cx + (double)q.cy * q.cy + (double)q.cz * q.cz) + q.r);
         }
         const double P2 = std::min(4.0 * P0, 1.01 * far + 1e-30);
-        if (!(P2 > P0)) return;
+        if (!(P2 > P0)) {
+            ++n.noTier2;
+            return;
+        }
         P0 = P2;  // from here on the construction is the first index's, for this radius
     }
     const double eps = 5.9604644775390625e-08;
@@ -670,6 +681,7 @@ void BuildShadowGridTier(const rt_sphere* signedSp, const SceneLayout& L, const 
         lo[0] = lo[1] = -1.0;
         hi[0] = hi[1] = 1.0;
         rhos.push_back(1.0);
+        ++n.onlyHuge;
     }
     std::nth_element(rhos.begin(), rhos.begin() + rhos.size() / 2, rhos.end());
     const double ext = std::max(hi[0] - lo[0], hi[1] - lo[1]);
@@ -698,6 +710,7 @@ void BuildShadowGridTier(const rt_sphere* signedSp, const SceneLayout& L, const 
         const size_t covered = outside ? 0 : (size_t)(x1 - x0 + 1) * (size_t)(y1 - y0 + 1);
         // a footprint reaching beyond the grid can shadow points outside it: it must be tested for every query
         if (spills || covered * 8 > ncell) {
+            ++(spills ? n.spilled : n.wide);
             G.global.push_back(f.entry);
             continue;
         }
@@ -706,11 +719,15 @@ void BuildShadowGridTier(const rt_sphere* signedSp, const SceneLayout& L, const 
     }
     size_t total = 0;
     for (const auto& c : cells) total += c.size();
-    if (total >= 65535 && maxCells > 64u) {  // too many entries for 16-bit cell starts: the coarser grid
-        BuildShadowGridTier(sp, L, sunDir, maxCells / 2u, tier, G);
+    if (total >= kShadowEntriesEnd && maxCells > 64u) {  // too many entries for 16-bit cell starts: the coarser grid
+        ++n.halved;
+        BuildShadowGridAt(sp, L, sunDir, maxCells / 2u, tier, G, n);
         return;
     }
-    if (total >= 65535 || G.global.size() > 64) return;  // pathological: keep the scan
+    if (total >= kShadowEntriesEnd || G.global.size() > kShadowGlobalMax) {  // pathological: keep the scan
+        ++n.gaveUp;
+        return;
+    }
     G.cellStart.resize(ncell + 1);
     G.entries.reserve(total);
     for (size_t c = 0; c < ncell; ++c) {
@@ -720,6 +737,16 @@ void BuildShadowGridTier(const rt_sphere* signedSp, const SceneLayout& L, const 
     G.cellStart[ncell] = (uint16_t)G.entries.size();
     G.p0sq = (float)(P0 * P0 * (1.0 - 1e-6));
     G.enabled = true;
+    ++n.enabled;
+}
+}  // namespace
+
+void BuildShadowGridTier(const rt_sphere* signedSp, const SceneLayout& L, const float sunDir[3], uint32_t maxCells, uint32_t tier, ShadowGrid& G,
+                         ShadowBuildCounts* counts) {
+    ShadowBuildCounts own;
+    ShadowBuildCounts& n = counts ? *counts : own;
+    ++n.built;
+    BuildShadowGridAt(signedSp, L, sunDir, maxCells, tier, G, n);
 }
 
 // The material table packed into 16 bytes per scan entry (rt_shade.h load_material16), or false when some material of the scene
@@ -764,6 +791,37 @@ PreparedMaterials PrepareMaterials(const rt_material* materials, uint32_t n, con
     return M;
 }
 
+PreparedShadows PrepareShadows(const rt_sphere* spheres, const SceneLayout& L, const rt_light* lights, uint32_t n_lights, const PrepOptions& opt,
+                               ShadowBuildCounts* counts) {
+    PreparedShadows S;
+    // the first light's index is staged into LDS where the scan's tables are; the others', one each, stay in global memory
+    if (opt.shadowGrid && n_lights != 0)
+        BuildShadowGridTier(spheres, L, lights[0].direction, L.InGlobalMemory() ? opt.shadowCellsGlobal : opt.shadowCellsLds, 1u, S.shadow, counts);
+    S.extraShadow.resize(n_lights > 1 ? n_lights - 1 : 0);
+    for (uint32_t k = 1; k < n_lights && opt.shadowGrid; ++k) 
+        BuildShadowGridTier(spheres, L, lights[k].direction, opt.shadowCellsGlobal, 1u, S.extraShadow[k - 1], counts);
+    // light 0's second index, for the hit points beyond the first one's radius: in global memory, like the extra lights'
+    if (S.shadow.enabled) BuildShadowGridTier(spheres, L, lights[0].direction, opt.shadowCellsGlobal, 2u, S.shadowFar, counts);
+    // RT_SG_SPH=1 (experiments): the index stays in global memory -- the sphere record of every entry side by side with the ids, so
+    // that a walk round is one round trip instead of two.  Measured on grid10k: 7.79 -> 7.66 Gsamples/s (700 KB of duplicated
+    // spheres hit the L1 less often than the 160 KB table they are shared from).  Default off.
+    if (S.shadow.enabled && L.InGlobalMemory() && opt.sgSph) {
+        S.sgSph.assign(S.shadow.entries.size() + 1, MakeF4(0.f, 0.f, 0.f, -1e30f));
+        for (size_t k = 0; k < S.shadow.entries.size(); ++k) S.sgSph[k] = L.scan[S.shadow.entries[k]];
+    }
+    return S;
+}
+
+SceneLayout ShadowLayoutOf(const SceneLayout& L, const PrepOptions& opt) {
+    SceneLayout K;
+    K.orig = L.orig;
+    K.nGroups = L.nGroups;
+    K.nLevels = L.nLevels;
+    K.gridOn = L.gridOn;
+    if (opt.sgSph && L.InGlobalMemory()) K.scan = L.scan;
+    return K;
+}
+
 PreparedScene PrepareScene(const rt_sphere* spheres, const rt_material* materials, uint32_t n, const rt_light* lights, uint32_t n_lights,
                            const PrepOptions& opt) {
     PreparedScene P;
@@ -779,20 +837,11 @@ PreparedScene PrepareScene(const rt_sphere* spheres, const rt_material* material
     P.mats16 = std::move(M.mats16);
     P.mats16Ok = M.mats16Ok;
     P.matType = std::move(M.matType);
-    // the first light's index is staged into LDS where the scan's tables are; the others', one each, stay in global memory
-    if (opt.shadowGrid && n_lights != 0)
-        BuildShadowGrid(spheres, L, lights[0].direction, L.InGlobalMemory() ? opt.shadowCellsGlobal : opt.shadowCellsLds, P.shadow);
-    P.extraShadow.resize(n_lights > 1 ? n_lights - 1 : 0);
-    for (uint32_t k = 1; k < n_lights && opt.shadowGrid; ++k) BuildShadowGrid(spheres, L, lights[k].direction, opt.shadowCellsGlobal, P.extraShadow[k - 1]);
-    // light 0's second index, for the hit points beyond the first one's radius: in global memory, like the extra lights'
-    if (P.shadow.enabled) BuildShadowGridTier(spheres, L, lights[0].direction, opt.shadowCellsGlobal, 2u, P.shadowFar);
-    // RT_SG_SPH=1 (experiments): the index stays in global memory -- the sphere record of every entry side by side with the ids, so
-    // that a walk round is one round trip instead of two.  Measured on grid10k: 7.79 -> 7.66 Gsamples/s (700 KB of duplicated
-    // spheres hit the L1 less often than the 160 KB table they are shared from).  Default off.
-    if (P.shadow.enabled && L.InGlobalMemory() && opt.sgSph) {
-        P.sgSph.assign(P.shadow.entries.size() + 1, MakeF4(0.f, 0.f, 0.f, -1e30f));
-        for (size_t k = 0; k < P.shadow.entries.size(); ++k) P.sgSph[k] = L.scan[P.shadow.entries[k]];
-    }
+    PreparedShadows S = PrepareShadows(spheres, L, lights, n_lights, opt);
+    P.shadow = std::move(S.shadow);
+    P.extraShadow = std::move(S.extraShadow);
+    P.shadowFar = std::move(S.shadowFar);
+    P.sgSph = std::move(S.sgSph);
     for (int h = 0; h < 2; ++h) P.singleMask[h] = opt.singleDirect ? L.singleMask[h] : 0ull;
     return P;
 }

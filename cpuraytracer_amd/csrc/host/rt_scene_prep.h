@@ -74,6 +74,13 @@ struct ShadowGrid {
     bool enabled = false;
 };
 
+// The bounds of an index's tables whatever the light's direction (BuildShadowGridTier gives up, or halves maxCells, beyond them).  One
+// place for the builder's tests and for whoever reserves room for an index whose direction is not yet known (rt_turn_lights).
+constexpr size_t kShadowEntriesEnd = 65535;  // cell starts are 16-bit: an index has fewer entries than this
+constexpr size_t kShadowGlobalMax = 64;      // ... and at most this many in its global list
+constexpr size_t ShadowCellWordsMax(uint32_t maxCells) { return (size_t)maxCells * maxCells + 1; }  // cellStart: nx * ny + 1, nx, ny <= maxCells
+constexpr size_t kShadowSphRecordsMax = kShadowEntriesEnd;  // sgSph: entries + 1
+
 // Everything rt_scene_upload copies to the device.
 struct PreparedScene {
     SceneLayout layout;
@@ -108,7 +115,21 @@ std::string MaterialFaultMessage(const char* who, const std::string& what, const
 void BuildLayout(const rt_sphere* spheres, uint32_t n, const PrepOptions& opt, SceneLayout& L);
 void BuildShadowGrid(const rt_sphere* spheres, const SceneLayout& L, const float lightDir[3], uint32_t maxCells, ShadowGrid& G);
 // tier 1: the same; tier 2: the index for the hit points beyond tier 1's radius (rt_scene_prep.cpp states its radius and why)
-void BuildShadowGridTier(const rt_sphere* spheres, const SceneLayout& L, const float lightDir[3], uint32_t maxCells, uint32_t tier, ShadowGrid& G);
+// counts (optional): which of the builder's branches the call took, added to what is there (host/light_turn_selftest.cpp)
+struct ShadowBuildCounts {
+    uint64_t built = 0;          // calls from outside (the halving rule's own calls are not counted again)
+    uint64_t notADirection = 0;  // |L| outside (0.5, 2): no index
+    uint64_t basisSwitch = 0;    // |Lx| dominates: the basis starts from the y axis
+    uint64_t noTier2 = 0;        // tier 2 asked for and P2 <= P0
+    uint64_t onlyHuge = 0;       // no ordinary sphere: the 1 x 1 grid, everything in the global list
+    uint64_t spilled = 0;        // footprints beyond the grid's extent -> global list
+    uint64_t wide = 0;           // footprints over more than an eighth of the cells -> global list
+    uint64_t halved = 0;         // too many entries and maxCells > 64: built again at maxCells / 2
+    uint64_t gaveUp = 0;         // too many entries at 64 cells, or a global list beyond kShadowGlobalMax: no index
+    uint64_t enabled = 0;
+};
+void BuildShadowGridTier(const rt_sphere* spheres, const SceneLayout& L, const float lightDir[3], uint32_t maxCells, uint32_t tier, ShadowGrid& G,
+                         ShadowBuildCounts* counts = nullptr);
 
 // The three tables that hold the materials, and nothing else of a scene: the 48-byte records in scan-entry order (padding entries
 // zero), the same packed into 16 bytes where every record fits, and the type by ORIGINAL sphere index.  orig: the layout's table of
@@ -121,6 +142,22 @@ struct PreparedMaterials {
     std::vector<uint32_t> matType;
 };
 PreparedMaterials PrepareMaterials(const rt_material* materials, uint32_t n, const uint32_t* orig, size_t nEntries);
+
+// Everything of a scene that a light's direction reaches: light 0's index, one index per further light, light 0's tier-2 index and the
+// optional sgSph table (PreparedScene's members of the same names).  The one writer of these tables: PrepareScene calls it with its own
+// layout, rt_turn_lights with the part of the layout kept from the upload (ShadowLayoutOf), so a turn's tables are an upload's by
+// construction.  Reads of `opt`: shadowGrid, the two cell limits, sgSph.  lights may be null where n_lights == 0.
+struct PreparedShadows {
+    ShadowGrid shadow;
+    std::vector<ShadowGrid> extraShadow;
+    ShadowGrid shadowFar;
+    std::vector<F4> sgSph;
+};
+PreparedShadows PrepareShadows(const rt_sphere* spheres, const SceneLayout& layout, const rt_light* lights, uint32_t n_lights, const PrepOptions& opt,
+                               ShadowBuildCounts* counts = nullptr);
+// What PrepareShadows reads of a layout, and nothing else of it: orig, nGroups, what InGlobalMemory() tests, and the scan records
+// where opt.sgSph asks for them.
+SceneLayout ShadowLayoutOf(const SceneLayout& layout, const PrepOptions& opt);
 
 // spheres: n > 0, all finite (AllFinite).  A layout of 65,536 scan entries or more cannot be indexed by the 16-bit ids of the
 // tables behind it: then only `layout` is filled, and the caller refuses the scene.

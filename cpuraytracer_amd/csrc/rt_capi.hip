@@ -104,7 +104,16 @@ struct DevBuf {
 };
 static_assert(!std::is_copy_constructible<DevBuf<float>>::value, "a DevBuf is the one owner of its memory");
 
-// A shadow index's three tables (the id lists with one spare element, so that an empty list still has an address).
+// Room for the three tables of an index of ANY direction: the builder's own bounds (host/rt_scene_prep.h), so that rt_turn_lights
+// never allocates under running kernels -- and an index that is disabled now has its buffers all the same, a turn can enable it.
+int ReserveShadowGrid(uint32_t maxCells, DevBuf<uint16_t>& cells, DevBuf<uint16_t>& entries, DevBuf<uint16_t>& global) {
+    int rc;
+    if ((rc = cells.Reserve(rtprep::ShadowCellWordsMax(maxCells))) != RT_OK) return rc;
+    if ((rc = entries.Reserve(rtprep::kShadowEntriesEnd)) != RT_OK) return rc;  // fewer entries than this, and the spare element
+    return global.Reserve(rtprep::kShadowGlobalMax + 1);
+}
+// A shadow index's three tables (the id lists with one spare element, so that an empty list still has an address): the actual bytes,
+// into buffers that ReserveShadowGrid has sized.
 int UploadShadowGrid(const rtprep::ShadowGrid& G, DevBuf<uint16_t>& cells, DevBuf<uint16_t>& entries, DevBuf<uint16_t>& global) {
     int rc;
     if ((rc = cells.Upload(G.cellStart)) != RT_OK) return rc;
@@ -155,11 +164,15 @@ struct rt_ctx {
     rt_camera camera{};       // the record of the last upload or rt_set_camera (rt_get_camera; the same-record test)
 
     // shading edits (rt_set_materials, rt_set_lights, rt_set_exposure): the records of the last upload or edit, for the
-    // same-record test, and the layout's orig table, over which an edit rebuilds the three material tables (rtprep::PrepareMaterials)
+    // same-record test (the layout's orig table, over which an edit rebuilds the three material tables, is shadowLayout.orig below)
     std::vector<rt_material> materials;  // by ORIGINAL sphere index (the sky's record is `sky` below)
-    std::vector<uint32_t> origHost;      // rtprep::SceneLayout::orig of the upload
     rt_light lights[RT_MAX_LIGHTS] = {};
     uint32_t nLights = 0;                // as the caller counted them (0: light 0's slots hold the dark light)
+    // rt_turn_lights: what rtprep::PrepareShadows reads -- the spheres, the part of the upload's layout that the
+    // index builder looks at (rtprep::ShadowLayoutOf), and the upload's preparation options (the environment is not read again)
+    std::vector<rt_sphere> spheres;
+    rtprep::SceneLayout shadowLayout;
+    rtprep::PrepOptions prepOpt;
     // Pinned staging for the copies an edit or rt_temporal_forget orders on the stream: two slots used in turn, each with an event
     // recorded behind its copies.  A slot is written again only once that event has completed -- the one host wait an edit may take,
     // and it takes it only when two newer edits are still queued.  Sized at the upload (never under running kernels).
@@ -313,11 +326,13 @@ static void SetQueue(rtd::TraceParams& tp, const rtplan::QueueCut& q) {
 
 // ---- how the host's records become launch parameters, each written down once.  P is rtd::TraceParams (light 0, the unit kernels) or
 // rtd::LightRec (lights 1 ..): the member names are equal (rt_params.h).
-// A shadow index's constants; a disabled index leaves them zero.  Where its three tables lie differs by caller and stays there.
+// A shadow index's constants; a disabled index sets them zero, whatever the builder left in it and whatever p held (rt_turn_lights
+// switches indices off and on in place).  Where its three tables lie differs by caller and stays there.
 template <typename P>
-static void SetShadowGrid(P& p, const rtprep::ShadowGrid& G) {
+static void SetShadowGrid(P& p, const rtprep::ShadowGrid& built) {
+    const rtprep::ShadowGrid none;
+    const rtprep::ShadowGrid& G = built.enabled ? built : none;
     p.sg_enabled = G.enabled ? 1u : 0u;
-    if (!G.enabled) return;
     for (int c = 0; c < 3; ++c) {
         p.sg_e1[c] = G.e1[c];
         p.sg_e2[c] = G.e2[c];
@@ -331,6 +346,45 @@ static void SetLight(P& p, const rt_light& light) {
         p.sun_dir[c] = light.direction[c];
         p.sun_rad[c] = light.luminance * light.color[c];  // m_luminance * m_color, light.cpp:27
     }
+}
+// ---- what the lights and their shadow indices become, written once for rt_scene_upload and rt_turn_lights.  The indices' tables lie
+// in buffers the upload reserved at the builder's bounds (ReserveShadowGrid), so their addresses are known before anything is copied.
+// The records behind base.extra_lights: lights 1 .. with their index each, then the far-tier record -- an empty light that carries
+// light 0's second index -- while that index exists.
+template <typename Prepared>  // rtprep::PreparedScene (the upload) or rtprep::PreparedShadows (a turn): the members have the same names
+static std::vector<rtd::LightRec> LightRecords(const rt_ctx* ctx, const Prepared& S, const rt_light* lights, uint32_t n_lights,
+                                               const float camO[3]) {
+    auto indexed = [](const rtprep::ShadowGrid& G, const rt_ctx::ExtraLight& X) {
+        rtd::LightRec R{};
+        SetShadowGrid(R, G);
+        if (G.enabled) R.cell_start = X.cells.ptr, R.entries = X.entries.ptr, R.global = X.global.ptr;
+        return R;
+    };
+    std::vector<rtd::LightRec> recs;
+    for (uint32_t k = 1; k < n_lights; ++k) {
+        rtd::LightRec R = indexed(S.extraShadow[k - 1], ctx->extraIdx[k]);
+        SetLight(R, lights[k]);
+        for (int c = 0; c < 3; ++c) R.cam_o[c] = camO[c];
+        recs.push_back(R);
+    }
+    if (S.shadowFar.enabled) recs.push_back(indexed(S.shadowFar, ctx->farIdx));  // (enabled only with light 0's first index: n_lights >= 1)
+    return recs;
+}
+// Light 0 and everything the by-value launch parameters say of the lights: the launch plan reads the index's sizes from here and picks
+// the variant and the LDS image.  nRecs: LightRecords' count.
+template <typename Prepared>
+static void SetSunAndIndices(rt_ctx* ctx, const Prepared& S, const rt_light& sun, size_t nRecs) {
+    rtd::TraceParams& b = ctx->base;
+    const rtprep::ShadowGrid& SG = S.shadow;
+    SetLight(b, sun);
+    SetShadowGrid(b, SG);
+    b.extra_lights = nRecs ? ctx->lightRecs.ptr : nullptr;
+    b.far_index = S.shadowFar.enabled ? 1u : 0u;
+    b.sg_cell_start = SG.enabled ? ctx->sgCells.ptr : nullptr;
+    b.sg_entries = SG.enabled ? ctx->sgEntries.ptr : nullptr;
+    b.sg_global = SG.enabled ? ctx->sgGlobal.ptr : nullptr;
+    b.sg_sph = SG.enabled && !S.sgSph.empty() ? ctx->sgSph.ptr : nullptr;
+    b.sg_nentries = SG.enabled ? (uint32_t)SG.entries.size() : 0u;  // (for the list's copy into LDS; a LightRec's index stays in global memory)
 }
 static void SetCamera(rtd::TraceParams& tp, const rt_camera& camera) {
     for (int c = 0; c < 3; ++c) {
@@ -794,6 +848,17 @@ int rt_api_version(void) { return RT_API_VERSION; }
 constexpr uint32_t kForgetMaxIds = 65536;
 constexpr uint32_t kForgetTableWords = kForgetMaxIds / 32u;
 static size_t MaterialStageBytes(size_t nPad, size_t n) { return nPad * (sizeof(rt_material) + sizeof(uint4)) + n * sizeof(uint32_t); }
+// ... and the tables rt_turn_lights copies: nIdx first-tier indices and light 0's far tier at the builder's bounds, each table on a
+// 16-byte boundary, and the sgSph records where the option is on.
+static uint32_t Light0CellsMax(bool inGlobalMemory, const rtprep::PrepOptions& opt) { return inGlobalMemory ? opt.shadowCellsGlobal : opt.shadowCellsLds; }
+static size_t StageAlign(size_t bytes) { return (bytes + 15u) & ~(size_t)15u; }
+static size_t ShadowStageBytesMax(uint32_t nIdx, bool inGlobalMemory, const rtprep::PrepOptions& opt) {
+    if (nIdx == 0u) return 0;
+    const size_t lists = StageAlign(rtprep::kShadowEntriesEnd * sizeof(uint16_t)) + StageAlign((rtprep::kShadowGlobalMax + 1) * sizeof(uint16_t));
+    const size_t one = StageAlign(rtprep::ShadowCellWordsMax(opt.shadowCellsGlobal) * sizeof(uint16_t)) + lists;
+    const size_t first = StageAlign(rtprep::ShadowCellWordsMax(Light0CellsMax(inGlobalMemory, opt)) * sizeof(uint16_t)) + lists;
+    return first + (size_t)nIdx * one + (opt.sgSph && inGlobalMemory ? StageAlign(rtprep::kShadowSphRecordsMax * sizeof(float4)) : 0);
+}
 // Both slots hold at least `bytes`.  Called where the stream has run dry or nothing was ever queued (rt_create, rt_scene_upload
 // behind its hipStreamSynchronize): a slot that grows is not being read.
 static int StageReserve(rt_ctx* ctx, size_t bytes) {
@@ -994,34 +1059,33 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     ctx->mats16Ok = P.mats16Ok;
     // (the packed table has its full size whether or not this scene packs: a later rt_set_materials that flips mats16Ok only copies)
     if ((rc = P.mats16Ok ? ctx->mats16.Upload(P.mats16) : ctx->mats16.Reserve(P.mats16.size())) != RT_OK) return rc;
-    if ((rc = StageReserve(ctx, MaterialStageBytes(nPad, n))) != RT_OK) return rc;
     if ((rc = ctx->matType.Upload(P.matType)) != RT_OK) return rc;
     rttile::SceneReplaced(ctx->tiles);  // (their inputs are overwritten: nothing of the tiles' tables is valid)
     (void)rtseq::TileTablesDropped(ctx->seq);
-    // lights 1 .. : one index each, in global memory (256 x 256 cells at most), and their records
-    std::vector<rtd::LightRec> recs;
+    // The shadow indices -- light 0's (staged into LDS by the flat scan's kernels, else read in global memory), one per further light
+    // and light 0's far tier, both in global memory (256 x 256 cells at most) -- each in buffers sized for an index of any direction,
+    // the disabled ones included: rt_turn_lights only copies.  So the records know their tables' addresses before the copies.
+    const uint32_t nIdx = opt.shadowGrid ? n_lights : 0u;  // lights that may have an index (RT_SHADOW_GRID=0: none, after any turn)
+    if (nIdx != 0u) {
+        if ((rc = ReserveShadowGrid(Light0CellsMax(L.InGlobalMemory(), opt), ctx->sgCells, ctx->sgEntries, ctx->sgGlobal)) != RT_OK) return rc;
+        if ((rc = ReserveShadowGrid(opt.shadowCellsGlobal, ctx->farIdx.cells, ctx->farIdx.entries, ctx->farIdx.global)) != RT_OK) return rc;
+        if (opt.sgSph && L.InGlobalMemory() && (rc = ctx->sgSph.Reserve(rtprep::kShadowSphRecordsMax)) != RT_OK) return rc;
+    }
+    for (uint32_t k = 1; k < nIdx; ++k)
+        if ((rc = ReserveShadowGrid(opt.shadowCellsGlobal, ctx->extraIdx[k].cells, ctx->extraIdx[k].entries, ctx->extraIdx[k].global)) != RT_OK) return rc;
+    // (both staging slots: the larger of what rt_set_materials and what rt_turn_lights copy)
+    if ((rc = StageReserve(ctx, std::max(MaterialStageBytes(nPad, n), ShadowStageBytesMax(nIdx, L.InGlobalMemory(), opt)))) != RT_OK) return rc;
+    std::vector<rtd::LightRec> recs = LightRecords(ctx, P, lights, n_lights, camera->origin);
+    const size_t nRecs = recs.size();
+    // (n_lights records lie there from now on, the far tier's slot empty while that index is off: a turn that switches it on writes
+    // every field of it but cam_o, which nothing reads of that record and which is zero from here)
+    recs.resize(std::max<size_t>(nRecs, n_lights), rtd::LightRec{});
+    if (!recs.empty() && (rc = ctx->lightRecs.Upload(recs)) != RT_OK) return rc;
     for (uint32_t k = 1; k < n_lights; ++k) {
         const rtprep::ShadowGrid& G2 = P.extraShadow[k - 1];
-        rt_ctx::ExtraLight& X = ctx->extraIdx[k];
-        rtd::LightRec R{};
-        SetLight(R, lights[k]);
-        for (int c = 0; c < 3; ++c) R.cam_o[c] = camera->origin[c];
-        SetShadowGrid(R, G2);
-        if (G2.enabled) {
-            if ((rc = UploadShadowGrid(G2, X.cells, X.entries, X.global)) != RT_OK) return rc;
-            R.cell_start = X.cells.ptr; R.entries = X.entries.ptr; R.global = X.global.ptr;
-        }
-        recs.push_back(R);
+        if (G2.enabled && (rc = UploadShadowGrid(G2, ctx->extraIdx[k].cells, ctx->extraIdx[k].entries, ctx->extraIdx[k].global)) != RT_OK) return rc;
     }
-    const rtprep::ShadowGrid& FG = P.shadowFar;  // (enabled only with light 0's first index, so n_lights >= 1: record n_lights - 1)
-    if (FG.enabled) {
-        rtd::LightRec R{};
-        SetShadowGrid(R, FG);
-        if ((rc = UploadShadowGrid(FG, ctx->farIdx.cells, ctx->farIdx.entries, ctx->farIdx.global)) != RT_OK) return rc;
-        R.cell_start = ctx->farIdx.cells.ptr; R.entries = ctx->farIdx.entries.ptr; R.global = ctx->farIdx.global.ptr;
-        recs.push_back(R);
-    }
-    if (!recs.empty() && (rc = ctx->lightRecs.Upload(recs)) != RT_OK) return rc;
+    if (P.shadowFar.enabled && (rc = UploadShadowGrid(P.shadowFar, ctx->farIdx.cells, ctx->farIdx.entries, ctx->farIdx.global)) != RT_OK) return rc;
     if (SG.enabled && (rc = UploadShadowGrid(SG, ctx->sgCells, ctx->sgEntries, ctx->sgGlobal)) != RT_OK) return rc;
     if (!P.sgSph.empty() && (rc = ctx->sgSph.Upload(P.sgSph)) != RT_OK) return rc;
     if (L.gridOn) {
@@ -1047,16 +1111,7 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
         for (int c = 0; c < 8; ++c) b.grid_q[c] = L.gridQc[c];
     }
     b.n_lights = n_lights;
-    b.extra_lights = recs.empty() ? nullptr : ctx->lightRecs.ptr;
-    SetShadowGrid(b, SG);
-    b.far_index = FG.enabled ? 1u : 0u;
-    if (SG.enabled) {
-        b.sg_cell_start = ctx->sgCells.ptr;
-        b.sg_entries = ctx->sgEntries.ptr;
-        b.sg_global = ctx->sgGlobal.ptr;
-        b.sg_sph = P.sgSph.empty() ? nullptr : ctx->sgSph.ptr;
-        b.sg_nentries = (uint32_t)SG.entries.size();  // (for the list's copy into LDS; a LightRec's index stays in global memory)
-    }
+    SetSunAndIndices(ctx, P, *sun, nRecs);
     b.scan = ctx->scan.ptr;
     b.orig = ctx->orig.ptr;
     b.leaf = ctx->leaf.ptr;
@@ -1079,14 +1134,15 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     b.n = n;
     b.n_padded = nPad;
     SetCamera(b, *camera);
-    SetLight(b, *sun);
     for (int k = 0; k < 3; ++k) b.sky_emit[k] = sky->luminance * sky->rgb0[k];  // Emissive::Emit, material.cpp:172-175
     b.exposure = exposure_scale;
     ctx->n = n;
     ctx->sky = *sky;
     ctx->camera = *camera;
     ctx->materials.assign(materials, materials + n);
-    ctx->origHost = L.orig;
+    ctx->spheres.assign(spheres, spheres + n);
+    ctx->shadowLayout = rtprep::ShadowLayoutOf(L, opt);
+    ctx->prepOpt = opt;
     ctx->nLights = n_lights;
     for (uint32_t k = 0; k < n_lights; ++k) ctx->lights[k] = lights[k];
     DropVoided(ctx, rtseq::SceneReplaced(ctx->seq));
@@ -1177,8 +1233,8 @@ int rt_set_materials(rt_ctx* ctx, const rt_material* materials, uint32_t n, cons
     if (!sameTable) {
         // The three tables, by their one writer over the upload's layout, through pinned staging and copies ordered on the stream behind
         // every launch of the old materials.  No allocation: each buffer has had its full size since the upload.
-        const size_t nPad = ctx->origHost.size();
-        const rtprep::PreparedMaterials M = rtprep::PrepareMaterials(materials, n, ctx->origHost.data(), nPad);
+        const size_t nPad = ctx->shadowLayout.orig.size();
+        const rtprep::PreparedMaterials M = rtprep::PrepareMaterials(materials, n, ctx->shadowLayout.orig.data(), nPad);
         rt_ctx::Stage* st = nullptr;
         if ((rc = StageAcquire(ctx, MaterialStageBytes(nPad, n), &st)) != RT_OK) return rc;
         char* h = static_cast<char*>(st->host);
@@ -1231,6 +1287,86 @@ int rt_set_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights) {
     SetLight(ctx->base, lights[0]);
     for (uint32_t k = 0; k < n_lights; ++k) ctx->lights[k] = lights[k];
     PictureInputChanged(ctx);
+    return RT_OK;
+}
+
+// ---- turning the lights without an upload (rt_api.h): direction, colour and luminance of every light as one event.
+// Of everything a scene becomes, a direction reaches the shadow indices alone: they are rebuilt on the host by their one writer over
+// what the upload kept, copied on the stream from pinned staging into buffers reserved at the builder's bounds, and the records of
+// lights 1 .. and of the far tier are rewritten on the stream by value.  No layout is built, nothing allocated, no wait but the staging's.
+int rt_turn_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights) {
+    if (!ctx || (!lights && n_lights != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_turn_lights: null argument");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_turn_lights: no scene uploaded");
+    if (n_lights != ctx->nLights)
+        return Fail(RT_ERR_INVALID_ARG, "rt_turn_lights: " + std::to_string(n_lights) + " lights for a scene uploaded with " + std::to_string(ctx->nLights));
+    bool same = true;
+    for (uint32_t k = 0; k < n_lights; ++k) {
+        const rt_light& l = lights[k];
+        if (!std::isfinite(l.direction[0]) || !std::isfinite(l.direction[1]) || !std::isfinite(l.direction[2]))
+            return Fail(RT_ERR_INVALID_ARG, "rt_turn_lights: light " + std::to_string(k) + " has a direction that is not finite");
+        if (!std::isfinite(l.luminance) || !std::isfinite(l.color[0]) || !std::isfinite(l.color[1]) || !std::isfinite(l.color[2]))
+            return Fail(RT_ERR_INVALID_ARG, "rt_turn_lights: light " + std::to_string(k) + " has a colour or a luminance that is not finite");
+        same = same && std::memcmp(l.direction, ctx->lights[k].direction, sizeof l.direction) == 0 &&
+               std::memcmp(l.color, ctx->lights[k].color, sizeof l.color) == 0 && std::memcmp(&l.luminance, &ctx->lights[k].luminance, sizeof(float)) == 0;
+    }
+    if (same) return RT_OK;  // (n_lights == 0 included)
+    RT_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old lights
+    const rtprep::PreparedShadows S = rtprep::PrepareShadows(ctx->spheres.data(), ctx->shadowLayout, lights, n_lights, ctx->prepOpt);
+    // The tables of every enabled index: through one staging slot, each on a 16-byte boundary, by copies ordered on the stream behind
+    // every launch of the old directions.  Only the actual bytes; the room is the upload's reservation.
+    struct Table {
+        const void* src;
+        void* dst;
+        size_t bytes, room;  // room: what the upload reserved at dst
+    };
+    std::vector<Table> tables;
+    const bool recsRoomShort = ctx->lightRecs.count < n_lights;
+    auto index = [&tables](const rtprep::ShadowGrid& G, DevBuf<uint16_t>& cells, DevBuf<uint16_t>& entries, DevBuf<uint16_t>& global) {
+        if (!G.enabled) return;
+        tables.push_back({G.cellStart.data(), cells.ptr, G.cellStart.size() * sizeof(uint16_t), cells.count * sizeof(uint16_t)});
+        tables.push_back({G.entries.data(), entries.ptr, G.entries.size() * sizeof(uint16_t), entries.count * sizeof(uint16_t)});
+        tables.push_back({G.global.data(), global.ptr, G.global.size() * sizeof(uint16_t), global.count * sizeof(uint16_t)});
+    };
+    index(S.shadow, ctx->sgCells, ctx->sgEntries, ctx->sgGlobal);
+    for (uint32_t k = 1; k < n_lights; ++k) index(S.extraShadow[k - 1], ctx->extraIdx[k].cells, ctx->extraIdx[k].entries, ctx->extraIdx[k].global);
+    index(S.shadowFar, ctx->farIdx.cells, ctx->farIdx.entries, ctx->farIdx.global);
+    if (!S.sgSph.empty()) tables.push_back({S.sgSph.data(), ctx->sgSph.ptr, S.sgSph.size() * sizeof(float4), ctx->sgSph.count * sizeof(float4)});
+    size_t total = 0;
+    if (recsRoomShort) return Fail(RT_ERR_HIP, "rt_turn_lights: the light records are fewer than the lights (no upload reserved them)");
+    for (const Table& t : tables) {
+        if (t.bytes > t.room) return Fail(RT_ERR_HIP, "rt_turn_lights: a table is larger than the room the upload reserved for it");
+        total += StageAlign(t.bytes);
+    }
+    if (total != 0) {
+        rt_ctx::Stage* st = nullptr;
+        if ((rc = StageAcquire(ctx, total, &st)) != RT_OK) return rc;
+        char* h = static_cast<char*>(st->host);
+        for (const Table& t : tables) {
+            if (t.bytes == 0) continue;
+            std::memcpy(h, t.src, t.bytes);
+            RT_HIP(hipMemcpyAsync(t.dst, h, t.bytes, hipMemcpyHostToDevice, ctx->stream));
+            h += StageAlign(t.bytes);
+        }
+        if ((rc = StageQueued(ctx, st)) != RT_OK) return rc;
+    }
+    // The records in device memory, behind the copies and behind every launch that reads the old ones: by value, cam_o left alone.
+    const std::vector<rtd::LightRec> recs = LightRecords(ctx, S, lights, n_lights, ctx->camera.origin);
+    RT_HIP((hipError_t)rtedit::LaunchLightIndex(ctx->stream, ctx->lightRecs.ptr, (uint32_t)recs.size(), recs.data()));
+    SetSunAndIndices(ctx, S, lights[0], recs.size());  // light 0, the index's sizes for the launch plan, far_index, extra_lights
+    for (uint32_t k = 0; k < n_lights; ++k) ctx->lights[k] = lights[k];
+    PictureInputChanged(ctx);
+    return RT_OK;
+}
+
+int rt_get_lights(rt_ctx* ctx, rt_light* out, uint32_t capacity, uint32_t* n_lights) {
+    if (!ctx || !n_lights || (!out && capacity != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_get_lights: null argument");
+    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_get_lights: no scene uploaded");
+    *n_lights = ctx->nLights;
+    if (capacity == 0) return RT_OK;  // the count alone
+    if (capacity < ctx->nLights) return Fail(RT_ERR_INVALID_ARG, "rt_get_lights: capacity too small for " + std::to_string(ctx->nLights) + " lights");
+    for (uint32_t k = 0; k < ctx->nLights; ++k) out[k] = ctx->lights[k];
     return RT_OK;
 }
 

@@ -178,13 +178,40 @@ class HipRenderer:
 
     def set_lights(self, lights):
         """rt_set_lights: new colours and luminances for the uploaded lights (a list of rt_light records, as many as uploaded, each
-        with the uploaded direction bit for bit: a direction change needs an upload()).  Equivalence, voids and keeps as
-        set_materials(); never waits."""
+        with the current direction bit for bit -- the uploaded one, or the one turn_lights() set last; a direction change goes through
+        turn_lights()).  Equivalence, voids and keeps as set_materials(); never waits."""
         ls = list(lights)
         arr = (_capi.RtLight * max(1, len(ls)))()
         for k, l in enumerate(ls):
             arr[k] = _capi.RtLight.from_buffer_copy(bytes(l))
         check(self._L.rt_set_lights(self._h, arr, len(ls)))
+
+    def turn_lights(self, lights, forget=True):
+        """rt_turn_lights: whole new records -- direction, colour and luminance -- for the uploaded lights (a list of rt_light records,
+        as many as uploaded; scenes.turn_light(...) turns one) without an upload: the shadow indices are rebuilt on the host over the
+        layout kept from the upload and copied on the stream; no layout is built, nothing allocated, no host wait of its own.
+        Everything computed afterwards equals, bit for bit, what an upload() of the same scene with these lights computes; voids
+        and keeps what set_camera() does.  The same records again change nothing.
+        forget=True: the temporal history's validation never looks at colour, and after a turn every shadow in it is stale, so
+        temporal_reset() is called when a direction changed.  forget=False is the bare C call.  Returns whether a direction changed."""
+        ls = list(lights)
+        arr = (_capi.RtLight * max(1, len(ls)))()
+        for k, l in enumerate(ls):
+            arr[k] = _capi.RtLight.from_buffer_copy(bytes(l))
+        old = self.get_lights() if forget else []
+        check(self._L.rt_turn_lights(self._h, arr, len(ls)))
+        turned = any(bytes(a)[:12] != bytes(b)[:12] for a, b in zip(arr, old))  # (direction: the record's first three floats)
+        if turned:
+            self.temporal_reset()
+        return turned
+
+    def get_lights(self):
+        """rt_get_lights: the RtLight records the context renders with now (the last upload(), set_lights() or turn_lights())."""
+        n = C.c_uint32(0)
+        check(self._L.rt_get_lights(self._h, None, 0, C.byref(n)))
+        arr = (_capi.RtLight * max(1, n.value))()
+        check(self._L.rt_get_lights(self._h, arr, n.value, C.byref(n)))
+        return [_capi.RtLight.from_buffer_copy(bytes(arr[k])) for k in range(n.value)]
 
     def set_exposure(self, exposure_scale):
         """rt_set_exposure: a new exposure for the uploaded scene.  Equivalence, voids and keeps as set_materials(); never waits."""

@@ -54,6 +54,25 @@ def build_scene(name="cover", seed=1, width=1200, height=800, vfov=-1.0, apertur
     return Scene(sph[:n.value].copy(), mat[:n.value].copy(), cam, sun, sky, exp.value, name, seed)
 
 
+def turn_light(light, degrees, axis=(0.0, 1.0, 0.0)):
+    """The light record with its direction turned by `degrees` about `axis` (any non-zero vector; right-handed, Rodrigues' formula);
+    colour and luminance stay.  A pure function of the record: evaluated in binary64 and rounded once to binary32, so the
+    direction keeps its length up to that rounding.  Returns a new RtLight (HipRenderer.turn_lights takes a list of them)."""
+    a = float(degrees) * (math.pi / 180.0)
+    c, s = math.cos(a), math.sin(a)
+    k = np.asarray(axis, dtype=np.float64)
+    norm = float(np.sqrt(np.dot(k, k)))
+    if not (norm > 0.0 and math.isfinite(norm)):
+        raise ValueError("turn_light: the axis must be a finite non-zero vector")
+    k = k / norm
+    v = np.array([light.direction[0], light.direction[1], light.direction[2]], dtype=np.float64)
+    r = v * c + np.cross(k, v) * s + k * (np.dot(k, v) * (1.0 - c))
+    out = _capi.RtLight.from_buffer_copy(bytes(light))
+    for j in range(3):
+        out.direction[j] = np.float32(r[j])
+    return out
+
+
 def orbit_camera(camera, degrees, pivot=(0.0, 0.0, 0.0)):
     """The camera record turned by `degrees` about the vertical (y) axis through `pivot`: origin and origin_image_plane rotate about the
     pivot, x and y rotate as vectors; aperture and focal length stay.  A pure function of the record: evaluated in binary64 and rounded

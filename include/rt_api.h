@@ -230,10 +230,39 @@ int rt_get_camera(rt_ctx* ctx, rt_camera* out);
  *     RT_ERR_INVALID_ARG;
  *   - rt_set_exposure: an exposure that is not finite: RT_ERR_INVALID_ARG.
  * Like rt_set_camera they are stricter than the upload in one place: rt_scene_upload keeps accepting light colours, luminances and
- * exposures that are not finite. */
+ * exposures that are not finite.
+ * rt_set_lights and directions: a direction change goes through rt_turn_lights below.  After a turn, "the uploaded direction" above
+ * reads "the direction set last": rt_set_lights compares with what rt_get_lights returns. */
 int rt_set_materials(rt_ctx* ctx, const rt_material* materials, uint32_t n, const rt_material* sky);
 int rt_set_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights);
 int rt_set_exposure(rt_ctx* ctx, float exposure_scale);
+
+/* Turns the lights of the uploaded scene without an upload: whole records, i.e. direction, colour and luminance of every light, as ONE
+ * event (a sun that reddens while it sets is one call and one void per frame).  Of everything an upload prepares, a direction reaches
+ * the shadow indices alone -- light 0's, one per further light, light 0's far tier -- and those are rebuilt on the host over the
+ * layout kept from the upload, under the preparation options the upload used (the environment is not read again).  No clustering,
+ * bounds, hierarchy or cell grid is built, no device memory allocated or freed, the stream is never synchronised.
+ * Equivalence: after a successful call everything the context computes is, bit for bit, what it computes after an rt_scene_upload of
+ * the same spheres, materials, camera, sky and exposure with the new lights: rt_render under every progressive mode (HDR, LDR, moments,
+ * rt_stats' counters), the trace variant and LDS image of rt_unit_last_trace_launch -- they change with the index's size and with an
+ * index switching on or off -- rt_unit_last_trace_far_state, rt_unit_shadow and rt_unit_shadow_tier, the per-tile unit entries,
+ * rt_render_features and the denoise family with its history and target.
+ * A finite direction that is no direction (length outside (0.5, 2)) is accepted, as the upload accepts it: that light gets no index
+ * and its shadow rays take the scan; a later turn to a direction switches the index on again.
+ * Void and keep: exactly what rt_set_camera voids and keeps; a pending batch is rendered first, under the old lights.  The temporal
+ * history survives and its validation never looks at colour: after a turn EVERY shadow in it is stale.  The remedy is the caller's --
+ * rt_temporal_reset, or rt_temporal_forget of what it knows moved.
+ * Same values: records equal to the current ones as bit patterns -- direction, colour and luminance of every light -- are no event.
+ * Waits: as rt_set_materials -- two staging sets in turn; the host waits only where the copies of the edit before the previous one
+ * have not run yet.
+ * Refused before any side effect, a refused call changes nothing: a null argument (lights may be NULL where n_lights == 0):
+ * RT_ERR_INVALID_ARG; no scene uploaded: RT_ERR_NO_SCENE; n_lights other than the uploaded count: RT_ERR_INVALID_ARG; a direction
+ * component, colour or luminance that is not finite: RT_ERR_INVALID_ARG (stricter than the upload, like the other setters). */
+int rt_turn_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights);
+/* The lights the context renders with now: the records of the last rt_scene_upload, rt_set_lights or rt_turn_lights that changed them.
+ * *n_lights receives their count; with capacity == 0 nothing else is written (out may be NULL), else capacity must be at least the
+ * count (RT_ERR_INVALID_ARG) and out[0 .. count) receives the records.  RT_ERR_NO_SCENE before any upload. */
+int rt_get_lights(rt_ctx* ctx, rt_light* out, uint32_t capacity, uint32_t* n_lights);
 
 /* ----------------------------------------------------------------- render */
 
