@@ -3,7 +3,9 @@
 //   (rtprep::ShadowLayoutOf).  For random scenes of every layout kind (flat, hierarchy, cell grid; negative radii included), 0 to 3
 //   lights and three consecutive turns each: PrepareShadows over the layout kept from PrepareScene(spheres, lights A) equals the shadow
 //   members of a fresh PrepareScene(spheres, lights B) -- shadow, extraShadow, shadowFar, sgSph -- byte for byte, and every table of an
-//   enabled index stays inside the bounds the upload reserves (rt_scene_prep.h kShadow...).
+//   enabled index stays inside the bounds the upload reserves (rt_scene_prep.h kShadow...).  The staging plan of every turn, and of the
+//   scene's material tables, lies inside the slot sized from the upload alone (rt_scene_edit.h StageBytesMax), every table inside its
+//   room and on a 16-byte boundary; the largest plan / slot ratio is printed and must not be zero.
 //   The builder's branches are counted (rtprep::ShadowBuildCounts) and the program fails where one that a scene can reach stayed at
 //   zero.  "Only huge spheres" is counted, reported and must stay at ZERO: the median radius is the radius of some sphere, and that
 //   sphere is not huge (r <= 4 median), so the branch cannot be reached by any scene; the directed scenes below try.
@@ -16,6 +18,7 @@
 #include <vector>
 
 #include "../../../include/rt_api.h"
+#include "rt_scene_edit.h"
 #include "rt_scene_prep.h"
 
 using namespace rtprep;
@@ -120,6 +123,26 @@ void CheckBounds(const ShadowGrid& G, uint32_t maxCells) {
     CHECK(G.cellStart.back() == G.entries.size());
 }
 
+// ... and the same through the staging plan (rt_scene_edit.h): every table inside the room reserved for an index of `maxCells` cells per
+// axis, on a 16-byte boundary of the slot, and the whole plan inside the slot as the upload sized it
+rtscene::IndexDest RoomAt(uint32_t maxCells) {
+    const rtscene::ShadowRoom r = rtscene::ShadowRoomOf(maxCells);
+    return {{nullptr, r.cellWords * sizeof(uint16_t)}, {nullptr, r.entries * sizeof(uint16_t)}, {nullptr, r.global * sizeof(uint16_t)}};
+}
+uint32_t g_plans = 0, g_emptyPlans = 0;
+void CheckPlan(const rtscene::StagePlan& plan, size_t slotBytes, double& largestRatio) {
+    CHECK(plan.status == RT_OK);
+    size_t at = 0;
+    for (const rtscene::StageItem& it : plan.items) {
+        CHECK(it.bytes <= it.dst.room && it.offset % 16 == 0 && it.offset >= at);
+        at = it.offset + it.bytes;
+    }
+    CHECK(at <= plan.total && plan.total <= slotBytes);
+    ++g_plans, g_emptyPlans += plan.total == 0;
+    const double ratio = (double)plan.total / (double)slotBytes;
+    largestRatio = ratio > largestRatio ? ratio : largestRatio;
+}
+
 }  // namespace
 
 int main() {
@@ -127,6 +150,7 @@ int main() {
     const uint32_t kCases = 800;  // x 3 turns: 2,400 scene x direction comparisons, each against a fresh PrepareScene
     uint32_t kinds[3] = {0, 0, 0}, lightCounts[4] = {0, 0, 0, 0}, tier2On = 0, tier2Off = 0, offOnOff = 0, onOffOn = 0, sgSphTables = 0, oneByOne = 0, turns = 0;
     uint32_t shapeChanged = 0, grew = 0;
+    double turnRatio = 0.0, materialRatio = 0.0;  // largest staging plan / slot
     ShadowBuildCounts counts;
     for (g_case = 0; g_case < kCases; ++g_case) {
         uint32_t want = g_case % 10 < 6 ? 0u : (g_case % 10 < 8 ? 1u : 2u);
@@ -160,6 +184,15 @@ int main() {
         CHECK(kept.scan.empty() || (opt.sgSph && L.InGlobalMemory()));
         CHECK(kept.leaf.empty() && kept.tree.empty() && kept.gridCellStart.empty() && kept.InGlobalMemory() == L.InGlobalMemory());
         const uint32_t cells0 = L.InGlobalMemory() ? opt.shadowCellsGlobal : opt.shadowCellsLds;
+        // the slot, from the upload alone; the material tables of the scene fit it too
+        rtscene::StageShape shape;
+        shape.nPad = L.scan.size(), shape.n = n, shape.nIdx = opt.shadowGrid ? nl : 0u, shape.inGlobalMemory = L.InGlobalMemory();
+        const size_t slotBytes = rtscene::StageBytesMax(shape, opt);
+        const std::vector<rtscene::IndexDest> extraRoom(nl, RoomAt(opt.shadowCellsGlobal));
+        const rtscene::TableDest sgSphRoom{nullptr, opt.sgSph && L.InGlobalMemory() ? kShadowSphRecordsMax * sizeof(F4) : 0};
+        const PreparedMaterials M = PrepareMaterials(mats.data(), n, L.orig.data(), L.orig.size());
+        CheckPlan(rtscene::PlanMaterialStage(M, {nullptr, L.orig.size() * sizeof(rt_material)}, {nullptr, L.orig.size() * sizeof(U4)}, {nullptr, n * sizeof(uint32_t)}),
+                  slotBytes, materialRatio);
         bool was[4] = {PA.shadow.enabled, false, false, false};
         ShadowGrid before = PA.shadow;
         for (uint32_t t = 1; t <= 3; ++t, ++turns) {
@@ -180,6 +213,7 @@ int main() {
             CheckBounds(S.shadowFar, opt.shadowCellsGlobal);
             CHECK(S.sgSph.size() <= kShadowSphRecordsMax && (S.sgSph.empty() || (S.shadow.enabled && S.sgSph.size() == S.shadow.entries.size() + 1)));
             CHECK(!S.shadowFar.enabled || S.shadow.enabled);  // the far tier exists only with light 0's first index
+            CheckPlan(rtscene::PlanShadowStage(S, RoomAt(cells0), extraRoom.data(), RoomAt(opt.shadowCellsGlobal), sgSphRoom), slotBytes, turnRatio);
             sgSphTables += !S.sgSph.empty();
             tier2On += S.shadowFar.enabled;
             tier2Off += S.shadow.enabled && !S.shadowFar.enabled;
@@ -213,6 +247,9 @@ int main() {
     CHECK(counts.notADirection > 0 && onOffOn > 0);
     CHECK(counts.halved > 0 && counts.gaveUp > 0);  // (both reached by directed scenes, kinds 3 and 4 above)
     CHECK(oneByOne > 0 && sgSphTables > 0 && shapeChanged > 0 && grew > 0);
+    std::printf("staging: %u plans (%u with nothing to stage), largest plan / slot: turns %.6f, material tables %.6f\n", g_plans, g_emptyPlans, turnRatio,
+                materialRatio);
+    CHECK(turnRatio > 0.0 && turnRatio <= 1.0 && materialRatio > 0.0 && materialRatio <= 1.0 && g_emptyPlans > 0);
     CHECK(counts.onlyHuge == 0);  // unreachable (the head of this file): if a scene ever gets here, the reasoning is wrong and this says so
     std::printf("light_turn_selftest ok\n");
     return 0;

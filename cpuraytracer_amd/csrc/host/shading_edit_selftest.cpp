@@ -15,6 +15,7 @@
 
 #include "../../../include/rt_api.h"
 #include "rt_edit_launch.h"
+#include "rt_scene_edit.h"
 #include "rt_scene_prep.h"
 
 using namespace rtprep;
@@ -104,6 +105,7 @@ bool SameBytes(const std::vector<T>& a, const std::vector<T>& b) {
 void MaterialTables() {
     Rng rng{20261021};
     uint32_t kinds[3] = {0, 0, 0}, flips[2][2] = {{0, 0}, {0, 0}};
+    double largestRatio = 0.0;
     for (g_case = 0; g_case < 2000; ++g_case) {
         const uint32_t want = g_case % 10 < 7 ? 0u : (g_case % 10 < 9 ? 1u : 2u);
         PrepOptions opt;
@@ -128,6 +130,17 @@ void MaterialTables() {
         CHECK(M.mats16Ok == PB.mats16Ok);
         CHECK(SameBytes(M.matType, PB.matType));
         CHECK(M.mats.size() == L.orig.size() && M.mats16.size() == L.orig.size() && M.matType.size() == n);  // the sizes an edit copies
+        // ... through the staging plan (rt_scene_edit.h): inside the slot as the upload sizes it -- a scene without lights reserves no
+        // index, so the slot is the material tables' or the forget table's -- every table inside its room, on a 16-byte boundary
+        rtscene::StageShape shape;
+        shape.nPad = L.orig.size(), shape.n = n, shape.inGlobalMemory = L.InGlobalMemory();
+        const size_t slotBytes = rtscene::StageBytesMax(shape, opt);
+        const rtscene::StagePlan plan =
+            rtscene::PlanMaterialStage(M, {nullptr, L.orig.size() * sizeof(rt_material)}, {nullptr, L.orig.size() * sizeof(U4)}, {nullptr, n * sizeof(uint32_t)});
+        CHECK(plan.status == RT_OK && plan.items.size() == 3 && plan.total > 0 && plan.total <= slotBytes);
+        for (const rtscene::StageItem& it : plan.items) CHECK(it.bytes <= it.dst.room && it.offset % 16 == 0 && it.offset + it.bytes <= plan.total);
+        const double ratio = (double)plan.total / (double)slotBytes;
+        largestRatio = ratio > largestRatio ? ratio : largestRatio;
         // ... and the radii, which PrepareScene still writes itself, do not depend on the table
         CHECK(SameBytes(PA.radius, PB.radius));
     }
@@ -135,6 +148,8 @@ void MaterialTables() {
     CHECK(flips[0][0] > 0 && flips[0][1] > 0 && flips[1][0] > 0 && flips[1][1] > 0);
     std::printf("material tables: 2000 scenes (flat %u, hierarchy %u, cell grid %u); packable A->B: no->no %u, no->yes %u, yes->no %u, yes->yes %u\n", kinds[0],
                 kinds[1], kinds[2], flips[0][0], flips[0][1], flips[1][0], flips[1][1]);
+    std::printf("staging: largest plan / slot %.6f\n", largestRatio);
+    CHECK(largestRatio > 0.0 && largestRatio <= 1.0);
 }
 
 void Forget() {

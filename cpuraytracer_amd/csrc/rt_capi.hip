@@ -25,6 +25,7 @@
 #include "host/rt_edit_launch.h"
 #include "host/rt_denoise_launch.h"
 #include "host/rt_launch_plan.h"
+#include "host/rt_scene_edit.h"
 #include "host/rt_scene_prep.h"
 #include "host/rt_sequence.h"
 #include "host/rt_tile_tables.h"
@@ -104,13 +105,15 @@ struct DevBuf {
 };
 static_assert(!std::is_copy_constructible<DevBuf<float>>::value, "a DevBuf is the one owner of its memory");
 
-// Room for the three tables of an index of ANY direction: the builder's own bounds (host/rt_scene_prep.h), so that rt_turn_lights
-// never allocates under running kernels -- and an index that is disabled now has its buffers all the same, a turn can enable it.
+// Room for the three tables of an index of ANY direction: the builder's own bounds (host/rt_scene_edit.h ShadowRoomOf), so that
+// rt_turn_lights never allocates under running kernels -- and an index that is disabled now has its buffers all the same, a turn can
+// enable it.
 int ReserveShadowGrid(uint32_t maxCells, DevBuf<uint16_t>& cells, DevBuf<uint16_t>& entries, DevBuf<uint16_t>& global) {
+    const rtscene::ShadowRoom room = rtscene::ShadowRoomOf(maxCells);
     int rc;
-    if ((rc = cells.Reserve(rtprep::ShadowCellWordsMax(maxCells))) != RT_OK) return rc;
-    if ((rc = entries.Reserve(rtprep::kShadowEntriesEnd)) != RT_OK) return rc;  // fewer entries than this, and the spare element
-    return global.Reserve(rtprep::kShadowGlobalMax + 1);
+    if ((rc = cells.Reserve(room.cellWords)) != RT_OK) return rc;
+    if ((rc = entries.Reserve(room.entries)) != RT_OK) return rc;
+    return global.Reserve(room.global);
 }
 // A shadow index's three tables (the id lists with one spare element, so that an empty list still has an address): the actual bytes,
 // into buffers that ReserveShadowGrid has sized.
@@ -119,6 +122,14 @@ int UploadShadowGrid(const rtprep::ShadowGrid& G, DevBuf<uint16_t>& cells, DevBu
     if ((rc = cells.Upload(G.cellStart)) != RT_OK) return rc;
     if ((rc = entries.Upload(G.entries, 1)) != RT_OK) return rc;
     return global.Upload(G.global, 1);
+}
+// ... and the same buffers as a staging plan's destinations (host/rt_scene_edit.h): the pointer and the room reserved at it
+template <typename T>
+rtscene::TableDest DestOf(const DevBuf<T>& b) {
+    return {b.ptr, b.count * sizeof(T)};
+}
+rtscene::IndexDest IndexDestOf(const DevBuf<uint16_t>& cells, const DevBuf<uint16_t>& entries, const DevBuf<uint16_t>& global) {
+    return {DestOf(cells), DestOf(entries), DestOf(global)};
 }
 
 }  // namespace
@@ -138,8 +149,9 @@ struct rt_ctx {
     // and the planes traced ahead.  Read freely here; changed only through rtseq's events and step reports.
     rtseq::State seq;
 
-    // scene
-    uint32_t n = 0;
+    // scene: what the caller gave, as of the last upload or edit (host/rt_scene_edit.h: read freely, changed only through rtscene's
+    // commits), and what it became on the device
+    rtscene::Record scene;
     DevBuf<float4> scan, tree, leaf;
     DevBuf<uint32_t> orig;
     DevBuf<uint16_t> sgCells, sgEntries, sgGlobal;
@@ -160,19 +172,7 @@ struct rt_ctx {
     DevBuf<rt_material> mats;
     DevBuf<uint4> mats16;     // the same table packed into 16 bytes per entry (rt_shade.h load_material16), when the scene allows it
     bool mats16Ok = false;
-    rtd::TraceParams base{};  // scene part filled at upload; its camera fields again by rt_set_camera
-    rt_camera camera{};       // the record of the last upload or rt_set_camera (rt_get_camera; the same-record test)
-
-    // shading edits (rt_set_materials, rt_set_lights, rt_set_exposure): the records of the last upload or edit, for the
-    // same-record test (the layout's orig table, over which an edit rebuilds the three material tables, is shadowLayout.orig below)
-    std::vector<rt_material> materials;  // by ORIGINAL sphere index (the sky's record is `sky` below)
-    rt_light lights[RT_MAX_LIGHTS] = {};
-    uint32_t nLights = 0;                // as the caller counted them (0: light 0's slots hold the dark light)
-    // rt_turn_lights: what rtprep::PrepareShadows reads -- the spheres, the part of the upload's layout that the
-    // index builder looks at (rtprep::ShadowLayoutOf), and the upload's preparation options (the environment is not read again)
-    std::vector<rt_sphere> spheres;
-    rtprep::SceneLayout shadowLayout;
-    rtprep::PrepOptions prepOpt;
+    rtd::TraceParams base{};  // scene part filled at upload; the part an edit reaches again by that edit
     // Pinned staging for the copies an edit or rt_temporal_forget orders on the stream: two slots used in turn, each with an event
     // recorded behind its copies.  A slot is written again only once that event has completed -- the one host wait an edit may take,
     // and it takes it only when two newer edits are still queued.  Sized at the upload (never under running kernels).
@@ -200,7 +200,6 @@ struct rt_ctx {
 
     // feature buffers (rt_render_features; rt_features.h): strips, ray-generation tables and sequencing of their own -- nothing
     // here is read or written by rt_render, and nothing of rt_render's by the feature pass
-    rt_material sky{};            // the scene's sky material (the miss albedo is its texture at uv (0, 0))
     bool featCleared = false;     // rt_clear_features was called: the next rt_render_features may start at any s0
     uint32_t featCount = 0;       // samples per pixel in the strips (0: nothing accumulated)
     uint32_t featNext = 0;        // the s0 that continues the accumulation (the previous call's s1)
@@ -396,6 +395,10 @@ static void SetCamera(rtd::TraceParams& tp, const rt_camera& camera) {
     tp.aperture = camera.aperture;
     tp.focal = camera.focal_length;
 }
+static void SetSky(rtd::TraceParams& tp, const rt_material& sky) {
+    for (int k = 0; k < 3; ++k) tp.sky_emit[k] = sky.luminance * sky.rgb0[k];  // Emissive::Emit, material.cpp:172-175
+}
+static void SetExposure(rtd::TraceParams& tp, const rtscene::Record& scene) { tp.exposure = scene.exposure; }  // the launch parameter's one writer
 static void SetPicture(rtd::TraceParams& tp, const rtseq::PictureKey& pic) { tp.W = pic.W, tp.H = pic.H, tp.rs = pic.rs; }
 // The parameters of one pass of the trace kernel: the scene (ctx->base, whose work part is zero: no path list, no tile tables, no
 // ray-generation tables, nothing of the pipeline) and the samples [s0, s0 + spp) of the npix local pixels of the picture.  The caller
@@ -844,21 +847,8 @@ extern "C" {
 const char* rt_last_error(void) { return rtprep::LastError(); }
 int rt_api_version(void) { return RT_API_VERSION; }
 
-// ---- pinned staging of the shading edits (rt_ctx::Stage).  The largest table rt_temporal_forget copies: one bit per id a scene can hold.
-constexpr uint32_t kForgetMaxIds = 65536;
-constexpr uint32_t kForgetTableWords = kForgetMaxIds / 32u;
-static size_t MaterialStageBytes(size_t nPad, size_t n) { return nPad * (sizeof(rt_material) + sizeof(uint4)) + n * sizeof(uint32_t); }
-// ... and the tables rt_turn_lights copies: nIdx first-tier indices and light 0's far tier at the builder's bounds, each table on a
-// 16-byte boundary, and the sgSph records where the option is on.
-static uint32_t Light0CellsMax(bool inGlobalMemory, const rtprep::PrepOptions& opt) { return inGlobalMemory ? opt.shadowCellsGlobal : opt.shadowCellsLds; }
-static size_t StageAlign(size_t bytes) { return (bytes + 15u) & ~(size_t)15u; }
-static size_t ShadowStageBytesMax(uint32_t nIdx, bool inGlobalMemory, const rtprep::PrepOptions& opt) {
-    if (nIdx == 0u) return 0;
-    const size_t lists = StageAlign(rtprep::kShadowEntriesEnd * sizeof(uint16_t)) + StageAlign((rtprep::kShadowGlobalMax + 1) * sizeof(uint16_t));
-    const size_t one = StageAlign(rtprep::ShadowCellWordsMax(opt.shadowCellsGlobal) * sizeof(uint16_t)) + lists;
-    const size_t first = StageAlign(rtprep::ShadowCellWordsMax(Light0CellsMax(inGlobalMemory, opt)) * sizeof(uint16_t)) + lists;
-    return first + (size_t)nIdx * one + (opt.sgSph && inGlobalMemory ? StageAlign(rtprep::kShadowSphRecordsMax * sizeof(float4)) : 0);
-}
+// ---- pinned staging of the edits' tables (rt_ctx::Stage).  What is laid where in a slot, and how large a slot must be, is
+// host/rt_scene_edit.h's to say (StagePlan, StageBytesMax); here are the slots themselves and the one copier.
 // Both slots hold at least `bytes`.  Called where the stream has run dry or nothing was ever queued (rt_create, rt_scene_upload
 // behind its hipStreamSynchronize): a slot that grows is not being read.
 static int StageReserve(rt_ctx* ctx, size_t bytes) {
@@ -890,6 +880,22 @@ static int StageQueued(rt_ctx* ctx, rt_ctx::Stage* st) {
     st->queued = true;
     ctx->stageNext ^= 1u;
     return RT_OK;
+}
+// The tables of a plan, through the slot whose turn it is: each laid at its offset and its copy ordered on the stream -- behind every
+// launch that reads the old table -- then the slot's event behind them all.  No allocation, and no host wait but StageAcquire's.
+static int StageCopy(rt_ctx* ctx, const rtscene::StagePlan& plan) {
+    if (plan.status != RT_OK) return Fail(plan.status, plan.message);
+    if (plan.total == 0) return RT_OK;
+    rt_ctx::Stage* st = nullptr;
+    int rc;
+    if ((rc = StageAcquire(ctx, plan.total, &st)) != RT_OK) return rc;
+    for (const rtscene::StageItem& it : plan.items) {
+        if (it.bytes == 0) continue;
+        char* h = static_cast<char*>(st->host) + it.offset;
+        std::memcpy(h, it.src, it.bytes);
+        if (it.dst.ptr) RT_HIP(hipMemcpyAsync(it.dst.ptr, h, it.bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return StageQueued(ctx, st);
 }
 
 int rt_create(int device_ordinal, rt_ctx** out) {
@@ -937,8 +943,8 @@ int rt_create(int device_ordinal, rt_ctx** out) {
     if (ctx->blockThreads != 256 && ctx->blockThreads != 512 && ctx->blockThreads != 1024) ctx->blockThreads = 256;
     int rc = ctx->queue.Reserve(rtd::kQueueShards * rtd::kShardStrideWords);  // eight queue cursors, 128 bytes apart
     if (rc == RT_OK) rc = ctx->counters.Reserve(6);
-    if (rc == RT_OK) rc = ctx->forgetBits.Reserve(kForgetTableWords);
-    if (rc == RT_OK) rc = StageReserve(ctx, kForgetTableWords * sizeof(uint32_t));
+    if (rc == RT_OK) rc = ctx->forgetBits.Reserve(rtscene::kForgetTableWords);
+    if (rc == RT_OK) rc = StageReserve(ctx, rtscene::StageBytesMax(rtscene::StageShape{}, rtprep::PrepOptions{}));  // no scene yet: the forget table
     if (rc != RT_OK) return rc;
     {
         // sample-buffer workspace: sized for this GPU's HBM (288 GB on MI355X), so that BASELINE configs 3 (on one GPU:
@@ -1022,19 +1028,12 @@ int rt_set_workspace_limit(rt_ctx* ctx, uint64_t bytes) {
 
 int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* materials, uint32_t n, const rt_camera* camera,
                     const rt_light* lights, uint32_t n_lights, const rt_material* sky, float exposure_scale) {
-    if (!ctx || !spheres || !materials || !camera || (!lights && n_lights != 0) || !sky || n == 0)
-        return Fail(RT_ERR_INVALID_ARG, "rt_scene_upload: null pointer or empty scene");
-    if (n_lights > RT_MAX_LIGHTS) return Fail(RT_ERR_INVALID_ARG, "rt_scene_upload: more than RT_MAX_LIGHTS lights");
+    // (refused before any side effect: pending frames stay pending, the previous scene stays)
+    const rtscene::Decision d = rtscene::DecideUpload(ctx ? &ctx->scene : nullptr, spheres, materials, n, camera, lights, n_lights, sky);
+    if (d.verdict == rtscene::Verdict::Refused) return Fail(d.code, d.message);
     // light 0 keeps the single-light kernel path's slots; an empty list is uploaded as one dark light that is never consulted
     const rt_light noLight{{0.f, 1.f, 0.f}, {0.f, 0.f, 0.f}, 0.f};
     const rt_light* sun = n_lights ? lights : &noLight;
-    uint32_t bad = 0;  // (refused before any side effect: pending frames stay pending, the previous scene stays)
-    if (!rtprep::AllFinite(spheres, n, &bad))
-        return Fail(RT_ERR_INVALID_ARG, "rt_scene_upload: sphere " + std::to_string(bad) + " has a centre or a radius that is not finite");
-    const char* field = nullptr;  // the material domain (rt_api.h at rt_material; the rule itself is host/rt_scene_prep.cpp's)
-    if (!rtprep::MaterialsInDomain(materials, n, &bad, &field))
-        return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_scene_upload", "sphere " + std::to_string(bad), materials[bad], field));
-    if ((field = rtprep::MaterialFault(*sky)) != nullptr) return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_scene_upload", "the sky", *sky, field));
     RT_HIP(hipSetDevice(ctx->device));
     int rc;
     if ((rc = Settle(ctx, rtseq::kSettleBeforeScene)) != RT_OK) return rc;
@@ -1067,14 +1066,16 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     // the disabled ones included: rt_turn_lights only copies.  So the records know their tables' addresses before the copies.
     const uint32_t nIdx = opt.shadowGrid ? n_lights : 0u;  // lights that may have an index (RT_SHADOW_GRID=0: none, after any turn)
     if (nIdx != 0u) {
-        if ((rc = ReserveShadowGrid(Light0CellsMax(L.InGlobalMemory(), opt), ctx->sgCells, ctx->sgEntries, ctx->sgGlobal)) != RT_OK) return rc;
+        if ((rc = ReserveShadowGrid(rtscene::Light0CellsMax(L.InGlobalMemory(), opt), ctx->sgCells, ctx->sgEntries, ctx->sgGlobal)) != RT_OK) return rc;
         if ((rc = ReserveShadowGrid(opt.shadowCellsGlobal, ctx->farIdx.cells, ctx->farIdx.entries, ctx->farIdx.global)) != RT_OK) return rc;
         if (opt.sgSph && L.InGlobalMemory() && (rc = ctx->sgSph.Reserve(rtprep::kShadowSphRecordsMax)) != RT_OK) return rc;
     }
     for (uint32_t k = 1; k < nIdx; ++k)
         if ((rc = ReserveShadowGrid(opt.shadowCellsGlobal, ctx->extraIdx[k].cells, ctx->extraIdx[k].entries, ctx->extraIdx[k].global)) != RT_OK) return rc;
-    // (both staging slots: the larger of what rt_set_materials and what rt_turn_lights copy)
-    if ((rc = StageReserve(ctx, std::max(MaterialStageBytes(nPad, n), ShadowStageBytesMax(nIdx, L.InGlobalMemory(), opt)))) != RT_OK) return rc;
+    // (both staging slots: the largest of what rt_set_materials, rt_turn_lights and rt_temporal_forget copy)
+    rtscene::StageShape stageShape;
+    stageShape.nPad = nPad, stageShape.n = n, stageShape.nIdx = nIdx, stageShape.inGlobalMemory = L.InGlobalMemory();
+    if ((rc = StageReserve(ctx, rtscene::StageBytesMax(stageShape, opt))) != RT_OK) return rc;
     std::vector<rtd::LightRec> recs = LightRecords(ctx, P, lights, n_lights, camera->origin);
     const size_t nRecs = recs.size();
     // (n_lights records lie there from now on, the far tier's slot empty while that index is off: a turn that switches it on writes
@@ -1134,52 +1135,33 @@ int rt_scene_upload(rt_ctx* ctx, const rt_sphere* spheres, const rt_material* ma
     b.n = n;
     b.n_padded = nPad;
     SetCamera(b, *camera);
-    for (int k = 0; k < 3; ++k) b.sky_emit[k] = sky->luminance * sky->rgb0[k];  // Emissive::Emit, material.cpp:172-175
-    b.exposure = exposure_scale;
-    ctx->n = n;
-    ctx->sky = *sky;
-    ctx->camera = *camera;
-    ctx->materials.assign(materials, materials + n);
-    ctx->spheres.assign(spheres, spheres + n);
-    ctx->shadowLayout = rtprep::ShadowLayoutOf(L, opt);
-    ctx->prepOpt = opt;
-    ctx->nLights = n_lights;
-    for (uint32_t k = 0; k < n_lights; ++k) ctx->lights[k] = lights[k];
+    SetSky(b, *sky);
+    rtscene::CommitUpload(ctx->scene, spheres, materials, n, *camera, lights, n_lights, *sky, exposure_scale, L, opt);
+    SetExposure(b, ctx->scene);
     DropVoided(ctx, rtseq::SceneReplaced(ctx->seq));
     return RT_OK;
 }
 
-// The 14 floats of a camera record that the renderer reads (SetCamera above), with their names; the fourth components are padding.
-struct CameraField {
-    const char* name;
-    size_t offset;
-    uint32_t count;
-};
-static const CameraField kCameraFields[] = {{"origin", offsetof(rt_camera, origin), 3},
-                                            {"x", offsetof(rt_camera, x), 3},
-                                            {"y", offsetof(rt_camera, y), 3},
-                                            {"origin_image_plane", offsetof(rt_camera, origin_image_plane), 3},
-                                            {"aperture", offsetof(rt_camera, aperture), 1},
-                                            {"focal_length", offsetof(rt_camera, focal_length), 1}};
-static const char* CameraFieldNotFinite(const rt_camera& c) {
-    for (const CameraField& f : kCameraFields)
-        for (uint32_t k = 0; k < f.count; ++k) {
-            float v;
-            std::memcpy(&v, reinterpret_cast<const char*>(&c) + f.offset + k * sizeof(float), sizeof(float));
-            if (!std::isfinite(v)) return f.name;
-        }
-    return nullptr;
+// ---- edits: camera, materials, sky, lights and exposure without an upload (rt_api.h).  What each refuses,
+// and when its arguments are the record's own and the call is not an event, is host/rt_scene_edit.h's decision.  An accepted edit
+// computes what an upload with the new values computes, runs no scene preparation but its own tables', and takes no host wait but the
+// staging's (StageAcquire).  Every entry reads: decide -- return or fail -- hipSetDevice -- settle -- its device work -- commit the
+// record -- PictureInputChanged.  A failed settle or launch leaves the record as it was.
+static const rtscene::Record* RecordOf(const rt_ctx* ctx) { return ctx ? &ctx->scene : nullptr; }
+static bool HasScene(const rt_ctx* ctx) { return ctx && ctx->seq.hasScene; }
+static int Answer(const rtscene::Decision& d) { return d.verdict == rtscene::Verdict::Refused ? Fail(d.code, d.message) : RT_OK; }
+// The head of an edit.  *go: the edit goes on (changed, and settled without error); else the entry returns what this returned.
+static int BeginEdit(rt_ctx* ctx, const rtscene::Decision& d, bool* go) {
+    *go = false;
+    if (d.verdict != rtscene::Verdict::Changed) return Answer(d);  // (the same record: not an event -- rt_set_sampler's precedent)
+    RT_HIP(hipSetDevice(ctx->device));
+    const int rc = Settle(ctx, rtseq::kSettleBeforeCamera);  // the pending batch was asked of the old values
+    *go = rc == RT_OK;
+    return rc;
 }
-static bool SameCameraBits(const rt_camera& a, const rt_camera& b) {
-    for (const CameraField& f : kCameraFields)
-        if (std::memcmp(reinterpret_cast<const char*>(&a) + f.offset, reinterpret_cast<const char*>(&b) + f.offset, f.count * sizeof(float)) != 0) return false;
-    return true;
-}
-
-// What a change of the camera voids, and a change of materials, sky, light radiance or exposure with it -- every picture and every
-// per-tile table is a function of each of them (the work order reads matType, the empty-list tiles' constant sample reads sky and
-// exposure): decided by the camera's two events, written here once for the four entries.  The caller has settled
-// rtseq::kSettleBeforeCamera and put the new values in place.
+// What a change of the camera voids, and a change of materials, sky, lights or exposure with it -- every picture and every per-tile
+// table is a function of each of them (the work order reads matType, the empty-list tiles' constant sample reads sky and exposure):
+// decided by the camera's two events, written here once for the five entries.
 static void PictureInputChanged(rt_ctx* ctx) {
     rttile::CameraChanged(ctx->tiles);
     (void)rtseq::TileTablesDropped(ctx->seq);
@@ -1187,94 +1169,44 @@ static void PictureInputChanged(rt_ctx* ctx) {
 }
 
 int rt_set_camera(rt_ctx* ctx, const rt_camera* camera) {
-    if (!ctx || !camera) return Fail(RT_ERR_INVALID_ARG, "rt_set_camera: null argument");
-    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_set_camera: no scene uploaded");
-    if (const char* field = CameraFieldNotFinite(*camera)) return Fail(RT_ERR_INVALID_ARG, std::string("rt_set_camera: ") + field + " is not finite");
-    if (SameCameraBits(*camera, ctx->camera)) return RT_OK;  // the same record: not an event (rt_set_sampler's precedent)
-    RT_HIP(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old camera
+    bool go;
+    const int rc = BeginEdit(ctx, rtscene::DecideSetCamera(RecordOf(ctx), HasScene(ctx), camera), &go);
+    if (!go) return rc;
     // The one piece of device memory that holds the camera: cam_o of lights 1 .. (the far-tier record behind them carries none).  On
     // the stream, behind every launch of the old camera, the origin by value: no host wait, nothing read later.
     const uint32_t extra = ctx->base.n_lights > 1u ? ctx->base.n_lights - 1u : 0u;
     RT_HIP((hipError_t)rtcam::LaunchLightCamera(ctx->stream, ctx->lightRecs.ptr, extra, camera->origin));
     SetCamera(ctx->base, *camera);
-    ctx->camera = *camera;
+    rtscene::CommitCamera(ctx->scene, *camera);
     PictureInputChanged(ctx);
     return RT_OK;
 }
 
-int rt_get_camera(rt_ctx* ctx, rt_camera* out) {
-    if (!ctx || !out) return Fail(RT_ERR_INVALID_ARG, "rt_get_camera: null argument");
-    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_get_camera: no scene uploaded");
-    *out = ctx->camera;
-    return RT_OK;
-}
+int rt_get_camera(rt_ctx* ctx, rt_camera* out) { return Answer(rtscene::GetCamera(RecordOf(ctx), HasScene(ctx), out)); }
 
-// ---- shading edits: materials, sky, light radiance and exposure without an upload (rt_api.h).  Each computes what an
-// upload with the new values computes, voids what rt_set_camera voids, runs no scene preparation and takes no host wait but the
-// staging's (StageAcquire).
 int rt_set_materials(rt_ctx* ctx, const rt_material* materials, uint32_t n, const rt_material* sky) {
-    if (!ctx || !materials || !sky) return Fail(RT_ERR_INVALID_ARG, "rt_set_materials: null argument");
-    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_set_materials: no scene uploaded");
-    if (n != ctx->n) return Fail(RT_ERR_INVALID_ARG, "rt_set_materials: " + std::to_string(n) + " records for a scene of " + std::to_string(ctx->n) + " spheres");
-    uint32_t bad = 0;
-    const char* field = nullptr;
-    if (!rtprep::MaterialsInDomain(materials, n, &bad, &field))
-        return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_set_materials", "sphere " + std::to_string(bad), materials[bad], field));
-    if ((field = rtprep::MaterialFault(*sky)) != nullptr) return Fail(RT_ERR_INVALID_ARG, rtprep::MaterialFaultMessage("rt_set_materials", "the sky", *sky, field));
-    // the same records, all 48 bytes of each (the device tables hold them whole): not an event
-    const bool sameTable = std::memcmp(materials, ctx->materials.data(), (size_t)n * sizeof(rt_material)) == 0;
-    const bool sameSky = std::memcmp(sky, &ctx->sky, sizeof(rt_material)) == 0;
-    if (sameTable && sameSky) return RT_OK;
-    RT_HIP(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old materials
-    if (!sameTable) {
-        // The three tables, by their one writer over the upload's layout, through pinned staging and copies ordered on the stream behind
-        // every launch of the old materials.  No allocation: each buffer has had its full size since the upload.
-        const size_t nPad = ctx->shadowLayout.orig.size();
-        const rtprep::PreparedMaterials M = rtprep::PrepareMaterials(materials, n, ctx->shadowLayout.orig.data(), nPad);
-        rt_ctx::Stage* st = nullptr;
-        if ((rc = StageAcquire(ctx, MaterialStageBytes(nPad, n), &st)) != RT_OK) return rc;
-        char* h = static_cast<char*>(st->host);
-        const size_t b0 = nPad * sizeof(rt_material), b1 = nPad * sizeof(uint4), b2 = (size_t)n * sizeof(uint32_t);
-        std::memcpy(h, M.mats.data(), b0);
-        std::memcpy(h + b0, M.mats16.data(), b1);
-        std::memcpy(h + b0 + b1, M.matType.data(), b2);
-        RT_HIP(hipMemcpyAsync(ctx->mats.ptr, h, b0, hipMemcpyHostToDevice, ctx->stream));
-        if (M.mats16Ok) RT_HIP(hipMemcpyAsync(ctx->mats16.ptr, h + b0, b1, hipMemcpyHostToDevice, ctx->stream));
-        RT_HIP(hipMemcpyAsync(ctx->matType.ptr, h + b0 + b1, b2, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = StageQueued(ctx, st)) != RT_OK) return rc;
+    const rtscene::Decision d = rtscene::DecideSetMaterials(RecordOf(ctx), HasScene(ctx), materials, n, sky);
+    bool go;
+    int rc = BeginEdit(ctx, d, &go);
+    if (!go) return rc;
+    if (d.table) {
+        // The three tables, by their one writer over the upload's layout.  Each buffer has had its full size since the upload.
+        const std::vector<uint32_t>& orig = ctx->scene.shadowLayout.orig;
+        const rtprep::PreparedMaterials M = rtprep::PrepareMaterials(materials, n, orig.data(), orig.size());
+        if ((rc = StageCopy(ctx, rtscene::PlanMaterialStage(M, DestOf(ctx->mats), DestOf(ctx->mats16), DestOf(ctx->matType)))) != RT_OK) return rc;
         ctx->mats16Ok = M.mats16Ok;  // (either way round: the launch plan reads the pointer)
         ctx->base.mats16 = M.mats16Ok ? ctx->mats16.ptr : nullptr;
-        ctx->materials.assign(materials, materials + n);
     }
-    for (int k = 0; k < 3; ++k) ctx->base.sky_emit[k] = sky->luminance * sky->rgb0[k];  // as the upload
-    ctx->sky = *sky;
+    SetSky(ctx->base, *sky);
+    rtscene::CommitMaterials(ctx->scene, d, materials, *sky);
     PictureInputChanged(ctx);
     return RT_OK;
 }
 
 int rt_set_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights) {
-    if (!ctx || (!lights && n_lights != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_set_lights: null argument");
-    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_set_lights: no scene uploaded");
-    if (n_lights != ctx->nLights)
-        return Fail(RT_ERR_INVALID_ARG, "rt_set_lights: " + std::to_string(n_lights) + " lights for a scene uploaded with " + std::to_string(ctx->nLights));
-    bool same = true;
-    for (uint32_t k = 0; k < n_lights; ++k) {
-        if (std::memcmp(lights[k].direction, ctx->lights[k].direction, sizeof lights[k].direction) != 0)
-            return Fail(RT_ERR_INVALID_ARG, "rt_set_lights: light " + std::to_string(k) +
-                                                " has another direction than the uploaded one: a direction change needs an rt_scene_upload (the light's shadow index is built for its direction)");
-        if (!std::isfinite(lights[k].luminance) || !std::isfinite(lights[k].color[0]) || !std::isfinite(lights[k].color[1]) || !std::isfinite(lights[k].color[2]))
-            return Fail(RT_ERR_INVALID_ARG, "rt_set_lights: light " + std::to_string(k) + " has a colour or a luminance that is not finite");
-        same = same && std::memcmp(lights[k].color, ctx->lights[k].color, sizeof lights[k].color) == 0 &&
-               std::memcmp(&lights[k].luminance, &ctx->lights[k].luminance, sizeof(float)) == 0;
-    }
-    if (same) return RT_OK;  // (n_lights == 0 included)
-    RT_HIP(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old lights
+    bool go;
+    const int rc = BeginEdit(ctx, rtscene::DecideSetLights(RecordOf(ctx), HasScene(ctx), lights, n_lights), &go);
+    if (!go) return rc;
     // Light 0's radiance is a launch parameter.  Lights 1 .. keep theirs in device memory: patched on the stream, by value, behind
     // every launch of the old radiance (the far-tier record behind them holds an index and no light).
     rtd::LightRec tmp{};
@@ -1285,100 +1217,46 @@ int rt_set_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights) {
     }
     RT_HIP((hipError_t)rtedit::LaunchLightRadiance(ctx->stream, ctx->lightRecs.ptr, n_lights - 1u, R));
     SetLight(ctx->base, lights[0]);
-    for (uint32_t k = 0; k < n_lights; ++k) ctx->lights[k] = lights[k];
+    rtscene::CommitLights(ctx->scene, lights);
     PictureInputChanged(ctx);
     return RT_OK;
 }
 
-// ---- turning the lights without an upload (rt_api.h): direction, colour and luminance of every light as one event.
-// Of everything a scene becomes, a direction reaches the shadow indices alone: they are rebuilt on the host by their one writer over
-// what the upload kept, copied on the stream from pinned staging into buffers reserved at the builder's bounds, and the records of
-// lights 1 .. and of the far tier are rewritten on the stream by value.  No layout is built, nothing allocated, no wait but the staging's.
+// Turning the lights: direction, colour and luminance of every light as one event.  Of everything a scene becomes, a
+// direction reaches the shadow indices alone: they are rebuilt on the host by their one writer over what the upload kept, copied into
+// buffers reserved at the builder's bounds, and the records of lights 1 .. and of the far tier are rewritten on the stream by value.
 int rt_turn_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights) {
-    if (!ctx || (!lights && n_lights != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_turn_lights: null argument");
-    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_turn_lights: no scene uploaded");
-    if (n_lights != ctx->nLights)
-        return Fail(RT_ERR_INVALID_ARG, "rt_turn_lights: " + std::to_string(n_lights) + " lights for a scene uploaded with " + std::to_string(ctx->nLights));
-    bool same = true;
-    for (uint32_t k = 0; k < n_lights; ++k) {
-        const rt_light& l = lights[k];
-        if (!std::isfinite(l.direction[0]) || !std::isfinite(l.direction[1]) || !std::isfinite(l.direction[2]))
-            return Fail(RT_ERR_INVALID_ARG, "rt_turn_lights: light " + std::to_string(k) + " has a direction that is not finite");
-        if (!std::isfinite(l.luminance) || !std::isfinite(l.color[0]) || !std::isfinite(l.color[1]) || !std::isfinite(l.color[2]))
-            return Fail(RT_ERR_INVALID_ARG, "rt_turn_lights: light " + std::to_string(k) + " has a colour or a luminance that is not finite");
-        same = same && std::memcmp(l.direction, ctx->lights[k].direction, sizeof l.direction) == 0 &&
-               std::memcmp(l.color, ctx->lights[k].color, sizeof l.color) == 0 && std::memcmp(&l.luminance, &ctx->lights[k].luminance, sizeof(float)) == 0;
-    }
-    if (same) return RT_OK;  // (n_lights == 0 included)
-    RT_HIP(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old lights
-    const rtprep::PreparedShadows S = rtprep::PrepareShadows(ctx->spheres.data(), ctx->shadowLayout, lights, n_lights, ctx->prepOpt);
-    // The tables of every enabled index: through one staging slot, each on a 16-byte boundary, by copies ordered on the stream behind
-    // every launch of the old directions.  Only the actual bytes; the room is the upload's reservation.
-    struct Table {
-        const void* src;
-        void* dst;
-        size_t bytes, room;  // room: what the upload reserved at dst
-    };
-    std::vector<Table> tables;
-    const bool recsRoomShort = ctx->lightRecs.count < n_lights;
-    auto index = [&tables](const rtprep::ShadowGrid& G, DevBuf<uint16_t>& cells, DevBuf<uint16_t>& entries, DevBuf<uint16_t>& global) {
-        if (!G.enabled) return;
-        tables.push_back({G.cellStart.data(), cells.ptr, G.cellStart.size() * sizeof(uint16_t), cells.count * sizeof(uint16_t)});
-        tables.push_back({G.entries.data(), entries.ptr, G.entries.size() * sizeof(uint16_t), entries.count * sizeof(uint16_t)});
-        tables.push_back({G.global.data(), global.ptr, G.global.size() * sizeof(uint16_t), global.count * sizeof(uint16_t)});
-    };
-    index(S.shadow, ctx->sgCells, ctx->sgEntries, ctx->sgGlobal);
-    for (uint32_t k = 1; k < n_lights; ++k) index(S.extraShadow[k - 1], ctx->extraIdx[k].cells, ctx->extraIdx[k].entries, ctx->extraIdx[k].global);
-    index(S.shadowFar, ctx->farIdx.cells, ctx->farIdx.entries, ctx->farIdx.global);
-    if (!S.sgSph.empty()) tables.push_back({S.sgSph.data(), ctx->sgSph.ptr, S.sgSph.size() * sizeof(float4), ctx->sgSph.count * sizeof(float4)});
-    size_t total = 0;
-    if (recsRoomShort) return Fail(RT_ERR_HIP, "rt_turn_lights: the light records are fewer than the lights (no upload reserved them)");
-    for (const Table& t : tables) {
-        if (t.bytes > t.room) return Fail(RT_ERR_HIP, "rt_turn_lights: a table is larger than the room the upload reserved for it");
-        total += StageAlign(t.bytes);
-    }
-    if (total != 0) {
-        rt_ctx::Stage* st = nullptr;
-        if ((rc = StageAcquire(ctx, total, &st)) != RT_OK) return rc;
-        char* h = static_cast<char*>(st->host);
-        for (const Table& t : tables) {
-            if (t.bytes == 0) continue;
-            std::memcpy(h, t.src, t.bytes);
-            RT_HIP(hipMemcpyAsync(t.dst, h, t.bytes, hipMemcpyHostToDevice, ctx->stream));
-            h += StageAlign(t.bytes);
-        }
-        if ((rc = StageQueued(ctx, st)) != RT_OK) return rc;
-    }
+    bool go;
+    int rc = BeginEdit(ctx, rtscene::DecideTurnLights(RecordOf(ctx), HasScene(ctx), lights, n_lights), &go);
+    if (!go) return rc;
+    if (ctx->lightRecs.count < n_lights) return Fail(RT_ERR_HIP, "rt_turn_lights: the light records are fewer than the lights (no upload reserved them)");
+    const rtscene::Record& scene = ctx->scene;
+    const rtprep::PreparedShadows S = rtprep::PrepareShadows(scene.spheres.data(), scene.shadowLayout, lights, n_lights, scene.prepOpt);
+    // The tables of every enabled index: only the actual bytes; the room is the upload's reservation.
+    rtscene::IndexDest extra[RT_MAX_LIGHTS];
+    for (uint32_t k = 1; k < n_lights; ++k) extra[k - 1] = IndexDestOf(ctx->extraIdx[k].cells, ctx->extraIdx[k].entries, ctx->extraIdx[k].global);
+    const rtscene::StagePlan plan = rtscene::PlanShadowStage(S, IndexDestOf(ctx->sgCells, ctx->sgEntries, ctx->sgGlobal), extra,
+                                                             IndexDestOf(ctx->farIdx.cells, ctx->farIdx.entries, ctx->farIdx.global), DestOf(ctx->sgSph));
+    if ((rc = StageCopy(ctx, plan)) != RT_OK) return rc;
     // The records in device memory, behind the copies and behind every launch that reads the old ones: by value, cam_o left alone.
-    const std::vector<rtd::LightRec> recs = LightRecords(ctx, S, lights, n_lights, ctx->camera.origin);
+    const std::vector<rtd::LightRec> recs = LightRecords(ctx, S, lights, n_lights, scene.camera.origin);
     RT_HIP((hipError_t)rtedit::LaunchLightIndex(ctx->stream, ctx->lightRecs.ptr, (uint32_t)recs.size(), recs.data()));
     SetSunAndIndices(ctx, S, lights[0], recs.size());  // light 0, the index's sizes for the launch plan, far_index, extra_lights
-    for (uint32_t k = 0; k < n_lights; ++k) ctx->lights[k] = lights[k];
+    rtscene::CommitLights(ctx->scene, lights);
     PictureInputChanged(ctx);
     return RT_OK;
 }
 
 int rt_get_lights(rt_ctx* ctx, rt_light* out, uint32_t capacity, uint32_t* n_lights) {
-    if (!ctx || !n_lights || (!out && capacity != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_get_lights: null argument");
-    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_get_lights: no scene uploaded");
-    *n_lights = ctx->nLights;
-    if (capacity == 0) return RT_OK;  // the count alone
-    if (capacity < ctx->nLights) return Fail(RT_ERR_INVALID_ARG, "rt_get_lights: capacity too small for " + std::to_string(ctx->nLights) + " lights");
-    for (uint32_t k = 0; k < ctx->nLights; ++k) out[k] = ctx->lights[k];
-    return RT_OK;
+    return Answer(rtscene::GetLights(RecordOf(ctx), HasScene(ctx), out, capacity, n_lights));
 }
 
 int rt_set_exposure(rt_ctx* ctx, float exposure_scale) {
-    if (!ctx) return Fail(RT_ERR_INVALID_ARG, "rt_set_exposure: null ctx");
-    if (!ctx->seq.hasScene) return Fail(RT_ERR_NO_SCENE, "rt_set_exposure: no scene uploaded");
-    if (!std::isfinite(exposure_scale)) return Fail(RT_ERR_INVALID_ARG, "rt_set_exposure: the exposure is not finite");
-    if (std::memcmp(&exposure_scale, &ctx->base.exposure, sizeof(float)) == 0) return RT_OK;
-    RT_HIP(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = Settle(ctx, rtseq::kSettleBeforeCamera)) != RT_OK) return rc;  // the batch was asked of the old exposure
-    ctx->base.exposure = exposure_scale;
+    bool go;
+    const int rc = BeginEdit(ctx, rtscene::DecideSetExposure(RecordOf(ctx), HasScene(ctx), exposure_scale), &go);
+    if (!go) return rc;
+    rtscene::CommitExposure(ctx->scene, exposure_scale);
+    SetExposure(ctx->base, ctx->scene);
     PictureInputChanged(ctx);
     return RT_OK;
 }
@@ -1793,7 +1671,7 @@ int rt_render_features(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
     fp.s0 = s0;
     fp.s1 = s1;
     fp.cont = starts ? 0u : 1u;
-    const rtd::V3 skyAlbedo = rtd::feature_sky_albedo(rtd::feature_material(ctx->sky));
+    const rtd::V3 skyAlbedo = rtd::feature_sky_albedo(rtd::feature_material(ctx->scene.sky));
     fp.sky[0] = skyAlbedo.x;
     fp.sky[1] = skyAlbedo.y;
     fp.sky[2] = skyAlbedo.z;
@@ -2124,20 +2002,14 @@ int rt_temporal_reset(rt_ctx* ctx) {
 int rt_temporal_forget(rt_ctx* ctx, const uint32_t* ids, uint32_t n_ids) {
     if (!ctx || (!ids && n_ids != 0)) return Fail(RT_ERR_INVALID_ARG, "rt_temporal_forget: null argument");
     if (n_ids == 0 || !ctx->tmpValid) return RT_OK;
-    const uint32_t nSpheres = ctx->seq.hasScene ? ctx->n : kForgetMaxIds;
-    rtedit::ForgetPlan P = rtedit::PlanForget(ids, n_ids, nSpheres < kForgetMaxIds ? nSpheres : kForgetMaxIds);
+    const uint32_t nSpheres = ctx->seq.hasScene ? ctx->scene.n : rtscene::kForgetMaxIds;
+    rtedit::ForgetPlan P = rtedit::PlanForget(ids, n_ids, nSpheres < rtscene::kForgetMaxIds ? nSpheres : rtscene::kForgetMaxIds);
     if (P.nothing) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->tmpPic.W * ctx->tmpPic.rs.num_rows;
     if (npix > 0x7fffffffull) return Fail(RT_ERR_INVALID_ARG, "rt_temporal_forget: a history of more than 2^31 pixels");
     if (!P.table.empty()) {
-        int rc;
-        rt_ctx::Stage* st = nullptr;
-        const size_t bytes = P.table.size() * sizeof(uint32_t);
-        if ((rc = StageAcquire(ctx, bytes, &st)) != RT_OK) return rc;
-        std::memcpy(st->host, P.table.data(), bytes);
-        RT_HIP(hipMemcpyAsync(ctx->forgetBits.ptr, st->host, bytes, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = StageQueued(ctx, st)) != RT_OK) return rc;
+        if (const int rc = StageCopy(ctx, rtscene::PlanForgetStage(P.table, DestOf(ctx->forgetBits)))) return rc;
         P.set.bits = ctx->forgetBits.ptr;
     }
     const rt_ctx::TemporalSet& t = ctx->tmpSet[ctx->tmpCur & 1u];
@@ -2537,10 +2409,10 @@ int rt_unit_tile_masks(rt_ctx* ctx, uint32_t W, uint32_t H, rt_rowset rs, uint32
         RT_HIP(hipMemcpy(words, ctx->tileMasks.ptr, (size_t)*n_tiles * rtd::kTileMaskWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     if (group_of_sphere) {
-        if (cap_spheres < ctx->n) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: sphere capacity too small");
+        if (cap_spheres < ctx->scene.n) return Fail(RT_ERR_INVALID_ARG, "rt_unit_tile_masks: sphere capacity too small");
         std::vector<uint32_t> orig(ctx->base.n_padded);
         RT_HIP(hipMemcpy(orig.data(), ctx->orig.ptr, orig.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        rtprep::EntryOfSphere(orig.data(), orig.size(), ctx->n, 2, group_of_sphere);  // flat scan: scan entry = 4 * group + member
+        rtprep::EntryOfSphere(orig.data(), orig.size(), ctx->scene.n, 2, group_of_sphere);  // flat scan: scan entry = 4 * group + member
     }
     if (scans) {
         unsigned long long c[4] = {0, 0, 0, 0};

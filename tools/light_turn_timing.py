@@ -111,8 +111,11 @@ def main():
     args = ap.parse_args()
     import bench
     import __graft_entry__ as g
+    from cpuraytracer_amd import _capi
+    if os.environ.get("RT_HIP_LIB"):  # A/B runs against another build of the library (tool only, as tools/bench_scene.py)
+        _capi.LIB_PATH = os.path.abspath(os.environ["RT_HIP_LIB"])
     g.build()
-    from cpuraytracer_amd import HipRenderer, _capi, scenes
+    from cpuraytracer_amd import HipRenderer, scenes
     print("turning the sun: rt_scene_upload against rt_turn_lights; kernel sources %s\n" % bench.kernel_sources_hash()[:16])
     ok = True
     for name, W, H in SCENES:

@@ -64,9 +64,12 @@ def main():
     args = ap.parse_args()
     import bench
     import __graft_entry__ as g
+    from cpuraytracer_amd import _capi
+    if os.environ.get("RT_HIP_LIB"):  # A/B runs against another build of the library (tool only, as tools/bench_scene.py)
+        _capi.LIB_PATH = os.path.abspath(os.environ["RT_HIP_LIB"])
     g.build()
-    from cpuraytracer_amd import HipRenderer, _capi, scenes
-    V = _capi.variance_params(source=_capi.RT_VARIANCE_SPATIAL)
+    from cpuraytracer_amd import HipRenderer, scenes
+    V =_capi.variance_params(source=_capi.RT_VARIANCE_SPATIAL)
     routes = ("upload", "set_materials")
     ctx = {m: HipRenderer(0) for m in routes}
     scs = {m: scenes.build_scene("cover", bench.SCENE_SEED, W, H) for m in routes}
